@@ -10,7 +10,13 @@ PSF, fp64, Cholesky kappa/C = 6e-4).  One process per GPU, no data
 (blocks/stamps are independent): weak scaling, each rank runs its own batch.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
+    python bench.py --full                                             # + every other leg, roofline, CPU baseline, detail file
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the steps and prints the line with the contract's keys.  Everything else -- the roofline
+(HIP-event times of the kernel families, the fp64 MFMA probe), per-step times and telemetry, the seams, the block leg, the other
+configurations, paper4, iter_default, the farm leg, the CPU baseline, the summary and the detail file -- runs with --full.
 """
 
 import argparse
@@ -1042,9 +1048,10 @@ def compact_line(out, detail_path=None, limit=COMPACT_LIMIT):
     line = {k: out[k] for k in keep if k in out}
     cf = out.get("config", {})
     line["config"] = {k: (cf[k][:200] if isinstance(cf[k], str) else cf[k]) for k in ("workload", "stamps_per_step_per_gpu", "N_mean", "m", "parallelism") if k in cf}
-    rf = out.get("roofline", {})
-    line["roofline"] = {k: (rf[k][:120] if isinstance(rf[k], str) else rf[k]) for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source",
-                                                                                         "avg_launch_ms", "launches", "flops_per_launch") if k in rf}
+    rf = out.get("roofline")
+    if isinstance(rf, dict):  # (a plain run measures no roofline: only --full has one)
+        line["roofline"] = {k: (rf[k][:120] if isinstance(rf[k], str) else rf[k]) for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic",
+                                                                                             "traffic_source", "avg_launch_ms", "launches", "flops_per_launch") if k in rf}
     cb = out.get("cpu_baseline")
     if isinstance(cb, dict):
         if "error" in cb:
@@ -1062,11 +1069,12 @@ def compact_line(out, detail_path=None, limit=COMPACT_LIMIT):
             line["farm"]["error"] = line["farm"]["error"][:120]
     if out.get("per_rank_value") and out.get("n_gpus", 1) > 1:
         line["per_rank_value"] = out["per_rank_value"]
-    line["summary"] = dict(out.get("summary") or {})
-    line["detail"] = detail_path
+    if "summary" in out:  # (--full: the legs' summary and the detail file; a plain run has neither)
+        line["summary"] = dict(out["summary"] or {})
+        line["detail"] = detail_path
     line = {k: (_sig(v, 10) if isinstance(v, float) else _sig(v)) for k, v in line.items()}  # (the contract's own numbers keep their digits: value x ms_per_step is checked)
     text = json.dumps(line, separators=(",", ":"))
-    while len(text) > limit and line["summary"]:
+    while len(text) > limit and line.get("summary"):
         line["summary"].pop(next(reversed(line["summary"])))
         line["summary_truncated"] = True
         text = json.dumps(line, separators=(",", ":"))
@@ -1290,6 +1298,37 @@ def seam_legs(ctx, dev, cfg, batch):
     return out
 
 
+DUMP_ARRAY_BYTES = 6 << 20  # per array of --dump-outputs: nine arrays stay below 64 MB whatever --batch is
+DUMP_SEED = 20240611
+
+
+def dump_outputs(res, outdir):
+    """What the caller of StampBatch.run() received from the last timed step, as ``outdir/<name>.npy`` in float32 / float64: the maps,
+    the coadded images, the T sums, Neff and the factorisations' info whole (a fixed, seeded sample of stamps when an array is above
+    DUMP_ARRAY_BYTES), and a fixed, seeded sample of T's entries [stamp, input pixel < N, output pixel < m] (T whole is ~5 GB at
+    cfg-2).  The inputs are synthesised from fixed seeds, so two builds with the same arguments can be compared file for file."""
+    import numpy as np
+    import torch
+
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    batch = int(res.n.size)
+    arrays = {name: getattr(res, name).cpu().numpy() for name in ("UC", "Sigma", "kappa", "outimage", "Tsum_stamp", "Tsum_inpix", "Neff")}
+    arrays["info"] = res.info.astype(np.float64)
+    for name, a in arrays.items():
+        if a.nbytes > DUMP_ARRAY_BYTES:
+            keep = max(1, DUMP_ARRAY_BYTES * batch // a.nbytes)
+            a = a[np.sort(rng.choice(batch, keep, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
+    m = res.UC.shape[-1] * res.UC.shape[-2]
+    k = DUMP_ARRAY_BYTES // 4
+    s = rng.integers(0, batch, k)
+    i = (rng.random(k) * res.n[s]).astype(np.int64)  # input pixel of stamp s: below its N (the rows above are padding)
+    j = rng.integers(0, m, k)
+    idx = [torch.from_numpy(v).to(res.Tt.device) for v in (s, i, j)]
+    np.save(os.path.join(outdir, "T_sample.npy"), res.Tt[idx[0], idx[1], idx[2]].cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1311,9 +1350,18 @@ def main():
     ap.add_argument("--rehearse-shared-gpu", action="store_true",
                     help="rehearsal of the multi-rank path on a box with ONE GPU: every rank uses cuda:0 and the ranks "
                          "rendezvous over gloo (not a measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline, per-step times, telemetry, the other legs (the --no-* switches "
+                         "trim them), the CPU baseline, the summary and the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0's batch) as DIR/<name>.npy, float32 / float64, below 64 MB in all")
     args = ap.parse_args()
     if args.cpu_worker is not None:
         return cpu_worker(args.config, args.cpu_worker)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.farm and not args.full:
+        ap.error("--farm is a leg of --full")
 
     import numpy as np
     import torch
@@ -1364,22 +1412,29 @@ def main():
     for _ in range(args.warmup):
         batch.run()
     barrier()
-    ctx.profile_enable(True)
-    ctx.profile_reset()
-    tel = Telemetry(local_rank).start()
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]  # per-step times: events on the stream the steps run on
+    if args.full:
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        tel = Telemetry(local_rank).start()
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]  # per-step times: events on the stream the steps run on
     t0 = time.perf_counter()
-    marks[0].record()
+    if args.full:
+        marks[0].record()
     for k in range(args.steps):
-        batch.run()
-        marks[k + 1].record()
+        res = batch.run()
+        if args.full:
+            marks[k + 1].record()
     barrier()
     elapsed = time.perf_counter() - t0
-    telemetry = tel.stop()
-    step_ms = [marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps)]
-    fams = {f: ctx.profile_get(f) for f in ("solve_gemm", "solve_dinv", "chol_gemm", "chol_diag", "eigen_repair", "build_A", "build_B",
-                                            "finalize", "epilogue")}
-    ctx.profile_enable(False)
+    if args.full:
+        telemetry = tel.stop()
+        step_ms = [marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps)]
+        fams = {f: ctx.profile_get(f) for f in ("solve_gemm", "solve_dinv", "chol_gemm", "chol_diag", "eigen_repair", "build_A", "build_B",
+                                                "finalize", "epilogue")}
+        ctx.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs)
+    del res
     n_keep, info_keep = batch.n.copy(), batch.info.copy()
     ranks_seen, per_rank = 1, [args.batch * args.steps / elapsed]
     if dist is not None:
@@ -1401,7 +1456,7 @@ def main():
             raise SystemExit(f"the all-reduce saw {ranks_seen} ranks, WORLD_SIZE says {world}")
 
     farm_out = None
-    if world > 1 and not args.no_farm:
+    if args.full and world > 1 and not args.no_farm:
         # every rank: the mosaic of BASELINE configs[3] farmed over the ranks (the headline above is N copies of one batch; this is the
         # configuration BASELINE names for N GPUs)
         from pyimcom_amd.blockrun import release_buffers as _rb
@@ -1416,23 +1471,6 @@ def main():
         batch = None
     if rank == 0:
         n_arr = n_keep.astype(np.float64)
-        # Algorithmic flops of the launches being timed.  SURVEY 8d counts 2 N^2 m per stamp for the two triangular
-        # solves, and the solve_fwd / solve_bwd launches carry all of it: the updates below the 128-row diagonal
-        # blocks and the diagonal blocks themselves (priced as the triangular solves they are, m rows_k^2 each,
-        # although the kernel multiplies by the dense inverse).  With IMCOM_SOLVE_UNFUSED=1 the diagonal blocks are
-        # separate solve_dinv launches, timed apart, and only 2 m (N^2 - sum_k rows_k^2) is attributed here.
-        rows_sq = np.array([(np.minimum(128, np.maximum(n - 128 * np.arange((n + 127) // 128), 0)) ** 2).sum() for n in n_keep], dtype=np.float64)
-        fused = fams["solve_dinv"][1] == 0
-        solve_flops_step = float((2.0 * cfg.m * (n_arr**2 - (0.0 if fused else 1.0) * rows_sq)).sum())
-        ms, launches = fams["solve_gemm"]
-        traffic, traffic_src = pmc_traffic(args.batch, cfg.name)
-        achieved = solve_flops_step * args.steps / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-        # a pure fp64 MFMA loop on every SIMD, measured now: what the pipe gives with no operand traffic -- for 50 ms (the clock of a
-        # cold chip) and sustained for more than a second (the clock the chip holds once it is warm and at its power limit)
-        probe = ctx.mfma_probe(50.0)
-        tel_p = Telemetry(local_rank).start()
-        probe_sustained = ctx.mfma_probe(1200.0)
-        probe_tel = tel_p.stop()
         out = {
             "metric": "postage-stamps/sec (and ms/stamp) for N~2k A-solve",
             "value": world * args.batch * args.steps / elapsed,
@@ -1458,6 +1496,28 @@ def main():
                 "m": cfg.m,
                 "parallelism": f"block-farming x{world} (no collective)",
             },
+        }
+        if not args.full:
+            print(compact_line(out), flush=True)
+    if rank == 0 and args.full:
+        # Algorithmic flops of the launches being timed.  SURVEY 8d counts 2 N^2 m per stamp for the two triangular
+        # solves, and the solve_fwd / solve_bwd launches carry all of it: the updates below the 128-row diagonal
+        # blocks and the diagonal blocks themselves (priced as the triangular solves they are, m rows_k^2 each,
+        # although the kernel multiplies by the dense inverse).  With IMCOM_SOLVE_UNFUSED=1 the diagonal blocks are
+        # separate solve_dinv launches, timed apart, and only 2 m (N^2 - sum_k rows_k^2) is attributed here.
+        rows_sq = np.array([(np.minimum(128, np.maximum(n - 128 * np.arange((n + 127) // 128), 0)) ** 2).sum() for n in n_keep], dtype=np.float64)
+        fused = fams["solve_dinv"][1] == 0
+        solve_flops_step = float((2.0 * cfg.m * (n_arr**2 - (0.0 if fused else 1.0) * rows_sq)).sum())
+        ms, launches = fams["solve_gemm"]
+        traffic, traffic_src = pmc_traffic(args.batch, cfg.name)
+        achieved = solve_flops_step * args.steps / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+        # a pure fp64 MFMA loop on every SIMD, measured now: what the pipe gives with no operand traffic -- for 50 ms (the clock of a
+        # cold chip) and sustained for more than a second (the clock the chip holds once it is warm and at its power limit)
+        probe = ctx.mfma_probe(50.0)
+        tel_p = Telemetry(local_rank).start()
+        probe_sustained = ctx.mfma_probe(1200.0)
+        probe_tel = tel_p.stop()
+        out.update({
             "roofline": {
                 "kernel": "solve_fwd_kernel+solve_bwd_kernel (blocked triangular solves: block-row updates" + (" and diagonal blocks" if fused else " below the diagonal blocks") + ", fp64 MFMA 16x16x4)",
                 "bound": "mfma",
@@ -1477,7 +1537,7 @@ def main():
             "stage_ms_per_step": {k: v[0] / args.steps for k, v in fams.items()},
             "step_ms": {"all": step_ms, **(spread(step_ms) or {})},  # HIP events between the steps, on the steps' stream
             "telemetry": telemetry,  # clocks / power / temperatures sampled while the timed steps ran
-        }
+        })
         if cfg.kernel == "Cholesky":
             facts = 1 + (1 if int((info_keep != 0).sum()) else 0)
             out["roofline_chol"] = roofline_chol(n_arr, facts, fams["chol_gemm"][0] / args.steps, fams["chol_diag"][0] / args.steps, fams["chol_gemm"][1] // max(args.steps, 1))

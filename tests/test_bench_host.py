@@ -123,7 +123,9 @@ def test_detail_goes_to_a_file_and_to_prefixed_stderr_lines(tmp_path, monkeypatc
     assert cap.out == "" and all(ln.startswith("[bench detail] ") for ln in cap.err.splitlines())
 
 
-def test_roofline_helpers_and_telemetry_without_a_card():
+def test_roofline_helpers_and_telemetry_without_a_card(monkeypatch):
+    import torch
+
     import bench
 
     n = np.full(256, 2204.0)
@@ -133,6 +135,11 @@ def test_roofline_helpers_and_telemetry_without_a_card():
     c = bench.roofline_chol(n, 1, 19.7, 1.65, 36)
     assert c["bound"] == "mfma" and abs(c["achieved"] - 256 * 2204.0**3 / 3 / 21.35e-3 / 1e12) < 1e-6 * c["achieved"] and 0.5 < c["frac"] < 0.6
     assert bench.spread([3.0, 1.0, 2.0]) == {"min": 1.0, "median": 2.0, "max": 3.0} and bench.spread([]) is None
+
+    def no_card(*args, **kwargs):
+        raise RuntimeError("No HIP GPUs are available")
+
+    monkeypatch.setattr(torch.cuda, "get_device_properties", no_card)  # (a host without a card, also where the suite runs beside one)
     t = bench.Telemetry(0)  # no GPU here: nothing to sample, never an error
     assert t.start() is t and t.stop()["source"] is None
 
@@ -142,3 +149,50 @@ def test_runs_of_a_mask():
 
     assert _runs([False, True, True, False, True]) == [(1, 3), (4, 5)]
     assert _runs([True] * 4) == [(0, 4)] and _runs([False] * 3) == [] and _runs([]) == []
+
+
+def test_a_plain_line_carries_the_contract_keys_only():
+    """A plain run (no --full) measures the headline alone: its line has the contract's keys and no roofline, summary or detail file."""
+    import bench
+
+    out = {k: v for k, v in _full_line().items() if k in ("metric", "value", "unit", "n_gpus", "ranks_seen", "per_rank_value", "steps", "warmup", "ms_per_step",
+                                                          "ms_per_stamp", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")}
+    line = json.loads(bench.compact_line(out))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert key in line, key
+    for key in ("roofline", "cpu_baseline", "summary", "detail", "farm"):
+        assert key not in line, key
+    assert line["value"] == 1662.123456 and line["ms_per_step"] == 154.0123 and line["higher_is_better"] is True and line["dtype"] == "f64"
+
+
+def test_dump_outputs_writes_a_bounded_reproducible_float_sample(tmp_path):
+    """--dump-outputs: the arrays of StampBatch.run()'s result as float32 / float64 .npy files below 64 MB in all, T as a fixed, seeded
+    sample of the entries below each stamp's N (never the padding rows), identical from one call to the next."""
+    import torch
+
+    import bench
+    from pyimcom_amd.stamps import StampBatchResult
+
+    g = np.random.default_rng(1)
+    B, ldn, ldm, n2f, nf, ne = 6, 256, 128, 10, 2, 3
+    n = np.array([200, 256, 130, 7, 180, 256], np.int32)
+    Tt = torch.full((B, ldn, ldm), float("nan"), dtype=torch.float32)  # padding rows: NaN, so a sample that touches them shows
+    for s in range(B):
+        Tt[s, : n[s], : n2f * n2f] = torch.from_numpy(g.standard_normal((n[s], n2f * n2f)).astype(np.float32))
+    f32 = lambda *sh: torch.from_numpy(g.standard_normal(sh).astype(np.float32))  # noqa: E731
+    f64 = lambda *sh: torch.from_numpy(g.standard_normal(sh))  # noqa: E731
+    res = StampBatchResult(Tt, f32(B, n2f, n2f), f32(B, n2f, n2f), f32(B, n2f, n2f), f32(B, nf, n2f, n2f), f64(B, ne), f64(B, n2f, n2f),
+                           f64(B, n2f, n2f), np.zeros(B, np.int32), n)
+    for d in ("a", "b"):
+        bench.dump_outputs(res, str(tmp_path / d))
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(f"{k}.npy" for k in ("UC", "Sigma", "kappa", "outimage", "Tsum_stamp", "Tsum_inpix", "Neff", "info", "T_sample"))
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b, equal_nan=True), name
+        total += (tmp_path / "a" / name).stat().st_size
+    assert total < 64e6
+    assert np.array_equal(np.load(tmp_path / "a" / "UC.npy"), res.UC.numpy()) and np.array_equal(np.load(tmp_path / "a" / "Neff.npy"), res.Neff.numpy())
+    ts = np.load(tmp_path / "a" / "T_sample.npy")
+    assert ts.size == bench.DUMP_ARRAY_BYTES // 4 and np.isfinite(ts).all()

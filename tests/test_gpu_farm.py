@@ -211,7 +211,7 @@ def test_bench_multi_rank_rehearsal(tmp_path):
     port = 29600 + os.getpid() % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "8",
-           "--rehearse-shared-gpu", "--farm-mosaic", "2", "--farm-n1P", "4"]
+           "--rehearse-shared-gpu", "--farm-mosaic", "2", "--farm-n1P", "4", "--full"]
     detail = str(tmp_path / "detail.json")
     out = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT, IMCOM_BENCH_DETAIL=detail), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]

@@ -6,7 +6,7 @@ O=$ROOT/gpurun_out/ab_fused; mkdir -p $O
 cd $ROOT
 for v in fused unfused fused unfused; do
   if [ $v = unfused ]; then export IMCOM_EPILOGUE_UNFUSED=1; else unset IMCOM_EPILOGUE_UNFUSED; fi
-  timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-configs --block-reps 1 > $O/bench_$v.json 2> $O/bench_$v.err || { echo "bench $v failed"; tail -3 $O/bench_$v.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-configs --block-reps 1 > $O/bench_$v.json 2> $O/bench_$v.err || { echo "bench $v failed"; tail -3 $O/bench_$v.err; exit 1; }
   python - <<PY
 import json
 d = json.loads(open("$O/bench_$v.json").read().strip().splitlines()[-1])
