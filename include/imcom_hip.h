@@ -475,6 +475,32 @@ int imcom_psf_overlap_spectra_slots(imcom_ctx *ctx, const double *spec1, int n1,
                                     const int *pairs, int npairs, const double *amp_penalty, const int *win, const int *slots,
                                     int nslots, double *tables);
 
+/* pyimcom.meta.ginterp (reference src/pyimcom/meta/ginterp.py), the deconvolution-shear-reconvolution resampler of
+ * MetaMosaic.shearimage (meta/distortimage.py:393-593).  Rsearch is served while the offsets number NN <= 320 and the corner
+ * system n_g <= 256 (Rsearch 8: 232 / 197); beyond that IMCOM_ERR_UNSUPPORTED.
+ *   imcom_ginterp_geometry   (host only, ginterp.py:62-83, 157-159) the NN grid offsets within the search radius in the reference's
+ *                            order (row-major meshgrid, filtered) and the corner subsets: posx, posy [NN], corners [4][n_g] = indices
+ *                            into posx.  With posx = posy = corners = NULL only NN and n_g; otherwise cap >= NN.
+ *   imcom_ginterp_matrix     InterpMatrix (ginterp.py:19-186): T [npts][NN], U and Sigma [ceil(npts / stest)] for the fractional
+ *                            positions x_out, y_out [npts].  Cov (HOST) [3] = Cxx, Cxy, Cyy.  Ad of corner 0 is factored once on the
+ *                            device (the library's blocked Cholesky), every point is solved by blocked substitution.
+ *   imcom_ginterp_resample   MultiInterp (ginterp.py:189-340) fused: output pixel i = y nx + x of an [ny][nx] grid maps to
+ *                            (x_in, y_in) = transform (HOST, [2][2] row-major) (x, y) + origin (HOST [2]); in [nlayer][ny_in][nx_in]
+ *                            float32 (in_f64 = 0) or float64 (1), in_mask [ny_in][nx_in] (1 = masked) -> out [nlayer][ny][nx] in the
+ *                            input's type, out_mask [ny][nx], UmaxSmax [2] over the points whose index within their `blocksize` chunk
+ *                            is a multiple of stest.  T exists only per tile of 16 points.  2 bb >= min(nx_in, ny_in): all zeros,
+ *                            all masked, Umax = Smax = 0 (the reference's early exit).  A position that is not finite or lies
+ *                            beyond the int32 range is masked, as the reference's int32 cast masks it; nothing outside `in` is read.
+ *                            Rsearch that is not finite or not positive: IMCOM_ERR_ARG, checked before the geometry is built.
+ *   in/out arrays follow `memspace`. */
+int imcom_ginterp_geometry(double Rsearch, int cap, int *NN, int *ng, int *posx, int *posy, int *corners);
+int imcom_ginterp_matrix(imcom_ctx *ctx, double Rsearch, double samp, int npts, const double *x_out, const double *y_out,
+                         const double *Cov, double epsilon, int stest, double *T, double *U, double *Sigma, int memspace);
+int imcom_ginterp_resample(imcom_ctx *ctx, int nlayer, int ny_in, int nx_in, const void *in, int in_f64, const unsigned char *in_mask,
+                           int ny, int nx, const double *origin, const double *transform, double Rsearch, double samp,
+                           const double *Cov, double epsilon, int stest, long blocksize, void *out, unsigned char *out_mask,
+                           double *UmaxSmax, int memspace);
+
 #ifdef __cplusplus
 }
 #endif

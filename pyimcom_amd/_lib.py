@@ -115,6 +115,9 @@ SIGNATURES = {
     "imcom_block_combine": [_vp, _i, _i, _i, _l, _vp, _i, _vp, _i, _i, _i, _i],
     "imcom_compress_map_f32": [_vp, _vp, _l, _i, _i, _vp],
     "imcom_trapezoid_recover_f32": [_vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i],
+    "imcom_ginterp_geometry": [_d, _i, _ip, _ip, _vp, _vp, _vp],
+    "imcom_ginterp_matrix": [_vp, _d, _d, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _vp, _i],
+    "imcom_ginterp_resample": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _d, _d, _vp, _d, _i, _l, _vp, _vp, _vp, _i],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():
