@@ -47,8 +47,6 @@ typedef struct imcom_ctx imcom_ctx;
 
 /* ------------------------------------------------------------------ library / context --------- */
 int imcom_version(void);
-/* 1 when the library was built with the developer extras (make DEV=1: experimental kernels and cross-checks), else 0. */
-int imcom_dev_build(void);
 const char *imcom_last_error(void);
 int imcom_device_count(int *count);
 /* device: HIP device ordinal.  Creates the context's own stream; block->GPU farming uses one
@@ -87,8 +85,9 @@ int imcom_ctx_profile_get(imcom_ctx *ctx, const char *family, double *ms, long *
  * matrix load, to set beside the guide's 78.6 TFLOP/s. */
 int imcom_ctx_mfma_probe(imcom_ctx *ctx, double millis, double *tflops);
 /* Diagnostic: the k loop of the tile engine as a plain batched product C[M][N] = A[M][K] (row-major) B[K][N] on pseudo-random
- * operands in workspace, `reps` launches; variant 0: the production 128 x 128 tiles (two 8-wave workgroups per CU), variant 1: 256 x 128
- * tiles by one 16-wave workgroup per CU (half the B traffic per flop).  M % 256 = N % 128 = K % 16 = 0. */
+ * operands in workspace, `reps` launches; variant 0: the production 128 x 128 tiles (two 8-wave workgroups per CU); variants 2, 3, 4:
+ * the same tiles on the engine's other operand layouts (both row-major; both k-major; A k-major, B row-major).  Any other variant is
+ * IMCOM_ERR_ARG.  M % 256 = N % 128 = K % 16 = 0. */
 int imcom_ctx_gemm_probe(imcom_ctx *ctx, int variant, int M, int N, int K, int batch, int reps, double *tflops);
 
 /* ------------------------------------------------------------------ native-routine seam --------

@@ -9,7 +9,7 @@ import os
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# IMCOM_HIP_LIB: another build of the same library (the developer build with its cross-check kernels, make DEV=1)
+# IMCOM_HIP_LIB: load the library from this path instead of pyimcom_amd/lib/libimcom_hip.so (another build of the same sources)
 LIB_PATH = os.environ.get("IMCOM_HIP_LIB") or os.path.join(_HERE, "lib", "libimcom_hip.so")
 
 MEM_HOST = 0
@@ -167,8 +167,6 @@ class _Lib:
 lib = _Lib(_cdll)
 _cdll.imcom_version.argtypes = []
 _cdll.imcom_version.restype = C.c_int
-_cdll.imcom_dev_build.argtypes = []
-_cdll.imcom_dev_build.restype = C.c_int
 _cdll.imcom_psf_spectra_size.argtypes = [_i, _i]
 _cdll.imcom_psf_spectra_size.restype = C.c_long
 _cdll.imcom_smooth_pad_width.argtypes = [_d, _d]
@@ -176,7 +174,7 @@ _cdll.imcom_smooth_pad_width.restype = C.c_int
 _cdll.imcom_last_error.argtypes = []
 _cdll.imcom_last_error.restype = C.c_char_p
 
-EXPORTED = sorted(list(SIGNATURES) + ["imcom_version", "imcom_dev_build", "imcom_last_error", "imcom_psf_spectra_size", "imcom_smooth_pad_width"])
+EXPORTED = sorted(list(SIGNATURES) + ["imcom_version", "imcom_last_error", "imcom_psf_spectra_size", "imcom_smooth_pad_width"])
 
 
 def source_sha16():
@@ -332,7 +330,7 @@ class Context:
         return tf.value
 
     def gemm_probe(self, variant, M=2304, N=2304, K=2304, batch=8, reps=5):
-        """TFLOP/s of the tile engine's k loop as a plain batched product (imcom_ctx_gemm_probe): variant 0 = 128 x 128 tiles, 1 = 256 x 128."""
+        """TFLOP/s of the tile engine's k loop as a plain batched product (imcom_ctx_gemm_probe): variant 0 = 128 x 128 tiles; 2, 3, 4 = the other operand layouts."""
         tf = _d(0.0)
         check(lib.imcom_ctx_gemm_probe(self.handle, int(variant), int(M), int(N), int(K), int(batch), int(reps), C.byref(tf)))
         return tf.value

@@ -116,8 +116,8 @@ int pin_reserve(imcom_ctx *ctx, size_t bytes)
 constexpr int REPAIR_GROUP = 32;  // failed stamps whose smallest eigenvalues are computed in one batch of the eigensolver (repair path, small matrices / fallback)
 constexpr int CHOL_MAXNV = 8;  // kappa nodes of the multi-kappa Cholesky kernel (launch_multi's MAXNV; 3 nv diagonal increments <= MAX_INC)
 static_assert(3 * CHOL_MAXNV <= MAX_INC_HOST, "diagonal increments of the repair sequence");
-constexpr int LMIN_P = NB;        // vectors of the subspace iteration for the smallest eigenvalue (one tile column of the solves)
-constexpr int LMIN_MIN_N = 1024;  // smaller matrices go through the eigensolver itself (cheap there; the block needs n >> LMIN_P)
+constexpr int LMIN_P = NB;        // vectors the workspace plan of the smallest-eigenvalue iteration is sized for (see lmin_ws_bytes)
+constexpr int LMIN_MIN_N = 1024;  // smaller matrices go through the eigensolver itself (cheap there; the block needs n >> LMIN_SKINNY_P)
 
 // Split-K for small batches: with fewer than ~256 tiles per launch (the kernel-class seam hands over one stamp: 18) the K
 // loop of every tile is dealt to up to 8 workgroups, so that a launch has ~512 of them (gemm_f64.hip).
@@ -143,11 +143,12 @@ static int nodes_per_pass(int batch, int mp, int nv)
 
 static bool lmin_subspace_enabled()
 {
-    static const bool off = getenv("IMCOM_LMIN") && strcmp(getenv("IMCOM_LMIN"), "eigh") == 0;  // (cross-check: the eigensolver for every repair)
-    return !off;
+    return !env_is("IMCOM_LMIN", "eigh");  // (cross-check: the eigensolver for every repair)
 }
 
-// workspace of lambda_min_subspace on top of the factorisation's own L / Dinv / dshift
+// workspace of lambda_min_subspace on top of the factorisation's own L / Dinv / dshift.  The plan is still the one of the 128-vector
+// form the iteration had before its blocks of 16 vectors: it fixes the pass sizes of the callers that plan with it (and with them the
+// timing), so it stays as it is until a change of its own, measured, shrinks it to what the 16-vector form takes.
 static size_t lmin_ws_bytes(int batch, int Np)
 {
     if (!lmin_subspace_enabled() || Np < LMIN_MIN_N) return 0;
@@ -184,7 +185,7 @@ static size_t chol_core_bytes(int batch, int Np, int m, int mp, int nv)
     // repair path (lakernel.py:262-279): the smallest eigenvalue of every failed stamp's A -- the subspace iteration on the stamps in
     // place (lambda_min_subspace), the eigensolver on up to REPAIR_GROUP gathered copies for small matrices and as its fallback
     const int rg = std::min(batch, REPAIR_GROUP);
-    p.add(std::max(eigh_ws_bytes(rg, Np, false) + (size_t)rg * Np * Np * 8 * (eigh_uses_jacobi() ? 2 : 1) + (size_t)rg * Np * 8 + 4096, lmin_ws_bytes(batch, Np)));
+    p.add(std::max(eigh_ws_bytes(rg, Np, false) + (size_t)rg * Np * Np * 8 + (size_t)rg * Np * 8 + 4096, lmin_ws_bytes(batch, Np)));
     p.add(splitk_bytes((int)eb, Np, mp));
     if (nv == 1) p.add((size_t)batch * 2 * nb * mp * 8 * 2);  // per-block-row column sums of Y^2 and X^2
     return p.total + 4096;
@@ -199,15 +200,13 @@ static int lambda_min_group(imcom_ctx *ctx, const double *A, const int *n_host, 
     const size_t mat = (size_t)Np * Np;
     double *G = (double *)ws_take(ctx, (size_t)count * mat * 8);
     double *lam = (double *)ws_take(ctx, (size_t)count * Np * 8);
-    double *Q = eigh_uses_jacobi() ? (double *)ws_take(ctx, (size_t)count * mat * 8) : nullptr;  // eigenvalues only otherwise
-    if (!G || !lam || (eigh_uses_jacobi() && !Q)) { set_error("internal: workspace (repair)"); return IMCOM_ERR_NOMEM; }
+    if (!G || !lam) { set_error("internal: workspace (repair)"); return IMCOM_ERR_NOMEM; }
     std::vector<int> ng(count);
     for (int q = 0; q < count; q++) {
         ng[q] = n_host[idx[q]];
         IMCOM_HIP_CHECK(hipMemcpyAsync(G + (size_t)q * mat, A + (size_t)idx[q] * mat, mat * 8, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    if (Q) IMCOM_HIP_CHECK(hipMemsetAsync(Q, 0, (size_t)count * mat * 8, ctx->stream));
-    int rc = eigh_device(ctx, count, ng.data(), Np, G, Np, (long)mat, lam, Np, Q, Np, (long)mat, nullptr);
+    int rc = eigh_device(ctx, count, ng.data(), Np, G, Np, (long)mat, lam, Np, nullptr, Np, (long)mat, nullptr);  // eigenvalues only
     if (rc == IMCOM_OK) {
         hipError_t e = hipMemcpy2DAsync(w0, 8, lam, (size_t)Np * 8, 8, count, hipMemcpyDeviceToHost, ctx->stream);  // lam[q][0]
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -223,21 +222,20 @@ static int lambda_min_group(imcom_ctx *ctx, const double *A, const int *n_host, 
 // memory speed (95 ms per stamp), the kernels this library is fast at are the blocked Cholesky and the triangular solves.  So:
 //   1. a shift sigma with A + sigma I positive definite (trial factorisations, sigma x 8 per failure; the first trial is 4 x the
 //      increment the failed factorisation had);
-//   2. subspace iteration with the inverse, X <- orth((A + sigma I)^-1 X), on a block of 128 vectors = one tile column of the solve
-//      kernels (CholQR twice per step: Gram matrix on the tile engine, its Cholesky factor and the factor's inverse from the diagonal-block
-//      kernel), then Rayleigh-Ritz with A ITSELF: theta = lambda_min(X^T A X) >= lambda_min(A), accurate to eps |A| once the block has
+//   2. subspace iteration with the inverse, X <- orth((A + sigma I)^-1 X), on a block of 16 vectors (lmin_skinny.hip: CholQR twice
+//      per step), then Rayleigh-Ritz with A ITSELF: theta = lambda_min(X^T A X) >= lambda_min(A), accurate to eps |A| once the block has
 //      converged -- the accuracy class of LAPACK's own w[0] -- with the residuals of the two lowest Ritz pairs as the error bound;
 //   3. re-factor at sigma' = |theta| (1 + eta) just above the estimate (eta from that bound; a sigma' that is not above
 //      |lambda_min| makes the factorisation fail: eta x 8), where the block converges by 1e-3 and more per step; stop when the bound is
 //      below 1e-11 |theta| (or two successive Rayleigh-Ritz values agree to that).
-// On a paper4 stamp: 2 factorisations, 6 + 3 steps, 2 Rayleigh-Ritz steps = 5.4 ms, theta within 2e-13 of LAPACK's w[0].
 // Everything runs on the stamps in place (L, Dinv, dshift of the caller's factorisation; stamps that are not wanted have no blocks in
 // these launches).  factor(shift, mask, fail): L L^T = A + shift[s] I for the stamps of mask, fail[s] != 0 where that is not positive
-// definite; solve(mask, X, Y): Y = (L L^T)^-1 X on LMIN_P columns.  ok[s] = 0: no answer (the caller takes the eigensolver).
+// definite; solve(mask, X, Y, part): Y = (L L^T)^-1 X on LMIN_SKINNY_P columns (part: scratch of the few-stamp form).  ok[s] = 0: no
+// answer (the caller takes the eigensolver).
 static int lambda_min_subspace(imcom_ctx *ctx, int batch, const int *n_host, const int *n_dev, int Np, const double *A, const std::vector<int> &idx,
                                const std::vector<double> &inc_failed, double hint, const std::vector<char> &may_decide, std::vector<char> &decided,
                                const std::function<int(const std::vector<double> &, const std::vector<char> &, std::vector<int> &)> &factor,
-                               const std::function<int(const std::vector<char> &, const double *, double *, double *, double *, int, int)> &solve,
+                               const std::function<int(const std::vector<char> &, const double *, double *, double *)> &solve,
                                std::vector<double> &w0, std::vector<char> &ok)
 {
     const size_t mark = ctx->ws_used;
@@ -247,38 +245,29 @@ static int lambda_min_subspace(imcom_ctx *ctx, int batch, const int *n_host, con
     // workgroup per stamp; fewer stamps (the kernel-class seam hands over one or four; a block's short last pass) two short launches
     // per block row with the sums dealt to many workgroups (on a pass of 168 stamps the two are within 2 % of each other: 1960
     // launches per pass against 10).
-    // IMCOM_LMIN_SKINNY=0: the 128-vector form of rounds 5 and 6a (kept as the cross-check: tests/test_gpu_stamps.py runs both).
-    const char *sk_env = getenv("IMCOM_LMIN_SKINNY");  // (read per call)
-    const bool skinny = sk_env ? atoi(sk_env) != 0 : true;
-    const int P = skinny ? LMIN_SKINNY_P : LMIN_P;
-    const size_t blk = (size_t)batch * Np * P * 8, sq = (size_t)batch * P * P * 8;
+    constexpr int P = LMIN_SKINNY_P;
+    const size_t blk = (size_t)batch * Np * P * 8;
     double *X = (double *)ws_take(ctx, blk), *Y = (double *)ws_take(ctx, blk), *Z = (double *)ws_take(ctx, blk);
-    double *G = (double *)ws_take(ctx, sq), *Gi = (double *)ws_take(ctx, sq), *H = (double *)ws_take(ctx, sq), *Qh = (double *)ws_take(ctx, sq);
     double *lam = (double *)ws_take(ctx, (size_t)batch * P * 8);
     double *rpart = (double *)ws_take(ctx, (size_t)batch * LMIN_RESID_GROUPS * 2 * 8);
     double *part = (double *)ws_take(ctx, (size_t)batch * 8 * NB * NB * 8);
     double *dmax_d = (double *)ws_take(ctx, (size_t)batch * 8);
-    int *want_d = (int *)ws_take(ctx, (size_t)batch * 4), *ones_d = (int *)ws_take(ctx, (size_t)batch * 4), *gfail_d = (int *)ws_take(ctx, (size_t)batch * 4);
-    int *nbrun_d = (int *)ws_take(ctx, (size_t)batch * 4);  // 128-blocks of the stamps a round runs (0: not in it), for the 16-vector kernels
-    if (!X || !Y || !Z || !G || !Gi || !H || !Qh || !lam || !rpart || !part || !dmax_d || !want_d || !ones_d || !gfail_d || !nbrun_d) { set_error("internal: workspace (smallest eigenvalue)"); return IMCOM_ERR_NOMEM; }
-    const size_t mark_eig = ctx->ws_used;
+    int *want_d = (int *)ws_take(ctx, (size_t)batch * 4), *gfail_d = (int *)ws_take(ctx, (size_t)batch * 4);
+    int *nbrun_d = (int *)ws_take(ctx, (size_t)batch * 4);  // 128-blocks of the stamps a round runs (0: not in it)
+    if (!X || !Y || !Z || !lam || !rpart || !part || !dmax_d || !want_d || !gfail_d || !nbrun_d) { set_error("internal: workspace (smallest eigenvalue)"); return IMCOM_ERR_NOMEM; }
     hipStream_t st = ctx->stream;
     std::vector<char> want(batch, 0);
-    std::vector<int> want_i(batch, 0), ones(batch, 1), nP(batch, P);
+    std::vector<int> want_i(batch, 0);
     for (int s : idx) { want[s] = 1; want_i[s] = 1; }
     IMCOM_TRY(upload(ctx, want_d, want_i.data(), (size_t)batch));
-    IMCOM_TRY(upload(ctx, ones_d, ones.data(), (size_t)batch));
     IMCOM_HIP_CHECK(hipMemsetAsync(gfail_d, 0, (size_t)batch * 4, st));
     IMCOM_HIP_CHECK(hipMemsetAsync(Y, 0, blk, st));
     IMCOM_HIP_CHECK(hipMemsetAsync(Z, 0, blk, st));
-    IMCOM_HIP_CHECK(hipMemsetAsync(G, 0, sq, st));  // (stamps that are not wanted keep zero blocks: gram_guard_kernel puts ones on their diagonals)
-    IMCOM_HIP_CHECK(hipMemsetAsync(H, 0, sq, st));
-    IMCOM_HIP_CHECK(hipMemsetAsync(Qh, 0, sq, st));
     IMCOM_TRY(launch_diag_max(ctx, A, Np, n_dev, dmax_d, batch));
     std::vector<double> dmax(batch, 0.0);
     IMCOM_HIP_CHECK(hipMemcpyAsync(dmax.data(), dmax_d, (size_t)batch * 8, hipMemcpyDeviceToHost, st));
     IMCOM_HIP_CHECK(hipStreamSynchronize(st));
-    static const bool dbg = getenv("IMCOM_LMIN_DEBUG") != nullptr;
+    const bool dbg = env_is("IMCOM_LMIN_DEBUG");
     int nfac = 0, nfac_failed = 0, rounds_run = 0;
     // 1. a positive definite shift
     std::vector<double> sigma(batch, 0.0);
@@ -289,8 +278,8 @@ static int lambda_min_subspace(imcom_ctx *ctx, int batch, const int *n_host, con
     // each other): the first shift is that estimate plus a margin instead of four times the failed increment, i.e. already as close as the
     // SECOND shift of a stamp that starts without one, and the iteration needs one factorisation instead of two.  An estimate that is too
     // small for a stamp costs that stamp one failed factorisation (then the shift it would have started with).
-    static const bool hint_off = getenv("IMCOM_LMIN_HINT") && strcmp(getenv("IMCOM_LMIN_HINT"), "0") == 0;
-    static const double hint_margin = getenv("IMCOM_LMIN_MARGIN") ? std::max(0.0, atof(getenv("IMCOM_LMIN_MARGIN"))) : 0.05;
+    const bool hint_off = env_is("IMCOM_LMIN_HINT", "0");
+    constexpr double hint_margin = 0.05;
     std::vector<char> hinted(batch, 0);
     std::vector<double> base(batch, 0.0);
     bool any_hinted = false;
@@ -318,23 +307,9 @@ static int lambda_min_subspace(imcom_ctx *ctx, int batch, const int *n_host, con
     }
     // 2. / 3. subspace iteration, Rayleigh-Ritz with A, closer shifts
     IMCOM_TRY(launch_lmin_init(ctx, X, Np, P, n_dev, want_d, batch));
-    const long sX = (long)Np * P, sG = (long)P * P;
-    // a product per stamp of the batch, or -- when few stamps are wanted -- per wanted stamp (the others' operands are zero)
-    const bool few = (long)idx.size() * 4 <= (long)batch;
-    auto gemm = [&](bool akm, bool bkm, int M, int N, int K, const double *Ao, long lda, long sA, const double *Bo, long ldb, long sB, double *Co, long ldc, long sC) -> int {
-        if (!few) return launch_gemm(ctx, akm, bkm, M, N, K, batch, Ao, lda, sA, Bo, ldb, sB, Co, ldc, sC, 1.0, 0.0);
-        for (int s : idx) IMCOM_TRY(launch_gemm(ctx, akm, bkm, M, N, K, 1, Ao + s * sA, lda, sA, Bo + s * sB, ldb, sB, Co + s * sC, ldc, sC, 1.0, 0.0));
-        return IMCOM_OK;
-    };
     auto orth = [&]() -> int {  // X <- orth(Y): CholQR twice (X = Y R^-1 with R^T R = Y^T Y; the second pass takes the loss of the first back)
-        for (int pass = 0; pass < 2; pass++) {
-            double *src = pass == 0 ? Y : X, *dst = pass == 0 ? X : Y;
-            if (skinny) { IMCOM_TRY(launch_skinny_orth(ctx, src, dst, Np, nbrun_d, gfail_d, batch)); continue; }
-            IMCOM_TRY(gemm(true, true, P, P, Np, src, P, sX, src, P, sX, G, P, sG));
-            IMCOM_TRY(launch_gram_guard(ctx, G, P, want_d, batch));
-            IMCOM_TRY(launch_chol_diag(ctx, G, Gi, P, 0, batch, ones_d, gfail_d));
-            IMCOM_TRY(gemm(false, false, Np, P, P, src, P, sX, Gi, P, sG, dst, P, sX));  // dst[i][c] = sum_j src[i][j] Linv[c][j]
-        }
+        IMCOM_TRY(launch_skinny_orth(ctx, Y, X, Np, nbrun_d, gfail_d, batch));
+        IMCOM_TRY(launch_skinny_orth(ctx, X, Y, Np, nbrun_d, gfail_d, batch));
         std::swap(X, Y);  // the orthonormal block is in the buffer pass 1 wrote
         return IMCOM_OK;
     };
@@ -342,7 +317,7 @@ static int lambda_min_subspace(imcom_ctx *ctx, int batch, const int *n_host, con
     std::vector<double> est(batch, 0.0), est_simple(batch, 0.0), dbg_th(batch, 0.0), dbg_r1(batch, 0.0), dbg_r2(batch, 0.0), dbg_g2(batch, 0.0), dbg_gP(batch, 0.0), lamP(batch, 0.0);
     std::vector<char> conv(batch, 0);
     std::vector<int> gfail(batch, 0);
-    // Per stamp two phases.  Coarse, at the first shift: six steps, then a Rayleigh-Ritz step that also yields the residuals r1, r2 of the
+    // Per stamp two phases.  Coarse, at the first shift: nine steps (ten at a hinted one), then a Rayleigh-Ritz step that also yields the residuals r1, r2 of the
     // two lowest Ritz pairs (theta1, y1), (theta2, y2) -- there is an eigenvalue within |r1| of theta1, and once theta1 is separated from
     // the rest, (theta2 - |r2|) - theta1 = gap > 4 |r1|, theta1 - lambda_min <= |r1|^2 / gap (Kato-Temple).  With that bound below 15 % the
     // stamp gets ONE factorisation at |theta1| (1 + eta), eta = 1.5 x the bound (a shift that is not above |lambda_min| makes the
@@ -351,16 +326,12 @@ static int lambda_min_subspace(imcom_ctx *ctx, int batch, const int *n_host, con
     // (configs/paper4: six coarse steps leave 2e-3, three fine ones 1e-13).  The change between two successive values of theta1 -- the
     // criterion of the first version, which cost a round of three steps and a Rayleigh-Ritz step in each phase only to confirm -- still
     // ends either phase when the residuals cannot (theta1 inside a cluster closer than its residual).
-    static const int coarse_steps_env = getenv("IMCOM_LMIN_COARSE") ? std::max(1, atoi(getenv("IMCOM_LMIN_COARSE"))) : 0;
-    const int coarse_steps = coarse_steps_env ? coarse_steps_env : (LMIN_SKINNY_P == P ? 9 : 6);  // (16 vectors at a blind shift: six steps leave 25-40 %, nine a few per cent)
-    static const int lmin_parts = getenv("IMCOM_LMIN_PARTS") ? std::min(8, std::max(1, atoi(getenv("IMCOM_LMIN_PARTS")))) : 0;  // (A/B: split-K parts of the 128-column solves)
-    static const int hinted_steps_env = getenv("IMCOM_LMIN_HINTED") ? std::max(1, atoi(getenv("IMCOM_LMIN_HINTED"))) : 0;  // (34 x (7.6e-3)^7: see the hint above)
-    const int hinted_steps = hinted_steps_env ? hinted_steps_env : (skinny ? 10 : 7);
-    // how far the spectrum the block has NOT captured lies above lambda_min, in units of |lambda_min| (production stamps: lambda_129 is 0.85,
-    // lambda_17 0.4 of the way to zero): the step counts below are planned with it
-    const double bulk = skinny ? 0.4 : 1.0;
-    static const int round_steps = getenv("IMCOM_LMIN_FINE") ? std::max(1, atoi(getenv("IMCOM_LMIN_FINE"))) : 3;
-    static const bool by_change = getenv("IMCOM_LMIN_BOUND") && strcmp(getenv("IMCOM_LMIN_BOUND"), "change") == 0;  // (A/B: the first version's criteria alone)
+    constexpr int coarse_steps = 9;   // (16 vectors at a blind shift: six steps leave 25-40 %, nine a few per cent)
+    constexpr int hinted_steps = 10;  // (at a hinted shift, see above)
+    constexpr int round_steps = 3;    // steps of a fine round
+    // how far the spectrum the block has NOT captured lies above lambda_min, in units of |lambda_min| (production stamps: lambda_17 is 0.4
+    // of the way to zero): the step counts below are planned with it
+    constexpr double bulk = 0.4;
     const int max_rounds = 14;
     std::vector<char> fine(batch, 0);
     std::vector<int> steps_wanted(batch, 0);
@@ -374,27 +345,16 @@ static int lambda_min_subspace(imcom_ctx *ctx, int batch, const int *n_host, con
         for (int s : idx) if (run[s]) iters = std::max(iters, steps_wanted[s]);  // (a stamp's first round at its closer shift: see below)
         std::fill(steps_wanted.begin(), steps_wanted.end(), 0);
         int nbrun_max = 0;
-        if (skinny) {
-            std::vector<int> nbr(batch, 0);
-            for (int s : idx) if (run[s]) { nbr[s] = (n_host[s] + NB - 1) / NB; nbrun_max = std::max(nbrun_max, nbr[s]); }
-            IMCOM_TRY(upload(ctx, nbrun_d, nbr.data(), (size_t)batch));
-        }
+        std::vector<int> nbr(batch, 0);
+        for (int s : idx) if (run[s]) { nbr[s] = (n_host[s] + NB - 1) / NB; nbrun_max = std::max(nbrun_max, nbr[s]); }
+        IMCOM_TRY(upload(ctx, nbrun_d, nbr.data(), (size_t)batch));
         for (int it = 0; it < iters; it++) {
-            IMCOM_TRY(solve(run, X, Y, Z, part, lmin_parts > 0 ? lmin_parts : splitk_parts(batch, 1), P));  // (Z: scratch here, the Rayleigh-Ritz step below fills it anew)
+            IMCOM_TRY(solve(run, X, Y, part));
             IMCOM_TRY(orth());
         }
-        // Z = A X, H = X^T Z, its eigenvalues and eigenvectors, the residuals of the two lowest pairs
-        if (skinny) {
-            IMCOM_TRY(launch_skinny_ax(ctx, A, X, Z, Np, nbrun_d, nbrun_max, batch));
-            IMCOM_TRY(launch_skinny_rr(ctx, X, Z, Np, nbrun_d, lam, rpart, LMIN_RESID_GROUPS, batch));
-        } else {
-            IMCOM_TRY(gemm(false, true, Np, P, Np, A, Np, (long)Np * Np, X, P, sX, Z, P, sX));
-            IMCOM_TRY(gemm(true, true, P, P, Np, X, P, sX, Z, P, sX, H, P, sG));
-            ctx->ws_used = mark_eig;
-            IMCOM_TRY(eigh_device(ctx, batch, nP.data(), P, H, P, sG, lam, P, Qh, P, sG, nullptr));
-            ctx->ws_used = mark_eig;
-            IMCOM_TRY(launch_ritz_residual(ctx, X, Z, Qh, lam, Np, P, n_dev, want_d, rpart, batch));
-        }
+        // Z = A X, H = X^T Z, its eigenvalues, the residuals of the two lowest pairs
+        IMCOM_TRY(launch_skinny_ax(ctx, A, X, Z, Np, nbrun_d, nbrun_max, batch));
+        IMCOM_TRY(launch_skinny_rr(ctx, X, Z, Np, nbrun_d, lam, rpart, LMIN_RESID_GROUPS, batch));
         IMCOM_HIP_CHECK(hipMemcpy2DAsync(lam01.data(), 16, lam, (size_t)P * 8, 16, batch, hipMemcpyDeviceToHost, st));
         IMCOM_HIP_CHECK(hipMemcpyAsync(rp.data(), rpart, rp.size() * 8, hipMemcpyDeviceToHost, st));
         IMCOM_HIP_CHECK(hipMemcpy2DAsync(lamP.data(), 8, lam + P - 1, (size_t)P * 8, 8, batch, hipMemcpyDeviceToHost, st));
@@ -421,7 +381,7 @@ static int lambda_min_subspace(imcom_ctx *ctx, int batch, const int *n_host, con
             prev[s] = theta[s];
             theta[s] = th1;
             const double rel = round == 0 ? 1.0 : fabs(theta[s] - prev[s]) / mag;
-            const double bound = by_change ? 1.0 : est[s] / mag;
+            const double bound = est[s] / mag;
             // A stamp whose failure is the CALLER's expectation, not an observed one (may_decide): all that is wanted first is whether
             // A + inc I is positive definite after all, and theta1 - |r1| decides that long before theta1 has converged (NOT a rigorous bound:
             // the residual only says that SOME eigenvalue lies within |r1| of theta1; lambda_min can lie below if the block has not captured
@@ -459,7 +419,7 @@ static int lambda_min_subspace(imcom_ctx *ctx, int batch, const int *n_host, con
                     refac[s] = 1; any_refac = true;
                     // steps of the first fine round: with e = bound / 3 the error of theta1 and the bulk of the spectrum |theta1| away, the shift
                     // leaves lambda_min + sigma' = 3.5 e |theta1| and a step multiplies the error by (3.5 e)^2: e (12 e^2)^j <= 3e-12
-                    steps_wanted[s] = (bound <= 1.5e-2 ? 3 : bound <= 4e-2 ? 4 : bound <= 7e-2 ? 5 : 6) + (skinny ? 1 : 0);
+                    steps_wanted[s] = (bound <= 1.5e-2 ? 3 : bound <= 4e-2 ? 4 : bound <= 7e-2 ? 5 : 6) + 1;
                 }
             } else if (rel > 0.05 * lastrel[s] && 16.0 * rel < 0.25 * eta[s] && theta[s] < 0.0) {
                 eta[s] = std::max(16.0 * rel, 1e-9);
@@ -514,11 +474,6 @@ static int lambda_min_subspace(imcom_ctx *ctx, int batch, const int *n_host, con
         for (int s : idx) if (ok[s]) { tmin = std::min(tmin, w0[s]); tmax = std::max(tmax, w0[s]); }
         int nok = 0;
         for (int s : idx) nok += ok[s] ? 1 : 0;
-        if (getenv("IMCOM_LMIN_DUMP")) {  // every stamp's value, in batch order
-            fprintf(stderr, "[lmin-w0]");
-            for (int s : idx) fprintf(stderr, " %.9e", ok[s] ? w0[s] : 0.0);
-            fprintf(stderr, "\n");
-        }
         fprintf(stderr, "[lmin] %zu stamps: %d factorisations (%d of them failed for some stamp), %d rounds; lambda_min %.6e .. %.6e; %d without an answer (the eigensolver's)\n", idx.size(), nfac,
                 nfac_failed, rounds_run, tmin, tmax, (int)idx.size() - nok);
     }
@@ -539,8 +494,7 @@ struct CoaddArgs {
 
 static bool coadd_fusable(int nv, int fade)
 {
-    static const bool off = getenv("IMCOM_SOLVE_UNFUSED") != nullptr || getenv("IMCOM_EPILOGUE_UNFUSED") != nullptr;
-    return !off && nv == 1 && fade == 0;  // one kappa node: T is final in the backward launches; no taper to apply to it first
+    return !env_is("IMCOM_SOLVE_UNFUSED") && nv == 1 && fade == 0;  // one kappa node: T is final in the backward launches; no taper to apply to it first
 }
 
 static size_t coadd_fuse_bytes(int batch, int Np, int m, int mp, int nv, const CoaddArgs *co)
@@ -592,7 +546,7 @@ static int chol_core(imcom_ctx *ctx, int batch, const int *n_host, int Np, int m
     const int parts_solve = partial ? splitk_parts(eb, mp / NB) : 1;
     // single kappa with the diagonal blocks fused into the solve launches: the launches leave T (float32) and the column sums
     // the maps need behind, and the pass of finalize_single_kernel over X and -B/2 (27 GB per 256 cfg-2 stamps) is not needed
-    static const bool unfused_solve = getenv("IMCOM_SOLVE_UNFUSED") != nullptr;
+    const bool unfused_solve = env_is("IMCOM_SOLVE_UNFUSED");
     double *colsums = (nv == 1 && !unfused_solve) ? (double *)ws_take(ctx, (size_t)batch * 2 * nbmax_all * mp * 8 * 2) : nullptr;
     double *Dpart = colsums, *Npart = colsums ? colsums + (size_t)batch * 2 * nbmax_all * mp : nullptr;
     // the coaddition of the same call: its sums ride in the backward launches when T is final there (else the stand-alone epilogue)
@@ -662,58 +616,18 @@ static int chol_core(imcom_ctx *ctx, int batch, const int *n_host, int Np, int m
         IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         return IMCOM_OK;
     };
-    // Yv = (L L^T)^-1 Xv on LMIN_P columns for the stamps of `mask`; Wv: scratch of the same size (may be null).
-    // Two forms.  Many stamps: the left-looking block rows of the solve kernels (a launch per block row, one 128-column tile per stamp,
-    // the K loop dealt to up to 8 workgroups).  FEW stamps (the kernel-class seam hands over one, a 2 x 2 group four): that form keeps 9
-    // workgroups per stamp busy and a 128-column solve of a production stamp (N = 6.2k) takes 10.8 ms -- 97 of the 135 ms of a seam call
-    // (profiles/r06_seam_paper4_kernel_stats.csv).  There the solve runs RIGHT-looking on the generic product kernel: block k is finished by
-    // its inverted diagonal block, then ALL block rows below it are updated at once, Y_i -= L_ik Y_k: nb - k - 1 workgroups per stamp
-    // and launch instead of 9, the same flops.
-    static const bool right_off = getenv("IMCOM_LMIN_RIGHT") && strcmp(getenv("IMCOM_LMIN_RIGHT"), "0") == 0;
-    auto solve_block = [&](const std::vector<char> &mask, const double *Xv, double *Yv, double *Wv, double *part, int parts, int Pv) -> int {
+    // Yv = (L L^T)^-1 Xv on blocks of 16 vectors (lmin_skinny.hip) for the stamps of `mask`: one workgroup per stamp, both sweeps in one
+    // launch -- or, for few stamps, two launches per block row with the sums dealt to many workgroups (part: their scratch).
+    // (Per-block-row launches: 1.8 ms of launches per solve + 44 us per production stamp at 7 TB/s; a workgroup per stamp: 12 ms whatever
+    // the count -- they meet near 200 stamps, and at 168 the single launch is 2 % ahead on the wall clock.)
+    auto solve_block = [&](const std::vector<char> &mask, const double *Xv, double *Yv, double *part) -> int {
         std::vector<int> nb(batch);
         int nbm = 0, cnt = 0;
         for (int s = 0; s < batch; s++) { nb[s] = mask[s] ? nblk[s] : 0; nbm = std::max(nbm, nb[s]); cnt += mask[s] ? 1 : 0; }
-        if (Pv == LMIN_SKINNY_P) {  // blocks of 16 vectors (lmin_skinny.hip): one workgroup per stamp, both sweeps in one launch -- or, for few stamps, two launches per block row
-            IMCOM_TRY(upload(ctx, nblk_sol, nb.data(), (size_t)batch));
-            // (per-block-row launches: 1.8 ms of launches per solve + 44 us per production stamp at 7 TB/s; a workgroup per stamp: 12 ms whatever the
-            // count -- they meet near 200 stamps, and at 168 the single launch is 2 % ahead on the wall clock.  Read per call: the tests run both forms.)
-            const int few_max = getenv("IMCOM_LMIN_FEW_MAX") ? atoi(getenv("IMCOM_LMIN_FEW_MAX")) : 128;
-            if (cnt <= few_max && part && skinny_few_partial_doubles(batch) <= (size_t)batch * 8 * NB * NB)
-                return launch_skinny_solve_few(ctx, L, Dinv, Xv, Yv, Np, nblk_sol, nbm, batch, part);
-            return launch_skinny_solve(ctx, L, Dinv, Xv, Yv, Np, nblk_sol, batch);
-        }
-        if (Wv && !right_off && cnt > 0 && cnt <= 8) {
-            const int P = LMIN_P;
-            const long sL = (long)Np * Np, sY = (long)Np * P, sD = (long)(Np / NB) * NB * NB;
-            for (int s0 = 0; s0 < batch;) {  // runs of consecutive wanted stamps with the same number of blocks: one batched launch each
-                if (!mask[s0] || nblk[s0] == 0) { s0++; continue; }
-                int s1 = s0 + 1;
-                while (s1 < batch && mask[s1] && nblk[s1] == nblk[s0]) s1++;
-                const int bc = s1 - s0, nbs = nblk[s0];
-                const double *L0 = L + s0 * sL, *D0 = Dinv + s0 * sD, *X0 = Xv + s0 * sY;
-                double *Y0 = Yv + s0 * sY, *W0 = Wv + s0 * sY;
-                IMCOM_HIP_CHECK(hipMemcpyAsync(W0, X0, (size_t)bc * sY * 8, hipMemcpyDeviceToDevice, ctx->stream));
-                for (int k = 0; k < nbs; k++) {  // L Y = X
-                    IMCOM_TRY(launch_gemm(ctx, false, true, NB, P, NB, bc, D0 + (long)k * NB * NB, NB, sD, W0 + (long)k * NB * P, P, sY, Y0 + (long)k * NB * P, P, sY, 1.0, 0.0));
-                    if (k + 1 < nbs)
-                        IMCOM_TRY(launch_gemm(ctx, false, true, (nbs - k - 1) * NB, P, NB, bc, L0 + (long)(k + 1) * NB * Np + (long)k * NB, Np, sL, Y0 + (long)k * NB * P, P, sY,
-                                              W0 + (long)(k + 1) * NB * P, P, sY, -1.0, 1.0));
-                }
-                IMCOM_HIP_CHECK(hipMemcpyAsync(W0, Y0, (size_t)bc * sY * 8, hipMemcpyDeviceToDevice, ctx->stream));
-                for (int k = nbs - 1; k >= 0; k--) {  // L^T Z = Y
-                    IMCOM_TRY(launch_gemm(ctx, true, true, NB, P, NB, bc, D0 + (long)k * NB * NB, NB, sD, W0 + (long)k * NB * P, P, sY, Y0 + (long)k * NB * P, P, sY, 1.0, 0.0));
-                    if (k > 0)
-                        IMCOM_TRY(launch_gemm(ctx, true, true, k * NB, P, NB, bc, L0 + (long)k * NB * Np, Np, sL, Y0 + (long)k * NB * P, P, sY, W0, P, sY, -1.0, 1.0));
-                }
-                s0 = s1;
-            }
-            return IMCOM_OK;
-        }
         IMCOM_TRY(upload(ctx, nblk_sol, nb.data(), (size_t)batch));
-        for (int k = 0; k < nbm; k++) IMCOM_TRY(launch_solve_fwd(ctx, L, Xv, Yv, Np, LMIN_P, k, batch, batch, nblk_sol, n_dev, Dinv, part, parts, nullptr));
-        for (int k = nbm - 1; k >= 0; k--) IMCOM_TRY(launch_solve_bwd(ctx, L, Yv, Np, LMIN_P, k, nbm, batch, nblk_sol, n_dev, Dinv, part, parts, nullptr, nullptr));
-        return IMCOM_OK;
+        if (cnt <= env_int("IMCOM_LMIN_FEW_MAX", 128) && part && skinny_few_partial_doubles(batch) <= (size_t)batch * 8 * NB * NB)
+            return launch_skinny_solve_few(ctx, L, Dinv, Xv, Yv, Np, nblk_sol, nbm, batch, part);
+        return launch_skinny_solve(ctx, L, Dinv, Xv, Yv, Np, nblk_sol, batch);
     };
 
     for (int attempt = 0;; attempt++) {
@@ -766,16 +680,15 @@ static int chol_core(imcom_ctx *ctx, int batch, const int *n_host, int Np, int m
             if (masked) IMCOM_TRY(launch_solve_mask(ctx, nblk_dev, fac_dev, failp, nblk_sol, act_dev, batch));
             if (!bt_ready) { IMCOM_TRY(before_solve()); bt_ready = true; }
             double *Yp = Y + p0 * node_stride;
-            // the diagonal blocks are applied inside the update launches; IMCOM_SOLVE_UNFUSED=1 keeps them apart (A/B runs)
-            static const bool unfused = getenv("IMCOM_SOLVE_UNFUSED") != nullptr;
-            const double *Dfused = unfused ? nullptr : Dinv;
+            // the diagonal blocks are applied inside the update launches; IMCOM_SOLVE_UNFUSED keeps them apart (A/B runs)
+            const double *Dfused = unfused_solve ? nullptr : Dinv;
             for (int k = 0; k < nbmax; k++) {
                 { ProfScope ps(ctx, "solve_gemm"); IMCOM_TRY(launch_solve_fwd(ctx, L, Bt, Yp, Np, mp, k, eb, batch, nb_sol, n_dev, Dfused, partial, parts_solve, Dpart)); }
-                if (unfused) { ProfScope ps(ctx, "solve_dinv"); IMCOM_TRY(launch_solve_dinv(ctx, Dinv, Yp, Np, mp, k, eb, nb_sol, false)); }
+                if (unfused_solve) { ProfScope ps(ctx, "solve_dinv"); IMCOM_TRY(launch_solve_dinv(ctx, Dinv, Yp, Np, mp, k, eb, nb_sol, false)); }
             }
             for (int k = nbmax - 1; k >= 0; k--) {
-                if (k < nbmax - 1 || !unfused) { ProfScope ps(ctx, "solve_gemm"); IMCOM_TRY(launch_solve_bwd(ctx, L, Yp, Np, mp, k, nbmax, eb, nb_sol, n_dev, Dfused, partial, parts_solve, Npart, Tt, cfuse.Epart ? &cfuse : nullptr)); }
-                if (unfused) { ProfScope ps(ctx, "solve_dinv"); IMCOM_TRY(launch_solve_dinv(ctx, Dinv, Yp, Np, mp, k, eb, nb_sol, true)); }
+                if (k < nbmax - 1 || !unfused_solve) { ProfScope ps(ctx, "solve_gemm"); IMCOM_TRY(launch_solve_bwd(ctx, L, Yp, Np, mp, k, nbmax, eb, nb_sol, n_dev, Dfused, partial, parts_solve, Npart, Tt, cfuse.Epart ? &cfuse : nullptr)); }
+                if (unfused_solve) { ProfScope ps(ctx, "solve_dinv"); IMCOM_TRY(launch_solve_dinv(ctx, Dinv, Yp, Np, mp, k, eb, nb_sol, true)); }
             }
         }
         if (any_fac) {
@@ -908,8 +821,7 @@ int ensure_aux(imcom_ctx *ctx)
     IMCOM_HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
     // IMCOM_AUX_CUS = k: the second queue confined to k of the CUs (bit i of the mask = CU i / 8 of XCD i % 8), so that the
     // main stream's one-workgroup-per-stamp kernels always find CUs without a product tile on them (A/B runs)
-    const char *cus = getenv("IMCOM_AUX_CUS");
-    const int k = cus ? atoi(cus) : 0;
+    const int k = env_int("IMCOM_AUX_CUS", 0);
     if (k > 0 && k < ctx->cu_count) {
         std::vector<uint32_t> mask((ctx->cu_count + 31) / 32, 0u);
         for (int i = 0; i < k; i++) mask[i / 32] |= 1u << (i % 32);
@@ -939,14 +851,6 @@ using namespace imcom;
 extern "C" {
 
 int imcom_version(void) { return IMCOM_HIP_VERSION; }
-int imcom_dev_build(void)
-{
-#ifdef IMCOM_DEV
-    return 1;
-#else
-    return 0;
-#endif
-}
 
 const char *imcom_last_error(void) { return g_err; }
 
@@ -1165,7 +1069,8 @@ int imcom_ctx_mfma_probe(imcom_ctx *ctx, double millis, double *tflops)
 int imcom_ctx_gemm_probe(imcom_ctx *ctx, int variant, int M, int N, int K, int batch, int reps, double *tflops)
 {
     IMCOM_TRY(check_ctx(ctx));
-    IMCOM_REQUIRE(tflops && variant >= 0 && variant <= 8 && M >= 256 && N >= 128 && K >= 16 && batch >= 1 && reps >= 1, "bad arguments");
+    IMCOM_REQUIRE(variant == 0 || (variant >= 2 && variant <= 4), "gemm probe variant %d: 0, 2, 3 or 4", variant);
+    IMCOM_REQUIRE(tflops && M >= 256 && N >= 128 && K >= 16 && batch >= 1 && reps >= 1, "bad arguments");
     IMCOM_REQUIRE(M % 256 == 0 && N % 128 == 0 && K % 16 == 0, "gemm probe: M % 256, N % 128, K % 16");
     const size_t a = (size_t)batch * M * K * 8, b = (size_t)batch * K * N * 8, c = (size_t)batch * M * N * 8;
     IMCOM_TRY(ws_reserve(ctx, a + b + c + 4096));
@@ -1177,14 +1082,8 @@ int imcom_ctx_gemm_probe(imcom_ctx *ctx, int variant, int M, int N, int K, int b
     IMCOM_HIP_CHECK(hipEventCreate(&e0));
     IMCOM_HIP_CHECK(hipEventCreate(&e1));
     auto run = [&]() -> int {
-#ifdef IMCOM_DEV
-        if (variant == 1) return launch_gemm_probe16(ctx, M, N, K, batch, A, B, C);  // probe_gemm.hip
-#else
-        if (variant == 1) { set_error("gemm probe variant 1 (256 x 128 tiles) is part of the developer build (make DEV=1)"); return IMCOM_ERR_ARG; }
-#endif
         // variants 2-4: the engine's other operand layouts (2: both row-major, the Cholesky updates' form C = A B^T; 3: both k-major,
         // the backward solves'; 4: A k-major, B row-major) on the same buffers
-        if (variant >= 5) return launch_gemm_abl(ctx, variant - 4, M, N, K, batch, A, B, C);  // 5: no DMA, 6: no barrier, 7: neither, 8: DMA and barrier but no wait for the DMA
         if (variant == 2) return launch_gemm(ctx, false, false, M, N, K, batch, A, K, (long)M * K, B, K, (long)K * N, C, N, (long)M * N, 1.0, 0.0);
         if (variant == 3) return launch_gemm(ctx, true, true, M, N, K, batch, A, M, (long)M * K, B, N, (long)K * N, C, N, (long)M * N, 1.0, 0.0);
         if (variant == 4) return launch_gemm(ctx, true, false, M, N, K, batch, A, M, (long)M * K, B, K, (long)K * N, C, N, (long)M * N, 1.0, 0.0);
@@ -1469,7 +1368,7 @@ int imcom_solve_chol_stamps(imcom_ctx *ctx, int nst, const int *n, int m, const 
         IMCOM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         ctx->sync_events.push_back(e);
     }
-    const bool timing = getenv("IMCOM_SEAM_TIMING") != nullptr;  // host-side timeline of the call on stderr (adds a synchronisation)
+    const bool timing = env_is("IMCOM_SEAM_TIMING");  // host-side timeline of the call on stderr (adds a synchronisation)
     auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
     double tA = 0, tB0 = 0, tB1 = 0, tcore = 0, tsync = 0;

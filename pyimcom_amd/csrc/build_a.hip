@@ -45,17 +45,11 @@ constexpr int NCH = 5;     // 16-byte chunks per stencil row
 
 // Row buffers per wave; A_RING - 1 rows are in flight.  Three buffers (two workgroups per CU instead of three)
 // measured slower, 40.9 against 33.7 ms per 256 cfg-2 stamps: the gather needs the waves more than the depth.
-#ifndef IMCOM_A_RING
-#define IMCOM_A_RING 2
-#endif
-constexpr int A_RING = IMCOM_A_RING;
-#ifndef IMCOM_A_PMAX
-#define IMCOM_A_PMAX 8
-#endif
-constexpr int A_PMAX = IMCOM_A_PMAX;  // stamp-local PSFs up to which the pair table is staged in LDS (one PSF group: 6 x 6 entries); a stamp of four
-                                      // groups (24 x 24) has every thread fetch its own entry instead: staging 576 entries per tile cost 1.3 ms per block
+constexpr int A_RING = 2;
+constexpr int A_PMAX = 8;  // stamp-local PSFs up to which the pair table is staged in LDS (one PSF group: 6 x 6 entries); a stamp of four
+                           // groups (24 x 24) has every thread fetch its own entry instead: staging 576 entries per tile cost 1.3 ms per block
 
-__global__ __launch_bounds__(256, A_RING == 2 ? 3 : 2) void build_A_kernel(const int *__restrict__ n, int ldn,
+__global__ __launch_bounds__(256, 3) void build_A_kernel(const int *__restrict__ n, int ldn,
                                                       const double *__restrict__ x,
                                                       const double *__restrict__ y,
                                                       const int *__restrict__ psf,
@@ -203,7 +197,6 @@ __global__ __launch_bounds__(256, A_RING == 2 ? 3 : 2) void build_A_kernel(const
     };
     if (!near_end) {
         stage(seg[0]);
-        if (A_RING > 2) stage(seg[1]);
     }
     // the interpolation weights, formed while the first stencil row is in flight
     if (active) {
@@ -311,44 +304,29 @@ __global__ void a_tile_scatter_kernel(const int *__restrict__ key, int *__restri
     desc[(long)s * ntri + atomicAdd(cursor + (long)s * nbin + key[g], 1)] = (int)(g - (long)s * ntri);  // the order inside a bucket decides only the schedule
 }
 
-#ifdef IMCOM_DEV
-int launch_build_A_win(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, const double *x, const double *y, const int *psf,
-                       const double *tables, int ntab, int ng, double nc, double dscale, const int *pair_tab, const double *pair_pen,
-                       int npsf_max, double *A);  // build_a_win.hip
-#endif
-
 int launch_build_A(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, const double *x, const double *y,
                    const int *psf, const double *tables, int ntab, int ng, double nc, double dscale,
                    const int *pair_tab, const double *pair_pen, int npsf_max, double *A)
 {
-#ifdef IMCOM_DEV
-    // developer build (make DEV=1): IMCOM_BUILD_A=window selects the experimental LDS-window builder (build_a_win.hip:
-    // parity-tested, but slower than this file's per-sample DMA builder on rotated exposures -- DESIGN.md, "A builder, round 2")
-    static const bool window = getenv("IMCOM_BUILD_A") && !strcmp(getenv("IMCOM_BUILD_A"), "window");
-    if (window) return launch_build_A_win(ctx, batch, n_dev, ldn, x, y, psf, tables, ntab, ng, nc, dscale, pair_tab, pair_pen, npsf_max, A);
-#endif
     IMCOM_REQUIRE(ntab >= 1 && ntab <= PAIR_MASK + 1, "table stack of %d tables (pair codes carry 28-bit table indices)", ntab);
     const int nt = (ldn + 15) / 16;
     const long ntri = (long)nt * (nt + 1) / 2;
     const long ngrid = (ntri + 7) / 8 * 8;  // padded to a multiple of 8 for the XCD-aware tile order
-    int *desc = nullptr;
     // Every stamp's tiles ordered by the PSF pair of their first sample (three small kernels: counting sort per stamp), so that the
     // tiles an XCD works on at one time read ONE table: 27.85 against 29.25 ms per 256 cfg-2 stamps, three A/B pairs on one box
-    // (ordering the whole BATCH by table instead lost 1.8x: profiles/r03_negative_results.txt).  IMCOM_A_ORDER=rows: row by row.
-    static const bool by_pair = !(getenv("IMCOM_A_ORDER") && !strcmp(getenv("IMCOM_A_ORDER"), "rows"));
-    if (by_pair) {
-        const long total = ntri * batch;
-        const int nbin = npsf_max * npsf_max + 1;
-        int *key = (int *)ws_take(ctx, (size_t)total * 4), *hist = (int *)ws_take(ctx, (size_t)batch * nbin * 4);
-        desc = (int *)ws_take(ctx, (size_t)total * 4);
-        if (key && hist && desc) {
-            IMCOM_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)batch * nbin * 4, ctx->stream));
-            hipLaunchKernelGGL(a_tile_key_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, n_dev, ldn, psf, npsf_max, nt, total, key, hist);
-            hipLaunchKernelGGL(a_tile_scan_kernel, dim3(batch), dim3(256), 0, ctx->stream, hist, nbin);
-            hipLaunchKernelGGL(a_tile_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, key, hist, npsf_max, nt, total, desc);
-            IMCOM_TRY(check_launch("build_A tile order"));
-        } else desc = nullptr;
-    }
+    // (ordering the whole BATCH by table instead lost 1.8x: profiles/r03_negative_results.txt).  Without the workspace for the order
+    // (desc == nullptr) the kernel takes the tiles row by row.
+    const long total = ntri * batch;
+    const int nbin = npsf_max * npsf_max + 1;
+    int *key = (int *)ws_take(ctx, (size_t)total * 4), *hist = (int *)ws_take(ctx, (size_t)batch * nbin * 4);
+    int *desc = (int *)ws_take(ctx, (size_t)total * 4);
+    if (key && hist && desc) {
+        IMCOM_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)batch * nbin * 4, ctx->stream));
+        hipLaunchKernelGGL(a_tile_key_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, n_dev, ldn, psf, npsf_max, nt, total, key, hist);
+        hipLaunchKernelGGL(a_tile_scan_kernel, dim3(batch), dim3(256), 0, ctx->stream, hist, nbin);
+        hipLaunchKernelGGL(a_tile_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, key, hist, npsf_max, nt, total, desc);
+        IMCOM_TRY(check_launch("build_A tile order"));
+    } else desc = nullptr;
     hipLaunchKernelGGL(build_A_kernel, dim3((unsigned)ngrid, batch), dim3(256), 0, ctx->stream, n_dev, ldn, x, y, psf,
                        tables, (long)ntab * ng * ng, ng, nc, dscale, pair_tab, pair_pen, npsf_max, A, nt, (const int *)desc);
     return check_launch("build_A_kernel");

@@ -235,8 +235,8 @@ __global__ __launch_bounds__(256) void chol_diag_kernel(double *__restrict__ L, 
 // Lm = diag(1 / tau) + stril(S) -- inverted here exactly as chol_diag_kernel inverts L[k,k]: 16 x 16 diagonal inverses (a column per
 // thread), then recursive doubling with MFMA products, everything in LDS.  Only tau itself is ever used (as the reciprocal of Lm's
 // diagonal), never 1 / tau: a reflector with tau = 0 (H = I: padding columns) gives a zero row and column of T by itself.
-// (tridiag.hip's trd_larft_kernel builds the same T column by column, a row per thread: 128 dependent steps of scalar loads,
-// 0.44 - 1.25 ms per panel where this takes tens of microseconds; it stays as IMCOM_LARFT=serial for cross-checks.)
+// (The column-by-column form, a row per thread -- 128 dependent steps of scalar loads -- took 0.44 - 1.25 ms per panel where this
+// takes tens of microseconds.)
 __global__ __launch_bounds__(256) void larft_inv_kernel(const double *__restrict__ Sg, const double *__restrict__ tauvec, int ld, int ps,
                                                         double *__restrict__ T)
 {

@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
@@ -99,6 +100,20 @@ struct imcom_ctx {
 namespace imcom {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// The library's environment switches, read at their point of use on every call: a process that sets one
+// between two calls sees the change at the next call.  env_is: the variable is set to exactly `value` (nullptr: set at all);
+// env_int: its value as an integer, `dflt` when it is not set.
+inline bool env_is(const char *name, const char *value = nullptr)
+{
+    const char *e = getenv(name);
+    return e && (!value || strcmp(e, value) == 0);
+}
+inline int env_int(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 // Reserve `bytes` in the context workspace.  The workspace only grows between calls: ws_reserve()
 // is called once per API call with the total, so pointers handed out by ws_take() stay valid.

@@ -507,8 +507,7 @@ extern "C" int imcom_eigh(imcom_ctx *ctx, int batch, const int *n, int ldn, cons
 // (A/B runs and a cross-check: the two bases share nothing but the block-reflector GEMMs).
 static bool eigen_uses_band(int np)
 {
-    static const bool tri = getenv("IMCOM_EIGEN_BASIS") && !strcmp(getenv("IMCOM_EIGEN_BASIS"), "tridiagonal");
-    return !tri && band_basis_fits(np);
+    return !env_is("IMCOM_EIGEN_BASIS", "tridiagonal") && band_basis_fits(np);
 }
 
 // Householder reduction to band form alone (tests, diagnostics): band [batch][BAND_BW + 1][ldn] with band[t][i] = B[i + t][i], the
@@ -563,7 +562,7 @@ static int eigen_fallback(imcom_ctx *ctx, const std::vector<int> &idx, const int
     limit = std::min(limit, ctx->ws_bytes);  // the end of the caller's share of the workspace
     const size_t mark = ctx->ws_used, room = limit - std::min(limit, align_up(mark, 256));
     int cap = (int)idx.size();
-    if (const char *e = getenv("IMCOM_EIGEN_FALLBACK_CAP")) cap = std::max(1, std::min(cap, atoi(e)));  // (tests: several rounds of the loop below)
+    if (env_is("IMCOM_EIGEN_FALLBACK_CAP")) cap = std::max(1, std::min(cap, env_int("IMCOM_EIGEN_FALLBACK_CAP", cap)));  // (tests: several rounds of the loop below)
     while (cap > 1 && eigen_fallback_bytes(cap, np, mp, m) > room) cap = (cap + 1) / 2;
     if (eigen_fallback_bytes(cap, np, mp, m) > room) { set_error("internal: no workspace for the eigendecomposition of a stamp"); return IMCOM_ERR_NOMEM; }
     const size_t mat = (size_t)np * np, big = (size_t)np * mp;
@@ -696,21 +695,18 @@ static int eigen_enqueue(imcom_ctx *ctx, EigenJob &j, int ldn, int m, int np, in
             ctx->sync_events.push_back(e);
         }
         hipEvent_t ev_main = ctx->sync_events[0], ev_aux = ctx->sync_events[1];
-        // (the second queue only where the overlap below will use it: see `overlap`)
-        const char *ov_ = getenv("IMCOM_EIGEN_OVERLAP");
-        if (allow_overlap && nmax > 0 && (ov_ ? atoi(ov_) != 0 : batch <= 128)) IMCOM_TRY(ensure_aux(ctx));
+        // Worth it while the reduction's one-workgroup-per-stamp step leaves most CUs idle: the products' tiles monopolise a CU
+        // (registers, LDS) and the reduction's dependent chain queues behind them.  cfg-3, with / without: batch 32 251 / 265 ms,
+        // 64 418 / 430, 128 762 / 772, 256 1485 / 1458.  IMCOM_EIGEN_OVERLAP=0 / 1 forces it.  (Not beside other sub-batches: the
+        // second stream is one, and the sub-batches' own phases already fill each other's gaps.)
+        const bool overlap = allow_overlap && nmax > 0 && (env_is("IMCOM_EIGEN_OVERLAP") ? env_int("IMCOM_EIGEN_OVERLAP", 0) != 0 : batch <= 128);
+        if (overlap) IMCOM_TRY(ensure_aux(ctx));  // (the second queue only where the overlap below uses it)
         hipStream_t aux = ctx->aux_stream;
         struct AuxDrain {  // whatever path leaves this scope, nothing may still run on the second stream (the workspace is reused)
             hipStream_t s;
             bool armed = true;
             ~AuxDrain() { if (armed && s) hipStreamSynchronize(s); }
         } drain{aux};
-        // Worth it while the reduction's one-workgroup-per-stamp step leaves most CUs idle: the products' tiles monopolise a CU
-        // (registers, LDS) and the reduction's dependent chain queues behind them.  cfg-3, with / without: batch 32 251 / 265 ms,
-        // 64 418 / 430, 128 762 / 772, 256 1485 / 1458.  IMCOM_EIGEN_OVERLAP=0 / 1 forces it.  (Not beside other sub-batches: the
-        // second stream is one, and the sub-batches' own phases already fill each other's gaps.)
-        const char *ov = getenv("IMCOM_EIGEN_OVERLAP");
-        const bool overlap = allow_overlap && nmax > 0 && (ov ? atoi(ov) != 0 : batch <= 128);
         auto on_panel = [&](int p) -> int {
             IMCOM_HIP_CHECK(hipEventRecord(ev_main, st));
             IMCOM_HIP_CHECK(hipStreamWaitEvent(aux, ev_main, 0));
@@ -815,8 +811,7 @@ static size_t solve_eigen_ws(int batch, int np, int mp, int m);
 // CUs per XCD (three, five, six parts) more than doubles the time.  Not the default.
 static int eigen_split(int batch, int np)
 {
-    const char *env = getenv("IMCOM_EIGEN_SPLIT");  // (read at every call: bench.py takes the per-launch timings of symv4 on one stream)
-    const int forced = env ? atoi(env) : 0;
+    const int forced = env_int("IMCOM_EIGEN_SPLIT", 0);  // (bench.py takes the per-launch timings of symv4 on one stream)
     int k = forced > 0 ? forced : (batch >= 24 ? 2 : 1);
     if (!eigen_uses_band(np)) k = 1;
     return std::max(1, std::min(std::min(k, batch), 8));
@@ -872,8 +867,7 @@ static int solve_eigen_core(imcom_ctx *ctx, int batch, const int *n, int ldn, in
     }
     // IMCOM_SPLIT_CUS=1 (A/B runs): every sub-batch on a stream confined to a share of the CUs of its own, so that one's
     // one-workgroup-per-stamp step finds free CUs while another's memory pass runs
-    const char *pc = getenv("IMCOM_SPLIT_CUS");
-    const bool parted = pc && atoi(pc) != 0;
+    const bool parted = env_int("IMCOM_SPLIT_CUS", 0) != 0;
     if (parted && (int)ctx->part_streams.size() != nsub) {
         for (auto s_ : ctx->part_streams) { hipStreamSynchronize(s_); hipStreamDestroy(s_); }
         ctx->part_streams.clear();

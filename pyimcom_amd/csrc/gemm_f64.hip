@@ -17,8 +17,8 @@ namespace imcom {
 
 constexpr int BK = DBK;  // K granularity of the tile engine (mma_dma.h)
 // waves per SIMD a kernel is compiled for: two 8-wave workgroups per CU = 4 (the compiler keeps these kernels at 128 registers on
-// its own; the attribute only has to allow it), or three 4-wave ones (64 x 64 per wave: 128 accumulator registers of 168)
-constexpr int MMA_MINWAVES = MMA_WAVES == 4 ? 3 : 2;
+// its own; the attribute only has to allow it)
+constexpr int MMA_MINWAVES = 2;
 
 __device__ __forceinline__ void zero_acc(f64x4 (&acc)[4][MMA_NJ])
 {
@@ -339,10 +339,11 @@ __global__ __launch_bounds__(MMA_THREADS, MMA_MINWAVES) void solve_fwd_kernel(co
     }
 }
 
-// CO: the coaddition's sums taken from the finished tile of T (tile_coadd_partials; opt-in, IMCOM_EPILOGUE_FUSED): an instantiation of
-// its own, bounded to four waves per SIMD, so that the default kernel's registers are exactly what they were without it
+// CO: the coaddition's sums taken from the finished tile of T (tile_coadd_partials; where the call's coaddition can ride along,
+// coadd_fusable in api.hip): an instantiation of its own, bounded to four waves per SIMD, so that the plain kernel's registers are
+// exactly what they were without it
 template <bool CO>
-__global__ __launch_bounds__(MMA_THREADS, (CO && MMA_WAVES == 8) ? 4 : MMA_MINWAVES) void solve_bwd_kernel(const double *__restrict__ L,
+__global__ __launch_bounds__(MMA_THREADS, CO ? 4 : MMA_MINWAVES) void solve_bwd_kernel(const double *__restrict__ L,
                                                            double *__restrict__ Y, int ldn, int ldm,
                                                            int k, const int *__restrict__ nblk,
                                                            const int *__restrict__ n, const double *__restrict__ Dinv,
@@ -457,74 +458,20 @@ int launch_syr2k_lower(imcom_ctx *ctx, int N, int K, int batch, const double *V,
     return check_launch("syr2k_lower_kernel");
 }
 
-// diagnostic: the k-major x k-major product with parts of the k loop taken out (mma_tile_dma's ABL); the result is not a product
-template <int ABL>
-__global__ __launch_bounds__(MMA_THREADS, MMA_MINWAVES) void gemm_abl_kernel(const double *__restrict__ A, long lda, long strideA,
-                                                                             const double *__restrict__ B, long ldb, long strideB,
-                                                                             double *__restrict__ C, long ldc, long strideC, int K)
-{
-    __shared__ __attribute__((aligned(16))) double smem[DMA_LDS_DOUBLES];
-    const int s = blockIdx.z, tm = blockIdx.y, tn = blockIdx.x;
-    f64x4 acc[4][MMA_NJ];
-    zero_acc(acc);
-    mma_tile_dma<true, true, false, 0, ABL>(acc, A + s * strideA + (long)tm * NB, lda, B + s * strideB + (long)tn * NB, ldb, K, smem);
-    double *Co = C + s * strideC + (long)tm * NB * ldc + (long)tn * NB;
-    IMCOM_FOR_ACC(row, col, v, { Co[(long)row * ldc + col] = v; })
-}
-
-int launch_gemm_abl(imcom_ctx *ctx, int abl, int M, int N, int K, int batch, const double *A, const double *B, double *C)
-{
-    dim3 grid(N / NB, M / NB, batch);
-#define IMCOM_ABL_CASE(a) hipLaunchKernelGGL(gemm_abl_kernel<a>, grid, dim3(MMA_THREADS), 0, ctx->stream, A, (long)M, (long)M * K, B, (long)N, (long)K * N, C, (long)N, (long)M * N, K)
-    if (abl == 1) IMCOM_ABL_CASE(1);
-    else if (abl == 2) IMCOM_ABL_CASE(2);
-    else if (abl == 4) IMCOM_ABL_CASE(4);
-    else IMCOM_ABL_CASE(3);
-#undef IMCOM_ABL_CASE
-    return check_launch("gemm_abl_kernel");
-}
-
 // ---------------------------------------------------------------------------------------------
 // Rate probe (imcom_ctx_mfma_probe): the fp64 MFMA pipe of every SIMD kept busy by four waves with eight independent
 // accumulators each, and nothing else -- no LDS, no memory, no barriers.  What it reaches (77.5 TFLOP/s measured, 98.6 % of the
 // guide's 78.6) is the ceiling a kernel with operand traffic can be compared with.
-template <int MODE>
 __global__ __launch_bounds__(MMA_THREADS, 2) void mfma_probe_kernel(int iters, double seed, double *__restrict__ sink)
 {
-    // MODE 0: constant operands (the ceiling quoted in DESIGN.md).  MODE 1: four A and two B fragments with full pseudo-random
-    // mantissas, different in every lane (the switching activity of real data; same instruction stream otherwise).
-    // MODE 2: as 1, but the six fragments are re-read from LDS in front of every eight MFMAs (three 16-byte ds_reads per lane, as
-    // the tile engine's k-quad does; no DMA, no barriers).
-    __shared__ double frag[MODE == 2 ? 6 * 64 * MMA_WAVES : 1];
+    // constant operands (the ceiling quoted in DESIGN.md)
     f64x4 acc[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) acc[i] = f64x4{seed, 0.0, 0.0, (double)i};
     double a[4], b[2];
-    if (MODE == 0) {
-        a[0] = a[1] = a[2] = a[3] = 1.0 + seed * (double)(threadIdx.x & 3);
-        b[0] = b[1] = 1.0 - seed;
-    } else {
-        unsigned long h = 0x9E3779B97F4A7C15ul * (threadIdx.x + 1 + 977ul * blockIdx.x);
-        auto rnd = [&]() { h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ul; h ^= h >> 32; return 0.5 + (double)(h >> 11) * (1.0 / 9007199254740992.0); };
-#pragma unroll
-        for (int i = 0; i < 4; i++) a[i] = rnd() * 1e-3;
-        b[0] = rnd() * 1e-3; b[1] = -rnd() * 1e-3;
-        if (MODE == 2) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) frag[(i * MMA_WAVES * 64) + threadIdx.x] = a[i];
-            frag[4 * MMA_WAVES * 64 + threadIdx.x] = b[0];
-            frag[5 * MMA_WAVES * 64 + threadIdx.x] = b[1];
-            __syncthreads();
-        }
-    }
+    a[0] = a[1] = a[2] = a[3] = 1.0 + seed * (double)(threadIdx.x & 3);
+    b[0] = b[1] = 1.0 - seed;
     for (int it = 0; it < iters; it++) {
-        if (MODE == 2) {
-            asm volatile("" ::: "memory");  // the reads stay inside the loop
-#pragma unroll
-            for (int i = 0; i < 4; i++) a[i] = frag[(i * MMA_WAVES * 64) + threadIdx.x];
-            b[0] = frag[4 * MMA_WAVES * 64 + threadIdx.x];
-            b[1] = frag[5 * MMA_WAVES * 64 + threadIdx.x];
-        }
 #pragma unroll
         for (int i = 0; i < 8; i++) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i >> 1], b[i & 1], acc[i], 0, 0, 0);
     }
@@ -537,11 +484,7 @@ __global__ __launch_bounds__(MMA_THREADS, 2) void mfma_probe_kernel(int iters, d
 int launch_mfma_probe(imcom_ctx *ctx, int nwg, int iters, double *sink, int *waves_per_wg)
 {
     *waves_per_wg = MMA_WAVES;
-    const char *e = getenv("IMCOM_MFMA_PROBE_MODE");  // diagnostic variants, see the kernel
-    const int mode = e ? atoi(e) : 0;
-    if (mode == 1) hipLaunchKernelGGL(mfma_probe_kernel<1>, dim3(nwg), dim3(MMA_THREADS), 0, ctx->stream, iters, 1e-9, sink);
-    else if (mode == 2) hipLaunchKernelGGL(mfma_probe_kernel<2>, dim3(nwg), dim3(MMA_THREADS), 0, ctx->stream, iters, 1e-9, sink);
-    else hipLaunchKernelGGL(mfma_probe_kernel<0>, dim3(nwg), dim3(MMA_THREADS), 0, ctx->stream, iters, 1e-9, sink);
+    hipLaunchKernelGGL(mfma_probe_kernel, dim3(nwg), dim3(MMA_THREADS), 0, ctx->stream, iters, 1e-9, sink);
     return check_launch("mfma_probe_kernel");
 }
 

@@ -474,7 +474,7 @@ extern "C" int imcom_solve_iter(imcom_ctx *ctx, int batch, const int *n, int ldn
     const int np = (int)align_up((size_t)std::max(nmax, 1), NB), mp = (int)align_up((size_t)m, NB);
     // Width of the output-pixel grid (pixels arrive row by row: yx_val.ravel(), lakernel.py:613-614): the first index whose y
     // differs from pixel 0's.  It only decides which 16 pixels share a workgroup of the blocked solver; any value is correct.
-    static const bool per_pixel = getenv("IMCOM_ITER_PER_PIXEL") != nullptr;  // A/B and cross-check: the one-pixel-per-workgroup kernel
+    const bool per_pixel = env_is("IMCOM_ITER_PER_PIXEL");  // A/B and cross-check: the one-pixel-per-workgroup kernel
     int gridW = m;
     if (!per_pixel && nmax > 0) {
         std::vector<double> y0((size_t)std::min(m, 8192));

@@ -464,10 +464,7 @@ __device__ __forceinline__ void taper_factors(int iy, int ix, int n2f, int fade,
 // exposures would not leave room in LDS), four row groups per block.
 // The per-exposure sums ride in registers while the exposure index of the rows stays the same (pixels are ordered
 // InStamp by InStamp, exposure-major inside) and are flushed to LDS when it changes.
-#ifndef IMCOM_EPI_U
-#define IMCOM_EPI_U 4
-#endif
-constexpr int EPI_U = IMCOM_EPI_U;  // rows in flight per thread
+constexpr int EPI_U = 4;  // rows in flight per thread
 
 template <int CPT>
 __global__ __launch_bounds__(256) void coadd_epilogue_kernel(float *__restrict__ Tt, int ldn, int ldm, int m,
@@ -746,54 +743,6 @@ __global__ __launch_bounds__(256) void diag_max_kernel(const double *__restrict_
     if (threadIdx.x == 0) dmax[s] = red[0];
 }
 
-// G[s] += I on the stamps that are not wanted (their Gram matrix is zero: the Cholesky of the block orthogonalisation must not fail on them)
-__global__ void gram_guard_kernel(double *__restrict__ G, int P, const int *__restrict__ want)
-{
-    const int s = blockIdx.x, c = threadIdx.x;
-    if (c < P && want[s] == 0) G[(long)s * P * P + (long)c * P + c] = 1.0;
-}
-
-// Residuals of the two lowest Ritz pairs of the iteration's Rayleigh-Ritz step: with y_k = X q_k (X orthonormal [ldn][128], q_k the k-th
-// eigenvector of H = X^T A X, eigenvectors in the COLUMNS of Qh) and Z = A X, r_k = Z q_k - theta_k y_k.  part[s][g][k] = the share of
-// |r_k|^2 of the rows workgroup g took (added up by the host in the order of g: the same sums on every run).
-constexpr int LMIN_RG = LMIN_RESID_GROUPS;
-__global__ __launch_bounds__(256) void ritz_residual_kernel(const double *__restrict__ X, const double *__restrict__ Z, const double *__restrict__ Qh,
-                                                            const double *__restrict__ lam, int ldn, const int *__restrict__ n, const int *__restrict__ want,
-                                                            double *__restrict__ part)
-{
-    constexpr int P = 128;
-    __shared__ double red[4][2];
-    const int s = blockIdx.y, g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double acc0 = 0.0, acc1 = 0.0;
-    if (want[s] != 0) {
-        const double *q = Qh + (long)s * P * P;
-        const double q0a = q[(long)lane * P], q0b = q[(long)(lane + 64) * P], q1a = q[(long)lane * P + 1], q1b = q[(long)(lane + 64) * P + 1];
-        const double th0 = lam[(long)s * P], th1 = lam[(long)s * P + 1];
-        const double *Xs = X + (long)s * ldn * P, *Zs = Z + (long)s * ldn * P;
-        for (int i = g * 4 + wave; i < n[s]; i += LMIN_RG * 4) {
-            const double xa = Xs[(long)i * P + lane], xb = Xs[(long)i * P + lane + 64], za = Zs[(long)i * P + lane], zb = Zs[(long)i * P + lane + 64];
-            double d0 = (za - th0 * xa) * q0a + (zb - th0 * xb) * q0b, d1 = (za - th1 * xa) * q1a + (zb - th1 * xb) * q1b;
-            for (int o = 32; o > 0; o >>= 1) {
-                d0 += __shfl_xor(d0, o);
-                d1 += __shfl_xor(d1, o);
-            }
-            acc0 += d0 * d0;
-            acc1 += d1 * d1;
-        }
-    }
-    if (lane == 0) { red[wave][0] = acc0; red[wave][1] = acc1; }
-    __syncthreads();
-    if (threadIdx.x < 2) part[((long)s * LMIN_RG + g) * 2 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-
-int launch_ritz_residual(imcom_ctx *ctx, const double *X, const double *Z, const double *Qh, const double *lam, int ldn, int P, const int *n,
-                         const int *want, double *part, int batch)
-{
-    IMCOM_REQUIRE(P == 128, "ritz_residual: blocks of 128 vectors");
-    hipLaunchKernelGGL(ritz_residual_kernel, dim3(LMIN_RG, batch), dim3(256), 0, ctx->stream, X, Z, Qh, lam, ldn, n, want, part);
-    return check_launch("ritz_residual_kernel");
-}
-
 int launch_lmin_init(imcom_ctx *ctx, double *X, int ldn, int P, const int *n, const int *want, int batch)
 {
     hipLaunchKernelGGL(lmin_init_kernel, dim3((unsigned)(((long)ldn * P + 255) / 256), batch), dim3(256), 0, ctx->stream, X, ldn, P, n, want);
@@ -804,12 +753,6 @@ int launch_diag_max(imcom_ctx *ctx, const double *A, int ldn, const int *n, doub
 {
     hipLaunchKernelGGL(diag_max_kernel, dim3(batch), dim3(256), 0, ctx->stream, A, ldn, n, dmax);
     return check_launch("diag_max_kernel");
-}
-
-int launch_gram_guard(imcom_ctx *ctx, double *G, int P, const int *want, int batch)
-{
-    hipLaunchKernelGGL(gram_guard_kernel, dim3(batch), dim3(P), 0, ctx->stream, G, P, want);
-    return check_launch("gram_guard_kernel");
 }
 
 int launch_multi(imcom_ctx *ctx, const double *Xs, long node_stride, const double *Bt, int ldn, int ldm, int m, const int *n,
@@ -866,9 +809,8 @@ int launch_epilogue(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, int m,
         const int nf = n_inframe - f0 < EPI_MAXF ? n_inframe - f0 : EPI_MAXF;
         const int nslot = n_expo > nf ? n_expo : nf;
         const int cpt = (size_t)nslot * 256 * 4 * sizeof(double) <= 64 * 1024 + 2048 ? 4 : 1;  // at least 2 blocks per CU with 4
-        size_t bytes = (size_t)nslot * 256 * cpt * sizeof(double);
+        const size_t bytes = (size_t)nslot * 256 * cpt * sizeof(double);
         IMCOM_REQUIRE(bytes <= 128 * 1024, "epilogue: n_expo = %d too large", n_expo);
-        if (const char *e = getenv("IMCOM_EPI_LDS_PAD")) bytes += (size_t)atoi(e);  // occupancy experiment (tools/ab_epi_occ.sh)
         if (cpt == 4) {
             IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)coadd_epilogue_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
             hipLaunchKernelGGL(coadd_epilogue_kernel<4>, dim3((m + 255) / 256, batch), dim3(256), bytes, ctx->stream, Tt, ldn, ldm, m, n2f, fade,

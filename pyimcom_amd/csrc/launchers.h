@@ -9,7 +9,6 @@ namespace imcom {
 // gemm_f64.hip
 int launch_chol_update(imcom_ctx *ctx, const double *A, double *L, int ldn, int k, int nbmax, int batch, int abatch,
                        const int *nblk, const double *dshift, double *partial, int nparts);  // nparts > 1: split-K through `partial`
-int launch_gemm_abl(imcom_ctx *ctx, int abl, int M, int N, int K, int batch, const double *A, const double *B, double *C);  // diagnostic
 int launch_chol_trsm(imcom_ctx *ctx, double *L, const double *Dinv, int ldn, int k, int nbmax, int batch,
                      const int *nblk);
 int launch_solve_fwd(imcom_ctx *ctx, const double *L, const double *Bt, double *Y, int ldn, int ldm, int k,
@@ -32,7 +31,6 @@ int launch_coadd_from_partials(imcom_ctx *ctx, int batch, const int *n_dev, cons
 int launch_solve_dinv(imcom_ctx *ctx, const double *Dinv, double *Y, int ldn, int ldm, int k, int batch,
                       const int *nblk, bool trans);
 int launch_probe_fill(imcom_ctx *ctx, double *p, long count, unsigned seed);
-int launch_gemm_probe16(imcom_ctx *ctx, int M, int N, int K, int batch, const double *A, const double *B, double *C);
 int launch_mfma_probe(imcom_ctx *ctx, int nwg, int iters, double *sink, int *waves_per_wg);
 int launch_syr2k_lower(imcom_ctx *ctx, int N, int K, int batch, const double *V, long ldv, long strideV, const double *W, long ldw, long strideW,
                        double *C, long ldc, long strideC, double alpha);  // lower 128-tiles of C += alpha (V^T W + W^T V), V, W k-major
@@ -40,8 +38,7 @@ int launch_gemm(imcom_ctx *ctx, bool akm, bool bkm, int M, int N, int K, int bat
                 long strideA, const double *B, long ldb, long strideB, double *C, long ldc, long strideC,
                 double alpha, double beta);
 
-// tridiag.hip (dispatch between the tridiagonal QR eigensolver and the Jacobi cross-check, jacobi.hip)
-bool eigh_uses_jacobi();
+// tridiag.hip: the tridiagonal QR eigensolver
 size_t eigh_ws_bytes(int batch, int ld, bool vectors);
 int eigh_device(imcom_ctx *ctx, int batch, const int *n_host, int ld, const double *A, long lda, long strideA, double *lam,
                 long ldlam, double *Q, long ldq, long strideQ, int *sweeps_out);
@@ -95,12 +92,9 @@ size_t skinny_few_partial_doubles(int batch);
 int launch_skinny_ax(imcom_ctx *ctx, const double *A, const double *X, double *Z, int ldn, const int *nblk, int nbmax, int batch);              // Z = A X
 int launch_skinny_orth(imcom_ctx *ctx, const double *src, double *dst, int ldn, const int *nblk, int *fail, int batch);                        // one CholQR pass
 int launch_skinny_rr(imcom_ctx *ctx, const double *X, const double *Z, int ldn, const int *nblk, double *lam, double *part, int ngroups, int batch);  // eigenvalues of X^T Z [batch][16], residuals of the two lowest pairs
-constexpr int LMIN_RESID_GROUPS = 32;  // row groups of launch_ritz_residual: part is [batch][32][2]
-int launch_ritz_residual(imcom_ctx *ctx, const double *X, const double *Z, const double *Qh, const double *lam, int ldn, int P, const int *n,
-                         const int *want, double *part, int batch);
+constexpr int LMIN_RESID_GROUPS = 32;  // row groups of launch_skinny_rr: part is [batch][32][2]
 int launch_lmin_init(imcom_ctx *ctx, double *X, int ldn, int P, const int *n, const int *want, int batch);
 int launch_diag_max(imcom_ctx *ctx, const double *A, int ldn, const int *n, double *dmax, int batch);
-int launch_gram_guard(imcom_ctx *ctx, double *G, int P, const int *want, int batch);
 int launch_finalize_single(imcom_ctx *ctx, const double *X, const double *Bt, int ldn, int ldm, int m, const int *n,
                            const double *kap, const double *Cs, float *Tt, float *UC, float *Sigma, float *kappa,
                            int batch, const int *act = nullptr);

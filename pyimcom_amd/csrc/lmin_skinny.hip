@@ -372,7 +372,7 @@ __global__ __launch_bounds__(SK_THREADS, 2) void skinny_orth_kernel(const double
 
 // Rayleigh-Ritz on the block: H = X^T Z (symmetrised), lam[s][0..15] its eigenvalues in ascending order (cyclic Jacobi in LDS:
 // a 16 x 16 matrix), and the squared residual norms |Z y - theta X y|^2 of the two lowest Ritz pairs -> part[s][0][0..1] (the other
-// groups of part[s] zero: the layout of launch_ritz_residual).
+// groups of part[s] zero: the [batch][LMIN_RESID_GROUPS][2] layout lambda_min_subspace adds up).
 __global__ __launch_bounds__(SK_THREADS, 2) void skinny_rr_kernel(const double *__restrict__ X, const double *__restrict__ Z, int ldn, const int *__restrict__ nblk,
                                                                   double *__restrict__ lam, double *__restrict__ part, int ngroups)
 {

@@ -288,14 +288,12 @@ static bool fft_plan(int n, FftPlan *pl)
     // as many waves (= lines) per workgroup as LDS holds next to the tables, WF_MAXWAVES at most
     const long line = (long)pl->npad * 16, lds = 160 * 1024;
     pl->waves = (int)std::min<long>(WF_MAXWAVES, (lds - (long)pl->twn * 16) / line);
-    if (const char *e = getenv("IMCOM_FFT_WAVES")) pl->waves = std::max(1, std::min(pl->waves, atoi(e)));  // tuning runs
     return pl->waves >= 1;
 }
 
 static bool fft_force_gemm()
 {
-    static const bool f = getenv("IMCOM_PSF_OVERLAP") && !strcmp(getenv("IMCOM_PSF_OVERLAP"), "gemm");
-    return f;
+    return env_is("IMCOM_PSF_OVERLAP", "gemm");
 }
 
 static size_t fft_lds_bytes(const FftPlan &pl) { return ((size_t)pl.waves * pl.npad + pl.twn) * 16; }
@@ -424,8 +422,7 @@ __global__ __launch_bounds__(WF_COLS_WAVES * 64) void wf16_inv_cols_kernel(const
             for (int l = 8 * (wave & 3) + (lane >> 3); l < rp; l += 32) {
                 const int i = 2 * l + h - nc + (2 * l + h < nc ? n : 0);
                 if (c2 < ncol && l >= llo && l < lhi) {
-                    const cplx v = src[wf_pad16(i)];
-                    if (!(IMCOM_FFT_ABL & 2) || v.x == 1.2345e300) dst[(long)l * (2 * nhp)] = v;
+                    dst[(long)l * (2 * nhp)] = src[wf_pad16(i)];
                 }
             }
         }
@@ -492,15 +489,12 @@ __global__ __launch_bounds__(WF_MAXWAVES * 64) void wf16_inv_rows_kernel(const c
 // n = 256 r with the plan {16, 16, r}?
 static int fft_static_r(const FftPlan &pl)
 {
-    static const bool off = getenv("IMCOM_FFT_GENERIC") != nullptr;  // A/B and test runs: the general kernels for every n
-    if (off || pl.nst != 3 || pl.radix[0] != 16 || pl.radix[1] != 16) return 0;
+    if (env_is("IMCOM_FFT_GENERIC") || pl.nst != 3 || pl.radix[0] != 16 || pl.radix[1] != 16) return 0;
     return pl.radix[2] >= 2 && pl.radix[2] <= 4 ? pl.radix[2] : 0;
 }
 template <int R2> static int wf16_waves()
 {
-    int w = (int)std::min<long>(WF_MAXWAVES, (160L * 1024 - Wf16<R2>::TWN * 16L) / (Wf16<R2>::LINE * 16L));
-    if (const char *e = getenv("IMCOM_FFT_WAVES")) w = std::max(4, std::min(w, atoi(e)));  // tuning runs
-    return w;
+    return (int)std::min<long>(WF_MAXWAVES, (160L * 1024 - Wf16<R2>::TWN * 16L) / (Wf16<R2>::LINE * 16L));
 }
 template <int R2> static size_t wf16_lds(int waves) { return ((size_t)waves * Wf16<R2>::LINE + Wf16<R2>::TWN) * 16; }
 
@@ -525,18 +519,14 @@ static int wf16_inverse(imcom_ctx *ctx, const cplx *Ra, const cplx *Rb, const in
     // the column kernel's waves write V in groups of four (four neighbouring columns = one 128-byte line per row pair)
     const int W = wf16_waves<R2>(), nh = Wf16<R2>::N / 2 + 1;
     // The column kernel's rounds -- transform, barrier, the groups' stores, barrier -- keep the waves of a workgroup in step.
-    // IMCOM_FFT_COLS_SPLIT=1: workgroups of ONE group of four waves, as many per CU as the LDS holds (two at n = 768), each in a phase
-    // of its own: 2.31 -> 2.22 us per table on a bare request of 3600 tables, nothing inside a block (1752 against 1754 ms per 48 x 48
-    // block; profiles/r04_negative_results.txt item 7) -- not the default.
-    static const bool split = getenv("IMCOM_FFT_COLS_SPLIT") && atoi(getenv("IMCOM_FFT_COLS_SPLIT")) > 0;
-    const int Wc = split ? 4 : std::min(WF_COLS_WAVES, W / 4 * 4);
+    // (Workgroups of one group of four waves, several per CU, gained nothing inside a block: profiles/r04_negative_results.txt item 7.)
+    const int Wc = std::min(WF_COLS_WAVES, W / 4 * 4);
     const size_t lds = wf16_lds<R2>(W), ldsc = (size_t)Wc * Wf16<R2>::LINE * 16;  // (the column kernel keeps no stage tables in LDS)
-    const int per_cu = split ? (int)std::max<size_t>(1, std::min<size_t>(WF_COLS_WAVES / 4, (160 * 1024) / ldsc)) : 1;
     IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)wf16_inv_cols_kernel<R2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc));
     IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)wf16_inv_cols_kernel<R2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc));
     IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)wf16_inv_rows_kernel<R2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const long cols = (long)npairs * nh, rows = (long)npairs * ((nsamp + 1) / 2);
-    const int g1 = (int)std::max<long>(8, std::min<long>((long)per_cu * ctx->cu_count, (cols + Wc - 1) / Wc) / 8 * 8);  // a multiple of the 8 XCDs
+    const int g1 = (int)std::max<long>(8, std::min<long>(ctx->cu_count, (cols + Wc - 1) / Wc) / 8 * 8);  // a multiple of the 8 XCDs
     const int g2 = (int)std::min<long>(ctx->cu_count, (rows + W - 1) / W);
     if (a0 != 0.0)
         hipLaunchKernelGGL((wf16_inv_cols_kernel<R2, true>), dim3(g1), dim3(64 * Wc), ldsc, ctx->stream, Ra, Rb, pairs_dev, npairs, nsamp, tw, a0, a1, win_dev, V);
@@ -765,8 +755,7 @@ extern "C" int imcom_psf_overlap_spectra_slots(imcom_ctx *ctx, const double *spe
     // in chunks of pairs, so that the intermediate (nsamp x nh complex per pair) stays within ~4 GB however many
     // tables a caller asks for at once; the chunks run back to back on the stream and reuse the workspace in order
     const size_t per_pair = (size_t)(nsamp + 1) * v_stride(nfft) * 16;
-    int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)npairs, ((size_t)4 << 30) / per_pair));
-    if (const char *e = getenv("IMCOM_FFT_CHUNK_PAIRS")) chunk = std::max(1, std::min(npairs, atoi(e)));  // tuning runs
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)npairs, ((size_t)4 << 30) / per_pair));
     IMCOM_TRY(ws_reserve(ctx, fft_inverse_ws(chunk, nsamp, nfft) + 8192));
     ProfScope ps(ctx, "psf_overlap");
     const size_t tab = (size_t)(nsamp + 12) * (nsamp + 12);

@@ -30,7 +30,6 @@ constexpr int TPL = 64;         // reflectors per tridiagonalisation panel (the 
 constexpr int QRS = 16;         // QR sweeps per chunk = depth of the rotation wavefront
 constexpr int ROTPAD = 4 * QRS; // identity margin of the rotation log on both sides
 constexpr int QR_RING = 4;      // rotation logs in flight between the QR chain and the rotation kernels
-constexpr int LARFT_LDS = TP * (TP + 1) * 8;  // trd_larft_kernel: T with padded rows
 
 // ascending rank of every eigenvalue (ties by index), lam[rank] = value
 __global__ void eig_rank_kernel(const double *__restrict__ lam_raw, int ld, const int *__restrict__ n,
@@ -332,46 +331,6 @@ __global__ __launch_bounds__(256) void trd_w_kernel(double *__restrict__ Vall, c
     if (threadIdx.x == 0) pdot[s * npart + blockIdx.x] = t;
 }
 
-static bool larft_serial()
-{
-    static const bool v = getenv("IMCOM_LARFT") && !strcmp(getenv("IMCOM_LARFT"), "serial");
-    return v;
-}
-
-// Triangular factor of a panel's block reflector H_ps ... H_pe-1 = I - V T V^T (forward, column-wise):
-// T[c][c] = tau_c, T[0:c, c] = -tau_c T[0:c, 0:c] (V^T v_c).  S = V^T V comes from a GEMM.  One block per stamp.
-__global__ __launch_bounds__(128) void trd_larft_kernel(const double *__restrict__ S, const double *__restrict__ tauvec, int ld,
-                                                        int ps, double *__restrict__ T)
-{
-    // T in LDS as [TP][TP + 1]: thread r walks row r, stride 129 doubles = conflict free; S[q][c] has the same address in every
-    // lane (scalar loads).  Row r of T depends on row r alone, so the 128 column steps need no barrier.  (The first version
-    // kept T unpadded and synchronised twice per step: 685 us per panel.)
-    extern __shared__ double Ts[];
-    const int s = blockIdx.x, r = threadIdx.x;
-    const double *Ss = S + (long)s * TP * TP;
-    for (int q = 0; q < TP; q++) Ts[r * (TP + 1) + q] = 0.0;
-    for (int c = 0; c < TP; c++) {
-        const int j = ps + c;
-        const double tau = j < ld ? tauvec[(long)s * ld + j] : 0.0;
-        double t = 0.0;
-        if (r < c) {
-            for (int q = 0; q < c; q++) t += Ts[r * (TP + 1) + q] * Ss[(long)q * TP + c];  // (T[r][q] = 0 for q < r: uniform trip count and addresses of S)
-            t *= -tau;
-        } else if (r == c) t = tau;
-        if (r <= c) Ts[r * (TP + 1) + c] = t;  // row r of T depends on row r alone: no barrier in this loop
-    }
-    __syncthreads();
-    for (int q = 0; q < TP; q++) T[(long)s * TP * TP + (long)q * TP + r] = Ts[q * (TP + 1) + r];
-}
-
-// T of one panel: the MFMA triangular inverse (chol_diag.hip); IMCOM_LARFT=serial keeps the column-by-column kernel above
-static int launch_larft(imcom_ctx *ctx, const double *S, const double *tauvec, int ld, int ps, double *T, int batch)
-{
-    if (!larft_serial()) return launch_larft_inv(ctx, S, tauvec, ld, ps, T, batch);
-    hipLaunchKernelGGL(trd_larft_kernel, dim3(batch), dim3(TP), LARFT_LDS, ctx->stream, S, tauvec, ld, ps, T);
-    return check_launch("trd_larft_kernel");
-}
-
 // One Givens step of the implicit QR bulge chase at position k of the block [lo, hi].  Carried state: (x, z) the
 // pair to be rotated, a1 = current d[k], b1 = current e[k].  Returns the rotation [c s; -s c].
 struct QrCarry {
@@ -654,8 +613,6 @@ __global__ void rot_identity_kernel(double2 *cs, long count)
 }
 
 // -------------------------------------------------------------------------------------------------
-size_t tridiag_ws_bytes(int batch, int ld, bool vectors);
-
 // The tridiagonalisation proper: At (working copy of A, already initialised) -> d, e, reflectors Vall / tauvec.
 struct TrdScratch {
     double *At, *Wp, *part, *ubuf, *pvec, *wprime, *wv, *hd, *pnorm, *pdot;
@@ -793,12 +750,11 @@ int trd_panel_factors(imcom_ctx *ctx, TrdBasis *out, int batch)
 {
     const int ld = out->ld;
     ProfScope ps_(ctx, "eigen_applyq");
-    IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)trd_larft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LARFT_LDS));
     for (int p = 0; p < out->npanels; p++) {
         const int ps = p * TP, rem = ld - ps;
         const double *Vp = out->Vall + (long)ps * ld + ps;
         IMCOM_TRY(launch_gemm(ctx, false, false, TP, TP, rem, batch, Vp, ld, (long)ld * ld, Vp, ld, (long)ld * ld, out->Sm, TP, (long)TP * TP, 1.0, 0.0));
-        IMCOM_TRY(launch_larft(ctx, out->Sm, out->tauvec, ld, ps, out->Tm + (size_t)p * batch * TP * TP, batch));
+        IMCOM_TRY(launch_larft_inv(ctx, out->Sm, out->tauvec, ld, ps, out->Tm + (size_t)p * batch * TP * TP, batch));
     }
     return trd_pair_factors(ctx, out, batch);
 }
@@ -810,9 +766,8 @@ int trd_panel_step(imcom_ctx *ctx, const TrdBasis &b, int batch, int p, double *
     const int ld = b.ld, ps = p * TP, rem = ld - ps;
     const double *Vp = b.Vall + (long)ps * ld + ps;
     double *Tm = b.Tm + (size_t)p * batch * TP * TP;
-    IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)trd_larft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LARFT_LDS));
     IMCOM_TRY(launch_gemm(ctx, false, false, TP, TP, rem, batch, Vp, ld, (long)ld * ld, Vp, ld, (long)ld * ld, b.Sm, TP, (long)TP * TP, 1.0, 0.0));
-    IMCOM_TRY(launch_larft(ctx, b.Sm, b.tauvec, ld, ps, Tm, batch));
+    IMCOM_TRY(launch_larft_inv(ctx, b.Sm, b.tauvec, ld, ps, Tm, batch));
     double *Cp = C + (long)ps * mp;
     IMCOM_TRY(launch_gemm(ctx, false, true, TP, mp, rem, batch, Vp, ld, (long)ld * ld, Cp, mp, (long)ld * mp, b.W1, mp, (long)TP * mp, 1.0, 0.0));
     IMCOM_TRY(launch_gemm(ctx, true, true, TP, mp, TP, batch, Tm, TP, (long)TP * TP, b.W1, mp, (long)TP * mp, b.W2, mp, (long)TP * mp, 1.0, 0.0));
@@ -879,7 +834,7 @@ int trd_apply_q(imcom_ctx *ctx, const TrdBasis &b, int batch, double *C, int mp,
     return IMCOM_OK;
 }
 
-size_t tridiag_ws_bytes(int batch, int ld, bool vectors)
+size_t eigh_ws_bytes(int batch, int ld, bool vectors)
 {
     const int ldr = ld + 2 * ROTPAD;
     size_t t = trd_scratch_bytes(batch, ld);
@@ -896,11 +851,11 @@ size_t tridiag_ws_bytes(int batch, int ld, bool vectors)
     return t + 8192;
 }
 
-// Same contract as jacobi_eigh_device: A [batch] matrices (lda, strideA) on the device, n_host ragged, ld the
+// The library's eigensolver: A [batch] matrices (lda, strideA) on the device, n_host ragged, ld the
 // padded size (multiple of 128).  lam[s*ldlam + k] ascending; Q[s*strideQ + i*ldq + k] eigenvectors in columns
 // (Q == nullptr: eigenvalues only).
-int tridiag_eigh_device(imcom_ctx *ctx, int batch, const int *n_host, int ld, const double *A, long lda, long strideA,
-                        double *lam, long ldlam, double *Q, long ldq, long strideQ, int *sweeps_out)
+int eigh_device(imcom_ctx *ctx, int batch, const int *n_host, int ld, const double *A, long lda, long strideA,
+                double *lam, long ldlam, double *Q, long ldq, long strideQ, int *sweeps_out)
 {
     IMCOM_REQUIRE(ld % NB == 0 && ld >= NB, "tridiag: ld=%d must be a multiple of %d", ld, NB);
     const bool vectors = Q != nullptr;
@@ -939,14 +894,13 @@ int tridiag_eigh_device(imcom_ctx *ctx, int batch, const int *n_host, int ld, co
     // ---- X = Qh^T: X <- X (I - V T^T V^T) panel by panel, last panel first
     if (vectors) {
         ProfScope ps_(ctx, "eigen_orgtr");
-        IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)trd_larft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LARFT_LDS));
         const int npanels = (std::max(nmax - 2, 0) + TP - 1) / TP;
         for (int p = npanels - 1; p >= 0; p--) {
             const int ps = p * TP, rem = ld - ps;
             const double *Vp = Vall + (long)ps * ld + ps;  // rows (reflectors) ps.., components ps..
             double *Xb = X + (long)ps * ld + ps;
             IMCOM_TRY(launch_gemm(ctx, false, false, TP, TP, rem, batch, Vp, ld, (long)ld * ld, Vp, ld, (long)ld * ld, Sm, TP, (long)TP * TP, 1.0, 0.0));
-            IMCOM_TRY(launch_larft(ctx, Sm, tauvec, ld, ps, Tm, batch));
+            IMCOM_TRY(launch_larft_inv(ctx, Sm, tauvec, ld, ps, Tm, batch));
             IMCOM_TRY(launch_gemm(ctx, false, false, rem, TP, rem, batch, Xb, ld, (long)ld * ld, Vp, ld, (long)ld * ld, W1, TP, (long)ld * TP, 1.0, 0.0));
             IMCOM_TRY(launch_gemm(ctx, false, false, rem, TP, TP, batch, W1, TP, (long)ld * TP, Tm, TP, (long)TP * TP, W2, TP, (long)ld * TP, 1.0, 0.0));
             IMCOM_TRY(launch_gemm(ctx, false, true, rem, rem, TP, batch, W2, TP, (long)ld * TP, Vp, ld, (long)ld * ld, Xb, ld, (long)ld * ld, -1.0, 1.0));
@@ -1037,43 +991,6 @@ int tridiag_eigh_device(imcom_ctx *ctx, int batch, const int *n_host, int ld, co
         *sweeps_out = mx;
     }
     return launch_eig_sort_scatter(ctx, X, ld, dvec, n_dev, rank, lam, ldlam, Q, ldq, strideQ, batch);
-}
-
-// -------------------------------------------------------------------------------------------------
-// Eigensolver used by the library.  The tridiagonal QR path is the product; a developer build (make DEV=1) also holds the
-// one-sided block Jacobi solver (jacobi.hip), an independent cross-check selected by IMCOM_EIGH=jacobi.
-#ifdef IMCOM_DEV
-size_t jacobi_ws_bytes(int batch, int ld);
-int jacobi_eigh_device(imcom_ctx *ctx, int batch, const int *n_host, int ld, const double *A, long lda, long strideA,
-                       double *lam, long ldlam, double *Q, long ldq, long strideQ, int *sweeps_out);
-
-bool eigh_uses_jacobi()
-{
-    const char *e = getenv("IMCOM_EIGH");
-    return e && strcmp(e, "jacobi") == 0;
-}
-#else
-static size_t jacobi_ws_bytes(int, int) { return 0; }
-static int jacobi_eigh_device(imcom_ctx *, int, const int *, int, const double *, long, long, double *, long, double *, long, long, int *)
-{
-    return IMCOM_ERR_ARG;
-}
-bool eigh_uses_jacobi() { return false; }
-#endif
-
-size_t eigh_ws_bytes(int batch, int ld, bool vectors)
-{
-    return eigh_uses_jacobi() ? jacobi_ws_bytes(batch, ld) : tridiag_ws_bytes(batch, ld, vectors);
-}
-
-int eigh_device(imcom_ctx *ctx, int batch, const int *n_host, int ld, const double *A, long lda, long strideA, double *lam,
-                long ldlam, double *Q, long ldq, long strideQ, int *sweeps_out)
-{
-    if (eigh_uses_jacobi()) {
-        IMCOM_REQUIRE(Q != nullptr, "jacobi eigensolver needs the eigenvector output");
-        return jacobi_eigh_device(ctx, batch, n_host, ld, A, lda, strideA, lam, ldlam, Q, ldq, strideQ, sweeps_out);
-    }
-    return tridiag_eigh_device(ctx, batch, n_host, ld, A, lda, strideA, lam, ldlam, Q, ldq, strideQ, sweeps_out);
 }
 
 }  // namespace imcom

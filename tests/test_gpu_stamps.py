@@ -180,37 +180,24 @@ def test_empty_stamp_in_resident_batch():
         assert torch.equal(getattr(res, name)[1], getattr(alone, name)[0]), name
 
 
-def test_alternative_code_paths_in_subprocess():
+def test_kept_switch_paths_in_subprocess():
     """The switches kept for A/B runs and as cross-checks must not rot: the unfused diagonal-block launches
-    (IMCOM_SOLVE_UNFUSED), the dense-DFT table path (IMCOM_PSF_OVERLAP=gemm) and -- in the developer build of the library
-    (make DEV=1 -> libimcom_hip_dev.so, selected by IMCOM_HIP_LIB; built by __graft_entry__.build()) -- the Jacobi eigensolver
-    (IMCOM_EIGH=jacobi) and the experimental LDS-window A builder (IMCOM_BUILD_A=window)
-    are read once per process, so the parity check runs in a child process with all of them set."""
+    (IMCOM_SOLVE_UNFUSED), the dense-DFT table path (IMCOM_PSF_OVERLAP=gemm) and the Eigen path's second queue, in one child
+    process that runs the parity check with all of them set; then the general line-FFT kernels (IMCOM_FFT_GENERIC) in another."""
     import os
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, IMCOM_SOLVE_UNFUSED="1", IMCOM_PSF_OVERLAP="gemm", PYTHONPATH=root)
-    dev_lib = os.path.join(root, "pyimcom_amd", "lib", "libimcom_hip_dev.so")
-    # __graft_entry__.build() makes the developer library: its absence is a broken build, not a reason to pass with half the test
-    assert os.path.exists(dev_lib), f"{dev_lib} is missing: run `make -C pyimcom_amd/csrc DEV=1` (or __graft_entry__.build())"
-    env.update(IMCOM_HIP_LIB=dev_lib, IMCOM_EIGH="jacobi", IMCOM_BUILD_A="window")
     # one Eigen batch with its reflector products beside the reduction on the second queue (the default below 24 stamps), that queue
-    # confined to 192 CUs (IMCOM_AUX_CUS: read when the context is created); the sub-batch variants: tests/test_gpu_eigen_indef.py
+    # confined to 192 CUs (IMCOM_AUX_CUS: read when that queue is created); the sub-batch variants: tests/test_gpu_eigen_indef.py
     env.update(IMCOM_EIGEN_SPLIT="1", IMCOM_EIGEN_OVERLAP="1", IMCOM_AUX_CUS="192")
-    env.update(IMCOM_LARFT="serial")   # the block reflectors' triangular factors column by column (default: MFMA triangular inverse)
     code = ("import dataclasses; from pyimcom_amd import synth; from tests import parity as smoke; "
             "smoke.check_batch(synth.CONFIGS['small'], 2); "
             "smoke.check_batch(dataclasses.replace(synth.CONFIGS['tiny'], kernel='Eigen'), 2); print('alt paths ok')")
     out = subprocess.run([sys.executable, "-c", code], env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "alt paths ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
-    # IMCOM_FFT_COLS_SPLIT: the tables' column transform as independent workgroups of four waves (same arithmetic: the static sizes'
-    # tables against numpy, and the resident path on them); IMCOM_EPI_LDS_PAD: the epilogue at one workgroup per CU
-    env = dict(os.environ, IMCOM_FFT_COLS_SPLIT="1", IMCOM_EPI_LDS_PAD="45000", PYTHONPATH=root)
-    out = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "tests/test_gpu_psfs.py", "tests/test_gpu_stamps.py", "-k",
-                          "(mixed_radix and (32-8 or 24-16 or 32-16)) or test_resident_path_vs_oracle or windows"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and " passed" in out.stdout and "failed" not in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
     # IMCOM_FFT_GENERIC: the general line-FFT kernels also at the sizes the static 16 x 16 x r kernels normally take
     env = dict(os.environ, IMCOM_FFT_GENERIC="1", PYTHONPATH=root)
     out = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "tests/test_gpu_psfs.py", "-k", "mixed_radix and (32-8 or 24-16)"],
@@ -351,14 +338,13 @@ def test_solve_retries_when_the_workspace_cannot_grow(monkeypatch):
         sb.solve()
 
 
-@pytest.mark.parametrize("block_of", [128, 16, -16])
+@pytest.mark.parametrize("block_of", [16, -16])
 @pytest.mark.parametrize("shifts_in_kappa", [(3.0, 0.0, 40.0, 1.5), (0.0, 0.0, 0.0, 2.0, 0.0)])
 def test_repair_of_large_stamps_by_the_subspace_iteration_vs_oracle(shifts_in_kappa, block_of, monkeypatch):
     """The Cholesky repair (lakernel.py:262-279: AA_ii += |w[0]| + 1e-16, w[0] the smallest eigenvalue of A) at a size where the library
     finds w[0] WITHOUT an eigendecomposition (api.hip lambda_min_subspace: trial factorisations, subspace iteration with the inverse
     on 16 vectors (lmin_skinny.hip; the sweeps as two launches per block row, the form few stamps take, or -- block_of = -16 -- as one
-    workgroup per stamp, the form of a pass of more than 128 stamps) or on 128 (the form of rounds 5 / 6a, IMCOM_LMIN_SKINNY=0), Rayleigh-Ritz
-    with A; matrices of 1024 rows and more).  cfg-2 stamps (N ~ 2.2k), a batch of four of which three
+    workgroup per stamp, the form of a pass of more than 128 stamps), Rayleigh-Ritz with A; matrices of 1024 rows and more).  cfg-2 stamps (N ~ 2.2k), a batch of four of which three
     are made indefinite by different amounts -- A - c I with c a multiple of kappa, so that w[0] = lambda_min(A) - c sits in the dense
     lower end of a real PSF-overlap spectrum -- and one stays as it is.  T, the maps and info against the oracle's CholKernel (numpy eigh
     + scipy cholesky), through the synchronous entry and through begin / end / redo (only the failed stamps are solved again: the healthy
@@ -369,7 +355,6 @@ def test_repair_of_large_stamps_by_the_subspace_iteration_vs_oracle(shifts_in_ka
     from pyimcom_amd import synth
     from pyimcom_amd.stamps import PSFGroupTables, StampBatch
 
-    monkeypatch.setenv("IMCOM_LMIN_SKINNY", "0" if block_of == 128 else "1")
     if block_of == -16:
         monkeypatch.setenv("IMCOM_LMIN_FEW_MAX", "0")
     cfg = synth.CONFIGS["cfg2"]

@@ -1,5 +1,5 @@
 """The Cholesky repair on paper4 stamps as a block's passes run it: a blind pass (expected repair, no hint), then hinted passes from the blind
-pass's record:  [IMCOM_LMIN_SKINNY=0|1] [IMCOM_LMIN_DEBUG=1] python tools/bench_repair_hinted.py [batch] [reps] [check]
+pass's record:  [IMCOM_LMIN_FEW_MAX=n] [IMCOM_LMIN_DEBUG=1] python tools/bench_repair_hinted.py [batch] [reps] [check]
 One JSON line: ms per stamp (whole solve / eigen_repair / chol_gemm / solve_gemm) of the hinted passes, the smallest eigenvalues' range
 (imcom_ctx_last_repair), digests of T and the maps; `check`: torch.linalg.eigvalsh of every stamp's A (the tool's cross-check) beside them."""
 import json, os, sys, time

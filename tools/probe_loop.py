@@ -1,4 +1,4 @@
-"""Runs one of the rate probes for a few seconds (for tools/poll_clocks.sh):  python tools/probe_loop.py mfma|gemm0|gemm1 [seconds]"""
+"""Runs one of the rate probes for a few seconds (for tools/poll_clocks.sh):  python tools/probe_loop.py mfma|gemm0|gemm2|gemm3|gemm4 [seconds]"""
 import sys, time
 from pyimcom_amd._lib import default_context
 ctx = default_context()
