@@ -343,11 +343,20 @@ __device__ inline double2 qr_step(double *d, double *e, int lo, int hi, int k, Q
     const double en = (k < hi - 1) ? e[k + 1] : 0.0;
     const double h = q.x * q.x + q.z * q.z;
     double c = 1.0, sn = 0.0, r = 0.0;
-    if (h > 0.0) {
+    if (h >= 1e-280 && h <= 1e280) {
         const double ir = rsqrt(h);
         c = q.x * ir;
         sn = q.z * ir;
         r = h * ir;
+    } else if (q.x != 0.0 || q.z != 0.0) {
+        // Squares near or below the normal range keep too few bits for c^2 + s^2 = 1: sweeps whose shifts repeat an
+        // eigenvalue (a tight cluster among the 32 shifts of a pipelined chunk) drive e[k] and the bulge below 1e-154,
+        // and the rotation made of them is no longer orthogonal (eigenvalues off by 6e-10 at n = 97, 1e4 n eps |A|).  Rescale first.
+        const double sc = fmax(fabs(q.x), fabs(q.z)), xs = q.x / sc, zs = q.z / sc;
+        const double hs = xs * xs + zs * zs, ir = rsqrt(hs);
+        c = xs * ir;
+        sn = zs * ir;
+        r = sc * (hs * ir);
     }
     if (k > lo) e[k - 1] = r;
     const double cc = c * c, ss = sn * sn, csn = c * sn;
