@@ -49,6 +49,16 @@ def _load():
 
 lib = _load()
 
+
+def ptr(a):
+    """The pointer an array argument of the C-ABI takes: None -> NULL, a torch tensor -> its data_ptr(), a numpy array -> its buffer."""
+    if a is None:
+        return None
+    if hasattr(a, "data_ptr"):
+        return C.c_void_p(a.data_ptr())
+    return a.ctypes.data_as(C.c_void_p)
+
+
 _vp, _i, _l, _d = C.c_void_p, C.c_int, C.c_long, C.c_double
 _ip = C.POINTER(C.c_int)
 

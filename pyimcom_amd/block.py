@@ -2,20 +2,10 @@
 _output_stamp_wrapper (reference src/pyimcom/coadd.py:2031-2047, 1975-1993) kept on the GPU, and the
 boundary recovery of Block.build_output_file (coadd.py:2163-2181)."""
 
-import ctypes as C
-
 import numpy as np
 import torch
 
-from ._lib import check, default_context, lib
-
-
-def _dp(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _hp(a):
-    return a.ctypes.data_as(C.c_void_p)
+from ._lib import check, default_context, lib, ptr
 
 
 class BlockMaps:
@@ -78,10 +68,10 @@ class BlockMaps:
             f64 = 1 if src.dtype == torch.float64 else 0
             if self.fade == 0:  # no overlap: one contribution per pixel
                 dst = self._out_map[o] if name == "out_map" else self._maps[name][o]
-                check(lib.imcom_block_accumulate(h, b, _hp(jst), _hp(ist), self.n2, self.fade, nlayer, _dp(src), f64, _dp(dst), self.nside))
+                check(lib.imcom_block_accumulate(h, b, ptr(jst), ptr(ist), self.n2, self.fade, nlayer, ptr(src), f64, ptr(dst), self.nside))
             else:
-                check(lib.imcom_block_place(h, b, _hp(jst), _hp(ist), self.n2, self.fade, nlayer, _dp(src), f64,
-                                            _dp(self._layer(name, nlayer, src.dtype)[o]), self.nside))
+                check(lib.imcom_block_place(h, b, ptr(jst), ptr(ist), self.n2, self.fade, nlayer, ptr(src), f64,
+                                            ptr(self._layer(name, nlayer, src.dtype)[o]), self.nside))
 
         results = list(res) if isinstance(res, (list, tuple)) else [res]
         assert len(results) == self.n_out
@@ -106,8 +96,8 @@ class BlockMaps:
         for name, lay in self.layers.items():
             for o in range(self.n_out):
                 dst = self._out_map[o] if name == "out_map" else self._maps[name][o]
-                check(lib.imcom_block_combine(self.ctx.handle, self.n1P, self.n2, self.fade, lay.shape[2], _dp(lay[o]),
-                                              1 if lay.dtype == torch.float64 else 0, _dp(dst), self.nside, 1 if self.order == "cells" else 0,
+                check(lib.imcom_block_combine(self.ctx.handle, self.n1P, self.n2, self.fade, lay.shape[2], ptr(lay[o]),
+                                              1 if lay.dtype == torch.float64 else 0, ptr(dst), self.nside, 1 if self.order == "cells" else 0,
                                               self.origin[0], self.origin[1]))
         self._dirty, self._recovered = False, False
 
@@ -149,7 +139,7 @@ class BlockMaps:
         m = self.maps[name][:, fk : self.nside - fk, fk : self.nside - fk].contiguous()
         out = torch.empty(m.shape, dtype=torch.uint16 if uns else torch.int16, device=m.device)
         self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
-        check(lib.imcom_compress_map_f32(self.ctx.handle, _dp(m), m.numel(), coef, 1 if uns else 0, _dp(out)))
+        check(lib.imcom_compress_map_f32(self.ctx.handle, ptr(m), m.numel(), coef, 1 if uns else 0, ptr(out)))
         return out
 
     def finalize(self, pad_sides="", postage_pad=0):
@@ -160,8 +150,8 @@ class BlockMaps:
         self._recovered = True
         self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
         h = self.ctx.handle
-        check(lib.imcom_trapezoid_recover_f32(h, _dp(self.out_map), self.n_out * self.n_inframe, self.nside, self.nside, self.fade, 0, 0, 0, 0))
+        check(lib.imcom_trapezoid_recover_f32(h, ptr(self.out_map), self.n_out * self.n_inframe, self.nside, self.nside, self.fade, 0, 0, 0, 0))
         w = postage_pad * self.n2
         pads = [w * (s not in pad_sides) for s in "BTLR"]
         for m in self.maps.values():
-            check(lib.imcom_trapezoid_recover_f32(h, _dp(m), self.n_out, self.nside, self.nside, self.fade, *pads))
+            check(lib.imcom_trapezoid_recover_f32(h, ptr(m), self.n_out, self.nside, self.nside, self.fade, *pads))

@@ -55,10 +55,39 @@ void *ws_take(imcom_ctx *ctx, size_t bytes)
     return ctx->ws + off;
 }
 
-struct WsPlan {
-    size_t total = 0;
-    size_t add(size_t bytes) { total = align_up(total, 256) + bytes; return total; }
-};
+int ws_short(const char *who)
+{
+    set_error("internal: workspace plan too small (%s)", who);
+    return IMCOM_ERR_NOMEM;
+}
+
+int enter(imcom_ctx *ctx)
+{
+    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) { set_error("hipSetDevice(%d): %s", ctx->device, hipGetErrorString(e)); return IMCOM_ERR_HIP; }
+    return IMCOM_OK;
+}
+
+int ensure_sync_events(imcom_ctx *ctx, size_t k)
+{
+    while (ctx->sync_events.size() < k) {
+        hipEvent_t e;
+        IMCOM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        ctx->sync_events.push_back(e);
+    }
+    return IMCOM_OK;
+}
+
+int batch_sizes(const int *n, int batch, int ldn, int *nmax)
+{
+    *nmax = 0;
+    for (int s = 0; s < batch; s++) {
+        IMCOM_REQUIRE(n[s] >= 0 && n[s] <= ldn, "n[%d]=%d exceeds ldn=%d", s, n[s], ldn);
+        *nmax = std::max(*nmax, n[s]);
+    }
+    return IMCOM_OK;
+}
 
 ProfScope::ProfScope(imcom_ctx *c, const char *fam, long n, bool fine) : ctx(c), family(fam), launches(n)
 {
@@ -200,7 +229,7 @@ static int lambda_min_group(imcom_ctx *ctx, const double *A, const int *n_host, 
     const size_t mat = (size_t)Np * Np;
     double *G = (double *)ws_take(ctx, (size_t)count * mat * 8);
     double *lam = (double *)ws_take(ctx, (size_t)count * Np * 8);
-    if (!G || !lam) { set_error("internal: workspace (repair)"); return IMCOM_ERR_NOMEM; }
+    if (!G || !lam) return ws_short("repair");
     std::vector<int> ng(count);
     for (int q = 0; q < count; q++) {
         ng[q] = n_host[idx[q]];
@@ -254,7 +283,7 @@ static int lambda_min_subspace(imcom_ctx *ctx, int batch, const int *n_host, con
     double *dmax_d = (double *)ws_take(ctx, (size_t)batch * 8);
     int *want_d = (int *)ws_take(ctx, (size_t)batch * 4), *gfail_d = (int *)ws_take(ctx, (size_t)batch * 4);
     int *nbrun_d = (int *)ws_take(ctx, (size_t)batch * 4);  // 128-blocks of the stamps a round runs (0: not in it)
-    if (!X || !Y || !Z || !lam || !rpart || !part || !dmax_d || !want_d || !gfail_d || !nbrun_d) { set_error("internal: workspace (smallest eigenvalue)"); return IMCOM_ERR_NOMEM; }
+    if (!X || !Y || !Z || !lam || !rpart || !part || !dmax_d || !want_d || !gfail_d || !nbrun_d) return ws_short("smallest eigenvalue");
     hipStream_t st = ctx->stream;
     std::vector<char> want(batch, 0);
     std::vector<int> want_i(batch, 0);
@@ -558,12 +587,10 @@ static int chol_core(imcom_ctx *ctx, int batch, const int *n_host, int Np, int m
             cfuse.indata = co->indata; cfuse.expo = co->expo; cfuse.n_inframe = co->n_inframe; cfuse.n_expo = co->n_expo;
             cfuse.Epart = (double *)ws_take(ctx, (size_t)batch * 2 * nbmax_all * (co->n_expo + co->n_inframe) * mp * 8);
         }
-        if (!Tsum_image || (colsums && coadd_fusable(nv, co->fade) && !cfuse.Epart)) { set_error("internal: workspace plan too small (coaddition)"); return IMCOM_ERR_NOMEM; }
+        if (!Tsum_image || (colsums && coadd_fusable(nv, co->fade) && !cfuse.Epart)) return ws_short("coaddition");
     }
-    if (!L || !Dinv || !Y || !dshift || !ints || !mints || !inc || !dbl || !kappaC_dev || (nv > 1 && (!Dp || !Npq || !W)) || (pbytes && !partial) || (nv == 1 && !unfused_solve && !colsums)) {
-        set_error("internal: workspace plan too small");
-        return IMCOM_ERR_NOMEM;
-    }
+    if (!L || !Dinv || !Y || !dshift || !ints || !mints || !inc || !dbl || !kappaC_dev || (nv > 1 && (!Dp || !Npq || !W)) || (pbytes && !partial) || (nv == 1 && !unfused_solve && !colsums))
+        return ws_short("Cholesky");
     const size_t ws_after_plan = ctx->ws_used;  // (the repair's own scratch is taken from here on and handed back)
     int *n_dev = ints, *nblk_dev = ints + eb, *ninc_dev = ints + 2 * eb, *fail_dev = ints + 3 * eb;  // n, nblk, ninc [eb]; fail[nv][batch]
     int *fac_dev = mints, *nblk_fac = mints + batch, *nblk_sol = mints + 2 * batch, *act_dev = mints + 3 * batch;  // one kappa node: this attempt's stamps
@@ -710,11 +737,7 @@ static int chol_core(imcom_ctx *ctx, int batch, const int *n_host, int Np, int m
                 ctx->flag_pin_count = std::max<size_t>(cnt, 256);
             }
             IMCOM_HIP_CHECK(hipMemcpyAsync(ctx->flag_pin, fail_dev, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-            while (ctx->sync_events.size() < 3) {
-                hipEvent_t e;
-                IMCOM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                ctx->sync_events.push_back(e);
-            }
+            IMCOM_TRY(ensure_sync_events(ctx, 3));
             IMCOM_HIP_CHECK(hipEventRecord(ctx->sync_events[2], ctx->stream));
             ctx->deferred_flags = (long)cnt;
             return IMCOM_OK;
@@ -831,18 +854,56 @@ int ensure_aux(imcom_ctx *ctx)
     return IMCOM_OK;
 }
 
-static int check_ctx(imcom_ctx *ctx)
+// The argument rules of the four resident Cholesky entries.  `more`: the entry's own pointers are there (info, redo); `redo`: one
+// kappa node only (imcom_solve_chol_resident_redo); `co`: the coaddition's rules too (imcom_solve_chol_resident_coadd).
+static int resident_args(int batch, const int *n_host, int ldn, int m, int ldm, const double *A, const double *Bt, const double *C_host,
+                         const double *kappaC_host, int nv, const float *Tt, const float *UC, const float *Sigma, const float *kappa, bool more,
+                         bool redo, const CoaddArgs *co)
 {
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) { set_error("hipSetDevice(%d): %s", ctx->device, hipGetErrorString(e)); return IMCOM_ERR_HIP; }
+    IMCOM_REQUIRE(batch >= 1 && n_host && A && Bt && C_host && kappaC_host && Tt && UC && Sigma && kappa && more, "null pointer");
+    if (co)
+        IMCOM_REQUIRE(co->indata && co->expo && co->outimage && co->Tsum_stamp && co->Tsum_inpix && co->Neff, "null pointer (coaddition)");
+    IMCOM_REQUIRE(ldn >= NB && ldn % NB == 0 && ldm % NB == 0 && m >= 1 && m <= ldm && (redo || nv >= 1), "ldn=%d / ldm=%d must be multiples of %d", ldn, ldm, NB);
+    if (redo) IMCOM_REQUIRE(nv == 1, "imcom_solve_chol_resident_redo: one kappa node (nv=%d: call imcom_solve_chol_resident)", nv);
+    else IMCOM_REQUIRE(nv <= CHOL_MAXNV, "nv=%d kappa nodes: at most %d", nv, CHOL_MAXNV);
+    if (co) {
+        IMCOM_REQUIRE(m == co->n2f * co->n2f && co->n_inframe >= 1 && co->n_expo >= 1 && co->fade >= 0 && co->n2 >= 1, "bad sizes (coaddition)");
+        IMCOM_REQUIRE(co->fade == 0, "imcom_solve_chol_resident_coadd: fade = %d -- the map tapers of coadd.py:1118-1122 come between the solve and the coaddition: "
+                                     "call imcom_solve_chol_resident, imcom_trapezoid_f32, imcom_coadd_epilogue", co->fade);
+    }
     return IMCOM_OK;
 }
 
-// staging helper: device view of a caller buffer (copy in when host)
-struct Staged {
-    void *dev = nullptr;
-};
+// A begin whose end never came (the caller failed in between): its work is waited for and forgotten.
+static int drain_begin(imcom_ctx *ctx)
+{
+    if (ctx->deferred_flags != 0) {
+        IMCOM_HIP_CHECK(hipEventSynchronize(ctx->sync_events[2]));
+        ctx->deferred_flags = 0;
+    }
+    return IMCOM_OK;
+}
+
+// The host Cholesky entries upload -B/2 on the context's second queue while the factorisation runs.  The copy lands in workspace that
+// kernels of an EARLIER, un-synchronised device-mode call on this context may still be using: it waits for the point the main stream had
+// reached when the entry began (mark_entry: sync_events[1]) -- not for the entry's own factorisation, behind which it is meant to hide --
+// and the main stream waits for the copy (sync_events[0]) before it packs.
+static int mark_entry(imcom_ctx *ctx)
+{
+    IMCOM_TRY(ensure_sync_events(ctx, 2));
+    IMCOM_HIP_CHECK(hipEventRecord(ctx->sync_events[1], ctx->stream));  // everything earlier calls left on the main stream
+    return IMCOM_OK;
+}
+
+static int upload_behind_entry(imcom_ctx *ctx, const std::function<int(hipStream_t)> &copies)
+{
+    IMCOM_TRY(ensure_aux(ctx));
+    IMCOM_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->sync_events[1], 0));
+    IMCOM_TRY(copies(ctx->aux_stream));
+    IMCOM_HIP_CHECK(hipEventRecord(ctx->sync_events[0], ctx->aux_stream));
+    IMCOM_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->sync_events[0], 0));
+    return IMCOM_OK;
+}
 
 }  // namespace imcom
 
@@ -890,7 +951,7 @@ int imcom_ctx_create(int device, imcom_ctx **out)
 int imcom_ctx_destroy(imcom_ctx *ctx)
 {
     if (!ctx) return IMCOM_OK;
-    hipSetDevice(ctx->device);
+    (void)enter(ctx);  // (the tear-down goes on whatever the device says)
     hipStreamSynchronize(ctx->stream);
     for (auto &p : ctx->pending) { hipEventDestroy(p.start); hipEventDestroy(p.stop); }
     for (auto e : ctx->event_pool) hipEventDestroy(e);
@@ -909,7 +970,7 @@ int imcom_ctx_destroy(imcom_ctx *ctx)
 
 int imcom_ctx_set_stream(imcom_ctx *ctx, void *hip_stream)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     hipStream_t next = (hipStream_t)hip_stream;  // NULL = the legacy default stream, which is what torch's default is
     if (next != ctx->stream) {
         // work queued on the old stream may still be using the context's bump workspace, which the next call on the new
@@ -924,14 +985,14 @@ int imcom_ctx_set_stream(imcom_ctx *ctx, void *hip_stream)
 
 int imcom_ctx_sync(imcom_ctx *ctx)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return IMCOM_OK;
 }
 
 int imcom_ctx_workspace_bytes(imcom_ctx *ctx, size_t *bytes)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(bytes, "null bytes");
     *bytes = ctx->ws_bytes;
     return IMCOM_OK;
@@ -939,7 +1000,7 @@ int imcom_ctx_workspace_bytes(imcom_ctx *ctx, size_t *bytes)
 
 int imcom_ctx_workspace_release(imcom_ctx *ctx)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->aux_stream) IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
     if (ctx->ws && !ctx->ws_external) IMCOM_HIP_CHECK(hipFree(ctx->ws));
@@ -953,7 +1014,7 @@ int imcom_ctx_workspace_release(imcom_ctx *ctx)
 // TEMPFILE "virtual memory" knob (psfutil.py:2056-2085): the user decides where the sub-blocks live, not luck.
 int imcom_ctx_set_workspace(imcom_ctx *ctx, void *ptr, size_t bytes)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE((ptr != nullptr) == (bytes > 0), "workspace pointer and size must come together (NULL, 0: none yet)");
     IMCOM_REQUIRE(((uintptr_t)ptr & 255) == 0, "the workspace must be aligned to 256 bytes");
     IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -969,7 +1030,7 @@ int imcom_ctx_set_workspace(imcom_ctx *ctx, void *ptr, size_t bytes)
 
 int imcom_ctx_workspace_needed(imcom_ctx *ctx, size_t *bytes)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(bytes, "null bytes");
     *bytes = ctx->ws_need;
     return IMCOM_OK;
@@ -977,7 +1038,7 @@ int imcom_ctx_workspace_needed(imcom_ctx *ctx, size_t *bytes)
 
 int imcom_ctx_set_repair_hint(imcom_ctx *ctx, double lmin_abs)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(lmin_abs >= 0.0 && std::isfinite(lmin_abs), "repair hint: a finite |lambda_min| >= 0 (0 clears it)");
     ctx->repair_hint = lmin_abs;
     return IMCOM_OK;
@@ -985,14 +1046,14 @@ int imcom_ctx_set_repair_hint(imcom_ctx *ctx, double lmin_abs)
 
 int imcom_ctx_set_repair_expect(imcom_ctx *ctx, int expect)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     ctx->repair_expect = expect != 0;
     return IMCOM_OK;
 }
 
 int imcom_ctx_last_repair(imcom_ctx *ctx, int *count, double *w0_min, double *w0_max)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(count && w0_min && w0_max, "null output");
     *count = ctx->last_repair_count;
     *w0_min = ctx->last_repair_count ? ctx->last_w0_min : 0.0;
@@ -1011,7 +1072,7 @@ int imcom_solve_chol_workspace(int batch, int ldn, int m, int ldm, int nv, size_
 
 int imcom_ctx_profile_enable(imcom_ctx *ctx, int on)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_TRY(profile_collect(ctx));
     ctx->profile = on != 0;
     ctx->profile_fine = on >= 2;
@@ -1020,7 +1081,7 @@ int imcom_ctx_profile_enable(imcom_ctx *ctx, int on)
 
 int imcom_ctx_profile_reset(imcom_ctx *ctx)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_TRY(profile_collect(ctx));
     ctx->prof.clear();
     return IMCOM_OK;
@@ -1028,7 +1089,7 @@ int imcom_ctx_profile_reset(imcom_ctx *ctx)
 
 int imcom_ctx_profile_get(imcom_ctx *ctx, const char *family, double *ms, long *launches)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(family && ms && launches, "null argument");
     IMCOM_TRY(profile_collect(ctx));
     auto it = ctx->prof.find(family);
@@ -1039,12 +1100,12 @@ int imcom_ctx_profile_get(imcom_ctx *ctx, const char *family, double *ms, long *
 
 int imcom_ctx_mfma_probe(imcom_ctx *ctx, double millis, double *tflops)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(tflops && millis > 0.0 && millis <= 5000.0, "bad arguments (millis in (0, 5000])");
     const int nwg = 2 * ctx->cu_count;  // two 8-wave workgroups per CU: four waves per SIMD, all resident at once
     IMCOM_TRY(ws_reserve(ctx, 4096));
-    double *sink = (double *)ws_take(ctx, 8);
-    if (!sink) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+    double *sink;
+    IMCOM_TRY(ws_take(ctx, 1, &sink, "imcom_ctx_mfma_probe"));
     hipEvent_t e0, e1;
     IMCOM_HIP_CHECK(hipEventCreate(&e0));
     IMCOM_HIP_CHECK(hipEventCreate(&e1));
@@ -1068,14 +1129,14 @@ int imcom_ctx_mfma_probe(imcom_ctx *ctx, double millis, double *tflops)
 
 int imcom_ctx_gemm_probe(imcom_ctx *ctx, int variant, int M, int N, int K, int batch, int reps, double *tflops)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(variant == 0 || (variant >= 2 && variant <= 4), "gemm probe variant %d: 0, 2, 3 or 4", variant);
     IMCOM_REQUIRE(tflops && M >= 256 && N >= 128 && K >= 16 && batch >= 1 && reps >= 1, "bad arguments");
     IMCOM_REQUIRE(M % 256 == 0 && N % 128 == 0 && K % 16 == 0, "gemm probe: M % 256, N % 128, K % 16");
     const size_t a = (size_t)batch * M * K * 8, b = (size_t)batch * K * N * 8, c = (size_t)batch * M * N * 8;
     IMCOM_TRY(ws_reserve(ctx, a + b + c + 4096));
     double *A = (double *)ws_take(ctx, a), *B = (double *)ws_take(ctx, b), *C = (double *)ws_take(ctx, c);
-    if (!A || !B || !C) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+    if (!A || !B || !C) return ws_short("imcom_ctx_gemm_probe");
     IMCOM_TRY(launch_probe_fill(ctx, A, (long)(a / 8), 1u));  // pseudo-random operands: the power (and clock) of real data
     IMCOM_TRY(launch_probe_fill(ctx, B, (long)(b / 8), 2u));
     hipEvent_t e0, e1;
@@ -1103,130 +1164,129 @@ int imcom_ctx_gemm_probe(imcom_ctx *ctx, int variant, int M, int N, int K, int b
 }
 
 // ---------------------------------------------------------------------------------------------
-// native-routine seam: host pointers are staged through the workspace; device pointers used as is.
-#define IMCOM_STAGE_IN(T, name, src, count)                                                   \
-    T *name = (T *)(src);                                                                     \
-    if (host) {                                                                               \
-        name = (T *)ws_take(ctx, (size_t)(count) * sizeof(T));                                \
-        if (!name) { set_error("internal: workspace plan too small"); return IMCOM_ERR_NOMEM; } \
-        IMCOM_HIP_CHECK(hipMemcpyAsync(name, src, (size_t)(count) * sizeof(T), hipMemcpyHostToDevice, ctx->stream)); \
-    }
-#define IMCOM_STAGE_OUT(T, name, dst, count)                                                  \
-    if (host) {                                                                               \
-        IMCOM_HIP_CHECK(hipMemcpyAsync(dst, name, (size_t)(count) * sizeof(T), hipMemcpyDeviceToHost, ctx->stream)); \
-    }
-
+// native-routine seam: host pointers are staged through the workspace; device pointers used as is (Stage).
 int imcom_d5512_getw(imcom_ctx *ctx, const double *fh, long n, double *w, int memspace)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(n >= 0 && (n == 0 || (fh && w)), "bad arguments");
     if (n == 0) return IMCOM_OK;
-    const bool host = memspace == IMCOM_MEM_HOST;
-    if (host) IMCOM_TRY(ws_reserve(ctx, (size_t)n * 11 * 8 + 1024));
-    IMCOM_STAGE_IN(double, fh_d, fh, n);
-    IMCOM_STAGE_IN(double, w_d, w, n * 10);
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    st.plan(plan, {(size_t)n * 8, (size_t)n * 10 * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *fh_d;
+    double *w_d;
+    IMCOM_TRY(st.in(fh, n, &fh_d));
+    IMCOM_TRY(st.inout(w, (size_t)n * 10, &w_d));
     IMCOM_TRY(launch_getw(ctx, fh_d, n, w_d));
-    IMCOM_STAGE_OUT(double, w_d, w, n * 10);
-    if (host) IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(w, w_d, (size_t)n * 10));
+    return st.done();
 }
 
 int imcom_interp_d5512(imcom_ctx *ctx, const double *infunc, int nlayer, int ngy, int ngx, const double *xpos,
                        const double *ypos, long nout, double *fhatout, int sym, int memspace)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(infunc && xpos && ypos && fhatout, "null pointer");
     IMCOM_REQUIRE(nlayer >= 1 && ngy >= 1 && ngx >= 1 && nout >= 0, "bad sizes");
     if (sym) {
         long sq = (long)sqrt((double)(nout + 1));
         IMCOM_REQUIRE(sq * sq <= nout, "iD5512C_sym: nout=%ld smaller than its square side^2", nout);
     }
-    const bool host = memspace == IMCOM_MEM_HOST;
+    Stage st(ctx, memspace, __func__);
     const size_t ntab = (size_t)nlayer * ngy * ngx, no = (size_t)nlayer * nout;
-    if (host) IMCOM_TRY(ws_reserve(ctx, (ntab + 2 * (size_t)nout + no) * 8 + 4096));
-    IMCOM_STAGE_IN(double, f_d, infunc, ntab);
-    IMCOM_STAGE_IN(double, x_d, xpos, nout);
-    IMCOM_STAGE_IN(double, y_d, ypos, nout);
-    IMCOM_STAGE_IN(double, o_d, fhatout, no);  // in-place semantics: untouched elements keep their values
+    WsPlan plan;
+    st.plan(plan, {ntab * 8, (size_t)nout * 8, (size_t)nout * 8, no * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *f_d, *x_d, *y_d;
+    double *o_d;
+    IMCOM_TRY(st.in(infunc, ntab, &f_d));
+    IMCOM_TRY(st.in(xpos, nout, &x_d));
+    IMCOM_TRY(st.in(ypos, nout, &y_d));
+    IMCOM_TRY(st.inout(fhatout, no, &o_d));  // in-place semantics: untouched elements keep their values
     { ProfScope ps(ctx, "interp"); IMCOM_TRY(launch_interp(ctx, f_d, nlayer, ngy, ngx, x_d, y_d, nout, o_d, sym)); }
-    IMCOM_STAGE_OUT(double, o_d, fhatout, no);
-    if (host) IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(fhatout, o_d, no));
+    return st.done();
 }
 
 int imcom_grid_d5512(imcom_ctx *ctx, const double *infunc, int ngy, int ngx, const double *xpos, const double *ypos,
                      long npi, int nxo, int nyo, double *fhatout, int memspace)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(infunc && xpos && ypos && fhatout, "null pointer");
     IMCOM_REQUIRE(ngy >= 10 && ngx >= 10 && npi >= 0 && nxo >= 1 && nyo >= 1, "bad sizes");
-    const bool host = memspace == IMCOM_MEM_HOST;
+    Stage st(ctx, memspace, __func__);
     const size_t ntab = (size_t)ngy * ngx, no = (size_t)npi * nxo * nyo;
-    if (host) IMCOM_TRY(ws_reserve(ctx, (ntab + (size_t)npi * (nxo + nyo) + no) * 8 + 4096));
-    IMCOM_STAGE_IN(double, f_d, infunc, ntab);
-    IMCOM_STAGE_IN(double, x_d, xpos, (size_t)npi * nxo);
-    IMCOM_STAGE_IN(double, y_d, ypos, (size_t)npi * nyo);
-    double *o_d = fhatout;
-    if (host) { o_d = (double *)ws_take(ctx, no * 8); if (!o_d) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; } }
+    WsPlan plan;
+    st.plan(plan, {ntab * 8, (size_t)npi * nxo * 8, (size_t)npi * nyo * 8, no * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *f_d, *x_d, *y_d;
+    double *o_d;
+    IMCOM_TRY(st.in(infunc, ntab, &f_d));
+    IMCOM_TRY(st.in(xpos, (size_t)npi * nxo, &x_d));
+    IMCOM_TRY(st.in(ypos, (size_t)npi * nyo, &y_d));
+    IMCOM_TRY(st.out(fhatout, no, &o_d));
     { ProfScope ps(ctx, "interp"); IMCOM_TRY(launch_grid(ctx, f_d, ngy, ngx, x_d, y_d, npi, nxo, nyo, o_d)); }
-    IMCOM_STAGE_OUT(double, o_d, fhatout, no);
-    if (host) IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(fhatout, o_d, no));
+    return st.done();
 }
 
 int imcom_lakernel1(imcom_ctx *ctx, const double *lam, const double *mPhalf, long m, long n, double C, double targetleak,
                     double kCmin, double kCmax, int nbis, double *kappa, double *Sigma, double *UC, double *T, double smax,
                     int memspace)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(lam && mPhalf && kappa && Sigma && UC && T, "null pointer");
     IMCOM_REQUIRE(m >= 0 && n >= 0 && nbis >= 0, "bad sizes");
-    const bool host = memspace == IMCOM_MEM_HOST;
-    if (host) IMCOM_TRY(ws_reserve(ctx, ((size_t)n + 2 * (size_t)m * n + 3 * (size_t)m) * 8 + 8192));
-    IMCOM_STAGE_IN(double, lam_d, lam, n);
-    IMCOM_STAGE_IN(double, p_d, mPhalf, (size_t)m * n);
-    double *k_d = kappa, *S_d = Sigma, *U_d = UC, *T_d = T;
-    if (host) {
-        k_d = (double *)ws_take(ctx, (size_t)m * 8); S_d = (double *)ws_take(ctx, (size_t)m * 8);
-        U_d = (double *)ws_take(ctx, (size_t)m * 8); T_d = (double *)ws_take(ctx, (size_t)m * n * 8);
-        if (!k_d || !S_d || !U_d || !T_d) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-    }
+    Stage st(ctx, memspace, __func__);
+    const size_t mn = (size_t)m * n;
+    WsPlan plan;
+    st.plan(plan, {(size_t)n * 8, mn * 8, (size_t)m * 8, (size_t)m * 8, (size_t)m * 8, mn * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *lam_d, *p_d;
+    double *k_d, *S_d, *U_d, *T_d;
+    IMCOM_TRY(st.in(lam, n, &lam_d));
+    IMCOM_TRY(st.in(mPhalf, mn, &p_d));
+    IMCOM_TRY(st.out(kappa, m, &k_d));
+    IMCOM_TRY(st.out(Sigma, m, &S_d));
+    IMCOM_TRY(st.out(UC, m, &U_d));
+    IMCOM_TRY(st.out(T, mn, &T_d));
     { ProfScope ps(ctx, "lakernel1"); IMCOM_TRY(launch_lakernel1(ctx, lam_d, p_d, m, n, n, C, targetleak, kCmin, kCmax, nbis, k_d, S_d, U_d, T_d, n, smax)); }
-    IMCOM_STAGE_OUT(double, k_d, kappa, m);
-    IMCOM_STAGE_OUT(double, S_d, Sigma, m);
-    IMCOM_STAGE_OUT(double, U_d, UC, m);
-    IMCOM_STAGE_OUT(double, T_d, T, (size_t)m * n);
-    if (host) IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(kappa, k_d, m));
+    IMCOM_TRY(st.back(Sigma, S_d, m));
+    IMCOM_TRY(st.back(UC, U_d, m));
+    IMCOM_TRY(st.back(T, T_d, mn));
+    return st.done();
 }
 
 int imcom_build_reduced_T(imcom_ctx *ctx, const double *Nflat, const double *Dflat, const double *Eflat, const double *kappa,
                           int nv, long m, double ucmin, double smax, double *out_kappa, double *out_Sigma, double *out_UC,
                           double *out_w, int memspace)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(Nflat && Dflat && Eflat && kappa && out_kappa && out_Sigma && out_UC && out_w, "null pointer");
     IMCOM_REQUIRE(m >= 0 && nv >= 2, "bad sizes (nv must be >= 2, routine.py:537)");
-    const bool host = memspace == IMCOM_MEM_HOST;
-    const size_t nv2 = (size_t)nv * nv;
-    if (host) IMCOM_TRY(ws_reserve(ctx, ((size_t)m * (2 * nv2 + 2 * nv + 3) + nv) * 8 + 8192));
-    IMCOM_STAGE_IN(double, N_d, Nflat, (size_t)m * nv2);
-    IMCOM_STAGE_IN(double, D_d, Dflat, (size_t)m * nv);
-    IMCOM_STAGE_IN(double, E_d, Eflat, (size_t)m * nv2);
-    IMCOM_STAGE_IN(double, k_d, kappa, nv);
-    double *ok = out_kappa, *oS = out_Sigma, *oU = out_UC, *ow = out_w;
-    if (host) {
-        ok = (double *)ws_take(ctx, (size_t)m * 8); oS = (double *)ws_take(ctx, (size_t)m * 8);
-        oU = (double *)ws_take(ctx, (size_t)m * 8); ow = (double *)ws_take(ctx, (size_t)m * nv * 8);
-        if (!ok || !oS || !oU || !ow) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-    }
+    Stage st(ctx, memspace, __func__);
+    const size_t nv2 = (size_t)nv * nv, mv = (size_t)m * nv;
+    WsPlan plan;
+    st.plan(plan, {(size_t)m * nv2 * 8, mv * 8, (size_t)m * nv2 * 8, (size_t)nv * 8, (size_t)m * 8, (size_t)m * 8, (size_t)m * 8, mv * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *N_d, *D_d, *E_d, *k_d;
+    double *ok, *oS, *oU, *ow;
+    IMCOM_TRY(st.in(Nflat, (size_t)m * nv2, &N_d));
+    IMCOM_TRY(st.in(Dflat, mv, &D_d));
+    IMCOM_TRY(st.in(Eflat, (size_t)m * nv2, &E_d));
+    IMCOM_TRY(st.in(kappa, nv, &k_d));
+    IMCOM_TRY(st.out(out_kappa, m, &ok));
+    IMCOM_TRY(st.out(out_Sigma, m, &oS));
+    IMCOM_TRY(st.out(out_UC, m, &oU));
+    IMCOM_TRY(st.out(out_w, mv, &ow));
     { ProfScope ps(ctx, "reduced_T"); IMCOM_TRY(launch_build_reduced_T(ctx, N_d, D_d, E_d, k_d, nv, m, ucmin, smax, ok, oS, oU, ow)); }
-    IMCOM_STAGE_OUT(double, ok, out_kappa, m);
-    IMCOM_STAGE_OUT(double, oS, out_Sigma, m);
-    IMCOM_STAGE_OUT(double, oU, out_UC, m);
-    IMCOM_STAGE_OUT(double, ow, out_w, (size_t)m * nv);
-    if (host) IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(out_kappa, ok, m));
+    IMCOM_TRY(st.back(out_Sigma, oS, m));
+    IMCOM_TRY(st.back(out_UC, oU, m));
+    IMCOM_TRY(st.back(out_w, ow, mv));
+    return st.done();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1234,73 +1294,51 @@ int imcom_solve_chol(imcom_ctx *ctx, int batch, const int *n, int ldn, int m, co
                      const double *C, const double *kappaC, int nv, double ucmin, double smax, float *T, float *UC,
                      float *Sigma, float *kappa, int *info, int memspace)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && n && C && kappaC && UC && Sigma && kappa && info, "null pointer / empty batch");
     IMCOM_REQUIRE(m >= 1 && nv >= 1 && ldn >= 0, "bad sizes");
     IMCOM_REQUIRE(nv <= CHOL_MAXNV, "nv=%d kappa nodes: at most %d", nv, CHOL_MAXNV);
-    int nmax = 0;
-    for (int s = 0; s < batch; s++) {
-        IMCOM_REQUIRE(n[s] >= 0 && n[s] <= ldn, "n[%d]=%d exceeds ldn=%d", s, n[s], ldn);
-        if (n[s] > nmax) nmax = n[s];
-    }
+    int nmax;
+    IMCOM_TRY(batch_sizes(n, batch, ldn, &nmax));
     IMCOM_REQUIRE(nmax == 0 || (A && mBhalf && T), "null matrix pointer");
-    const bool host = memspace == IMCOM_MEM_HOST;
+    Stage st(ctx, memspace, __func__);
     const int Np = (int)align_up((size_t)(nmax > 0 ? nmax : 1), NB), mp = (int)align_up((size_t)m, NB);
     const size_t szA = (size_t)batch * ldn * ldn, szB = (size_t)batch * m * ldn, szM = (size_t)batch * m;
     WsPlan plan;
-    if (host) { plan.add(szA * 8); plan.add(szB * 8); plan.add(szB * 4); plan.add(szM * 4 * 3); }
+    st.plan(plan, {szA * 8, szB * 8, szB * 4, szM * 4, szM * 4, szM * 4});
     plan.add((size_t)batch * Np * Np * 8);  // Ap
     plan.add((size_t)batch * Np * mp * 8);  // Bt
     plan.add((size_t)batch * Np * mp * 4);  // Tt
     plan.add((size_t)batch * 4);            // n
     IMCOM_TRY(ws_reserve(ctx, plan.total + chol_core_bytes(batch, Np, m, mp, nv) + 8192));
-    IMCOM_STAGE_IN(double, A_d, A, szA);
+    const double *A_d;
+    double *B_d;
+    float *T_d, *UC_d, *Sig_d, *kap_d;
+    IMCOM_TRY(st.in(A, szA, &A_d));
     // -B/2 is not needed before the triangular solves: from host memory it is uploaded on the context's second queue while the
     // factorisation runs (a third of a stamp's 100 MB over PCIe moves behind 3 ms of Cholesky)
-    double *B_d = (double *)mBhalf;
-    if (host) {
-        B_d = (double *)ws_take(ctx, szB * 8);
-        if (!B_d) { set_error("internal: workspace plan too small"); return IMCOM_ERR_NOMEM; }
-    }
-    float *T_d = T, *UC_d = UC, *Sig_d = Sigma, *kap_d = kappa;
-    if (host) {
-        T_d = (float *)ws_take(ctx, szB * 4);
-        UC_d = (float *)ws_take(ctx, szM * 4 * 3);
-        Sig_d = UC_d + szM;
-        kap_d = Sig_d + szM;
-    }
+    IMCOM_TRY(st.out((double *)mBhalf, szB, &B_d));
+    IMCOM_TRY(st.out(T, szB, &T_d));
+    IMCOM_TRY(st.out(UC, szM, &UC_d));
+    IMCOM_TRY(st.out(Sigma, szM, &Sig_d));
+    IMCOM_TRY(st.out(kappa, szM, &kap_d));
     double *Ap = (double *)ws_take(ctx, (size_t)batch * Np * Np * 8);
     double *Bt = (double *)ws_take(ctx, (size_t)batch * Np * mp * 8);
     float *Tt = (float *)ws_take(ctx, (size_t)batch * Np * mp * 4);
     int *n_dev = (int *)ws_take(ctx, (size_t)batch * 4);
-    if (!Ap || !Bt || !Tt || !n_dev || (host && (!T_d || !UC_d))) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+    if (!Ap || !Bt || !Tt || !n_dev) return ws_short(__func__);
     IMCOM_TRY(upload(ctx, n_dev, n, batch));
     {
         ProfScope ps(ctx, "pack");
         IMCOM_TRY(launch_pack_A(ctx, A_d, ldn, n_dev, Ap, Np, batch));
     }
-    hipEvent_t ev_entry = nullptr;
-    if (host && szB > 0) {
-        while (ctx->sync_events.size() < 2) {
-            hipEvent_t e;
-            IMCOM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ctx->sync_events.push_back(e);
-        }
-        ev_entry = ctx->sync_events[1];
-        IMCOM_HIP_CHECK(hipEventRecord(ev_entry, ctx->stream));  // everything earlier calls left on the main stream
-    }
+    const bool aux_B = st.host && szB > 0;
+    if (aux_B) IMCOM_TRY(mark_entry(ctx));
     auto stage_B = [&]() -> int {
-        if (host && szB > 0) {
-            hipEvent_t ev = ctx->sync_events[0];
-            // the copy lands in workspace that kernels of an EARLIER, un-synchronised device-mode call on this context may still be
-            // using: it waits for the point the main stream had reached when this call began (ev_entry) -- not for this call's own
-            // factorisation, behind which it is meant to hide
-            IMCOM_TRY(ensure_aux(ctx));
-            IMCOM_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ev_entry, 0));
-            IMCOM_HIP_CHECK(hipMemcpyAsync(B_d, mBhalf, szB * 8, hipMemcpyHostToDevice, ctx->aux_stream));
-            IMCOM_HIP_CHECK(hipEventRecord(ev, ctx->aux_stream));
-            IMCOM_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ev, 0));
-        }
+        if (aux_B) IMCOM_TRY(upload_behind_entry(ctx, [&](hipStream_t aux) -> int {
+            IMCOM_HIP_CHECK(hipMemcpyAsync(B_d, mBhalf, szB * 8, hipMemcpyHostToDevice, aux));
+            return IMCOM_OK;
+        }));
         ProfScope ps(ctx, "pack");
         return launch_pack_Bt(ctx, B_d, ldn, m, n_dev, Bt, Np, mp, batch);
     };
@@ -1310,16 +1348,15 @@ int imcom_solve_chol(imcom_ctx *ctx, int batch, const int *n, int ldn, int m, co
     const int rc_core = chol_core(ctx, batch, n, Np, m, mp, Ap, Bt, C, kappaC, nv, ucmin, smax, Tt, UC_d, Sig_d, kap_d, info, stage_B, nullptr, false,
                                   (ctx->repair_expect && nv == 1) ? expect_all.data() : nullptr);
     if (rc_core != IMCOM_OK) {
-        if (host && ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream);  // nothing of this call may still be copying into the workspace
+        if (st.host && ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream);  // nothing of this call may still be copying into the workspace
         return rc_core;
     }
     if (ldn > 0) { ProfScope ps(ctx, "pack"); IMCOM_TRY(launch_unpack_T(ctx, Tt, Np, mp, n_dev, m, T_d, ldn, batch)); }
-    IMCOM_STAGE_OUT(float, T_d, T, szB);
-    IMCOM_STAGE_OUT(float, UC_d, UC, szM);
-    IMCOM_STAGE_OUT(float, Sig_d, Sigma, szM);
-    IMCOM_STAGE_OUT(float, kap_d, kappa, szM);
-    if (host) IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(T, T_d, szB));
+    IMCOM_TRY(st.back(UC, UC_d, szM));
+    IMCOM_TRY(st.back(Sigma, Sig_d, szM));
+    IMCOM_TRY(st.back(kappa, kap_d, szM));
+    return st.done();
 }
 
 // The same kernel for SEVERAL OutStamps per call, each with its own host arrays (the four OutStamps of a 2 x 2 group, say): one
@@ -1328,7 +1365,7 @@ int imcom_solve_chol_stamps(imcom_ctx *ctx, int nst, const int *n, int m, const 
                             const double *C, const double *kappaC, int nv, double ucmin, double smax, float *const *T,
                             float *const *UC, float *const *Sigma, float *const *kappa, int *info)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(nst >= 1 && n && A && mBhalf && C && kappaC && T && UC && Sigma && kappa && info, "null pointer / no stamps");
     IMCOM_REQUIRE(m >= 1 && nv >= 1, "bad sizes");
     IMCOM_REQUIRE(nv <= CHOL_MAXNV, "nv=%d kappa nodes: at most %d", nv, CHOL_MAXNV);
@@ -1355,18 +1392,13 @@ int imcom_solve_chol_stamps(imcom_ctx *ctx, int nst, const int *n, int m, const 
     double *Ap = (double *)ws_take(ctx, (size_t)nst * Np * Np * 8), *Bt = (double *)ws_take(ctx, (size_t)nst * Np * mp * 8);
     float *Tt = (float *)ws_take(ctx, (size_t)nst * Np * mp * 4);
     int *n_dev = (int *)ws_take(ctx, (size_t)nst * 4);
-    if (!rawA || !rawB || !rawT || !maps || !Ap || !Bt || !Tt || !n_dev) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+    if (!rawA || !rawB || !rawT || !maps || !Ap || !Bt || !Tt || !n_dev) return ws_short(__func__);
     float *UC_d = maps, *Sig_d = maps + szM, *kap_d = maps + 2 * szM;
     IMCOM_TRY(upload(ctx, n_dev, n, nst));
     std::vector<size_t> offA(nst), offB(nst);
     {
         size_t a = 0, b = 0;
         for (int s = 0; s < nst; s++) { offA[s] = a; offB[s] = b; a += align_up((size_t)n[s] * n[s], 32); b += align_up((size_t)m * n[s], 32); }
-    }
-    while (ctx->sync_events.size() < 2) {
-        hipEvent_t e;
-        IMCOM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->sync_events.push_back(e);
     }
     const bool timing = env_is("IMCOM_SEAM_TIMING");  // host-side timeline of the call on stderr (adds a synchronisation)
     auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -1379,20 +1411,17 @@ int imcom_solve_chol_stamps(imcom_ctx *ctx, int nst, const int *n, int m, const 
         ProfScope ps(ctx, "pack");
         IMCOM_TRY(launch_pack_A(ctx, rawA + offA[s], n[s], n_dev + s, Ap + (size_t)s * Np * Np, Np, 1));
     }
-    hipEvent_t ev_entry = ctx->sync_events[1];
-    IMCOM_HIP_CHECK(hipEventRecord(ev_entry, ctx->stream));
+    IMCOM_TRY(mark_entry(ctx));
     tA = now();
     // -B/2 is called for when the factorisation's launches are queued: its upload (host-blocking from pageable memory) runs on the
     // second queue while the GPU factors
     auto stage_B = [&]() -> int {
-        hipEvent_t ev = ctx->sync_events[0];
         tB0 = now();
-        IMCOM_TRY(ensure_aux(ctx));
-        IMCOM_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ev_entry, 0));
-        for (int s = 0; s < nst; s++)
-            if (n[s] > 0) IMCOM_HIP_CHECK(hipMemcpyAsync(rawB + offB[s], mBhalf[s], (size_t)m * n[s] * 8, hipMemcpyHostToDevice, ctx->aux_stream));
-        IMCOM_HIP_CHECK(hipEventRecord(ev, ctx->aux_stream));
-        IMCOM_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ev, 0));
+        IMCOM_TRY(upload_behind_entry(ctx, [&](hipStream_t aux) -> int {
+            for (int s = 0; s < nst; s++)
+                if (n[s] > 0) IMCOM_HIP_CHECK(hipMemcpyAsync(rawB + offB[s], mBhalf[s], (size_t)m * n[s] * 8, hipMemcpyHostToDevice, aux));
+            return IMCOM_OK;
+        }));
         tB1 = now();
         ProfScope ps(ctx, "pack");
         for (int s = 0; s < nst; s++)
@@ -1428,10 +1457,8 @@ int imcom_solve_chol_resident(imcom_ctx *ctx, int batch, const int *n_host, int 
                               const double *Bt, const double *C_host, const double *kappaC_host, int nv, double ucmin,
                               double smax, float *Tt, float *UC, float *Sigma, float *kappa, int *info_host)
 {
-    IMCOM_TRY(check_ctx(ctx));
-    IMCOM_REQUIRE(batch >= 1 && n_host && A && Bt && C_host && kappaC_host && Tt && UC && Sigma && kappa && info_host, "null pointer");
-    IMCOM_REQUIRE(ldn >= NB && ldn % NB == 0 && ldm % NB == 0 && m >= 1 && m <= ldm && nv >= 1, "ldn=%d / ldm=%d must be multiples of %d", ldn, ldm, NB);
-    IMCOM_REQUIRE(nv <= CHOL_MAXNV, "nv=%d kappa nodes: at most %d", nv, CHOL_MAXNV);
+    IMCOM_TRY(enter(ctx));
+    IMCOM_TRY(resident_args(batch, n_host, ldn, m, ldm, A, Bt, C_host, kappaC_host, nv, Tt, UC, Sigma, kappa, info_host != nullptr, false, nullptr));
     IMCOM_TRY(ws_reserve(ctx, chol_core_bytes(batch, ldn, m, ldm, nv)));
     return chol_core(ctx, batch, n_host, ldn, m, ldm, A, Bt, C_host, kappaC_host, nv, ucmin, smax, Tt, UC, Sigma, kappa, info_host);
 }
@@ -1446,14 +1473,9 @@ int imcom_solve_chol_resident_begin(imcom_ctx *ctx, int batch, const int *n_host
                                     const double *C_host, const double *kappaC_host, int nv, double ucmin, double smax, float *Tt, float *UC,
                                     float *Sigma, float *kappa)
 {
-    IMCOM_TRY(check_ctx(ctx));
-    IMCOM_REQUIRE(batch >= 1 && n_host && A && Bt && C_host && kappaC_host && Tt && UC && Sigma && kappa, "null pointer");
-    IMCOM_REQUIRE(ldn >= NB && ldn % NB == 0 && ldm % NB == 0 && m >= 1 && m <= ldm && nv >= 1, "ldn=%d / ldm=%d must be multiples of %d", ldn, ldm, NB);
-    IMCOM_REQUIRE(nv <= CHOL_MAXNV, "nv=%d kappa nodes: at most %d", nv, CHOL_MAXNV);
-    if (ctx->deferred_flags != 0) {  // a begin whose end never came (the caller failed in between): its work is waited for and forgotten
-        IMCOM_HIP_CHECK(hipEventSynchronize(ctx->sync_events[2]));
-        ctx->deferred_flags = 0;
-    }
+    IMCOM_TRY(enter(ctx));
+    IMCOM_TRY(resident_args(batch, n_host, ldn, m, ldm, A, Bt, C_host, kappaC_host, nv, Tt, UC, Sigma, kappa, true, false, nullptr));
+    IMCOM_TRY(drain_begin(ctx));
     IMCOM_TRY(ws_reserve(ctx, chol_core_bytes(batch, ldn, m, ldm, nv)));
     std::vector<int> info(batch, 0);
     return chol_core(ctx, batch, n_host, ldn, m, ldm, A, Bt, C_host, kappaC_host, nv, ucmin, smax, Tt, UC, Sigma, kappa, info.data(), nullptr, nullptr, true);
@@ -1461,7 +1483,7 @@ int imcom_solve_chol_resident_begin(imcom_ctx *ctx, int batch, const int *n_host
 
 int imcom_solve_chol_resident_end(imcom_ctx *ctx, int batch, int *info_host)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(info_host && batch >= 1, "null pointer");
     IMCOM_REQUIRE(ctx->deferred_flags > 0 && ctx->deferred_flags % batch == 0, "imcom_solve_chol_resident_end without a matching begin");
     const long cnt = ctx->deferred_flags;
@@ -1487,14 +1509,9 @@ int imcom_solve_chol_resident_redo(imcom_ctx *ctx, int batch, const int *n_host,
                                    const double *C_host, const double *kappaC_host, int nv, double ucmin, double smax, float *Tt, float *UC,
                                    float *Sigma, float *kappa, const int *redo_host, int *info_host)
 {
-    IMCOM_TRY(check_ctx(ctx));
-    IMCOM_REQUIRE(batch >= 1 && n_host && A && Bt && C_host && kappaC_host && Tt && UC && Sigma && kappa && redo_host && info_host, "null pointer");
-    IMCOM_REQUIRE(ldn >= NB && ldn % NB == 0 && ldm % NB == 0 && m >= 1 && m <= ldm, "ldn=%d / ldm=%d must be multiples of %d", ldn, ldm, NB);
-    IMCOM_REQUIRE(nv == 1, "imcom_solve_chol_resident_redo: one kappa node (nv=%d: call imcom_solve_chol_resident)", nv);
-    if (ctx->deferred_flags != 0) {
-        IMCOM_HIP_CHECK(hipEventSynchronize(ctx->sync_events[2]));
-        ctx->deferred_flags = 0;
-    }
+    IMCOM_TRY(enter(ctx));
+    IMCOM_TRY(resident_args(batch, n_host, ldn, m, ldm, A, Bt, C_host, kappaC_host, nv, Tt, UC, Sigma, kappa, redo_host && info_host, true, nullptr));
+    IMCOM_TRY(drain_begin(ctx));
     IMCOM_TRY(ws_reserve(ctx, chol_core_bytes(batch, ldn, m, ldm, nv)));
     return chol_core(ctx, batch, n_host, ldn, m, ldm, A, Bt, C_host, kappaC_host, nv, ucmin, smax, Tt, UC, Sigma, kappa, info_host, nullptr, nullptr, false, redo_host);
 }
@@ -1507,15 +1524,9 @@ int imcom_solve_chol_resident_coadd(imcom_ctx *ctx, int batch, const int *n_host
                                     float *Sigma, float *kappa, int *info_host, int n2f, int fade, int n2, const float *indata, int n_inframe,
                                     const int *expo, int n_expo, float *outimage, double *Tsum_stamp, double *Tsum_inpix, double *Neff)
 {
-    IMCOM_TRY(check_ctx(ctx));
-    IMCOM_REQUIRE(batch >= 1 && n_host && A && Bt && C_host && kappaC_host && Tt && UC && Sigma && kappa && info_host, "null pointer");
-    IMCOM_REQUIRE(indata && expo && outimage && Tsum_stamp && Tsum_inpix && Neff, "null pointer (coaddition)");
-    IMCOM_REQUIRE(ldn >= NB && ldn % NB == 0 && ldm % NB == 0 && m >= 1 && m <= ldm && nv >= 1, "ldn=%d / ldm=%d must be multiples of %d", ldn, ldm, NB);
-    IMCOM_REQUIRE(nv <= CHOL_MAXNV, "nv=%d kappa nodes: at most %d", nv, CHOL_MAXNV);
-    IMCOM_REQUIRE(m == n2f * n2f && n_inframe >= 1 && n_expo >= 1 && fade >= 0 && n2 >= 1, "bad sizes (coaddition)");
-    IMCOM_REQUIRE(fade == 0, "imcom_solve_chol_resident_coadd: fade = %d -- the map tapers of coadd.py:1118-1122 come between the solve and the coaddition: "
-                             "call imcom_solve_chol_resident, imcom_trapezoid_f32, imcom_coadd_epilogue", fade);
+    IMCOM_TRY(enter(ctx));
     const CoaddArgs co{n2f, fade, n2, n_inframe, n_expo, indata, expo, outimage, Tsum_stamp, Tsum_inpix, Neff};
+    IMCOM_TRY(resident_args(batch, n_host, ldn, m, ldm, A, Bt, C_host, kappaC_host, nv, Tt, UC, Sigma, kappa, info_host != nullptr, false, &co));
     IMCOM_TRY(ws_reserve(ctx, chol_core_bytes(batch, ldn, m, ldm, nv) + coadd_fuse_bytes(batch, ldn, m, ldm, nv, &co)));
     return chol_core(ctx, batch, n_host, ldn, m, ldm, A, Bt, C_host, kappaC_host, nv, ucmin, smax, Tt, UC, Sigma, kappa, info_host, nullptr, &co);
 }
@@ -1525,7 +1536,7 @@ int imcom_build_A(imcom_ctx *ctx, int batch, const int *n_host, int ldn, const d
                   const double *tables, int ntab, const imcom_table_geom *geom, const int *pair_tab, const double *pair_pen,
                   int npsf_max, double *A)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && n_host && x && y && psf && tables && geom && pair_tab && pair_pen && A, "null pointer");
     IMCOM_REQUIRE(ldn >= 1 && ntab >= 1 && npsf_max >= 1 && geom->nsamp >= 1 && geom->dscale > 0, "bad sizes");
     const long nt_ = (ldn + 15) / 16, tiles_ = nt_ * (nt_ + 1) / 2 * batch;  // per-stamp tile order by PSF pair: key + descriptor per tile, bins per stamp
@@ -1541,7 +1552,7 @@ int imcom_build_B(imcom_ctx *ctx, int batch, const int *n_host, int ldn, const d
                   const double *tables, int ntab, const imcom_table_geom *geom, const int *io_tab, int npsf_max,
                   const double *out_x0, const double *out_y0, int n2f, int ldm, double *Bt)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && n_host && x && y && psf && tables && geom && io_tab && out_x0 && out_y0 && Bt, "null pointer");
     IMCOM_REQUIRE(ldn >= 1 && ntab >= 1 && npsf_max >= 1 && n2f >= 1 && ldm >= n2f * n2f, "bad sizes");
     IMCOM_TRY(ws_reserve(ctx, (size_t)batch * 4 + 1024));
@@ -1556,7 +1567,7 @@ int imcom_coadd_epilogue(imcom_ctx *ctx, int batch, const int *n_host, int ldn, 
                          float *Tt, const float *indata, int n_inframe, const int *expo, int n_expo, float *outimage,
                          double *Tsum_stamp, double *Tsum_inpix, double *Neff)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && n_host && Tt && indata && expo && outimage && Tsum_stamp && Tsum_inpix && Neff, "null pointer");
     IMCOM_REQUIRE(m == n2f * n2f && m <= ldm && n_inframe >= 1 && n_expo >= 1 && fade >= 0 && n2 >= 1, "bad sizes");
     IMCOM_TRY(ws_reserve(ctx, (size_t)batch * 4 + (size_t)batch * m * n_expo * 8 + 2048));
@@ -1570,14 +1581,14 @@ int imcom_coadd_epilogue(imcom_ctx *ctx, int batch, const int *n_host, int ldn, 
 
 int imcom_trapezoid_f32(imcom_ctx *ctx, float *maps, long nmaps, int n2f, int fade)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(maps && nmaps >= 0 && n2f >= 1 && fade >= 0, "bad arguments");
     return launch_trapezoid_f32(ctx, maps, nmaps, n2f, fade);
 }
 
 int imcom_clamp_min_f32(imcom_ctx *ctx, float *maps, long count, float lo)
 {
-    IMCOM_TRY(check_ctx(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(count >= 0 && (count == 0 || maps), "bad arguments");
     return launch_clamp_min_f32(ctx, maps, count, lo);
 }

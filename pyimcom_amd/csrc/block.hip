@@ -104,8 +104,7 @@ using namespace imcom;
 extern "C" int imcom_block_accumulate(imcom_ctx *ctx, int batch, const int *jst_host, const int *ist_host, int n2, int fade,
                                       int nlayer, const void *src, int src_is_f64, float *dst, int nside_pf)
 {
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && jst_host && ist_host && src && dst && n2 >= 1 && fade >= 0 && nlayer >= 1, "bad arguments");
     const int n2f = n2 + 2 * fade;
     IMCOM_REQUIRE(2 * fade <= n2, "fade=%d: neighbouring stamps must overlap by less than a stamp", fade);
@@ -143,8 +142,7 @@ extern "C" int imcom_block_accumulate(imcom_ctx *ctx, int batch, const int *jst_
 extern "C" int imcom_block_place(imcom_ctx *ctx, int batch, const int *jst_host, const int *ist_host, int n2, int fade, int nlayer,
                                  const void *src, int src_is_f64, void *layers, int nside_pf)
 {
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && jst_host && ist_host && src && layers && n2 >= 1 && fade >= 0 && nlayer >= 1, "bad arguments");
     const int n2f = n2 + 2 * fade;
     IMCOM_REQUIRE(2 * fade <= n2, "fade=%d: neighbouring stamps must overlap by less than a stamp", fade);
@@ -169,8 +167,7 @@ extern "C" int imcom_block_place(imcom_ctx *ctx, int batch, const int *jst_host,
 extern "C" int imcom_block_combine(imcom_ctx *ctx, int n1P, int n2, int fade, long nlayer, const void *layers, int src_is_f64, float *dst,
                                    int nside_pf, int order, int j_st_min, int i_st_min)
 {
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(n1P >= 1 && n1P < 32000 && n2 >= 1 && fade >= 0 && nlayer >= 1 && layers && dst && (order == 0 || order == 1) && j_st_min >= 1 && i_st_min >= 1,
                   "bad arguments");
     const int cells = order, pj = j_st_min & 1, pi = i_st_min & 1;  // (only the parity of the window's origin decides which stamps share a cell)
@@ -188,8 +185,7 @@ extern "C" int imcom_block_combine(imcom_ctx *ctx, int n1P, int n2, int fade, lo
 extern "C" int imcom_trapezoid_recover_f32(imcom_ctx *ctx, float *maps, long nmaps, int ny, int nx, int fade, int pad_b, int pad_t,
                                            int pad_l, int pad_r)
 {
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(maps && nmaps >= 0 && ny >= 1 && nx >= 1 && fade >= 0 && pad_b >= 0 && pad_t >= 0 && pad_l >= 0 && pad_r >= 0, "bad arguments");
     if (fade == 0 || nmaps == 0) return IMCOM_OK;
     const long tot = nmaps * ny * nx;
@@ -220,8 +216,7 @@ __global__ void compress_map_kernel(const float *__restrict__ map, long count, f
 
 extern "C" int imcom_compress_map_f32(imcom_ctx *ctx, const float *map, long count, int coef, int is_unsigned, void *out)
 {
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(map && out && count >= 0, "bad arguments");
     if (count == 0) return IMCOM_OK;
     hipLaunchKernelGGL(compress_map_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, map, count, (float)coef,

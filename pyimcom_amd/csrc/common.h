@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -119,6 +120,19 @@ inline int env_int(const char *name, int dflt)
 // is called once per API call with the total, so pointers handed out by ws_take() stay valid.
 int ws_reserve(imcom_ctx *ctx, size_t bytes);
 void *ws_take(imcom_ctx *ctx, size_t bytes);
+// A take that found the workspace short of its plan: the one message for every entry (`who` names it), IMCOM_ERR_NOMEM.
+int ws_short(const char *who);
+template <typename T>
+inline int ws_take(imcom_ctx *ctx, size_t count, T **out, const char *who)
+{
+    *out = (T *)ws_take(ctx, count * sizeof(T));
+    return *out ? IMCOM_OK : ws_short(who);
+}
+// The total a call reserves, summed from the very buffers it then takes (each one at ws_take's 256-byte alignment).
+struct WsPlan {
+    size_t total = 0;
+    size_t add(size_t bytes) { total = align_up(total, 256) + bytes; return total; }
+};
 int pin_reserve(imcom_ctx *ctx, size_t bytes);
 void *pin_take(imcom_ctx *ctx, size_t bytes);
 
@@ -174,5 +188,70 @@ inline int check_launch(const char *what)
     }
     return IMCOM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The C-ABI boundary: what every extern "C" entry does on the way in and out (host code only).
+
+// The entry's context: not null, its device current.
+int enter(imcom_ctx *ctx);
+
+// ctx->sync_events holds at least k plain (no timing) events.
+int ensure_sync_events(imcom_ctx *ctx, size_t k);
+
+// The per-stamp sizes of a batch: 0 <= n[s] <= ldn; *nmax = their largest.
+int batch_sizes(const int *n, int batch, int ldn, int *nmax);
+
+// The `memspace` contract of the staged entries: with IMCOM_MEM_HOST the caller's arrays are host memory and go through the
+// workspace (`plan` counts them, `in` / `inout` copy them over, `out` takes device room for an output, `back` copies it home,
+// `done` waits for the copies); with IMCOM_MEM_DEVICE every pointer is used as it is and nothing is taken, copied or waited for.
+struct Stage {
+    imcom_ctx *ctx;
+    bool host;
+    const char *who;  // the entry (workspace messages)
+    Stage(imcom_ctx *c, int memspace, const char *entry) : ctx(c), host(memspace == IMCOM_MEM_HOST), who(entry) {}
+    void plan(WsPlan &p, std::initializer_list<size_t> bytes) const  // one entry per staged buffer, in bytes
+    {
+        if (host)
+            for (size_t b : bytes) p.add(b);
+    }
+    template <typename T>
+    int in(const T *src, size_t count, const T **dev)
+    {
+        *dev = src;
+        if (!host || !src || count == 0) return IMCOM_OK;
+        T *d;
+        IMCOM_TRY(ws_take(ctx, count, &d, who));
+        IMCOM_HIP_CHECK(hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        *dev = d;
+        return IMCOM_OK;
+    }
+    template <typename T>
+    int inout(T *user, size_t count, T **dev)  // an output the call updates in place: untouched elements keep their values
+    {
+        const T *d;
+        IMCOM_TRY(in((const T *)user, count, &d));
+        *dev = (T *)d;
+        return IMCOM_OK;
+    }
+    template <typename T>
+    int out(T *user, size_t count, T **dev)
+    {
+        *dev = user;
+        if (!host || count == 0) return IMCOM_OK;
+        return ws_take(ctx, count, dev, who);
+    }
+    template <typename T>
+    int back(T *user, const T *dev, size_t count)
+    {
+        if (!host || count == 0) return IMCOM_OK;
+        IMCOM_HIP_CHECK(hipMemcpyAsync(user, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        return IMCOM_OK;
+    }
+    int done()
+    {
+        if (host) IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return IMCOM_OK;
+    }
+};
 
 }  // namespace imcom

@@ -462,45 +462,31 @@ __global__ __launch_bounds__(256) void tri_store_ref_kernel(const double *__rest
 
 using namespace imcom;
 
-static int ctx_ok(imcom_ctx *ctx)
-{
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
-    return IMCOM_OK;
-}
-
 extern "C" int imcom_eigh(imcom_ctx *ctx, int batch, const int *n, int ldn, const double *A, double *lam, double *Q,
                           int memspace)
 {
-    IMCOM_TRY(ctx_ok(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && n && A && lam && Q && ldn >= 1, "bad arguments");
-    int nmax = 0;
-    for (int s = 0; s < batch; s++) { IMCOM_REQUIRE(n[s] >= 0 && n[s] <= ldn, "n[%d]=%d exceeds ldn", s, n[s]); nmax = std::max(nmax, n[s]); }
-    const bool host = memspace == IMCOM_MEM_HOST;
+    int nmax;
+    IMCOM_TRY(batch_sizes(n, batch, ldn, &nmax));
+    Stage st(ctx, memspace, __func__);
     const int ld = (int)align_up((size_t)std::max(nmax, 1), NB);
     const size_t szA = (size_t)batch * ldn * ldn, szL = (size_t)batch * ldn;
-    size_t total = eigh_ws_bytes(batch, ld, true) + 8192;
-    if (host) total += (2 * szA + szL) * 8 + 1024;
-    IMCOM_TRY(ws_reserve(ctx, total));
-    const double *A_d = A;
-    double *lam_d = lam, *Q_d = Q;
-    if (host) {
-        double *t = (double *)ws_take(ctx, szA * 8);
-        Q_d = (double *)ws_take(ctx, szA * 8);
-        lam_d = (double *)ws_take(ctx, szL * 8);
-        if (!t || !Q_d || !lam_d) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-        IMCOM_HIP_CHECK(hipMemcpyAsync(t, A, szA * 8, hipMemcpyHostToDevice, ctx->stream));
-        A_d = t;
-    }
+    WsPlan plan;
+    st.plan(plan, {szA * 8, szA * 8, szL * 8});
+    plan.add(eigh_ws_bytes(batch, ld, true) + 8192);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *A_d;
+    double *lam_d, *Q_d;
+    IMCOM_TRY(st.in(A, szA, &A_d));
+    IMCOM_TRY(st.out(Q, szA, &Q_d));
+    IMCOM_TRY(st.out(lam, szL, &lam_d));
     IMCOM_HIP_CHECK(hipMemsetAsync(Q_d, 0, szA * 8, ctx->stream));
     IMCOM_HIP_CHECK(hipMemsetAsync(lam_d, 0, szL * 8, ctx->stream));
     IMCOM_TRY(eigh_device(ctx, batch, n, ld, A_d, ldn, (long)ldn * ldn, lam_d, ldn, Q_d, ldn, (long)ldn * ldn, nullptr));
-    if (host) {
-        IMCOM_HIP_CHECK(hipMemcpyAsync(lam, lam_d, szL * 8, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(Q, Q_d, szA * 8, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(lam, lam_d, szL));
+    IMCOM_TRY(st.back(Q, Q_d, szA));
+    return st.done();
 }
 
 // The band basis (band.hip) whenever its N x 4 panel fits the LDS (N <= 4.8k); IMCOM_EIGEN_BASIS=tridiagonal keeps round 3's first form
@@ -514,27 +500,26 @@ static bool eigen_uses_band(int np)
 // reflectors V [batch][ldn][ldn] (row r = v_r) and tau [batch][ldn]; A = Q B Q^T with Q = H_0 H_1 ...; ldn a multiple of 128.
 extern "C" int imcom_band_reduce(imcom_ctx *ctx, int batch, const int *n, int ldn, const double *A, double *band, double *V, double *tau, int memspace)
 {
-    IMCOM_TRY(ctx_ok(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && n && A && band && V && tau && ldn >= NB && ldn % NB == 0 && band_basis_fits(ldn), "bad arguments (ldn a multiple of 128, <= 4.8k)");
-    for (int s = 0; s < batch; s++) IMCOM_REQUIRE(n[s] >= 0 && n[s] <= ldn, "n[%d]=%d exceeds ldn", s, n[s]);
-    const bool host = memspace == IMCOM_MEM_HOST;
-    const size_t szA = (size_t)batch * ldn * ldn * 8, szB = (size_t)batch * (BAND_BW + 1) * ldn * 8, szT = (size_t)batch * ldn * 8;
-    IMCOM_TRY(ws_reserve(ctx, band_basis_ws_bytes(batch, ldn, NB) + (host ? szA : 0) + 65536));
-    const double *A_d = A;
-    if (host) {
-        double *t = (double *)ws_take(ctx, szA);
-        if (!t) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-        IMCOM_HIP_CHECK(hipMemcpyAsync(t, A, szA, hipMemcpyHostToDevice, ctx->stream));
-        A_d = t;
-    }
+    int nmax;
+    IMCOM_TRY(batch_sizes(n, batch, ldn, &nmax));
+    Stage st(ctx, memspace, __func__);
+    const size_t szA = (size_t)batch * ldn * ldn, szB = (size_t)batch * (BAND_BW + 1) * ldn, szT = (size_t)batch * ldn;
+    WsPlan plan;
+    st.plan(plan, {szA * 8});
+    plan.add(band_basis_ws_bytes(batch, ldn, NB) + 65536);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *A_d;
+    IMCOM_TRY(st.in(A, szA, &A_d));
     TrdBasis tb;
     IMCOM_TRY(band_basis_device(ctx, batch, n, ldn, NB, A_d, ldn, (long)ldn * ldn, &tb));
-    const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    IMCOM_HIP_CHECK(hipMemcpyAsync(band, tb.band, szB, kind, ctx->stream));
-    IMCOM_HIP_CHECK(hipMemcpyAsync(V, tb.Vall, szA, kind, ctx->stream));
-    IMCOM_HIP_CHECK(hipMemcpyAsync(tau, tb.tauvec, szT, kind, ctx->stream));
-    if (host) IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return IMCOM_OK;
+    // the outputs live in the basis' own buffers: copied out in either memory space
+    const hipMemcpyKind kind = st.host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    IMCOM_HIP_CHECK(hipMemcpyAsync(band, tb.band, szB * 8, kind, ctx->stream));
+    IMCOM_HIP_CHECK(hipMemcpyAsync(V, tb.Vall, szA * 8, kind, ctx->stream));
+    IMCOM_HIP_CHECK(hipMemcpyAsync(tau, tb.tauvec, szT * 8, kind, ctx->stream));
+    return st.done();
 }
 
 static size_t eigen_fallback_bytes(int nf, int np, int mp, int m)
@@ -573,7 +558,7 @@ static int eigen_fallback(imcom_ctx *ctx, const std::vector<int> &idx, const int
         double *X = (double *)ws_take(ctx, nf * big * 8), *P = (double *)ws_take(ctx, nf * big * 8), *S = (double *)ws_take(ctx, nf * big * 8);
         double *pix = (double *)ws_take(ctx, (size_t)nf * m * 8 * 3);
         int *map = (int *)ws_take(ctx, (size_t)nf * 4);
-        if (!Ag || !lam || !Q || !X || !P || !S || !pix || !map) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+        if (!Ag || !lam || !Q || !X || !P || !S || !pix || !map) return ws_short("eigenbasis fallback");
         std::vector<int> nsub(nf);
         IMCOM_HIP_CHECK(hipMemsetAsync(Ag, 0, nf * mat * 8, st));
         IMCOM_HIP_CHECK(hipMemsetAsync(Q, 0, nf * mat * 8, st));
@@ -671,7 +656,7 @@ static int eigen_enqueue(imcom_ctx *ctx, EigenJob &j, int ldn, int m, int np, in
     // the factors between the two sweeps of the final solve: [np][mp] in the tridiagonal basis; in the band basis BAND_BW of them per
     // CHUNK of mp / BAND_BW columns (the same bytes), taken once the reduction has handed its scratch back -- over it, not beside it
     double *Lb = banded ? nullptr : (double *)ws_take(ctx, big);
-    if (!Cb || (!banded && !Lb) || !kpix || !par || !n_early || !flag) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+    if (!Cb || (!banded && !Lb) || !kpix || !par || !n_early || !flag) return ws_short("eigen");
     std::vector<double> ph(4 * (size_t)batch);
     for (int s = 0; s < batch; s++) {
         ph[s] = j.C[s];
@@ -689,11 +674,7 @@ static int eigen_enqueue(imcom_ctx *ctx, EigenJob &j, int ldn, int m, int np, in
     if (banded) {
         // c = Qh^T b panel by panel ON THE SECOND STREAM while the reduction goes on: a panel of 128 reflectors is final long
         // before the matrix is reduced, its GEMMs are matrix-pipe work, the reduction's passes are memory work
-        while (ctx->sync_events.size() < 2) {
-            hipEvent_t e;
-            IMCOM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ctx->sync_events.push_back(e);
-        }
+        IMCOM_TRY(ensure_sync_events(ctx, 2));
         hipEvent_t ev_main = ctx->sync_events[0], ev_aux = ctx->sync_events[1];
         // Worth it while the reduction's one-workgroup-per-stamp step leaves most CUs idle: the products' tiles monopolise a CU
         // (registers, LDS) and the reduction's dependent chain queues behind them.  cfg-3, with / without: batch 32 251 / 265 ms,
@@ -746,8 +727,7 @@ static int eigen_enqueue(imcom_ctx *ctx, EigenJob &j, int ldn, int m, int np, in
             }
             const int mc = band_solve_chunk(mp, batch);
             const size_t mark_l = ctx->ws_used;
-            Lb = (double *)ws_take(ctx, (size_t)batch * BAND_BW * np * mc * 8);
-            if (!Lb) { set_error("internal: workspace (band factors)"); return IMCOM_ERR_NOMEM; }
+            IMCOM_TRY(ws_take(ctx, (size_t)batch * BAND_BW * np * mc, &Lb, "band factors"));
             for (int a0 = 0; a0 < m; a0 += mc)
                 hipLaunchKernelGGL(band_solve_kernel<BAND_BW>, dim3((mc + 63) / 64, batch), dim3(64), 0, st, tb.band, Cb, Lb, np, mp, m, n_early, par, par + batch,
                                    nv > 1 ? kpix : nullptr, j.UC_d, j.Sig_d, j.kap_d, a0, mc);
@@ -860,11 +840,7 @@ static int solve_eigen_core(imcom_ctx *ctx, int batch, const int *n, int ldn, in
         IMCOM_HIP_CHECK(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
         ctx->sub_streams.push_back(s_);
     }
-    while ((int)ctx->sync_events.size() < 3 + nsub) {
-        hipEvent_t e;
-        IMCOM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->sync_events.push_back(e);
-    }
+    IMCOM_TRY(ensure_sync_events(ctx, 3 + nsub));
     // IMCOM_SPLIT_CUS=1 (A/B runs): every sub-batch on a stream confined to a share of the CUs of its own, so that one's
     // one-workgroup-per-stamp step finds free CUs while another's memory pass runs
     const bool parted = env_int("IMCOM_SPLIT_CUS", 0) != 0;
@@ -957,61 +933,47 @@ extern "C" int imcom_solve_eigen(imcom_ctx *ctx, int batch, const int *n, int ld
                                  const double *C, const double *kappaC, int nv, double ucmin, double smax, int nbis, float *T,
                                  float *UC, float *Sigma, float *kappa, int *info, int memspace)
 {
-    IMCOM_TRY(ctx_ok(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && n && C && kappaC && UC && Sigma && kappa && info, "null pointer / empty batch");
     IMCOM_REQUIRE(m >= 1 && nv >= 1 && ldn >= 0 && nbis >= 0, "bad sizes");
-    int nmax = 0;
-    for (int s = 0; s < batch; s++) {
-        IMCOM_REQUIRE(n[s] >= 0 && n[s] <= ldn, "n[%d]=%d exceeds ldn=%d", s, n[s], ldn);
-        nmax = std::max(nmax, n[s]);
-        info[s] = 0;
-    }
+    int nmax;
+    IMCOM_TRY(batch_sizes(n, batch, ldn, &nmax));
+    std::fill(info, info + batch, 0);
     IMCOM_REQUIRE(nmax == 0 || (A && mBhalf && T), "null matrix pointer");
-    const bool host = memspace == IMCOM_MEM_HOST;
+    Stage st(ctx, memspace, __func__);
     const int np = (int)align_up((size_t)std::max(nmax, 1), NB), mp = (int)align_up((size_t)m, NB);
     const size_t szA = (size_t)batch * ldn * ldn, szB = (size_t)batch * m * ldn, szM = (size_t)batch * m;
-    size_t total = solve_eigen_ws_total(batch, np, mp, m);
-    if (host) total += szA * 8 + szB * 8 + szB * 4 + szM * 12 + 4096;
-    IMCOM_TRY(ws_reserve(ctx, total));
-    const double *A_d = A, *B_d = mBhalf;
-    float *T_d = T, *UC_d = UC, *Sig_d = Sigma, *kap_d = kappa;
-    if (host) {
-        double *ta = (double *)ws_take(ctx, szA * 8), *tb = (double *)ws_take(ctx, szB * 8);
-        T_d = (float *)ws_take(ctx, szB * 4);
-        UC_d = (float *)ws_take(ctx, szM * 12);
-        if (!ta || !tb || !T_d || !UC_d) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-        Sig_d = UC_d + szM;
-        kap_d = Sig_d + szM;
-        if (szA) IMCOM_HIP_CHECK(hipMemcpyAsync(ta, A, szA * 8, hipMemcpyHostToDevice, ctx->stream));
-        if (szB) IMCOM_HIP_CHECK(hipMemcpyAsync(tb, mBhalf, szB * 8, hipMemcpyHostToDevice, ctx->stream));
-        A_d = ta;
-        B_d = tb;
-    }
+    WsPlan plan;
+    st.plan(plan, {szA * 8, szB * 8, szB * 4, szM * 4, szM * 4, szM * 4});
+    plan.add(solve_eigen_ws_total(batch, np, mp, m));
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *A_d, *B_d;
+    float *T_d, *UC_d, *Sig_d, *kap_d;
+    IMCOM_TRY(st.in(A, szA, &A_d));
+    IMCOM_TRY(st.in(mBhalf, szB, &B_d));
+    IMCOM_TRY(st.out(T, szB, &T_d));
+    IMCOM_TRY(st.out(UC, szM, &UC_d));
+    IMCOM_TRY(st.out(Sigma, szM, &Sig_d));
+    IMCOM_TRY(st.out(kappa, szM, &kap_d));
     IMCOM_TRY(solve_eigen_core(ctx, batch, n, ldn, m, np, mp, A_d, nullptr, B_d, C, kappaC, nv, ucmin, smax, nbis, nullptr, T_d, UC_d, Sig_d,
                                kap_d, nmax, info));
-    if (host) {
-        if (szB) IMCOM_HIP_CHECK(hipMemcpyAsync(T, T_d, szB * 4, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(UC, UC_d, szM * 4, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(Sigma, Sig_d, szM * 4, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(kappa, kap_d, szM * 4, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(T, T_d, szB));
+    IMCOM_TRY(st.back(UC, UC_d, szM));
+    IMCOM_TRY(st.back(Sigma, Sig_d, szM));
+    IMCOM_TRY(st.back(kappa, kap_d, szM));
+    return st.done();
 }
 
 extern "C" int imcom_solve_eigen_resident(imcom_ctx *ctx, int batch, const int *n, int ldn, int m, int ldm, const double *A,
                                           const double *Bt, const double *C, const double *kappaC, int nv, double ucmin, double smax,
                                           int nbis, float *Tt, float *UC, float *Sigma, float *kappa, int *info)
 {
-    IMCOM_TRY(ctx_ok(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && n && C && kappaC && A && Bt && Tt && UC && Sigma && kappa && info, "null pointer / empty batch");
     IMCOM_REQUIRE(m >= 1 && nv >= 1 && nbis >= 0 && ldn >= NB && ldn % NB == 0 && ldm % NB == 0 && ldm >= m, "bad sizes (ldn, ldm multiples of 128)");
-    int nmax = 0;
-    for (int s = 0; s < batch; s++) {
-        IMCOM_REQUIRE(n[s] >= 0 && n[s] <= ldn, "n[%d]=%d exceeds ldn=%d", s, n[s], ldn);
-        nmax = std::max(nmax, n[s]);
-        info[s] = 0;
-    }
+    int nmax;
+    IMCOM_TRY(batch_sizes(n, batch, ldn, &nmax));
+    std::fill(info, info + batch, 0);
     IMCOM_TRY(ws_reserve(ctx, solve_eigen_ws_total(batch, ldn, ldm, m)));
     return solve_eigen_core(ctx, batch, n, ldn, m, ldn, ldm, A, Bt, nullptr, C, kappaC, nv, ucmin, smax, nbis, Tt, nullptr, UC, Sigma, kappa, nmax, info);
 }

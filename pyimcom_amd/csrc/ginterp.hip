@@ -372,13 +372,6 @@ GiGeom gi_geometry(double Rsearch)
     return G;
 }
 
-int gi_ctx_ok(imcom_ctx *ctx)
-{
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
-    return IMCOM_OK;
-}
-
 // everything one call needs on the device: geometry tables, the factor, its 16 x 16 inverses, A
 struct GiSystem {
     GiParams P;
@@ -448,10 +441,7 @@ int gi_system(imcom_ctx *ctx, const GiGeom &G, double samp, const double *Cov, d
     S.gidx = (int *)ws_take(ctx, (size_t)4 * ngp * 4);
     S.posc = (int *)ws_take(ctx, (size_t)4 * NN * 4);
     int *g0 = (int *)ws_take(ctx, (size_t)ng * 4), *ints = (int *)ws_take(ctx, 64);
-    if (!Ad || !dg || !S.L || !Dinv || !S.Linv16 || !S.A || !S.posx || !S.posy || !S.gidx || !S.posc || !g0 || !ints) {
-        set_error("internal: workspace plan too small (ginterp)");
-        return IMCOM_ERR_NOMEM;
-    }
+    if (!Ad || !dg || !S.L || !Dinv || !S.Linv16 || !S.A || !S.posx || !S.posy || !S.gidx || !S.posc || !g0 || !ints) return ws_short("ginterp");
     std::vector<double> px(NN), py(NN);
     std::vector<int> gidx((size_t)4 * ngp, -1), posc((size_t)4 * NN, -1);
     for (int k = 0; k < NN; k++) { px[k] = G.posx[k]; py[k] = G.posy[k]; }
@@ -532,41 +522,35 @@ extern "C" int imcom_ginterp_geometry(double Rsearch, int cap, int *NN, int *ng,
 extern "C" int imcom_ginterp_matrix(imcom_ctx *ctx, double Rsearch, double samp, int npts, const double *x_out, const double *y_out,
                                     const double *Cov, double epsilon, int stest, double *T, double *U, double *Sigma, int memspace)
 {
-    IMCOM_TRY(gi_ctx_ok(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(npts >= 0 && Cov && stest >= 1 && (npts == 0 || (x_out && y_out && T && U && Sigma)), "ginterp_matrix: bad arguments");
     IMCOM_TRY(gi_check_args(Rsearch, samp));
     const GiGeom G = gi_geometry(Rsearch);
     IMCOM_TRY(gi_check_range(G, Rsearch));
-    const bool host = memspace == IMCOM_MEM_HOST;
+    Stage st(ctx, memspace, __func__);
     const size_t NN = G.posx.size(), nu = ((size_t)npts + stest - 1) / stest;
-    const size_t szX = (size_t)npts * 8, szT = (size_t)npts * NN * 8, szU = nu * 8;
-    IMCOM_TRY(ws_reserve(ctx, gi_system_bytes(G) + (host ? align_up(2 * szX, 256) + align_up(szT, 256) + 2 * align_up(szU, 256) + 1024 : 0) + 4096));
+    const size_t szX = (size_t)npts, szT = (size_t)npts * NN;
+    WsPlan plan;
+    plan.add(gi_system_bytes(G) + 4096);
+    st.plan(plan, {szX * 8, szX * 8, szT * 8, nu * 8, nu * 8});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
     GiSystem S;
     IMCOM_TRY(gi_system(ctx, G, samp, Cov, epsilon, S));
     S.P.stest = stest;
     S.P.blocksize = 0;
-    const double *xd = x_out, *yd = y_out;
-    double *Td = T, *Ud = U, *Sd = Sigma;
-    if (host && npts > 0) {
-        double *xy = (double *)ws_take(ctx, 2 * szX);
-        Td = (double *)ws_take(ctx, szT);
-        Ud = (double *)ws_take(ctx, szU);
-        Sd = (double *)ws_take(ctx, szU);
-        if (!xy || !Td || !Ud || !Sd) { set_error("internal: workspace plan too small (ginterp_matrix)"); return IMCOM_ERR_NOMEM; }
-        IMCOM_HIP_CHECK(hipMemcpyAsync(xy, x_out, szX, hipMemcpyHostToDevice, ctx->stream));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(xy + npts, y_out, szX, hipMemcpyHostToDevice, ctx->stream));
-        xd = xy;
-        yd = xy + npts;
-    }
+    const double *xd, *yd;
+    double *Td, *Ud, *Sd;
+    IMCOM_TRY(st.in(x_out, szX, &xd));
+    IMCOM_TRY(st.in(y_out, szX, &yd));
+    IMCOM_TRY(st.out(T, szT, &Td));
+    IMCOM_TRY(st.out(U, nu, &Ud));
+    IMCOM_TRY(st.out(Sigma, nu, &Sd));
     GiResample R{};
     IMCOM_TRY(gi_launch_tiles(ctx, S, npts, xd, yd, Td, Ud, Sd, R));
-    if (host && npts > 0) {
-        IMCOM_HIP_CHECK(hipMemcpyAsync(T, Td, szT, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(U, Ud, szU, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(Sigma, Sd, szU, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(T, Td, szT));
+    IMCOM_TRY(st.back(U, Ud, nu));
+    IMCOM_TRY(st.back(Sigma, Sd, nu));
+    return st.done();
 }
 
 extern "C" int imcom_ginterp_resample(imcom_ctx *ctx, int nlayer, int ny_in, int nx_in, const void *in, int in_f64, const unsigned char *in_mask,
@@ -574,7 +558,7 @@ extern "C" int imcom_ginterp_resample(imcom_ctx *ctx, int nlayer, int ny_in, int
                                       const double *Cov, double epsilon, int stest, long blocksize, void *out, unsigned char *out_mask,
                                       double *UmaxSmax, int memspace)
 {
-    IMCOM_TRY(gi_ctx_ok(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(nlayer >= 1 && ny_in >= 1 && nx_in >= 1 && in && in_mask && ny >= 0 && nx >= 0 && origin && transform && Cov && stest >= 1 &&
                       blocksize >= 1 && out && out_mask && UmaxSmax && (in_f64 == 0 || in_f64 == 1),
                   "ginterp_resample: bad arguments");
@@ -582,14 +566,14 @@ extern "C" int imcom_ginterp_resample(imcom_ctx *ctx, int nlayer, int ny_in, int
     IMCOM_TRY(gi_check_args(Rsearch, samp));
     const GiGeom G = gi_geometry(Rsearch);
     IMCOM_TRY(gi_check_range(G, Rsearch));
-    const bool host = memspace == IMCOM_MEM_HOST;
+    Stage st(ctx, memspace, __func__);
     const int npts = ny * nx, es = in_f64 ? 8 : 4;
     const size_t szIn = (size_t)nlayer * ny_in * nx_in * es, szM = (size_t)ny_in * nx_in, szOut = (size_t)nlayer * npts * es, szOM = (size_t)npts;
     int bb = 0;  // ginterp.py:298-302
     for (size_t k = 0; k < G.posx.size(); k++)
         bb = std::max({bb, -G.posx[k], G.posx[k] - 1, -G.posy[k], G.posy[k] - 1});
     if (2 * bb >= std::min(nx_in, ny_in) || npts == 0) {  // the reference's early exit: all zeros, everything masked
-        if (host) {
+        if (st.host) {
             memset(out, 0, szOut);
             memset(out_mask, 1, szOM);
             UmaxSmax[0] = UmaxSmax[1] = 0.0;
@@ -600,40 +584,35 @@ extern "C" int imcom_ginterp_resample(imcom_ctx *ctx, int nlayer, int ny_in, int
         }
         return IMCOM_OK;
     }
-    IMCOM_TRY(ws_reserve(ctx, gi_system_bytes(G) + (host ? align_up(szIn, 256) + align_up(szM, 256) + align_up(szOut, 256) + align_up(szOM, 256) : 0) +
-                                  4096));
+    WsPlan plan;
+    plan.add(gi_system_bytes(G) + 4096);
+    st.plan(plan, {szIn, szM, szOut, szOM});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
     GiSystem S;
     IMCOM_TRY(gi_system(ctx, G, samp, Cov, epsilon, S));
     S.P.stest = stest;
     S.P.blocksize = blocksize;
-    unsigned long long *um = (unsigned long long *)ws_take(ctx, 16);
+    unsigned long long *um;
+    IMCOM_TRY(ws_take(ctx, 2, &um, __func__));
     GiResample R;
     R.nlayer = nlayer; R.ny_in = ny_in; R.nx_in = nx_in; R.nx = nx; R.f64 = in_f64; R.bb = bb;
     R.t00 = transform[0]; R.t01 = transform[1]; R.t10 = transform[2]; R.t11 = transform[3];
     R.o0 = origin[0]; R.o1 = origin[1];
-    R.in = in; R.in_mask = in_mask; R.out = out; R.out_mask = out_mask; R.umax_bits = um;
-    if (host) {
-        void *ind = ws_take(ctx, szIn);
-        unsigned char *md = (unsigned char *)ws_take(ctx, szM);
-        R.out = ws_take(ctx, szOut);
-        R.out_mask = (unsigned char *)ws_take(ctx, szOM);
-        if (!ind || !md || !R.out || !R.out_mask) { set_error("internal: workspace plan too small (ginterp_resample)"); return IMCOM_ERR_NOMEM; }
-        IMCOM_HIP_CHECK(hipMemcpyAsync(ind, in, szIn, hipMemcpyHostToDevice, ctx->stream));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(md, in_mask, szM, hipMemcpyHostToDevice, ctx->stream));
-        R.in = ind;
-        R.in_mask = md;
-    }
-    if (!um) { set_error("internal: workspace plan too small (ginterp_resample)"); return IMCOM_ERR_NOMEM; }
+    R.umax_bits = um;
+    // (the layers as bytes: float32 or float64)
+    const unsigned char *ind;
+    unsigned char *outd;
+    IMCOM_TRY(st.in((const unsigned char *)in, szIn, &ind));
+    IMCOM_TRY(st.in(in_mask, szM, &R.in_mask));
+    IMCOM_TRY(st.out((unsigned char *)out, szOut, &outd));
+    IMCOM_TRY(st.out(out_mask, szOM, &R.out_mask));
+    R.in = ind;
+    R.out = outd;
     IMCOM_HIP_CHECK(hipMemsetAsync(um, 0, 16, ctx->stream));
     IMCOM_TRY(gi_launch_tiles(ctx, S, npts, nullptr, nullptr, nullptr, nullptr, nullptr, R));
-    if (host) {
-        if (npts > 0) {
-            IMCOM_HIP_CHECK(hipMemcpyAsync(out, R.out, szOut, hipMemcpyDeviceToHost, ctx->stream));
-            IMCOM_HIP_CHECK(hipMemcpyAsync(out_mask, R.out_mask, szOM, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        IMCOM_HIP_CHECK(hipMemcpyAsync(UmaxSmax, um, 16, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    } else
-        IMCOM_HIP_CHECK(hipMemcpyAsync(UmaxSmax, um, 16, hipMemcpyDeviceToDevice, ctx->stream));
-    return IMCOM_OK;
+    IMCOM_TRY(st.back((unsigned char *)out, outd, szOut));
+    IMCOM_TRY(st.back(out_mask, R.out_mask, szOM));
+    // UmaxSmax: a copy in either memory space (the kernel's maxima are bit patterns in the workspace)
+    IMCOM_HIP_CHECK(hipMemcpyAsync(UmaxSmax, um, 16, st.host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    return st.done();
 }

@@ -344,68 +344,26 @@ __global__ __launch_bounds__(256) void iter_combine_kernel(const float *__restri
 
 using namespace imcom;
 
-static int ctx_ok2(imcom_ctx *ctx)
-{
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
-    return IMCOM_OK;
-}
-
-namespace {
-struct Stage {  // host -> device staging of one array through the context workspace
-    imcom_ctx *ctx;
-    bool host;
-    template <typename T>
-    int in(const T *src, size_t count, const T **dst)
-    {
-        *dst = src;
-        if (!host || !src || count == 0) return IMCOM_OK;
-        T *d = (T *)ws_take(ctx, count * sizeof(T));
-        if (!d) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-        IMCOM_HIP_CHECK(hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-        *dst = d;
-        return IMCOM_OK;
-    }
-    template <typename T>
-    int out(T *user, size_t count, T **dev)
-    {
-        *dev = user;
-        if (!host || count == 0) return IMCOM_OK;
-        *dev = (T *)ws_take(ctx, count * sizeof(T));
-        if (!*dev) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-        return IMCOM_OK;
-    }
-    template <typename T>
-    int back(T *user, const T *dev, size_t count)
-    {
-        if (!host || count == 0) return IMCOM_OK;
-        IMCOM_HIP_CHECK(hipMemcpyAsync(user, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        return IMCOM_OK;
-    }
-};
-}  // namespace
-
 extern "C" int imcom_solve_empir(imcom_ctx *ctx, int batch, const int *n, int ldn, int m, const double *A, const double *mBhalf,
                                  const double *C, double kappaC0, const double *out_yx, const double *in_y, const double *in_x,
                                  double rho_acc, int no_qlt_ctrl, float *T, float *UC, float *Sigma, float *kappa, int memspace)
 {
-    IMCOM_TRY(ctx_ok2(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && n && out_yx && m >= 1 && ldn >= 0 && UC && Sigma && kappa, "null pointer / bad sizes");
-    int nmax = 0;
-    for (int s = 0; s < batch; s++) {
-        IMCOM_REQUIRE(n[s] >= 0 && n[s] <= ldn, "n[%d]=%d exceeds ldn=%d", s, n[s], ldn);
-        nmax = std::max(nmax, n[s]);
-    }
+    int nmax;
+    IMCOM_TRY(batch_sizes(n, batch, ldn, &nmax));
     IMCOM_REQUIRE(nmax == 0 || (in_y && in_x && T), "null coordinate / T pointer");
     IMCOM_REQUIRE(no_qlt_ctrl || nmax == 0 || (A && mBhalf && C), "quality control needs A, -B/2 and C");
-    const bool host = memspace == IMCOM_MEM_HOST, qc = !no_qlt_ctrl;
+    const bool qc = !no_qlt_ctrl;
+    Stage st(ctx, memspace, __func__);
     const int np = (int)align_up((size_t)std::max(nmax, 1), NB), mp = (int)align_up((size_t)m, NB);
     const size_t szA = (size_t)batch * ldn * ldn, szB = (size_t)batch * m * ldn, szM = (size_t)batch * m;
     const size_t big = (size_t)batch * mp * np * 8;
-    size_t total = 65536 + (qc ? 2 * big + (size_t)batch * np * np * 8 : 0) + (size_t)batch * 24;
-    if (host) total += (qc ? (szA + szB) * 8 : 0) + szB * 4 + szM * 12 + szM * 16 + (size_t)batch * ldn * 16 + 4096;
-    IMCOM_TRY(ws_reserve(ctx, total));
-    Stage st{ctx, host};
+    WsPlan plan;
+    if (qc) st.plan(plan, {szA * 8, szB * 8});
+    st.plan(plan, {2 * szM * 8, (size_t)batch * ldn * 8, (size_t)batch * ldn * 8, szB * 4, szM * 4, szM * 4, szM * 4});
+    plan.add(65536 + (qc ? 2 * big + (size_t)batch * np * np * 8 : 0) + (size_t)batch * 24);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
     const double *A_d = nullptr, *B_d = nullptr, *yx_d, *iy_d, *ix_d;
     if (qc) { IMCOM_TRY(st.in(A, szA, &A_d)); IMCOM_TRY(st.in(mBhalf, szB, &B_d)); }
     IMCOM_TRY(st.in(out_yx, 2 * szM, &yx_d));
@@ -418,7 +376,7 @@ extern "C" int imcom_solve_empir(imcom_ctx *ctx, int batch, const int *n, int ld
     IMCOM_TRY(st.out(kappa, szM, &kap_d));
     int *n_dev = (int *)ws_take(ctx, (size_t)batch * 4);
     double *kc = (double *)ws_take(ctx, (size_t)batch * 16);
-    if (!n_dev || !kc) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+    if (!n_dev || !kc) return ws_short(__func__);
     std::vector<double> kch(2 * (size_t)batch, 0.0);
     for (int s = 0; s < batch && qc; s++) { kch[s] = kappaC0 * C[s]; kch[batch + s] = C[s]; }
     IMCOM_HIP_CHECK(hipMemcpyAsync(n_dev, n, (size_t)batch * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -429,7 +387,7 @@ extern "C" int imcom_solve_empir(imcom_ctx *ctx, int batch, const int *n, int ld
         Tp = (double *)ws_take(ctx, big);
         G = (double *)ws_take(ctx, big);
         Ap = (double *)ws_take(ctx, (size_t)batch * np * np * 8);
-        if (!Tp || !G || !Ap) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+        if (!Tp || !G || !Ap) return ws_short(__func__);
         IMCOM_HIP_CHECK(hipMemsetAsync(Tp, 0, big, ctx->stream));
     }
     IMCOM_HIP_CHECK(hipMemsetAsync(UC_d, 0, szM * 4, ctx->stream));  // no quality control: maps stay zero (lakernel.py:123-125, 774-777)
@@ -452,8 +410,7 @@ extern "C" int imcom_solve_empir(imcom_ctx *ctx, int batch, const int *n, int ld
     IMCOM_TRY(st.back(UC, UC_d, szM));
     IMCOM_TRY(st.back(Sigma, Sig_d, szM));
     IMCOM_TRY(st.back(kappa, kap_d, szM));
-    if (host) IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return IMCOM_OK;
+    return st.done();
 }
 
 extern "C" int imcom_solve_iter(imcom_ctx *ctx, int batch, const int *n, int ldn, int m, const double *A, const double *mBhalf,
@@ -461,16 +418,14 @@ extern "C" int imcom_solve_iter(imcom_ctx *ctx, int batch, const int *n, int ldn
                                 const double *in_y, const double *in_x, double rho_acc, double rtol, int maxiter, int exact_UC,
                                 float *T, float *UC, float *Sigma, float *kappa, int memspace)
 {
-    IMCOM_TRY(ctx_ok2(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && n && C && kappaC && out_yx && UC && Sigma && kappa, "null pointer / empty batch");
     IMCOM_REQUIRE(m >= 1 && nv >= 1 && nv <= IT_MAXNV && ldn >= 0 && maxiter >= 0, "bad sizes (nv <= %d)", IT_MAXNV);
-    int nmax = 0;
-    for (int s = 0; s < batch; s++) {
-        IMCOM_REQUIRE(n[s] >= 0 && n[s] <= ldn, "n[%d]=%d exceeds ldn=%d", s, n[s], ldn);
-        nmax = std::max(nmax, n[s]);
-    }
+    int nmax;
+    IMCOM_TRY(batch_sizes(n, batch, ldn, &nmax));
     IMCOM_REQUIRE(nmax == 0 || (A && mBhalf && T && in_y && in_x), "null matrix / coordinate pointer");
-    const bool host = memspace == IMCOM_MEM_HOST, exact = exact_UC != 0;
+    const bool exact = exact_UC != 0;
+    Stage st(ctx, memspace, __func__);
     const int np = (int)align_up((size_t)std::max(nmax, 1), NB), mp = (int)align_up((size_t)m, NB);
     // Width of the output-pixel grid (pixels arrive row by row: yx_val.ravel(), lakernel.py:613-614): the first index whose y
     // differs from pixel 0's.  It only decides which 16 pixels share a workgroup of the blocked solver; any value is correct.
@@ -478,7 +433,7 @@ extern "C" int imcom_solve_iter(imcom_ctx *ctx, int batch, const int *n, int ldn
     int gridW = m;
     if (!per_pixel && nmax > 0) {
         std::vector<double> y0((size_t)std::min(m, 8192));
-        if (host) std::copy(out_yx, out_yx + y0.size(), y0.begin());
+        if (st.host) std::copy(out_yx, out_yx + y0.size(), y0.begin());
         else {
             IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
             IMCOM_HIP_CHECK(hipMemcpy(y0.data(), out_yx, y0.size() * 8, hipMemcpyDeviceToHost));
@@ -491,14 +446,15 @@ extern "C" int imcom_solve_iter(imcom_ctx *ctx, int batch, const int *n, int ldn
     const size_t big = (size_t)batch * mp * np * 8;
     size_t total = 65536 + (size_t)nv * szB * 4 + (size_t)batch * ldn * 8 + (size_t)batch * (MAX_INC + 4) * 8 + szM * 8 * (4 + nv + 2 * nv * nv);
     if (exact) total += big * (1 + nv) + (size_t)batch * np * np * 8;
-    if (host) total += (szA + szB) * 8 + szB * 4 + szM * 12 + szM * 16 + (size_t)batch * ldn * 16 + 4096;
     // The blocked solver keeps one dense sub-matrix per 4 x 4 patch (4 MB at the reference's default configuration, 64 patches per
     // stamp): the patches of a call go through it in groups that fit a fixed share of workspace instead of batch x 0.3 GB.
     const size_t blk_budget = per_pixel ? 0 : std::min<size_t>((size_t)8 << 30, (size_t)batch * nblocks * iter_block_patch_bytes(iter_block_umax()));
     if (!per_pixel) total += iter_block_select_bytes(batch, nblocks) + blk_budget + 8192;
     total += szM * 4 + 64;  // per-pixel step counts, statistics
-    IMCOM_TRY(ws_reserve(ctx, total));
-    Stage st{ctx, host};
+    WsPlan plan;
+    st.plan(plan, {szA * 8, szB * 8, 2 * szM * 8, (size_t)batch * ldn * 8, (size_t)batch * ldn * 8, szB * 4, szM * 4, szM * 4, szM * 4});
+    plan.add(total);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
     const double *A_d, *B_d, *yx_d, *iy_d, *ix_d;
     IMCOM_TRY(st.in(A, szA, &A_d));
     IMCOM_TRY(st.in(mBhalf, szB, &B_d));
@@ -519,7 +475,7 @@ extern "C" int imcom_solve_iter(imcom_ctx *ctx, int batch, const int *n, int ldn
     void *blkws = per_pixel ? nullptr : ws_take(ctx, iter_block_select_bytes(batch, nblocks) + blk_budget + 4096);
     int *steps_d = (int *)ws_take(ctx, szM * 4);
     unsigned long long *stats_d = (unsigned long long *)ws_take(ctx, 64);
-    if (!Tn || !dsh || !inc || !ints || !kc || !flat || (!per_pixel && !blkws) || !steps_d || !stats_d) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+    if (!Tn || !dsh || !inc || !ints || !kc || !flat || (!per_pixel && !blkws) || !steps_d || !stats_d) return ws_short(__func__);
     IMCOM_HIP_CHECK(hipMemsetAsync(stats_d, 0, 64, ctx->stream));
     IMCOM_HIP_CHECK(hipMemsetAsync(steps_d, 0, szM * 4, ctx->stream));
     ctx->iter_steps.clear();
@@ -586,7 +542,7 @@ extern "C" int imcom_solve_iter(imcom_ctx *ctx, int batch, const int *n, int ldn
         if (exact) {
             double *Tp = (double *)ws_take(ctx, big), *Ap = (double *)ws_take(ctx, (size_t)batch * np * np * 8);
             G = (double *)ws_take(ctx, big * nv);
-            if (!Tp || !Ap || !G) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+            if (!Tp || !Ap || !G) return ws_short(__func__);
             IMCOM_TRY(launch_pack_A(ctx, A_d, ldn, n_dev, Ap, np, batch));
             for (int p = 0; p < nv; p++) {
                 hipLaunchKernelGGL(iter_widen_kernel, dim3((np + 255) / 256, mp, batch), dim3(256), 0, ctx->stream, Tn + (size_t)p * szB, (long)ldn, m,
@@ -610,14 +566,13 @@ extern "C" int imcom_solve_iter(imcom_ctx *ctx, int batch, const int *n, int ldn
     IMCOM_TRY(st.back(UC, UC_d, szM));
     IMCOM_TRY(st.back(Sigma, Sig_d, szM));
     IMCOM_TRY(st.back(kappa, kap_d, szM));
-    if (host) IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return IMCOM_OK;
+    return st.done();
 }
 
 
 extern "C" int imcom_solve_iter_stats(imcom_ctx *ctx, double *stats, int *steps, long nsteps)
 {
-    IMCOM_TRY(ctx_ok2(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(stats, "null pointer");
     for (int k = 0; k < 8; k++) stats[k] = ctx->iter_stats[k];
     if (steps) {

@@ -201,8 +201,7 @@ extern "C" int imcom_partition_pixels(imcom_ctx *ctx, long npix, const double *o
                                       int n2, double pix_lower, double pix_upper, int npixmax, unsigned short *y_idx,
                                       unsigned short *x_idx, double *y_val, double *x_val, unsigned int *pix_count)
 {
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(npix >= 0 && npix < (1L << 32) - 2 && nst >= 1 && n2 >= 1 && npixmax >= 1, "bad sizes");
     IMCOM_REQUIRE(use_instamps && y_idx && x_idx && y_val && x_val && pix_count, "null pointer");
     IMCOM_REQUIRE(npix == 0 || (out_x && out_y && in_x && in_y), "null input pointer");
@@ -217,7 +216,7 @@ extern "C" int imcom_partition_pixels(imcom_ctx *ctx, long npix, const double *o
     unsigned int *hist = (unsigned int *)ws_take(ctx, (size_t)nblk * RS_BINS * 4 + 16);
     unsigned int *start = (unsigned int *)ws_take(ctx, (size_t)(nkeys + 1) * 4);
     int *status = (int *)ws_take(ctx, 4);
-    if (!k0 || !k1 || !v0 || !v1 || !hist || !start || !status) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+    if (!k0 || !k1 || !v0 || !v1 || !hist || !start || !status) return ws_short(__func__);
     unsigned int *ks = k0, *vs = v0;  // the sorted pairs
     IMCOM_HIP_CHECK(hipMemsetAsync(start, 0xff, (size_t)(nkeys + 1) * 4, st));
     IMCOM_HIP_CHECK(hipMemsetAsync(status, 0, 4, st));

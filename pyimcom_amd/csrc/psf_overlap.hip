@@ -552,7 +552,7 @@ static int fft_forward(imcom_ctx *ctx, const FftPlan &pl, const double *psf, int
     const int nfft = pl.n, nh = nfft / 2 + 1;
     cplx *tw = fft_twiddles(ctx, pl);
     cplx *Y1 = (cplx *)ws_take(ctx, (size_t)n * nsamp * nh * 16);
-    if (!tw || !Y1) { set_error("internal: workspace plan too small"); return IMCOM_ERR_NOMEM; }
+    if (!tw || !Y1) return ws_short("psf_overlap forward");
     switch (fft_static_r(pl)) {
     case 2: return wf16_forward<2>(ctx, psf, n, nsamp, tw, Y1, R);
     case 3: return wf16_forward<3>(ctx, psf, n, nsamp, tw, Y1, R);
@@ -578,7 +578,7 @@ static int fft_inverse(imcom_ctx *ctx, const FftPlan &pl, const cplx *Ra, const 
     int *pairs_dev = (int *)ws_take(ctx, (size_t)npairs * 8);
     int *win_dev = win_host ? (int *)ws_take(ctx, (size_t)npairs * 16) : nullptr;  // the static kernels honour it; the general ones fill whole tables
     int *slot_dev = slots_host ? (int *)ws_take(ctx, (size_t)npairs * 4) : nullptr;
-    if (!tw || !V || !pairs_dev || (win_host && !win_dev) || (slots_host && !slot_dev)) { set_error("internal: workspace plan too small"); return IMCOM_ERR_NOMEM; }
+    if (!tw || !V || !pairs_dev || (win_host && !win_dev) || (slots_host && !slot_dev)) return ws_short("psf_overlap inverse");
     IMCOM_TRY(fft_set_lds(pl));
     hipStream_t st = ctx->stream;
     IMCOM_TRY(upload(ctx, pairs_dev, pairs_host, 2 * (size_t)npairs));  // through the pinned ring: no stream drain
@@ -607,8 +607,7 @@ using namespace imcom;
 extern "C" int imcom_psf_overlap(imcom_ctx *ctx, const double *psf1, int n1, const double *psf2, int n2, int nsamp,
                                  int nfft, const int *pairs_host, int npairs, const double *amp_penalty, double *tables)
 {
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(psf1 && psf2 && pairs_host && tables, "null pointer");
     IMCOM_REQUIRE(n1 >= 1 && n2 >= 1 && npairs >= 1 && nsamp >= 1 && nfft >= 2 * nsamp && nfft % 2 == 0,
                   "bad sizes (need nfft even and >= 2*nsamp)");
@@ -623,7 +622,7 @@ extern "C" int imcom_psf_overlap(imcom_ctx *ctx, const double *psf1, int n1, con
         const int npsf_ = same_ ? n1 : n1 + n2;
         IMCOM_TRY(ws_reserve(ctx, fft_forward_ws(npsf_, nsamp, nfft) + (size_t)npsf_ * nfft * nh_ * 16 + fft_inverse_ws(npairs, nsamp, nfft) + (size_t)nfft * 64 + 65536));
         cplx *R = (cplx *)ws_take(ctx, (size_t)npsf_ * nfft * nh_ * 16);
-        if (!R) { set_error("internal: workspace plan too small"); return IMCOM_ERR_NOMEM; }
+        if (!R) return ws_short(__func__);
         ProfScope ps(ctx, "psf_overlap");
         IMCOM_TRY(fft_forward(ctx, pl, psf1, n1, nsamp, R));
         if (!same_) IMCOM_TRY(fft_forward(ctx, pl, psf2, n2, nsamp, R + (long)n1 * nfft * nh_));
@@ -662,10 +661,7 @@ extern "C" int imcom_psf_overlap(imcom_ctx *ctx, const double *psf1, int n1, con
     double *U = (double *)ws_take(ctx, B8((long)npairs * Sp * Hp) * 2);
     double *W = (double *)ws_take(ctx, B8((long)npairs * Sp * Sp));
     int *pairs_dev = (int *)ws_take(ctx, (size_t)npairs * 8);
-    if (!FXc || !FYc || !IYc || !IXc || !X || !Y1 || !R || !Z || !U || !W || !pairs_dev) {
-        set_error("internal: workspace plan too small");
-        return IMCOM_ERR_NOMEM;
-    }
+    if (!FXc || !FYc || !IYc || !IXc || !X || !Y1 || !R || !Z || !U || !W || !pairs_dev) return ws_short(__func__);
     hipStream_t st = ctx->stream;
     ProfScope ps(ctx, "psf_overlap");
     // second group's PSFs are stored after the first's; remap q
@@ -721,8 +717,7 @@ extern "C" long imcom_psf_spectra_size(int nsamp, int nfft)
 
 extern "C" int imcom_psf_spectra(imcom_ctx *ctx, const double *psf, int n, int nsamp, int nfft, double *spectra)
 {
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(psf && spectra && n >= 1, "null pointer / empty set");
     IMCOM_REQUIRE(imcom_psf_spectra_size(nsamp, nfft) > 0, "no butterfly plan for nfft=%d (use imcom_psf_overlap)", nfft);
     FftPlan pl;
@@ -736,8 +731,7 @@ extern "C" int imcom_psf_overlap_spectra_slots(imcom_ctx *ctx, const double *spe
                                                int nfft, const int *pairs_host, int npairs, const double *amp_penalty,
                                                const int *win_host, const int *slots_host, int nslots, double *tables)
 {
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(spec1 && spec2 && pairs_host && tables && npairs >= 1, "null pointer / no pairs");
     IMCOM_REQUIRE(imcom_psf_spectra_size(nsamp, nfft) > 0, "no butterfly plan for nfft=%d (use imcom_psf_overlap)", nfft);
     for (int t = 0; t < npairs; t++)

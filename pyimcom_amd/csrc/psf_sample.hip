@@ -213,48 +213,32 @@ __global__ __launch_bounds__(256) void lattice_positions_kernel(const double *__
 
 using namespace imcom;
 
-static int ctx_ok3(imcom_ctx *ctx)
-{
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
-    return IMCOM_OK;
-}
-
 extern "C" int imcom_sample_psf(imcom_ctx *ctx, int n_psf, const double *psf, int ny, int nx, const double *yxco, int nsamp,
                                 int psf_circ, int psf_norm, double *psf_arr, int memspace)
 {
-    IMCOM_TRY(ctx_ok3(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(n_psf >= 1 && psf && psf_arr && ny >= 1 && nx >= 1 && nsamp >= 1, "bad arguments");
-    const bool host = memspace == IMCOM_MEM_HOST;
+    Stage st(ctx, memspace, __func__);
     const long npts = (long)nsamp * nsamp, gy = ny + 12, gx = nx + 12;
-    const size_t szin = (size_t)n_psf * ny * nx * 8, szout = (size_t)n_psf * npts * 8, szco = yxco ? (size_t)n_psf * 2 * npts * 8 : 0;
-    size_t total = 65536 + (size_t)n_psf * gy * gx * 8 + 2 * (size_t)npts * 8 + (size_t)n_psf * 8 + (size_t)n_psf * nsamp * 8;
-    if (host) total += szin + szout + szco + 1024;
-    IMCOM_TRY(ws_reserve(ctx, total));
-    const double *psf_d = psf, *co_d = yxco;
-    double *out_d = psf_arr;
-    if (host) {
-        double *t = (double *)ws_take(ctx, szin);
-        out_d = (double *)ws_take(ctx, szout);
-        if (!t || !out_d) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-        IMCOM_HIP_CHECK(hipMemcpyAsync(t, psf, szin, hipMemcpyHostToDevice, ctx->stream));
-        psf_d = t;
-        if (yxco) {
-            double *c = (double *)ws_take(ctx, szco);
-            if (!c) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-            IMCOM_HIP_CHECK(hipMemcpyAsync(c, yxco, szco, hipMemcpyHostToDevice, ctx->stream));
-            co_d = c;
-        }
-    }
+    const size_t szin = (size_t)n_psf * ny * nx, szout = (size_t)n_psf * npts, szco = yxco ? (size_t)n_psf * 2 * npts : 0;
+    WsPlan plan;
+    st.plan(plan, {szin * 8, szout * 8, szco * 8});
+    plan.add(65536 + (size_t)n_psf * gy * gx * 8 + 2 * (size_t)npts * 8 + (size_t)n_psf * 8 + (size_t)n_psf * nsamp * 8);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *psf_d, *co_d;
+    double *out_d;
+    IMCOM_TRY(st.in(psf, szin, &psf_d));
+    IMCOM_TRY(st.out(psf_arr, szout, &out_d));
+    IMCOM_TRY(st.in(yxco, szco, &co_d));
     double *pad = (double *)ws_take(ctx, (size_t)n_psf * gy * gx * 8);
     double *xpos = (double *)ws_take(ctx, (size_t)npts * 8), *ypos = (double *)ws_take(ctx, (size_t)npts * 8);
     double *sums = (double *)ws_take(ctx, (size_t)n_psf * 8), *rowsum = (double *)ws_take(ctx, (size_t)n_psf * nsamp * 8);
-    if (!pad || !xpos || !ypos || !sums || !rowsum) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+    if (!pad || !xpos || !ypos || !sums || !rowsum) return ws_short(__func__);
     const double xctr = (nx - 1) / 2.0, yctr = (ny - 1) / 2.0;
     ProfScope ps(ctx, "psf_sample");
     hipLaunchKernelGGL(pad6_kernel, dim3((unsigned)((gx + 255) / 256), (unsigned)gy, n_psf), dim3(256), 0, ctx->stream, psf_d, ny, nx, pad);
     IMCOM_TRY(check_launch("pad6_kernel"));
-    IMCOM_HIP_CHECK(hipMemsetAsync(out_d, 0, szout, ctx->stream));  // off-grid samples stay zero (psfutil.py:775, 785)
+    IMCOM_HIP_CHECK(hipMemsetAsync(out_d, 0, szout * 8, ctx->stream));  // off-grid samples stay zero (psfutil.py:775, 785)
     if (!co_d) {
         hipLaunchKernelGGL(grid_pos_kernel, dim3((nsamp + 255) / 256), dim3(256), 0, ctx->stream, nsamp, xctr, yctr, xpos, ypos);
         IMCOM_TRY(check_launch("grid_pos_kernel"));
@@ -274,33 +258,28 @@ extern "C" int imcom_sample_psf(imcom_ctx *ctx, int n_psf, const double *psf, in
             hipLaunchKernelGGL(psf_scale_kernel, dim3((unsigned)((npts + 255) / 256), n_psf), dim3(256), 0, ctx->stream, out_d, npts, sums);
         IMCOM_TRY(check_launch("psf circ/norm"));
     }
-    if (host) {
-        IMCOM_HIP_CHECK(hipMemcpyAsync(psf_arr, out_d, szout, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(psf_arr, out_d, szout));
+    return st.done();
 }
 
 extern "C" int imcom_lattice_positions(imcom_ctx *ctx, int count, int L, const double *W, const double *lattice, int nsamp, double *yxco,
                                        int memspace)
 {
-    IMCOM_TRY(ctx_ok3(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(count >= 1 && L >= 2 && L <= 33 && W && lattice && yxco && nsamp >= 1 && nsamp <= 600, "bad arguments (2 <= L <= 33, nsamp <= 600)");
-    const bool host = memspace == IMCOM_MEM_HOST;
-    const size_t szW = (size_t)nsamp * L * 8, szL = (size_t)count * 2 * L * L * 8, szO = (size_t)count * 2 * nsamp * nsamp * 8;
-    IMCOM_TRY(ws_reserve(ctx, szW + (host ? szL + szO : 0) + 8192));
-    double *W_d = (double *)ws_take(ctx, szW);
-    const double *lat_d = lattice;
-    double *out_d = yxco;
-    if (!W_d) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-    IMCOM_TRY(upload(ctx, W_d, W, (size_t)nsamp * L));
-    if (host) {
-        double *l = (double *)ws_take(ctx, szL);
-        out_d = (double *)ws_take(ctx, szO);
-        if (!l || !out_d) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-        IMCOM_HIP_CHECK(hipMemcpyAsync(l, lattice, szL, hipMemcpyHostToDevice, ctx->stream));
-        lat_d = l;
-    }
+    Stage st(ctx, memspace, __func__);
+    const size_t szW = (size_t)nsamp * L, szL = (size_t)count * 2 * L * L, szO = (size_t)count * 2 * nsamp * nsamp;
+    WsPlan plan;
+    plan.add(szW * 8 + 8192);
+    st.plan(plan, {szL * 8, szO * 8});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    double *W_d;
+    IMCOM_TRY(ws_take(ctx, szW, &W_d, __func__));
+    IMCOM_TRY(upload(ctx, W_d, W, szW));
+    const double *lat_d;
+    double *out_d;
+    IMCOM_TRY(st.in(lattice, szL, &lat_d));
+    IMCOM_TRY(st.out(yxco, szO, &out_d));
     const size_t lds = (size_t)L * nsamp * 8;
     IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)lattice_positions_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     {
@@ -309,45 +288,40 @@ extern "C" int imcom_lattice_positions(imcom_ctx *ctx, int count, int L, const d
                            L, nsamp, out_d);
         IMCOM_TRY(check_launch("lattice_positions_kernel"));
     }
-    if (host) {
-        IMCOM_HIP_CHECK(hipMemcpyAsync(yxco, out_d, szO, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(yxco, out_d, szO));
+    return st.done();
 }
 
 extern "C" int imcom_psf_gaussian(imcom_ctx *ctx, int n, double sigmax, double sigmay, double *out, int memspace)
 {
-    IMCOM_TRY(ctx_ok3(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(n >= 1 && out && sigmax > 0.0 && sigmay > 0.0, "bad arguments");
-    const bool host = memspace == IMCOM_MEM_HOST;
-    const size_t sz = (size_t)n * n * 8;
-    IMCOM_TRY(ws_reserve(ctx, sz + 4096));
-    double *o = host ? (double *)ws_take(ctx, sz) : out;
-    if (!o) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+    Stage st(ctx, memspace, __func__);
+    const size_t sz = (size_t)n * n;
+    IMCOM_TRY(ws_reserve(ctx, sz * 8 + 4096));
+    double *o;
+    IMCOM_TRY(st.out(out, sz, &o));
     hipLaunchKernelGGL(gaussian_kernel, dim3((n + 255) / 256, n), dim3(256), 0, ctx->stream, n, sigmax, sigmay, o);
     IMCOM_TRY(check_launch("gaussian_kernel"));
-    if (host) {
-        IMCOM_HIP_CHECK(hipMemcpyAsync(out, o, sz, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(out, o, sz));
+    return st.done();
 }
 
 extern "C" int imcom_psf_simple_airy(imcom_ctx *ctx, int n, double ldp, double obsc, double tophat_conv, double sigma, double *out,
                                      int memspace)
 {
-    IMCOM_TRY(ctx_ok3(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(n >= 1 && out && ldp > 0.0 && obsc >= 0.0 && obsc < 1.0 && tophat_conv >= 0.0 && sigma >= 0.0, "bad arguments");
-    const bool host = memspace == IMCOM_MEM_HOST;
+    Stage st(ctx, memspace, __func__);
     const int kp = 1 + (int)ceil(tophat_conv + 6.0 * sigma), npad = n + 2 * kp;  // psfutil.py:185-186
     const int P = (int)align_up((size_t)npad, NB);
-    const size_t szP = (size_t)P * P * 8, sz = (size_t)n * n * 8;
-    IMCOM_TRY(ws_reserve(ctx, 4 * szP + (size_t)npad * 8 + sz + 8192));
+    const size_t szP = (size_t)P * P * 8, sz = (size_t)n * n;
+    IMCOM_TRY(ws_reserve(ctx, 4 * szP + (size_t)npad * 8 + sz * 8 + 8192));
     double *I = (double *)ws_take(ctx, szP), *Cm = (double *)ws_take(ctx, szP), *Y = (double *)ws_take(ctx, szP), *Z = (double *)ws_take(ctx, szP);
     double *kvec = (double *)ws_take(ctx, (size_t)npad * 8);
-    double *o = host ? (double *)ws_take(ctx, sz) : out;
-    if (!I || !Cm || !Y || !Z || !kvec || !o) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+    if (!I || !Cm || !Y || !Z || !kvec) return ws_short(__func__);
+    double *o;
+    IMCOM_TRY(st.out(out, sz, &o));
     hipLaunchKernelGGL(airy_kernel, dim3((P + 255) / 256, P), dim3(256), 0, ctx->stream, npad, P, ldp, obsc, I);
     hipLaunchKernelGGL(airy_filter_kernel, dim3(npad), dim3(256), 0, ctx->stream, npad, sigma, tophat_conv, kvec);
     hipLaunchKernelGGL(circulant_kernel, dim3((P + 255) / 256, P), dim3(256), 0, ctx->stream, kvec, npad, P, Cm);
@@ -356,11 +330,8 @@ extern "C" int imcom_psf_simple_airy(imcom_ctx *ctx, int n, double ldp, double o
     IMCOM_TRY(launch_gemm(ctx, false, true, P, P, P, 1, Cm, P, 0, Y, P, 0, Z, P, 0, 1.0, 0.0));   // Z = C Y
     hipLaunchKernelGGL(crop_kernel, dim3((n + 255) / 256, n), dim3(256), 0, ctx->stream, Z, P, kp, n, o);
     IMCOM_TRY(check_launch("crop_kernel"));
-    if (host) {
-        IMCOM_HIP_CHECK(hipMemcpyAsync(out, o, sz, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(out, o, sz));
+    return st.done();
 }
 
 extern "C" int imcom_smooth_pad_width(double tophatwidth, double gaussiansigma)
@@ -377,40 +348,35 @@ extern "C" int imcom_smooth_pad_width(double tophatwidth, double gaussiansigma)
 extern "C" int imcom_smooth_and_pad(imcom_ctx *ctx, int n, const double *in, int ny, int nx, double tophatwidth, double gaussiansigma,
                                     double *out, int memspace)
 {
-    IMCOM_TRY(ctx_ok3(ctx));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(n >= 1 && in && out && ny >= 1 && nx >= 1 && tophatwidth >= 0.0 && gaussiansigma >= 0.0, "bad arguments");
-    const bool host = memspace == IMCOM_MEM_HOST;
+    Stage st(ctx, memspace, __func__);
     const int npad = imcom_smooth_pad_width(tophatwidth, gaussiansigma), nyy = ny + 2 * npad, nxx = nx + 2 * npad;
     const int Py = (int)align_up((size_t)nyy, NB), Px = (int)align_up((size_t)nxx, NB);
-    const size_t szI = (size_t)n * Py * Px * 8, szIn = (size_t)n * ny * nx * 8, szOut = (size_t)n * nyy * nxx * 8;
-    IMCOM_TRY(ws_reserve(ctx, 3 * szI + (size_t)Py * Py * 8 + (size_t)Px * Px * 8 + (size_t)(nyy + nxx) * 8 + (host ? szIn + szOut : 0) + 16384));
+    const size_t szI = (size_t)n * Py * Px * 8, szIn = (size_t)n * ny * nx, szOut = (size_t)n * nyy * nxx;
+    WsPlan plan;
+    plan.add(3 * szI + (size_t)Py * Py * 8 + (size_t)Px * Px * 8 + (size_t)(nyy + nxx) * 8 + 16384);
+    st.plan(plan, {szIn * 8, szOut * 8});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
     double *I = (double *)ws_take(ctx, szI), *Y = (double *)ws_take(ctx, szI), *Z = (double *)ws_take(ctx, szI);
     double *Cy = (double *)ws_take(ctx, (size_t)Py * Py * 8), *Cx = (double *)ws_take(ctx, (size_t)Px * Px * 8);
     double *ky = (double *)ws_take(ctx, (size_t)nyy * 8), *kx = (double *)ws_take(ctx, (size_t)nxx * 8);
-    const double *src = in;
-    double *dst = out;
-    if (host) {
-        double *in_d = (double *)ws_take(ctx, szIn);
-        dst = (double *)ws_take(ctx, szOut);
-        if (!in_d || !dst) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-        IMCOM_HIP_CHECK(hipMemcpyAsync(in_d, in, szIn, hipMemcpyHostToDevice, ctx->stream));
-        src = in_d;
-    }
-    if (!I || !Y || !Z || !Cy || !Cx || !ky || !kx) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-    hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(pad_rect_kernel, dim3((Px + 255) / 256, Py, n), dim3(256), 0, st, src, ny, nx, npad, Py, Px, I);
-    hipLaunchKernelGGL(airy_filter_kernel, dim3(nyy), dim3(256), 0, st, nyy, gaussiansigma, tophatwidth, ky);
-    hipLaunchKernelGGL(airy_filter_kernel, dim3(nxx), dim3(256), 0, st, nxx, gaussiansigma, tophatwidth, kx);
-    hipLaunchKernelGGL(circulant_kernel, dim3((Py + 255) / 256, Py), dim3(256), 0, st, ky, nyy, Py, Cy);
-    hipLaunchKernelGGL(circulant_kernel, dim3((Px + 255) / 256, Px), dim3(256), 0, st, kx, nxx, Px, Cx);
+    if (!I || !Y || !Z || !Cy || !Cx || !ky || !kx) return ws_short(__func__);
+    const double *src;
+    double *dst;
+    IMCOM_TRY(st.in(in, szIn, &src));
+    IMCOM_TRY(st.out(out, szOut, &dst));
+    hipStream_t hs = ctx->stream;
+    hipLaunchKernelGGL(pad_rect_kernel, dim3((Px + 255) / 256, Py, n), dim3(256), 0, hs, src, ny, nx, npad, Py, Px, I);
+    hipLaunchKernelGGL(airy_filter_kernel, dim3(nyy), dim3(256), 0, hs, nyy, gaussiansigma, tophatwidth, ky);
+    hipLaunchKernelGGL(airy_filter_kernel, dim3(nxx), dim3(256), 0, hs, nxx, gaussiansigma, tophatwidth, kx);
+    hipLaunchKernelGGL(circulant_kernel, dim3((Py + 255) / 256, Py), dim3(256), 0, hs, ky, nyy, Py, Cy);
+    hipLaunchKernelGGL(circulant_kernel, dim3((Px + 255) / 256, Px), dim3(256), 0, hs, kx, nxx, Px, Cx);
     IMCOM_TRY(check_launch("smooth_and_pad setup"));
     IMCOM_TRY(launch_gemm(ctx, false, false, Py, Px, Px, n, I, Px, (long)Py * Px, Cx, Px, 0, Y, Px, (long)Py * Px, 1.0, 0.0));  // Y = I Cx^T
     IMCOM_TRY(launch_gemm(ctx, false, true, Py, Px, Py, n, Cy, Py, 0, Y, Px, (long)Py * Px, Z, Px, (long)Py * Px, 1.0, 0.0));   // Z = Cy Y
-    hipLaunchKernelGGL(crop_rect_kernel, dim3((nxx + 255) / 256, nyy, n), dim3(256), 0, st, Z, Py, Px, nyy, nxx, dst);
+    hipLaunchKernelGGL(crop_rect_kernel, dim3((nxx + 255) / 256, nyy, n), dim3(256), 0, hs, Z, Py, Px, nyy, nxx, dst);
     IMCOM_TRY(check_launch("crop_rect_kernel"));
-    if (host) {
-        IMCOM_HIP_CHECK(hipMemcpyAsync(out, dst, szOut, hipMemcpyDeviceToHost, st));
-        IMCOM_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    return IMCOM_OK;
+    IMCOM_TRY(st.back(out, dst, szOut));
+    return st.done();
 }

@@ -86,66 +86,51 @@ extern "C" int imcom_select_pixels(imcom_ctx *ctx, int batch, const double *pool
                                    const int *inst_id, const double *pivot_x, const double *pivot_y, double radius, int ldn,
                                    double *x, double *y, float *indata, int *expo, int *cumsum, int memspace)
 {
-    if (!ctx) { set_error("null context"); return IMCOM_ERR_ARG; }
-    IMCOM_HIP_CHECK(hipSetDevice(ctx->device));
+    IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && npool >= 0 && n_inframe >= 1 && n_inst >= 1 && ldn >= 1, "bad sizes");
     IMCOM_REQUIRE(inst_off && inst_id && pivot_x && pivot_y && x && y && indata && expo && cumsum, "null pointer");
     IMCOM_REQUIRE(npool == 0 || (pool_x && pool_y && pool_data && pool_expo), "null pool pointer");
-    const bool host = memspace == IMCOM_MEM_HOST;
-    const size_t nb = (size_t)batch;
-    size_t total = 65536;
-    if (host)
-        total += (size_t)npool * (16 + 4 * (size_t)n_inframe + 4) + (size_t)(n_inst + 1) * 8 + nb * 9 * (4 + 16) +
-                 nb * ldn * (16 + 4 * (size_t)n_inframe + 4) + nb * 40 + 8192;
-    IMCOM_TRY(ws_reserve(ctx, total));
-    auto take = [&](size_t bytes) { return ws_take(ctx, bytes); };
-    auto up = [&](const void *src, size_t bytes, const void **dst) -> int {
-        *dst = src;
-        if (!host || bytes == 0) return IMCOM_OK;
-        void *d = take(bytes);
-        if (!d) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-        IMCOM_HIP_CHECK(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        *dst = d;
-        return IMCOM_OK;
-    };
-    const void *px_, *py_, *pd_, *pe_, *io_, *ii_, *vx_, *vy_;
-    IMCOM_TRY(up(pool_x, (size_t)npool * 8, &px_));
-    IMCOM_TRY(up(pool_y, (size_t)npool * 8, &py_));
-    IMCOM_TRY(up(pool_data, (size_t)npool * 4 * n_inframe, &pd_));
-    IMCOM_TRY(up(pool_expo, (size_t)npool * 4, &pe_));
-    IMCOM_TRY(up(inst_off, (size_t)(n_inst + 1) * 8, &io_));
-    IMCOM_TRY(up(inst_id, nb * 9 * 4, &ii_));
-    IMCOM_TRY(up(pivot_x, nb * 9 * 8, &vx_));
-    IMCOM_TRY(up(pivot_y, nb * 9 * 8, &vy_));
-    double *x_d = x, *y_d = y;
-    float *d_d = indata;
-    int *e_d = expo, *c_d = cumsum;
-    if (host) {
-        x_d = (double *)take(nb * ldn * 8);
-        y_d = (double *)take(nb * ldn * 8);
-        d_d = (float *)take(nb * ldn * 4 * n_inframe);
-        e_d = (int *)take(nb * ldn * 4);
-        c_d = (int *)take(nb * 40);
-        if (!x_d || !y_d || !d_d || !e_d || !c_d) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
-    }
-    int *status = (int *)take(4);
-    if (!status) { set_error("internal: workspace"); return IMCOM_ERR_NOMEM; }
+    Stage st(ctx, memspace, __func__);
+    const size_t nb = (size_t)batch, np = (size_t)npool, nd = nb * ldn;
+    WsPlan plan;
+    st.plan(plan, {np * 8, np * 8, np * 4 * n_inframe, np * 4, (size_t)(n_inst + 1) * 8, nb * 9 * 4, nb * 9 * 8, nb * 9 * 8,  // inputs
+                   nd * 8, nd * 8, nd * 4 * n_inframe, nd * 4, nb * 40});                                                  // outputs
+    plan.add(65536);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *px_, *py_, *vx_, *vy_;
+    const float *pd_;
+    const int *pe_, *ii_;
+    const long *io_;
+    IMCOM_TRY(st.in(pool_x, np, &px_));
+    IMCOM_TRY(st.in(pool_y, np, &py_));
+    IMCOM_TRY(st.in(pool_data, np * n_inframe, &pd_));
+    IMCOM_TRY(st.in(pool_expo, np, &pe_));
+    IMCOM_TRY(st.in(inst_off, (size_t)(n_inst + 1), &io_));
+    IMCOM_TRY(st.in(inst_id, nb * 9, &ii_));
+    IMCOM_TRY(st.in(pivot_x, nb * 9, &vx_));
+    IMCOM_TRY(st.in(pivot_y, nb * 9, &vy_));
+    double *x_d, *y_d;
+    float *d_d;
+    int *e_d, *c_d, *status;
+    IMCOM_TRY(st.out(x, nd, &x_d));
+    IMCOM_TRY(st.out(y, nd, &y_d));
+    IMCOM_TRY(st.out(indata, nd * n_inframe, &d_d));
+    IMCOM_TRY(st.out(expo, nd, &e_d));
+    IMCOM_TRY(st.out(cumsum, nb * 10, &c_d));
+    IMCOM_TRY(ws_take(ctx, 1, &status, __func__));
     IMCOM_HIP_CHECK(hipMemsetAsync(status, 0, 4, ctx->stream));
     { ProfScope ps(ctx, "select");
-    hipLaunchKernelGGL(select_pixels_kernel, dim3(batch), dim3(256), 0, ctx->stream, (const double *)px_, (const double *)py_,
-                       (const float *)pd_, npool, n_inframe, (const int *)pe_, (const long *)io_, (const int *)ii_, (const double *)vx_,
-                       (const double *)vy_, radius, ldn, x_d, y_d, d_d, e_d, c_d, status); }
+    hipLaunchKernelGGL(select_pixels_kernel, dim3(batch), dim3(256), 0, ctx->stream, px_, py_, pd_, npool, n_inframe, pe_, io_, ii_, vx_, vy_, radius,
+                       ldn, x_d, y_d, d_d, e_d, c_d, status); }
     IMCOM_TRY(check_launch("select_pixels_kernel"));
-    int st = 0;
-    IMCOM_HIP_CHECK(hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (host) {
-        IMCOM_HIP_CHECK(hipMemcpyAsync(x, x_d, nb * ldn * 8, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(y, y_d, nb * ldn * 8, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(indata, d_d, nb * ldn * 4 * n_inframe, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(expo, e_d, nb * ldn * 4, hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(cumsum, c_d, nb * 40, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    IMCOM_REQUIRE(st == 0, "a stamp selects %d input pixels, more than ldn=%d", st, ldn);
+    int sel = 0;
+    IMCOM_HIP_CHECK(hipMemcpyAsync(&sel, status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    IMCOM_TRY(st.back(x, x_d, nd));
+    IMCOM_TRY(st.back(y, y_d, nd));
+    IMCOM_TRY(st.back(indata, d_d, nd * n_inframe));
+    IMCOM_TRY(st.back(expo, e_d, nd));
+    IMCOM_TRY(st.back(cumsum, c_d, nb * 10));
+    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // in either memory space: the status word is read here
+    IMCOM_REQUIRE(sel == 0, "a stamp selects %d input pixels, more than ldn=%d", sel, ldn);
     return IMCOM_OK;
 }

@@ -927,11 +927,7 @@ int eigh_device(imcom_ctx *ctx, int batch, const int *n_host, int ld, const doub
     IMCOM_TRY(check_launch("tql init"));
     const size_t qr_lds = (size_t)2 * ld * 8;
     IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)tql_chunk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qr_lds));
-    while ((int)ctx->sync_events.size() < 2 * QR_RING + 1) {
-        hipEvent_t e;
-        IMCOM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->sync_events.push_back(e);
-    }
+    IMCOM_TRY(ensure_sync_events(ctx, 2 * QR_RING + 1));
     hipEvent_t *ev_qr = ctx->sync_events.data(), *ev_ap = ev_qr + QR_RING, ev_x = ctx->sync_events[2 * QR_RING];
     IMCOM_TRY(ensure_aux(ctx));
     hipStream_t sb = ctx->aux_stream;

@@ -9,17 +9,13 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import MEM_DEVICE, MEM_HOST, check, default_context, lib
+from ._lib import MEM_DEVICE, MEM_HOST, check, default_context, lib, ptr
 
 __all__ = ["InterpMatrix", "MultiInterp", "geometry", "stest_points"]
 
 
 def _is_torch(a):
     return a is not None and type(a).__module__.startswith("torch")
-
-
-def _p(a):
-    return C.c_void_p(a.data_ptr()) if _is_torch(a) else a.ctypes.data_as(C.c_void_p)
 
 
 def geometry(Rsearch):
@@ -30,7 +26,7 @@ def geometry(Rsearch):
     px = np.zeros(nn.value, dtype=np.int32)
     py = np.zeros(nn.value, dtype=np.int32)
     corners = np.zeros((4, ng.value), dtype=np.int32)
-    check(lib.imcom_ginterp_geometry(float(Rsearch), nn.value, C.byref(nn), C.byref(ng), _p(px), _p(py), _p(corners)))
+    check(lib.imcom_ginterp_geometry(float(Rsearch), nn.value, C.byref(nn), C.byref(ng), ptr(px), ptr(py), ptr(corners)))
     return px.astype(np.int16), py.astype(np.int16), corners
 
 
@@ -73,8 +69,8 @@ def InterpMatrix(Rsearch, samp, x_out, y_out, Cov, epsilon=1.0e-7, stest=1):
         mem = MEM_HOST
     if y.shape[0] != n:
         raise ValueError("x_out and y_out differ in length")
-    check(lib.imcom_ginterp_matrix(ctx.handle, float(Rsearch), float(samp), int(n), _p(x), _p(y), _p(cov), float(epsilon), stest, _p(T), _p(U),
-                                   _p(S), mem))
+    check(lib.imcom_ginterp_matrix(ctx.handle, float(Rsearch), float(samp), int(n), ptr(x), ptr(y), ptr(cov), float(epsilon), stest, ptr(T), ptr(U),
+                                   ptr(S), mem))
     return posx, posy, T, U, S
 
 
@@ -121,9 +117,9 @@ def MultiInterp(in_array, in_mask, out_size, out_origin, out_transform, Rsearch,
     ctx = default_context()
     if tor:
         ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    check(lib.imcom_ginterp_resample(ctx.handle, int(nlayer), int(ny_in), int(nx_in), _p(a3), f64, _p(m), ny, nx, _p(origin), _p(transform),
-                                     float(Rsearch), float(samp), _p(cov), float(epsilon), int(stest), int(blocksize), _p(out), _p(omask),
-                                     _p(us), mem))
+    check(lib.imcom_ginterp_resample(ctx.handle, int(nlayer), int(ny_in), int(nx_in), ptr(a3), f64, ptr(m), ny, nx, ptr(origin), ptr(transform),
+                                     float(Rsearch), float(samp), ptr(cov), float(epsilon), int(stest), int(blocksize), ptr(out), ptr(omask),
+                                     ptr(us), mem))
     if tor:
         umax, smax = (float(v) for v in us.cpu())
         omask = omask.bool()

@@ -20,11 +20,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import MEM_HOST, check, default_context, lib
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
+from ._lib import MEM_HOST, check, default_context, lib, ptr
 
 
 def _host_out(shape, dtype=np.float32, zero=False):
@@ -136,9 +132,9 @@ class HipCholKernel(_HipLAKernel):
     def _solve(self, A, B, C_, T, UC, Sigma, kappa, info):
         n_arr = np.array([self.n], dtype=np.int32)
         with _repair_memory(self.ctx):
-            check(lib.imcom_solve_chol(self.ctx.handle, 1, _ptr(n_arr), self.n, self.m, _ptr(A), _ptr(B), _ptr(C_),
-                                       _ptr(self.kappaC_arr), self.nv, self.ucmin, self.smax, _ptr(T), _ptr(UC),
-                                       _ptr(Sigma), _ptr(kappa), _ptr(info), MEM_HOST))
+            check(lib.imcom_solve_chol(self.ctx.handle, 1, ptr(n_arr), self.n, self.m, ptr(A), ptr(B), ptr(C_),
+                                       ptr(self.kappaC_arr), self.nv, self.ucmin, self.smax, ptr(T), ptr(UC),
+                                       ptr(Sigma), ptr(kappa), ptr(info), MEM_HOST))
 
 
 def solve_chol_stamps(outstamps, ctx=None):
@@ -181,9 +177,9 @@ def solve_chol_stamps(outstamps, ctx=None):
     for j in range(n_out):
         Cj = np.ascontiguousarray(Cs[:, j])
         with _repair_memory(k0.ctx):
-                check(lib.imcom_solve_chol_stamps(k0.ctx.handle, nst, _ptr(n_arr), m, pA, ptrs([b[j] for b in Bs]), _ptr(Cj), _ptr(k0.kappaC_arr), k0.nv,
+                check(lib.imcom_solve_chol_stamps(k0.ctx.handle, nst, ptr(n_arr), m, pA, ptrs([b[j] for b in Bs]), ptr(Cj), ptr(k0.kappaC_arr), k0.nv,
                                               k0.ucmin, k0.smax, ptrs([t[j] for t in T]), ptrs([UC[i, j] for i in range(nst)]),
-                                              ptrs([Sigma[i, j] for i in range(nst)]), ptrs([kappa[i, j] for i in range(nst)]), _ptr(info[j])))
+                                              ptrs([Sigma[i, j] for i in range(nst)]), ptrs([kappa[i, j] for i in range(nst)]), ptr(info[j])))
     for i, k in enumerate(kernels):
         k.info = np.ascontiguousarray(info[:, i])
         k.outst.T = T[i]
@@ -201,9 +197,9 @@ class HipEigenKernel(_HipLAKernel):
 
     def _solve(self, A, B, C_, T, UC, Sigma, kappa, info):
         n_arr = np.array([self.n], dtype=np.int32)
-        check(lib.imcom_solve_eigen(self.ctx.handle, 1, _ptr(n_arr), self.n, self.m, _ptr(A), _ptr(B), _ptr(C_),
-                                    _ptr(self.kappaC_arr), self.nv, self.ucmin, self.smax, int(self.nbis), _ptr(T),
-                                    _ptr(UC), _ptr(Sigma), _ptr(kappa), _ptr(info), MEM_HOST))
+        check(lib.imcom_solve_eigen(self.ctx.handle, 1, ptr(n_arr), self.n, self.m, ptr(A), ptr(B), ptr(C_),
+                                    ptr(self.kappaC_arr), self.nv, self.ucmin, self.smax, int(self.nbis), ptr(T),
+                                    ptr(UC), ptr(Sigma), ptr(kappa), ptr(info), MEM_HOST))
 
 
 class _HipGeomKernel(_HipLAKernel):
@@ -233,10 +229,10 @@ class HipIterKernel(_HipGeomKernel):
         yx, iny, inx, rho = self._geometry()
         exact = (self.nv > 1) if self.exact_UC is None else bool(self.exact_UC)
         n_arr = np.array([self.n], dtype=np.int32)
-        check(lib.imcom_solve_iter(self.ctx.handle, 1, _ptr(n_arr), self.n, self.m, _ptr(A), _ptr(B), _ptr(C_),
-                                   _ptr(self.kappaC_arr), self.nv, self.ucmin, self.smax, _ptr(yx), _ptr(iny), _ptr(inx),
-                                   rho, float(cfg.iter_rtol), int(cfg.iter_max), int(exact), _ptr(T), _ptr(UC),
-                                   _ptr(Sigma), _ptr(kappa), MEM_HOST))
+        check(lib.imcom_solve_iter(self.ctx.handle, 1, ptr(n_arr), self.n, self.m, ptr(A), ptr(B), ptr(C_),
+                                   ptr(self.kappaC_arr), self.nv, self.ucmin, self.smax, ptr(yx), ptr(iny), ptr(inx),
+                                   rho, float(cfg.iter_rtol), int(cfg.iter_max), int(exact), ptr(T), ptr(UC),
+                                   ptr(Sigma), ptr(kappa), MEM_HOST))
 
 
 class HipEmpirKernel(_HipGeomKernel):
@@ -251,8 +247,8 @@ class HipEmpirKernel(_HipGeomKernel):
         T = np.zeros((self.n_out, self.m, self.n), dtype=np.float32)
         maps = np.zeros((3, self.m), dtype=np.float32)
         n_arr = np.array([self.n], dtype=np.int32)
-        check(lib.imcom_solve_empir(self.ctx.handle, 1, _ptr(n_arr), self.n, self.m, None, None, None, 0.0, _ptr(yx),
-                                    _ptr(iny), _ptr(inx), rho, 1, _ptr(T[0]), _ptr(maps[0]), _ptr(maps[1]), _ptr(maps[2]),
+        check(lib.imcom_solve_empir(self.ctx.handle, 1, ptr(n_arr), self.n, self.m, None, None, None, 0.0, ptr(yx),
+                                    ptr(iny), ptr(inx), rho, 1, ptr(T[0]), ptr(maps[0]), ptr(maps[1]), ptr(maps[2]),
                                     MEM_HOST))
         T[1:] = T[0]  # the same weights for every target PSF (lakernel.py:775)
         self.outst.T = T
@@ -263,9 +259,9 @@ class HipEmpirKernel(_HipGeomKernel):
     def _solve(self, A, B, C_, T, UC, Sigma, kappa, info):
         yx, iny, inx, rho = self._geometry()
         n_arr = np.array([self.n], dtype=np.int32)
-        check(lib.imcom_solve_empir(self.ctx.handle, 1, _ptr(n_arr), self.n, self.m, _ptr(A), _ptr(B), _ptr(C_),
-                                    float(self.kappaC_arr[0]), _ptr(yx), _ptr(iny), _ptr(inx), rho, 0, _ptr(T), _ptr(UC),
-                                    _ptr(Sigma), _ptr(kappa), MEM_HOST))
+        check(lib.imcom_solve_empir(self.ctx.handle, 1, ptr(n_arr), self.n, self.m, ptr(A), ptr(B), ptr(C_),
+                                    float(self.kappaC_arr[0]), ptr(yx), ptr(iny), ptr(inx), rho, 0, ptr(T), ptr(UC),
+                                    ptr(Sigma), ptr(kappa), MEM_HOST))
 
 
 LAKERNEL = {"Cholesky": HipCholKernel, "Eigen": HipEigenKernel, "Iterative": HipIterKernel, "Empirical": HipEmpirKernel}

@@ -3,11 +3,9 @@
 
 Arrays may be numpy (host in, host out) or torch CUDA tensors (device in, device out)."""
 
-import ctypes as C
-
 import numpy as np
 
-from ._lib import MEM_DEVICE, MEM_HOST, check, default_context, lib
+from ._lib import MEM_DEVICE, MEM_HOST, check, default_context, lib, ptr
 
 QFILTER_NATIVE = [1.155, 1.456, 1.250, 1.021, 0.834, 0.689, 0.491, 1.009, 0.000, 1.159, 1.685]  # config.py:85-98
 OBSC = 0.31
@@ -25,12 +23,6 @@ def _out(shape, like, device):
     return np.empty(shape, dtype=np.float64)
 
 
-def _p(a):
-    if a is None:
-        return None
-    return C.c_void_p(a.data_ptr()) if _is_torch(a) else a.ctypes.data_as(C.c_void_p)
-
-
 def _bind(ctx, device):
     """Device-mode calls enqueue on the context's stream and return without a sync: that stream must be torch's current
     one, or torch could consume the output tensor before the kernel has written it."""
@@ -45,7 +37,7 @@ def psf_gaussian(n, sigmax, sigmay, device=None, ctx=None):
     ctx = ctx or default_context()
     out = _out((n, n), "torch" if device else "numpy", device)
     _bind(ctx, device)
-    check(lib.imcom_psf_gaussian(ctx.handle, int(n), float(sigmax), float(sigmay), _p(out), MEM_DEVICE if device else MEM_HOST))
+    check(lib.imcom_psf_gaussian(ctx.handle, int(n), float(sigmax), float(sigmay), ptr(out), MEM_DEVICE if device else MEM_HOST))
     return out
 
 
@@ -54,7 +46,7 @@ def psf_simple_airy(n, ldp, obsc=0.0, tophat_conv=0.0, sigma=0.0, device=None, c
     ctx = ctx or default_context()
     out = _out((n, n), "torch" if device else "numpy", device)
     _bind(ctx, device)
-    check(lib.imcom_psf_simple_airy(ctx.handle, int(n), float(ldp), float(obsc), float(tophat_conv), float(sigma), _p(out),
+    check(lib.imcom_psf_simple_airy(ctx.handle, int(n), float(ldp), float(obsc), float(tophat_conv), float(sigma), ptr(out),
                                     MEM_DEVICE if device else MEM_HOST))
     return out
 
@@ -78,7 +70,7 @@ def smooth_and_pad(inArray, tophatwidth=0.0, gaussiansigma=0.0, ctx=None):
         a = np.ascontiguousarray(a, dtype=np.float64)
         out = np.empty((n, ny + 2 * npad, nx + 2 * npad))
         mem = MEM_HOST
-    check(lib.imcom_smooth_and_pad(ctx.handle, n, _p(a), ny, nx, float(tophatwidth), float(gaussiansigma), _p(out), mem))
+    check(lib.imcom_smooth_and_pad(ctx.handle, n, ptr(a), ny, nx, float(tophatwidth), float(gaussiansigma), ptr(out), mem))
     return out[0] if single else out
 
 
@@ -112,8 +104,8 @@ def sample_psf(psf, nsamp, yxco=None, psf_circ=False, psf_norm=False, ctx=None):
     if yxco is not None:
         assert tuple(yxco.shape) == (n_psf, 2, nsamp, nsamp)
     out = _out((n_psf, nsamp, nsamp), "torch" if tor else "numpy", psf.device if tor else None)
-    check(lib.imcom_sample_psf(ctx.handle, n_psf, _p(psf), ny, nx, _p(yxco), int(nsamp), int(bool(psf_circ)), int(bool(psf_norm)),
-                               _p(out), MEM_DEVICE if tor else MEM_HOST))
+    check(lib.imcom_sample_psf(ctx.handle, n_psf, ptr(psf), ny, nx, ptr(yxco), int(nsamp), int(bool(psf_circ)), int(bool(psf_norm)),
+                               ptr(out), MEM_DEVICE if tor else MEM_HOST))
     return out
 
 
@@ -154,5 +146,5 @@ def lattice_positions(lattice, W, nsamp, ctx=None):
     else:
         lattice = np.ascontiguousarray(lattice, dtype=np.float64)
     out = _out((count, 2, nsamp, nsamp), "torch" if tor else "numpy", lattice.device if tor else None)
-    check(lib.imcom_lattice_positions(ctx.handle, int(count), int(L), _p(W), _p(lattice), int(nsamp), _p(out), MEM_DEVICE if tor else MEM_HOST))
+    check(lib.imcom_lattice_positions(ctx.handle, int(count), int(L), ptr(W), ptr(lattice), int(nsamp), ptr(out), MEM_DEVICE if tor else MEM_HOST))
     return out

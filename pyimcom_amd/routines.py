@@ -6,12 +6,10 @@ imported at lakernel.py:41-47 and psfutil.py:37-49).  Arguments are C-contiguous
 the work runs on the GPU (host buffers are staged by the library).  No CPU fallback.
 """
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
-from ._lib import MEM_HOST, check, default_context, lib
+from ._lib import MEM_HOST, check, default_context, lib, ptr
 
 
 def _f64(a, name, writable=False):
@@ -19,7 +17,7 @@ def _f64(a, name, writable=False):
         raise TypeError(f"{name} must be a C-contiguous float64 numpy array")
     if writable and not a.flags.writeable:
         raise ValueError(f"{name} must be writable")
-    return a.ctypes.data_as(C.c_void_p)
+    return ptr(a)
 
 
 def iD5512C_getw(w, fh):

@@ -2,11 +2,9 @@
 ``InStamp.make_selection`` 716-749): the block's InStamps are uploaded once as a pool, every output stamp then
 gathers its nine neighbours' pixels inside the acceptance region straight into the StampBatch layouts."""
 
-import ctypes as C
-
 import numpy as np
 
-from ._lib import MEM_DEVICE, check, default_context, lib
+from ._lib import MEM_DEVICE, check, default_context, lib, ptr
 
 
 class InStampPool:
@@ -61,11 +59,10 @@ def select_pixels(pool, inst_id, pivot_x, pivot_y, radius, ldn, ctx=None):
     indata = torch.empty((B, pool.n_inframe, ldn), dtype=torch.float32, device=dev)
     expo = torch.empty((B, ldn), dtype=torch.int32, device=dev)
     cumsum = torch.empty((B, 10), dtype=torch.int32, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    check(lib.imcom_select_pixels(ctx.handle, B, p(pool.x), p(pool.y), p(pool.data), pool.npool, pool.n_inframe, p(pool.expo),
-                                  p(pool.inst_off_dev), pool.n_inst, p(iid), p(pvx), p(pvy), float(radius), int(ldn), p(x), p(y),
-                                  p(indata), p(expo), p(cumsum), MEM_DEVICE))
+    check(lib.imcom_select_pixels(ctx.handle, B, ptr(pool.x), ptr(pool.y), ptr(pool.data), pool.npool, pool.n_inframe, ptr(pool.expo),
+                                  ptr(pool.inst_off_dev), pool.n_inst, ptr(iid), ptr(pvx), ptr(pvy), float(radius), int(ldn), ptr(x), ptr(y),
+                                  ptr(indata), ptr(expo), ptr(cumsum), MEM_DEVICE))
     return x, y, indata, expo, cumsum.cpu().numpy()
 
 
@@ -107,8 +104,7 @@ def partition_pixels(out_x, out_y, in_x, in_y, mask, use_instamps, n2, n1P, npix
     x_val = torch.zeros_like(y_val)
     count = torch.zeros((nst, nst), dtype=torch.uint32, device=dev)
     pix_lower, pix_upper = -n2 - 0.5, n1P * n2 + n2 - 0.5  # coadd.py:208-209 (NsideP = n1P * n2)
-    p = lambda a: None if a is None else C.c_void_p(a.data_ptr())  # noqa: E731
     ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    check(lib.imcom_partition_pixels(ctx.handle, npix, p(ox), p(oy), p(ix), p(iy), p(mk), p(use), nst, int(n2), pix_lower, pix_upper,
-                                     int(npixmax), p(y_idx), p(x_idx), p(y_val), p(x_val), p(count)))
+    check(lib.imcom_partition_pixels(ctx.handle, npix, ptr(ox), ptr(oy), ptr(ix), ptr(iy), ptr(mk), ptr(use), nst, int(n2), pix_lower, pix_upper,
+                                     int(npixmax), ptr(y_idx), ptr(x_idx), ptr(y_val), ptr(x_val), ptr(count)))
     return y_idx, x_idx, y_val, x_val, count

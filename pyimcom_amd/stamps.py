@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ._lib import PAIR_SWAP,  PAIR_FLIP, ImcomError, TableGeom, check, default_context, lib
+from ._lib import PAIR_SWAP,  PAIR_FLIP, ImcomError, TableGeom, check, default_context, lib, ptr
 
 NB = 128
 SPECTRA_CHUNK = 1024  # PSFs sampled and transformed per call (BlockTables._ensure_spectra)
@@ -21,14 +21,6 @@ SPECTRA_CHUNK = 1024  # PSFs sampled and transformed per call (BlockTables._ensu
 
 def _roundup(v, a):
     return (v + a - 1) // a * a
-
-
-def _dp(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _hp(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _runs(mask):
@@ -91,7 +83,7 @@ def psf_spectra(ctx, psf, nfft):
         return None
     spec = torch.empty((n, size), dtype=torch.float64, device=psf.device)
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)
-    check(lib.imcom_psf_spectra(ctx.handle, _dp(psf), n, ns, nfft, _dp(spec)))
+    check(lib.imcom_psf_spectra(ctx.handle, ptr(psf), n, ns, nfft, ptr(spec)))
     return spec
 
 
@@ -101,25 +93,25 @@ def overlap_tables(ctx, p1, s1, p2, s2, nsamp, nfft, pairs, amp, out, win=None, 
     that will be read, imcom_psf_overlap_spectra_win.  ``slots`` [npairs] (spectra form only): pair t goes to table
     ``out[slots[t]]`` of the arena ``out`` instead of ``out[t]``, imcom_psf_overlap_spectra_slots."""
     pairs = np.ascontiguousarray(pairs, dtype=np.int32)
-    ampp = None if amp is None else _hp(amp)
+    ampp = None if amp is None else ptr(amp)
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)
     if s1 is not None and s2 is not None:
         winp = None
         if win is not None:
             win = np.ascontiguousarray(win, dtype=np.int32)
             assert win.shape == (len(pairs), 4)
-            winp = _hp(win)
+            winp = ptr(win)
         slp = None
         if slots is not None:
             slots = np.ascontiguousarray(slots, dtype=np.int32)
             assert slots.shape == (len(pairs),)
-            slp = _hp(slots)
-        check(lib.imcom_psf_overlap_spectra_slots(ctx.handle, _dp(s1), s1.shape[0], _dp(s2), s2.shape[0], nsamp, nfft, _hp(pairs),
-                                                  len(pairs), ampp, winp, slp, out.shape[0], _dp(out)))
+            slp = ptr(slots)
+        check(lib.imcom_psf_overlap_spectra_slots(ctx.handle, ptr(s1), s1.shape[0], ptr(s2), s2.shape[0], nsamp, nfft, ptr(pairs),
+                                                  len(pairs), ampp, winp, slp, out.shape[0], ptr(out)))
     else:
         assert slots is None
-        check(lib.imcom_psf_overlap(ctx.handle, _dp(p1), p1.shape[0], _dp(p2), p2.shape[0], nsamp, nfft, _hp(pairs), len(pairs),
-                                    ampp, _dp(out)))
+        check(lib.imcom_psf_overlap(ctx.handle, ptr(p1), p1.shape[0], ptr(p2), p2.shape[0], nsamp, nfft, ptr(pairs), len(pairs),
+                                    ampp, ptr(out)))
 
 
 class PSFGroupTables:
@@ -305,7 +297,7 @@ class BlockTables:
         self._dev_psf = {}  # device copies of the sampled PSFs, kept only when there are no spectra to keep instead
         if size:
             self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
-            check(lib.imcom_psf_spectra(self.ctx.handle, _dp(self.pout), O, self.nsamp, self.nfft, _dp(self._spec_all[:O])))
+            check(lib.imcom_psf_spectra(self.ctx.handle, ptr(self.pout), O, self.nsamp, self.nfft, ptr(self._spec_all[:O])))
         cc = torch.empty((O, ng, ng), dtype=torch.float64, device=dev)
         self._compute([(None, None, [(o, o) for o in range(O)])], cc)
         nc = self.nsamp // 2
@@ -388,7 +380,7 @@ class BlockTables:
             p = self._sampled(part)
             r0 = self._spec_next
             self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
-            check(lib.imcom_psf_spectra(self.ctx.handle, _dp(p), p.shape[0], self.nsamp, self.nfft, _dp(self._spec_all[r0 : r0 + p.shape[0]])))
+            check(lib.imcom_psf_spectra(self.ctx.handle, ptr(p), p.shape[0], self.nsamp, self.nfft, ptr(self._spec_all[r0 : r0 + p.shape[0]])))
             for g in part:
                 self._spec_row[g] = self._spec_next
                 self._spec_next += self._count_of[g]
@@ -747,14 +739,14 @@ class StampBatch:
             return  # coadd.py:1020-1025: the Empirical kernel without quality control never builds the system matrices
         self._stream()
         h = self.ctx.handle
-        check(lib.imcom_build_A(h, self.batch, _hp(self.n), self.ldn, _dp(self.x), _dp(self.y), _dp(self.psf),
-                                _dp(self.tables.tables), self.tables.tables.shape[0], C.byref(self.geom),
-                                _dp(self.pair_tab), _dp(self.pair_pen), self.npsf, _dp(self.A)))
+        check(lib.imcom_build_A(h, self.batch, ptr(self.n), self.ldn, ptr(self.x), ptr(self.y), ptr(self.psf),
+                                ptr(self.tables.tables), self.tables.tables.shape[0], C.byref(self.geom),
+                                ptr(self.pair_tab), ptr(self.pair_pen), self.npsf, ptr(self.A)))
         for o in range(self.n_out):
-            check(lib.imcom_build_B(h, self.batch, _hp(self.n), self.ldn, _dp(self.x), _dp(self.y), _dp(self.psf),
-                                    _dp(self.tables.tables), self.tables.tables.shape[0], C.byref(self.geom),
-                                    _dp(self.io_tab_o[o]), self.npsf, _dp(self.out_x0), _dp(self.out_y0), self.n2f, self.ldm,
-                                    _dp(self.Bt_o[o])))
+            check(lib.imcom_build_B(h, self.batch, ptr(self.n), self.ldn, ptr(self.x), ptr(self.y), ptr(self.psf),
+                                    ptr(self.tables.tables), self.tables.tables.shape[0], C.byref(self.geom),
+                                    ptr(self.io_tab_o[o]), self.npsf, ptr(self.out_x0), ptr(self.out_y0), self.n2f, self.ldm,
+                                    ptr(self.Bt_o[o])))
 
     def _no_qlt_ctrl(self):
         return self.cfg.kernel == "Empirical" and bool(getattr(self.cfg, "no_qlt_ctrl", False))
@@ -807,16 +799,16 @@ class StampBatch:
             return
         self._stream()
         self._coadded = set()
-        rc = lib.imcom_solve_chol_resident_begin(self.ctx.handle, self.batch, _hp(self.n), self.ldn, self.m, self.ldm, _dp(self.A), _dp(self.Bt_o[0]),
-                                                 _hp(self.Cs_o[0]), _hp(self.kappaC), len(self.kappaC), float(cfg.uctarget), float(cfg.sigmamax),
-                                                 _dp(self.Tt_o[0]), _dp(self.UC_o[0]), _dp(self.Sigma_o[0]), _dp(self.kappa_o[0]))
+        rc = lib.imcom_solve_chol_resident_begin(self.ctx.handle, self.batch, ptr(self.n), self.ldn, self.m, self.ldm, ptr(self.A), ptr(self.Bt_o[0]),
+                                                 ptr(self.Cs_o[0]), ptr(self.kappaC), len(self.kappaC), float(cfg.uctarget), float(cfg.sigmamax),
+                                                 ptr(self.Tt_o[0]), ptr(self.UC_o[0]), ptr(self.Sigma_o[0]), ptr(self.kappa_o[0]))
         if rc == -3:  # the workspace could not grow (nothing has been queued): the synchronous path hands torch's cached memory back and retries
             self._unsolved = True
             return
         check(rc)
         if cfg.fade > 0:
             for t in (self.kappa_o[0], self.Sigma_o[0], self.UC_o[0]):
-                check(lib.imcom_trapezoid_f32(self.ctx.handle, _dp(t), self.batch, self.n2f, cfg.fade))
+                check(lib.imcom_trapezoid_f32(self.ctx.handle, ptr(t), self.batch, self.n2f, cfg.fade))
         self._deferred = True
 
     def solve_end(self):
@@ -843,12 +835,12 @@ class StampBatch:
             self._coadded = set()
             cfg, info = self.cfg, self.info_o[0]
             redo = np.full(self.batch, 3, dtype=np.int32)  # 3: the failure is this driver's EXPECTATION (2: observed by solve_end, below)
-            check(lib.imcom_solve_chol_resident_redo(self.ctx.handle, self.batch, _hp(self.n), self.ldn, self.m, self.ldm, _dp(self.A), _dp(self.Bt_o[0]),
-                                                     _hp(self.Cs_o[0]), _hp(self.kappaC), 1, float(cfg.uctarget), float(cfg.sigmamax),
-                                                     _dp(self.Tt_o[0]), _dp(self.UC_o[0]), _dp(self.Sigma_o[0]), _dp(self.kappa_o[0]), _hp(redo), _hp(info)))
+            check(lib.imcom_solve_chol_resident_redo(self.ctx.handle, self.batch, ptr(self.n), self.ldn, self.m, self.ldm, ptr(self.A), ptr(self.Bt_o[0]),
+                                                     ptr(self.Cs_o[0]), ptr(self.kappaC), 1, float(cfg.uctarget), float(cfg.sigmamax),
+                                                     ptr(self.Tt_o[0]), ptr(self.UC_o[0]), ptr(self.Sigma_o[0]), ptr(self.kappa_o[0]), ptr(redo), ptr(info)))
             if cfg.fade > 0:
                 for t in (self.kappa_o[0], self.Sigma_o[0], self.UC_o[0]):
-                    check(lib.imcom_trapezoid_f32(self.ctx.handle, _dp(t), self.batch, self.n2f, cfg.fade))
+                    check(lib.imcom_trapezoid_f32(self.ctx.handle, ptr(t), self.batch, self.n2f, cfg.fade))
             self.repair_share = float((info != 0).mean())
             self._note_repair()
             return False
@@ -857,20 +849,20 @@ class StampBatch:
         self._deferred = False
         self._stream()
         cfg, info = self.cfg, self.info_o[0]
-        rc = lib.imcom_solve_chol_resident_end(self.ctx.handle, self.batch, _hp(info))
+        rc = lib.imcom_solve_chol_resident_end(self.ctx.handle, self.batch, ptr(info))
         if rc == 1:
             again = info != 0
             if len(self.kappaC) != 1 or os.environ.get("IMCOM_REDO_ALL") == "1":  # several kappa nodes: every stamp again (the synchronous entry)
                 self.solve()
                 return np.ones(self.batch, dtype=bool)
             redo = np.where(again, 2, 0).astype(np.int32)
-            check(lib.imcom_solve_chol_resident_redo(self.ctx.handle, self.batch, _hp(self.n), self.ldn, self.m, self.ldm, _dp(self.A), _dp(self.Bt_o[0]),
-                                                     _hp(self.Cs_o[0]), _hp(self.kappaC), 1, float(cfg.uctarget), float(cfg.sigmamax),
-                                                     _dp(self.Tt_o[0]), _dp(self.UC_o[0]), _dp(self.Sigma_o[0]), _dp(self.kappa_o[0]), _hp(redo), _hp(info)))
+            check(lib.imcom_solve_chol_resident_redo(self.ctx.handle, self.batch, ptr(self.n), self.ldn, self.m, self.ldm, ptr(self.A), ptr(self.Bt_o[0]),
+                                                     ptr(self.Cs_o[0]), ptr(self.kappaC), 1, float(cfg.uctarget), float(cfg.sigmamax),
+                                                     ptr(self.Tt_o[0]), ptr(self.UC_o[0]), ptr(self.Sigma_o[0]), ptr(self.kappa_o[0]), ptr(redo), ptr(info)))
             if cfg.fade > 0:  # the map tapers of coadd.py:1118-1122 on the stamps that were solved again (the others have theirs)
                 for s0, s1 in _runs(again):
                     for t in (self.kappa_o[0], self.Sigma_o[0], self.UC_o[0]):
-                        check(lib.imcom_trapezoid_f32(self.ctx.handle, _dp(t[s0:]), s1 - s0, self.n2f, cfg.fade))
+                        check(lib.imcom_trapezoid_f32(self.ctx.handle, ptr(t[s0:]), s1 - s0, self.n2f, cfg.fade))
             self.repair_share = float(again.mean())
             self._note_repair()
             return again
@@ -882,9 +874,9 @@ class StampBatch:
         cfg = self.cfg
         if cfg.kernel == "Eigen":
             # lakernel.EigenKernel (lakernel.py:141-223) on the resident layouts
-            check(lib.imcom_solve_eigen_resident(self.ctx.handle, self.batch, _hp(self.n), self.ldn, self.m, self.ldm, _dp(self.A), _dp(Bt),
-                                                 _hp(Cs), _hp(self.kappaC), len(self.kappaC), float(cfg.uctarget), float(cfg.sigmamax), 13,
-                                                 _dp(Tt), _dp(UC), _dp(Sigma), _dp(kappa), _hp(info)))
+            check(lib.imcom_solve_eigen_resident(self.ctx.handle, self.batch, ptr(self.n), self.ldn, self.m, self.ldm, ptr(self.A), ptr(Bt),
+                                                 ptr(Cs), ptr(self.kappaC), len(self.kappaC), float(cfg.uctarget), float(cfg.sigmamax), 13,
+                                                 ptr(Tt), ptr(UC), ptr(Sigma), ptr(kappa), ptr(info)))
         elif cfg.kernel in ("Iterative", "Empirical"):
             # lakernel.IterKernel / EmpirKernel (lakernel.py:533-805) on device pointers; the output pixel centres
             # are the integer grid starting at (out_y0, out_x0), the acceptance radius is INPAD in output pixels
@@ -897,39 +889,39 @@ class StampBatch:
             yx = torch.stack([oy.reshape(self.batch, self.m), ox.reshape(self.batch, self.m)], dim=1).contiguous()
             if cfg.kernel == "Iterative":
                 nv = len(self.kappaC)
-                check(lib.imcom_solve_iter(self.ctx.handle, self.batch, _hp(self.n), self.ldn, self.m, _dp(self.A), _dp(mB),
-                                           _hp(Cs), _hp(self.kappaC), nv, float(cfg.uctarget), float(cfg.sigmamax), _dp(yx),
-                                           _dp(self.y), _dp(self.x), float(cfg.rho), float(getattr(cfg, "iter_rtol", 1.5e-3)),
-                                           int(getattr(cfg, "iter_max", 30)), int(nv > 1), _dp(T), _dp(UC), _dp(Sigma),
-                                           _dp(kappa), 1))
+                check(lib.imcom_solve_iter(self.ctx.handle, self.batch, ptr(self.n), self.ldn, self.m, ptr(self.A), ptr(mB),
+                                           ptr(Cs), ptr(self.kappaC), nv, float(cfg.uctarget), float(cfg.sigmamax), ptr(yx),
+                                           ptr(self.y), ptr(self.x), float(cfg.rho), float(getattr(cfg, "iter_rtol", 1.5e-3)),
+                                           int(getattr(cfg, "iter_max", 30)), int(nv > 1), ptr(T), ptr(UC), ptr(Sigma),
+                                           ptr(kappa), 1))
                 self.iter_stats = self.ctx.iter_stats()  # patches, flops and bytes of the CG steps, largest union (bench.py's roofline)
             else:
                 # (no quality control, lakernel.py:774-777: T alone, the maps stay zero, A and -B/2 are never read)
-                check(lib.imcom_solve_empir(self.ctx.handle, self.batch, _hp(self.n), self.ldn, self.m, None if nqc else _dp(self.A), None if nqc else _dp(mB),
-                                            _hp(Cs), float(self.kappaC[0]), _dp(yx), _dp(self.y), _dp(self.x), float(cfg.rho),
-                                            1 if nqc else 0, _dp(T), _dp(UC), _dp(Sigma), _dp(kappa), 1))
+                check(lib.imcom_solve_empir(self.ctx.handle, self.batch, ptr(self.n), self.ldn, self.m, None if nqc else ptr(self.A), None if nqc else ptr(mB),
+                                            ptr(Cs), float(self.kappaC[0]), ptr(yx), ptr(self.y), ptr(self.x), float(cfg.rho),
+                                            1 if nqc else 0, ptr(T), ptr(UC), ptr(Sigma), ptr(kappa), 1))
             Tt.zero_()
             Tt[:, :, : self.m] = T.transpose(1, 2)
         elif cfg.kernel != "Cholesky":
             raise NotImplementedError(f"resident path: no {cfg.kernel} kernel")
         elif cfg.fade == 0 and os.environ.get("IMCOM_EPILOGUE_FUSED") == "1":
-            check(lib.imcom_solve_chol_resident_coadd(self.ctx.handle, self.batch, _hp(self.n), self.ldn, self.m, self.ldm,
-                                                      _dp(self.A), _dp(Bt), _hp(Cs), _hp(self.kappaC), len(self.kappaC),
-                                                      float(cfg.uctarget), float(cfg.sigmamax), _dp(Tt), _dp(UC), _dp(Sigma), _dp(kappa), _hp(info),
-                                                      self.n2f, 0, cfg.n2, _dp(self.indata), cfg.n_inframe, _dp(self.expo), self.n_expo,
-                                                      _dp(self.outimage_o[o]), _dp(self.Tsum_stamp_o[o]), _dp(self.Tsum_inpix_o[o]), _dp(self.Neff_o[o])))
+            check(lib.imcom_solve_chol_resident_coadd(self.ctx.handle, self.batch, ptr(self.n), self.ldn, self.m, self.ldm,
+                                                      ptr(self.A), ptr(Bt), ptr(Cs), ptr(self.kappaC), len(self.kappaC),
+                                                      float(cfg.uctarget), float(cfg.sigmamax), ptr(Tt), ptr(UC), ptr(Sigma), ptr(kappa), ptr(info),
+                                                      self.n2f, 0, cfg.n2, ptr(self.indata), cfg.n_inframe, ptr(self.expo), self.n_expo,
+                                                      ptr(self.outimage_o[o]), ptr(self.Tsum_stamp_o[o]), ptr(self.Tsum_inpix_o[o]), ptr(self.Neff_o[o])))
             self._coadded.add(o)
         else:
-            check(lib.imcom_solve_chol_resident(self.ctx.handle, self.batch, _hp(self.n), self.ldn, self.m, self.ldm,
-                                            _dp(self.A), _dp(Bt), _hp(Cs), _hp(self.kappaC), len(self.kappaC),
-                                            float(cfg.uctarget), float(cfg.sigmamax), _dp(Tt), _dp(UC),
-                                            _dp(Sigma), _dp(kappa), _hp(info)))
+            check(lib.imcom_solve_chol_resident(self.ctx.handle, self.batch, ptr(self.n), self.ldn, self.m, self.ldm,
+                                            ptr(self.A), ptr(Bt), ptr(Cs), ptr(self.kappaC), len(self.kappaC),
+                                            float(cfg.uctarget), float(cfg.sigmamax), ptr(Tt), ptr(UC),
+                                            ptr(Sigma), ptr(kappa), ptr(info)))
         if cfg.kernel == "Iterative":  # coadd.py:1104-1107: "these could be negative as the iterative kernel is not exact"
             for t in (UC, Sigma):
-                check(lib.imcom_clamp_min_f32(self.ctx.handle, _dp(t), t.numel(), 1e-32))
+                check(lib.imcom_clamp_min_f32(self.ctx.handle, ptr(t), t.numel(), 1e-32))
         if cfg.fade > 0 and not self._no_qlt_ctrl():  # (without quality control _build_system_matrices returns before the map tapers, coadd.py:1020-1025)
             for t in (kappa, Sigma, UC):
-                check(lib.imcom_trapezoid_f32(self.ctx.handle, _dp(t), self.batch, self.n2f, cfg.fade))
+                check(lib.imcom_trapezoid_f32(self.ctx.handle, ptr(t), self.batch, self.n2f, cfg.fade))
 
     def coadd(self, only=None):
         """OutStamp._perform_coaddition (coadd.py:1294-1363).  ``only``: boolean mask [batch] -- the stamps to coadd (the call tapers T in
@@ -942,10 +934,10 @@ class StampBatch:
             if o in done:  # coadded inside solve()
                 continue
             for s0, s1 in spans:
-                check(lib.imcom_coadd_epilogue(self.ctx.handle, s1 - s0, _hp(self.n[s0:s1]), self.ldn, self.m, self.ldm, self.n2f,
-                                               cfg.fade, cfg.n2, _dp(self.Tt_o[o][s0:]), _dp(self.indata[s0:]), cfg.n_inframe, _dp(self.expo[s0:]),
-                                               self.n_expo, _dp(self.outimage_o[o][s0:]), _dp(self.Tsum_stamp_o[o][s0:]), _dp(self.Tsum_inpix_o[o][s0:]),
-                                               _dp(self.Neff_o[o][s0:])))
+                check(lib.imcom_coadd_epilogue(self.ctx.handle, s1 - s0, ptr(self.n[s0:s1]), self.ldn, self.m, self.ldm, self.n2f,
+                                               cfg.fade, cfg.n2, ptr(self.Tt_o[o][s0:]), ptr(self.indata[s0:]), cfg.n_inframe, ptr(self.expo[s0:]),
+                                               self.n_expo, ptr(self.outimage_o[o][s0:]), ptr(self.Tsum_stamp_o[o][s0:]), ptr(self.Tsum_inpix_o[o][s0:]),
+                                               ptr(self.Neff_o[o][s0:])))
 
     repair_share = 0.0   # share of the batch's stamps that took the Cholesky repair in its last solve (solve_begin / solve_end)
     EXPECT_REPAIR = 0.75  # a driver skips the doomed first factorisation of a pass when the pass before it was above this

@@ -84,3 +84,40 @@ def test_import_after_the_runtime_is_up_warns_and_changes_nothing():
     env["PYTHONPATH"] = root
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert out.stdout.split() == ["False", "1"], (out.stdout, out.stderr[-500:])
+
+
+# One entry per source file whose entries take a context (pyimcom_amd/csrc/): a null context is refused before anything else
+# is looked at, so every other argument may be zero / NULL and no device is touched.
+NULL_CTX_ENTRIES = {
+    "api.hip": "imcom_ctx_sync",
+    "block.hip": "imcom_block_accumulate",
+    "eigen.hip": "imcom_eigh",
+    "ginterp.hip": "imcom_ginterp_matrix",
+    "iter_empir.hip": "imcom_solve_iter",
+    "partition.hip": "imcom_partition_pixels",
+    "psf_overlap.hip": "imcom_psf_overlap",
+    "psf_sample.hip": "imcom_sample_psf",
+    "select.hip": "imcom_select_pixels",
+}
+
+
+@pytest.mark.parametrize("source", sorted(NULL_CTX_ENTRIES))
+def test_null_context_is_refused(source):
+    import ctypes as C
+
+    from pyimcom_amd import _lib
+
+    name = NULL_CTX_ENTRIES[source]
+    args = [0.0 if t is C.c_double else 0 if t in (C.c_int, C.c_long) else None for t in _lib.SIGNATURES[name]]
+    assert getattr(_lib.lib, name)(*args) == -1  # IMCOM_ERR_ARG
+    assert "null context" in _lib.lib.imcom_last_error().decode()
+
+
+def test_every_context_source_is_covered():
+    """The table above names every source file that defines an entry taking a context."""
+    csrc = os.path.join(ROOT, "pyimcom_amd", "csrc")
+    have = set()
+    for f in os.listdir(csrc):
+        if f.endswith(".hip") and re.search(r'^(extern "C" )?int imcom_\w+\(imcom_ctx \*', open(os.path.join(csrc, f)).read(), re.M):
+            have.add(f)
+    assert have == set(NULL_CTX_ENTRIES), have ^ set(NULL_CTX_ENTRIES)

@@ -11,12 +11,11 @@ stamps = [synth.make_stamp(cfg, i) for i in range(B)]
 psfs, target = synth.make_psfs(cfg, max(s.n_expo for s in stamps))
 sb = StampBatch(cfg, stamps, PSFGroupTables(psfs, target, cfg.nfft))
 import ctypes as C
-from pyimcom_amd._lib import lib, check
-from pyimcom_amd.stamps import _dp, _hp
+from pyimcom_amd._lib import lib, check, ptr
 def buildA():
     sb._stream()
-    check(lib.imcom_build_A(sb.ctx.handle, sb.batch, _hp(sb.n), sb.ldn, _dp(sb.x), _dp(sb.y), _dp(sb.psf), _dp(sb.tables.tables),
-                            sb.tables.tables.shape[0], C.byref(sb.geom), _dp(sb.pair_tab), _dp(sb.pair_pen), sb.npsf, _dp(sb.A)))
+    check(lib.imcom_build_A(sb.ctx.handle, sb.batch, ptr(sb.n), sb.ldn, ptr(sb.x), ptr(sb.y), ptr(sb.psf), ptr(sb.tables.tables),
+                            sb.tables.tables.shape[0], C.byref(sb.geom), ptr(sb.pair_tab), ptr(sb.pair_pen), sb.npsf, ptr(sb.A)))
 buildA(); torch.cuda.synchronize()
 t0 = time.perf_counter()
 for _ in range(reps):
