@@ -500,6 +500,25 @@ int imcom_ginterp_resample(imcom_ctx *ctx, int nlayer, int ny_in, int nx_in, con
                            const double *Cov, double epsilon, int stest, long blocksize, void *out, unsigned char *out_mask,
                            double *UmaxSmax, int memspace);
 
+/* Injected point-source layers (reference src/pyimcom/layer.py:792-854, GridInject.make_image_from_grid: the image of `cstar`, and the
+ * brightness of `nstar`, layer.py:1346-1388).
+ *   imcom_psf_from_cube   the draw PSFs of InImage.get_psf_pos for the Legendre-cube formats (coadd.py:624-640) at a batch of positions:
+ *                         out[s] = scale * smooth_and_pad(sum_a lpoly[s][a] cube[a], tophatwidth, gaussiansigma), cube [na][ny][nx],
+ *                         lpoly [nstar][na] (InImage.LPolyArr, coadd.py:476-510), out [nstar][ny + 2 npad][nx + 2 npad] with npad =
+ *                         imcom_smooth_pad_width(); scale = 1/64 for `anlsim`, 1 for `L2_2506` (coadd.py:628-640).  The smearing is linear
+ *                         and is applied to the na planes once per call; a star costs the contraction alone (rounding differs).
+ *   imcom_draw_stars      layer.py:825-852: for every star s at (xsca[s], ysca[s]) (may lie off the chip) and every native pixel of its
+ *                         box [int(x) - d, int(x) + d) x [int(y) - d, int(y) + d) clipped to the image (int() truncates towards zero),
+ *                         image[iy][ix] += oversamp^2 * iD5512C(psfs[s] zero-padded by 6) at
+ *                         (oversamp (ix - x) + (px - 1)/2 + 6, oversamp (iy - y) + (py - 1)/2 + 6); points off the interpolation grid add
+ *                         nothing (routine.py:166-167).  psfs [nstar][py][px], image [nside][nside].  Every pixel adds its stars in
+ *                         ascending s, without atomics: the image is the same bit for bit for every split of the star list into calls.
+ *   all arrays follow `memspace`. */
+int imcom_psf_from_cube(imcom_ctx *ctx, int na, const double *cube, int ny, int nx, int nstar, const double *lpoly, double tophatwidth,
+                        double gaussiansigma, double scale, double *out, int memspace);
+int imcom_draw_stars(imcom_ctx *ctx, int nstar, const double *psfs, int py, int px, const double *xsca, const double *ysca, double oversamp,
+                     int d, int nside, double *image, int memspace);
+
 #ifdef __cplusplus
 }
 #endif

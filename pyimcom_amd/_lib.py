@@ -128,6 +128,8 @@ SIGNATURES = {
     "imcom_ginterp_geometry": [_d, _i, _ip, _ip, _vp, _vp, _vp],
     "imcom_ginterp_matrix": [_vp, _d, _d, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _vp, _i],
     "imcom_ginterp_resample": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _d, _d, _vp, _d, _i, _l, _vp, _vp, _vp, _i],
+    "imcom_psf_from_cube": [_vp, _i, _vp, _i, _i, _i, _vp, _d, _d, _d, _vp, _i],
+    "imcom_draw_stars": [_vp, _i, _vp, _i, _i, _vp, _vp, _d, _i, _i, _vp, _i],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

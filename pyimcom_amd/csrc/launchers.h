@@ -125,4 +125,19 @@ int launch_build_B(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, const d
                    const int *psf, const double *tables, int ng, double nc, double dscale, const int *io_tab,
                    int npsf_max, const double *out_x0, const double *out_y0, int n2f, int ldm, double *Bt);
 
+
+// psf_sample.hip: the device work of imcom_smooth_and_pad on its own (src, dst in device memory), its scratch out of the workspace
+struct SmoothPadWs {
+    double *I, *Y, *Z, *Cy, *Cx, *ky, *kx;
+};
+size_t smooth_pad_ws_bytes(int n, int ny, int nx, double tophatwidth, double gaussiansigma);
+int smooth_pad_take(imcom_ctx *ctx, int n, int ny, int nx, double tophatwidth, double gaussiansigma, SmoothPadWs *w, const char *who);
+int smooth_pad_device(imcom_ctx *ctx, const SmoothPadWs &w, int n, const double *src, int ny, int nx, double tophatwidth, double gaussiansigma,
+                      double *dst);
+
+// inject.hip
+int launch_cube_contract(imcom_ctx *ctx, const double *planes, int na, long npix, const double *lpoly, int nstar, double scale, double *out);
+int launch_draw_stars(imcom_ctx *ctx, int nstar, const double *psfs, int py, int px, const double *xsca, const double *ysca, double oversamp,
+                      int d, int nside, double *image);
+
 }  // namespace imcom

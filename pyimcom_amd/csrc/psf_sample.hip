@@ -209,6 +209,50 @@ __global__ __launch_bounds__(256) void lattice_positions_kernel(const double *__
     }
 }
 
+// imcom_smooth_and_pad's device work, shared with imcom_psf_from_cube (api.hip): the scratch is taken from the workspace the caller
+// has reserved (smooth_pad_ws_bytes counts it), src [n][ny][nx] and dst [n][ny + 2 npad][nx + 2 npad] are device memory.
+size_t smooth_pad_ws_bytes(int n, int ny, int nx, double tophatwidth, double gaussiansigma)
+{
+    const int npad = imcom_smooth_pad_width(tophatwidth, gaussiansigma), nyy = ny + 2 * npad, nxx = nx + 2 * npad;
+    const int Py = (int)align_up((size_t)nyy, NB), Px = (int)align_up((size_t)nxx, NB);
+    return 3 * (size_t)n * Py * Px * 8 + (size_t)Py * Py * 8 + (size_t)Px * Px * 8 + (size_t)(nyy + nxx) * 8 + 16384;
+}
+
+int smooth_pad_take(imcom_ctx *ctx, int n, int ny, int nx, double tophatwidth, double gaussiansigma, SmoothPadWs *w, const char *who)
+{
+    const int npad = imcom_smooth_pad_width(tophatwidth, gaussiansigma), nyy = ny + 2 * npad, nxx = nx + 2 * npad;
+    const int Py = (int)align_up((size_t)nyy, NB), Px = (int)align_up((size_t)nxx, NB);
+    const size_t szI = (size_t)n * Py * Px * 8;
+    w->I = (double *)ws_take(ctx, szI), w->Y = (double *)ws_take(ctx, szI), w->Z = (double *)ws_take(ctx, szI);
+    w->Cy = (double *)ws_take(ctx, (size_t)Py * Py * 8), w->Cx = (double *)ws_take(ctx, (size_t)Px * Px * 8);
+    w->ky = (double *)ws_take(ctx, (size_t)nyy * 8), w->kx = (double *)ws_take(ctx, (size_t)nxx * 8);
+    if (!w->I || !w->Y || !w->Z || !w->Cy || !w->Cx || !w->ky || !w->kx) return ws_short(who);
+    return IMCOM_OK;
+}
+
+// InImage.smooth_and_pad (coadd.py:433-474).  The reference multiplies the 2-D DFT of the padded image by the real, even,
+// separable filter sinc(ux w) sinc(uy w) exp(-2 pi^2 s^2 (ux^2 + uy^2)) and keeps the real part of the inverse: a
+// circular convolution along each axis with k[d] = (1/N) sum_u h(u) cos(2 pi u d / N), i.e. out = Cy I Cx^T with
+// symmetric circulants -- two products on the fp64 MFMA GEMM for any image size, exact twiddles.
+int smooth_pad_device(imcom_ctx *ctx, const SmoothPadWs &w, int n, const double *src, int ny, int nx, double tophatwidth, double gaussiansigma,
+                      double *dst)
+{
+    const int npad = imcom_smooth_pad_width(tophatwidth, gaussiansigma), nyy = ny + 2 * npad, nxx = nx + 2 * npad;
+    const int Py = (int)align_up((size_t)nyy, NB), Px = (int)align_up((size_t)nxx, NB);
+    double *I = w.I, *Y = w.Y, *Z = w.Z, *Cy = w.Cy, *Cx = w.Cx, *ky = w.ky, *kx = w.kx;
+    hipStream_t hs = ctx->stream;
+    hipLaunchKernelGGL(pad_rect_kernel, dim3((Px + 255) / 256, Py, n), dim3(256), 0, hs, src, ny, nx, npad, Py, Px, I);
+    hipLaunchKernelGGL(airy_filter_kernel, dim3(nyy), dim3(256), 0, hs, nyy, gaussiansigma, tophatwidth, ky);
+    hipLaunchKernelGGL(airy_filter_kernel, dim3(nxx), dim3(256), 0, hs, nxx, gaussiansigma, tophatwidth, kx);
+    hipLaunchKernelGGL(circulant_kernel, dim3((Py + 255) / 256, Py), dim3(256), 0, hs, ky, nyy, Py, Cy);
+    hipLaunchKernelGGL(circulant_kernel, dim3((Px + 255) / 256, Px), dim3(256), 0, hs, kx, nxx, Px, Cx);
+    IMCOM_TRY(check_launch("smooth_and_pad setup"));
+    IMCOM_TRY(launch_gemm(ctx, false, false, Py, Px, Px, n, I, Px, (long)Py * Px, Cx, Px, 0, Y, Px, (long)Py * Px, 1.0, 0.0));  // Y = I Cx^T
+    IMCOM_TRY(launch_gemm(ctx, false, true, Py, Px, Py, n, Cy, Py, 0, Y, Px, (long)Py * Px, Z, Px, (long)Py * Px, 1.0, 0.0));   // Z = Cy Y
+    hipLaunchKernelGGL(crop_rect_kernel, dim3((nxx + 255) / 256, nyy, n), dim3(256), 0, hs, Z, Py, Px, nyy, nxx, dst);
+    return check_launch("crop_rect_kernel");
+}
+
 }  // namespace imcom
 
 using namespace imcom;
@@ -341,10 +385,6 @@ extern "C" int imcom_smooth_pad_width(double tophatwidth, double gaussiansigma)
     return npad;
 }
 
-// InImage.smooth_and_pad (coadd.py:433-474).  The reference multiplies the 2-D DFT of the padded image by the real, even,
-// separable filter sinc(ux w) sinc(uy w) exp(-2 pi^2 s^2 (ux^2 + uy^2)) and keeps the real part of the inverse: a
-// circular convolution along each axis with k[d] = (1/N) sum_u h(u) cos(2 pi u d / N), i.e. out = Cy I Cx^T with
-// symmetric circulants -- two products on the fp64 MFMA GEMM for any image size, exact twiddles.
 extern "C" int imcom_smooth_and_pad(imcom_ctx *ctx, int n, const double *in, int ny, int nx, double tophatwidth, double gaussiansigma,
                                     double *out, int memspace)
 {
@@ -352,31 +392,18 @@ extern "C" int imcom_smooth_and_pad(imcom_ctx *ctx, int n, const double *in, int
     IMCOM_REQUIRE(n >= 1 && in && out && ny >= 1 && nx >= 1 && tophatwidth >= 0.0 && gaussiansigma >= 0.0, "bad arguments");
     Stage st(ctx, memspace, __func__);
     const int npad = imcom_smooth_pad_width(tophatwidth, gaussiansigma), nyy = ny + 2 * npad, nxx = nx + 2 * npad;
-    const int Py = (int)align_up((size_t)nyy, NB), Px = (int)align_up((size_t)nxx, NB);
-    const size_t szI = (size_t)n * Py * Px * 8, szIn = (size_t)n * ny * nx, szOut = (size_t)n * nyy * nxx;
+    const size_t szIn = (size_t)n * ny * nx, szOut = (size_t)n * nyy * nxx;
     WsPlan plan;
-    plan.add(3 * szI + (size_t)Py * Py * 8 + (size_t)Px * Px * 8 + (size_t)(nyy + nxx) * 8 + 16384);
+    plan.add(smooth_pad_ws_bytes(n, ny, nx, tophatwidth, gaussiansigma));
     st.plan(plan, {szIn * 8, szOut * 8});
     IMCOM_TRY(ws_reserve(ctx, plan.total));
-    double *I = (double *)ws_take(ctx, szI), *Y = (double *)ws_take(ctx, szI), *Z = (double *)ws_take(ctx, szI);
-    double *Cy = (double *)ws_take(ctx, (size_t)Py * Py * 8), *Cx = (double *)ws_take(ctx, (size_t)Px * Px * 8);
-    double *ky = (double *)ws_take(ctx, (size_t)nyy * 8), *kx = (double *)ws_take(ctx, (size_t)nxx * 8);
-    if (!I || !Y || !Z || !Cy || !Cx || !ky || !kx) return ws_short(__func__);
+    SmoothPadWs w;
+    IMCOM_TRY(smooth_pad_take(ctx, n, ny, nx, tophatwidth, gaussiansigma, &w, __func__));
     const double *src;
     double *dst;
     IMCOM_TRY(st.in(in, szIn, &src));
     IMCOM_TRY(st.out(out, szOut, &dst));
-    hipStream_t hs = ctx->stream;
-    hipLaunchKernelGGL(pad_rect_kernel, dim3((Px + 255) / 256, Py, n), dim3(256), 0, hs, src, ny, nx, npad, Py, Px, I);
-    hipLaunchKernelGGL(airy_filter_kernel, dim3(nyy), dim3(256), 0, hs, nyy, gaussiansigma, tophatwidth, ky);
-    hipLaunchKernelGGL(airy_filter_kernel, dim3(nxx), dim3(256), 0, hs, nxx, gaussiansigma, tophatwidth, kx);
-    hipLaunchKernelGGL(circulant_kernel, dim3((Py + 255) / 256, Py), dim3(256), 0, hs, ky, nyy, Py, Cy);
-    hipLaunchKernelGGL(circulant_kernel, dim3((Px + 255) / 256, Px), dim3(256), 0, hs, kx, nxx, Px, Cx);
-    IMCOM_TRY(check_launch("smooth_and_pad setup"));
-    IMCOM_TRY(launch_gemm(ctx, false, false, Py, Px, Px, n, I, Px, (long)Py * Px, Cx, Px, 0, Y, Px, (long)Py * Px, 1.0, 0.0));  // Y = I Cx^T
-    IMCOM_TRY(launch_gemm(ctx, false, true, Py, Px, Py, n, Cy, Py, 0, Y, Px, (long)Py * Px, Z, Px, (long)Py * Px, 1.0, 0.0));   // Z = Cy Y
-    hipLaunchKernelGGL(crop_rect_kernel, dim3((nxx + 255) / 256, nyy, n), dim3(256), 0, hs, Z, Py, Px, nyy, nxx, dst);
-    IMCOM_TRY(check_launch("crop_rect_kernel"));
+    IMCOM_TRY(smooth_pad_device(ctx, w, n, src, ny, nx, tophatwidth, gaussiansigma, dst));
     IMCOM_TRY(st.back(out, dst, szOut));
     return st.done();
 }
