@@ -519,6 +519,34 @@ int imcom_psf_from_cube(imcom_ctx *ctx, int na, const double *cube, int ny, int 
 int imcom_draw_stars(imcom_ctx *ctx, int nstar, const double *psfs, int py, int px, const double *xsca, const double *ysca, double oversamp,
                      int d, int nside, double *image, int memspace);
 
+/* The long-range PSF part of an SCA image (reference src/pyimcom/splitpsf/imsubtract.py, run_imsubtract_single).  s = oversamp, ax = the
+ * side of the kernel planes, nside = the side of the SCA, Nl = the Legendre order used (imsubtract.py:482-485).
+ *   imcom_imsub_sizes     imsubtract.py:387-389, 451 and the layout of the prepared kernel: out[6] = {I_pad, first_index, A, np = ax / s,
+ *                         npp = np rounded up to 8, Nl^2 s^2 np npp = the doubles of the prepared kernel}.  IMCOM_ERR_ARG unless s >= 2,
+ *                         ax >= s, nside >= 1, Nl >= 1 and ax is a multiple of 2 s (imsubtract.py:365-366) or, for the kernels that
+ *                         bin2x2 trims (imsubtract.py:373-376), s is odd and ax a multiple of s.
+ *   imcom_imsub_prepare_kernel_f32   the Nl^2 planes K[0 .. Nl^2-1] of K [ncoeff][ax][ax] (float32; the plane of a term is lu + lv Nl with
+ *                         the Nl used, imsubtract.py:698) split into their s^2 phases, flipped and widened: kf [Nl^2][s][s][np][npp]
+ *                         doubles in DEVICE memory whatever `memspace` says of K -- the operand that stays resident over the layers of an
+ *                         SCA.  IMCOM_ERR_ARG when Nl^2 > ncoeff.
+ *   imcom_imsub_canvas_add_f32       imsubtract.py:665-682: canvas[row0 + j][col0 + i] += H[j][i] * area[j / s][i / s] for the hh x hw
+ *                         (multiples of s) float64 block H and the float32 native-pixel areas area [hh / s][hw / s]; canvas [A][A] float32.
+ *   imcom_imsub_convolve_subtract_f32   imsubtract.py:689-707 for the rows y0 .. y0 + ny - 1 of one layer, without the full-resolution KH:
+ *                           image[Y - y0][X] -= sum_c sum_{j,i < ax} K[c][j][i] arr_c[first_index + s Y + ax-1 - j][first_index + s X + ax-1 - i]
+ *                         with arr_c = canvas * f32(P_lu(u_x)) * f32(P_lv(u_y)) in float32 (imsubtract.py:487-488, 694-696), c = lu + lv Nl.
+ *                         canvas holds the rows crow0 .. crow0 + crows - 1 of the [A][A] canvas and must cover the rows
+ *                         first_index + s y0 .. first_index + s (y0 + ny - 1) + ax - 1 the call reads.  kf: the prepared kernel (device
+ *                         memory) or NULL, then K is prepared into the workspace by this call.  image [ny][nside] float32 in / out;
+ *                         kh (may be NULL) [ny][nside] doubles receives the sums.  Every sample has one owner thread and a fixed order
+ *                         of terms, sums are float64: the result is the same bit for bit for every split of the rows into calls.
+ *   canvas, K, H, area, image and kh follow `memspace`. */
+int imcom_imsub_sizes(int ax, int s, int nside, int Nl, long *out);
+int imcom_imsub_prepare_kernel_f32(imcom_ctx *ctx, const float *K, int ncoeff, int ax, int Nl, int s, double *kf, int memspace);
+int imcom_imsub_canvas_add_f32(imcom_ctx *ctx, float *canvas, int A, const double *H, int hh, int hw, const float *area, int s, int row0,
+                               int col0, int memspace);
+int imcom_imsub_convolve_subtract_f32(imcom_ctx *ctx, const float *canvas, int A, long crow0, long crows, const float *K, const double *kf,
+                                      int ncoeff, int ax, int Nl, int s, int nside, int y0, int ny, float *image, double *kh, int memspace);
+
 #ifdef __cplusplus
 }
 #endif

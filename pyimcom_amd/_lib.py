@@ -130,6 +130,10 @@ SIGNATURES = {
     "imcom_ginterp_resample": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _d, _d, _vp, _d, _i, _l, _vp, _vp, _vp, _i],
     "imcom_psf_from_cube": [_vp, _i, _vp, _i, _i, _i, _vp, _d, _d, _d, _vp, _i],
     "imcom_draw_stars": [_vp, _i, _vp, _i, _i, _vp, _vp, _d, _i, _i, _vp, _i],
+    "imcom_imsub_sizes": [_i, _i, _i, _i, _vp],
+    "imcom_imsub_prepare_kernel_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _i],
+    "imcom_imsub_canvas_add_f32": [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i],
+    "imcom_imsub_convolve_subtract_f32": [_vp, _vp, _i, _l, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

@@ -140,4 +140,10 @@ int launch_cube_contract(imcom_ctx *ctx, const double *planes, int na, long npix
 int launch_draw_stars(imcom_ctx *ctx, int nstar, const double *psfs, int py, int px, const double *xsca, const double *ysca, double oversamp,
                       int d, int nside, double *image);
 
+// imsubtract.hip
+int launch_imsub_prepare(imcom_ctx *ctx, const float *K, int ax, int s, int Nl, double *Kf);
+int launch_imsub_convolve(imcom_ctx *ctx, const float *canvas, int A, long crow0, long crows, const float *leg, const double *Kf, int ax, int Nl, int s,
+                          int nside, int first, int y0, int ny, float *image, double *kh);
+int launch_imsub_canvas_add(imcom_ctx *ctx, float *canvas, int A, const double *H, int hh, int hw, const float *area, int s, int row0, int col0);
+
 }  // namespace imcom
