@@ -547,6 +547,40 @@ int imcom_imsub_canvas_add_f32(imcom_ctx *ctx, float *canvas, int A, const doubl
 int imcom_imsub_convolve_subtract_f32(imcom_ctx *ctx, const float *canvas, int A, long crow0, long crows, const float *K, const double *kf,
                                       int ncoeff, int ax, int Nl, int s, int nside, int y0, int ny, float *image, double *kh, int memspace);
 
+/* The split of a Legendre PSF cube into a short-range PSF and a long-range kernel (reference src/pyimcom/splitpsf/splitpsf.py, class
+ * SplitPSF).  n = the side of the cube's planes, npoly = (lorder + 1)^2 planes, plane a = l_y (lorder + 1) + l_x.  Transforms of side
+ * N <= 1024 with N a product of 2, 3, 5 run as wave-per-line butterflies (route 1), every other side up to 4096 as dense DFTs on the
+ * fp64 MFMA tile engine (route 2): the same formula either way.  A side beyond 4096 (a cube side beyond 2048 in imcom_splitpsf_points):
+ * IMCOM_ERR_UNSUPPORTED.
+ *   imcom_splitpsf_sizes    out[6] = {npad of tophatfilter (splitpsf.py:134-135), n + 2 npad, the route of the tophat filter's transforms,
+ *                           the route of the 2n transforms of imcom_splitpsf_points (0: not served), the workspace bytes of
+ *                           imcom_splitpsf_tophat for npoly planes, the workspace bytes of imcom_splitpsf_points for nsca SCAs and npts grid
+ *                           points with device pointers and K_real = NULL}.
+ *   imcom_splitpsf_tophat   splitpsf.py:131-154: out = the planes of cube [nplane][n][n] smoothed with a tophat of `width` samples: zero
+ *                           pad by npad, cyclic 2-D transform, times sinc(u_x width) sinc(u_y width), inverse, crop.  out may be cube.
+ *   imcom_splitpsf_split    splitpsf.py:92-128, 223-234: smallpsf [npoly][ns][ns] = W * cube trimmed by (n - ns) / 2 and
+ *                           resid [npoly][n][n] = cube * (1 - W) * Trunc, W = Window_2D_integratedBlackman(n, r_in, r_out) (radii in
+ *                           samples: oversamp * r_in of the reference), Trunc = Truncate_2D_integratedBlackman(n, m_trunc).  n, ns even
+ *                           (IMCOM_ERR_ARG otherwise, as the reference's ValueError).
+ *   imcom_splitpsf_points   splitpsf.py:253-284 for the grid points i0 .. i0 + npts - 1 of nsca SCAs at once: locLRP = sum_a lpw[i][a]
+ *                           resid[s][a] (267); K_real = gauss_deconv(locLRP, cov[s][i], eps) (156-170); zeta_real = locLRP -
+ *                           convolve(K_real, gauss_stamp(n, cov[s][i]), "same") (172-185, 269-274); K_Legendre[s][a] += wg[i] lpw[i][a]
+ *                           K_real (277) in ascending i, every element by one owner thread, products and sums rounded one by one; the call
+ *                           that holds grid point 0 starts from zero, the one that holds the last applies (l_x + 1/2)(l_y + 1/2)
+ *                           (282-284).  The result is the same bit for bit for every split of grid points and SCAs into calls (calls of
+ *                           one SCA in ascending i0).  resid, K_Legendre [nsca][npoly][n][n]; K_real, zeta_real (each may be NULL)
+ *                           [nsca][npts][n][n]; zetamax [nsca] = max |zeta_real| over the grid points so far (365).  lpw [npoly][npoly]
+ *                           (row i: outer(P(y_i), P(x_i)).flatten(), 263-265), wg [npoly] and cov [nsca][npoly][2][2] are HOST arrays
+ *                           whatever `memspace` says.  IMCOM_ERR_ARG: npoly not a square, n odd, a covariance that is not positive
+ *                           definite (of its off-diagonal elements C[0][1] is the one read, as in the reference).
+ *   cube, out, smallpsf, resid, K_Legendre, K_real, zeta_real and zetamax follow `memspace`. */
+int imcom_splitpsf_sizes(int n, int npoly, double width, int nsca, int npts, long *out);
+int imcom_splitpsf_tophat(imcom_ctx *ctx, const double *cube, int nplane, int n, double width, double *out, int memspace);
+int imcom_splitpsf_split(imcom_ctx *ctx, const double *cube, int npoly, int n, int ns, double r_in, double r_out, int m_trunc, double *smallpsf,
+                         double *resid, int memspace);
+int imcom_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npoly, int n, int i0, int npts, const double *lpw, const double *wg,
+                          const double *cov, double eps, double *K_Legendre, double *K_real, double *zeta_real, double *zetamax, int memspace);
+
 #ifdef __cplusplus
 }
 #endif

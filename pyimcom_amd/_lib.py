@@ -134,6 +134,10 @@ SIGNATURES = {
     "imcom_imsub_prepare_kernel_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _i],
     "imcom_imsub_canvas_add_f32": [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i],
     "imcom_imsub_convolve_subtract_f32": [_vp, _vp, _i, _l, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i],
+    "imcom_splitpsf_sizes": [_i, _i, _d, _i, _i, _vp],
+    "imcom_splitpsf_tophat": [_vp, _vp, _i, _i, _d, _vp, _i],
+    "imcom_splitpsf_split": [_vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _i],
+    "imcom_splitpsf_points": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _i],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

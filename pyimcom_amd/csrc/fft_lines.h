@@ -25,6 +25,21 @@ struct FftPlan {
     int n, npad, nst, radix[WF_MAXST], twoff[WF_MAXST], twn, waves;  // npad: n rounded up to 16; waves per workgroup
 };
 
+// twiddle(k, n) = (cos, sin)(2 pi k / nfft) with k reduced mod nfft exactly
+__device__ __forceinline__ void twiddle(long k, int nfft, double *c, double *s)
+{
+    long r = k % nfft;
+    if (r < 0) r += nfft;
+    // exact special angles
+    if (r == 0) { *c = 1.0; *s = 0.0; return; }
+    if (2 * r == nfft) { *c = -1.0; *s = 0.0; return; }
+    if (4 * r == nfft) { *c = 0.0; *s = 1.0; return; }
+    if (4 * r == 3L * nfft) { *c = 0.0; *s = -1.0; return; }
+    const double x = 2.0 * (double)r / (double)nfft;  // angle / pi in (0, 2)
+    *c = cospi(x);
+    *s = sinpi(x);
+}
+
 __device__ __forceinline__ int wf_swz(int i) { return i ^ ((i >> 4) & 15); }
 
 template <int R> struct WfQ { static constexpr int value = (WF_MAXN / R + 63) / 64; };  // butterflies per lane

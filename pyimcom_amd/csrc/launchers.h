@@ -146,4 +146,23 @@ int launch_imsub_convolve(imcom_ctx *ctx, const float *canvas, int A, long crow0
                           int nside, int first, int y0, int ny, float *image, double *kh);
 int launch_imsub_canvas_add(imcom_ctx *ctx, float *canvas, int A, const double *H, int hh, int hw, const float *area, int s, int row0, int col0);
 
+
+// psf_overlap.hip: the plan of the wave-per-line transforms (fft_lines.h) and its stage tables (tw: pl.n complex values, device memory)
+struct FftPlan;
+bool fft_line_plan(int n, FftPlan *pl);
+int fft_line_twiddles(imcom_ctx *ctx, const FftPlan &pl, double2 *tw);
+
+// splitpsf.hip
+constexpr int SPLITPSF_MAXN = 4096;  // largest transform side (2 x the cube side)
+constexpr int SPLITPSF_ROUTE_NONE = 0, SPLITPSF_ROUTE_LINES = 1, SPLITPSF_ROUTE_DENSE = 2;
+int splitpsf_route(int nfft);
+int splitpsf_tophat_npad(double width);
+size_t splitpsf_tophat_ws(int nplane, int n, double width);
+int launch_splitpsf_tophat(imcom_ctx *ctx, const double *cube, int nplane, int n, double width, double *out);
+int launch_splitpsf_split(imcom_ctx *ctx, const double *cube, int npoly, int n, int ns, double r1, double r2, const double *trunc_dev, double *smallpsf,
+                          double *resid);
+size_t splitpsf_points_ws(int n, int nsca, int npts, bool own_kreal);
+int launch_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npoly, int n, int i0, int npts, const double *lpw, const double *wg,
+                           const double *cov, double eps, double *KL, double *K_real, double *zeta, double *zmax);
+
 }  // namespace imcom

@@ -22,21 +22,6 @@
 
 namespace imcom {
 
-// twiddle(k, n) = (cos, sin)(2 pi k / nfft) with k reduced mod nfft exactly
-__device__ __forceinline__ void twiddle(long k, int nfft, double *c, double *s)
-{
-    long r = k % nfft;
-    if (r < 0) r += nfft;
-    // exact special angles
-    if (r == 0) { *c = 1.0; *s = 0.0; return; }
-    if (2 * r == nfft) { *c = -1.0; *s = 0.0; return; }
-    if (4 * r == nfft) { *c = 0.0; *s = 1.0; return; }
-    if (4 * r == 3L * nfft) { *c = 0.0; *s = -1.0; return; }
-    const double x = 2.0 * (double)r / (double)nfft;  // angle / pi in (0, 2)
-    *c = cospi(x);
-    *s = sinpi(x);
-}
-
 // kind 0: FX  [Kp x Np]  rows c (< nsamp), cols kx (< nh):   cos / -sin (2 pi c kx / nfft)
 // kind 1: FY  [Mp x Kp]  rows ky (< nfft), cols r (< nsamp): cos / -sin (2 pi ky r / nfft)
 // kind 2: IY  [Mp x Kp]  rows y' (< nsamp), cols ky (< nfft): cos / +sin (2 pi ky (y'-nc) / nfft)
@@ -599,6 +584,14 @@ static int fft_inverse(imcom_ctx *ctx, const FftPlan &pl, const cplx *Ra, const 
 }
 
 static int up(int v, int a) { return (v + a - 1) / a * a; }
+
+// the line engine's plan and stage tables for its other users (splitpsf.hip); tw: pl.n complex values
+bool fft_line_plan(int n, FftPlan *pl) { return fft_plan(n, pl); }
+int fft_line_twiddles(imcom_ctx *ctx, const FftPlan &pl, cplx *tw)
+{
+    hipLaunchKernelGGL(fft_twiddle_kernel, dim3((pl.twn + 255) / 256), dim3(256), 0, ctx->stream, pl, tw);
+    return check_launch("fft_twiddle_kernel");
+}
 
 }  // namespace imcom
 

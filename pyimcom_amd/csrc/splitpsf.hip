@@ -1,0 +1,484 @@
+// splitpsf.hip -- the split of a Legendre PSF cube into a short-range PSF and a long-range kernel on the device.
+//
+// Replaces the numerical content of SplitPSF (reference src/pyimcom/splitpsf/splitpsf.py): the tophat filter of the constructor
+// (tophatfilter, 131-154), the windows and the split (92-128, 223-234) and, per Gauss-Legendre grid point, the Legendre combination (267),
+// the Gaussian deconvolution (gauss_deconv, 156-170), the error map zeta (269-274) and the update of K_Legendre (277, 282-284).
+//
+// Every transform is a cyclic 2-D DFT of complex planes [plane][N][N], done as two passes of ONE primitive: "transform the contiguous
+// lines of every plane and store the result transposed" -- after two passes the spectrum is in natural order again.  The primitive has
+// two routes: (1) the wave-per-line butterflies of fft_lines.h when N <= 1024 is a product of 2, 3, 5; (2) for every other N the dense
+// DFT as ONE real product on the fp64 MFMA tile engine (gemm_f64.hip): a complex line [N] is a real row [2N], the DFT a real
+// [2N x 2N] matrix of 2 x 2 rotation blocks, then a transposing copy.  Both routes compute the same formula.
+//
+// Determinism: a plane's transforms involve that plane only (a real plane rides as a complex one with a zero imaginary part; in the
+// zeta step K_real and its own Gaussian stamp ride together), every output element has one owner thread, and K_Legendre adds its
+// grid points in ascending order with separately rounded products and sums: the result is the same bit for bit for every split
+// of the grid points and the SCAs into calls.  Only the tophat filter pairs planes (2j, 2j+1 of one cube: a fixed pairing).
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "common.h"
+#include "fft_lines.h"
+#include "launchers.h"
+
+namespace imcom {
+
+static int up(int v, int a) { return (v + a - 1) / a * a; }
+
+int splitpsf_route(int nfft)
+{
+    if (nfft < 2 || nfft > SPLITPSF_MAXN) return SPLITPSF_ROUTE_NONE;
+    FftPlan pl;
+    return fft_line_plan(nfft, &pl) ? SPLITPSF_ROUTE_LINES : SPLITPSF_ROUTE_DENSE;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the primitive, route 1: line L = (plane b, row y) of `in`, transformed, goes to column y of plane b of `out`
+template <bool INV>
+__global__ __launch_bounds__(WF_MAXWAVES * 64) void sp_lines_kernel(const cplx *__restrict__ in, cplx *__restrict__ out, long nlines, FftPlan pl,
+                                                                    const cplx *__restrict__ tw)
+{
+    extern __shared__ cplx fbuf[];
+    const int n = pl.n, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    cplx *twl = fbuf + pl.waves * pl.npad;  // the stage tables ride in LDS behind the lines
+    for (int e = threadIdx.x; e < pl.twn; e += blockDim.x) twl[e] = tw[e];
+    __syncthreads();
+    cplx *line = fbuf + wave * pl.npad;
+    const long L = (long)blockIdx.x * pl.waves + wave;
+    if (L >= nlines) return;  // (no workgroup barrier below)
+    const long b = L / n;
+    const int y = (int)(L - b * n);
+    const cplx *src = in + L * n;
+    cplx *dst = out + b * n * n + y;
+    auto load0 = [&](int x) { return src[x]; };
+    auto storeN = [&](int k, cplx v) { dst[(long)k * n] = v; };
+    wf_line<INV>(line, twl, pl, load0, storeN);
+}
+
+// route 2: the [Kp x Np] real matrix of the DFT of interleaved complex rows: element x (re, im) to element k (re, im) by the rotation
+// (a + i b)(c -+ i s) = (a c +- b s) + i (b c -+ a s), c + i s = exp(2 pi i x k / N); zero outside 2N x 2N
+__global__ void sp_dft_matrix_kernel(int N, int Kp, int Np, int inv, double *__restrict__ M)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+    if (j >= Np || i >= Kp) return;
+    double v = 0.0;
+    if (i < 2 * N && j < 2 * N) {
+        double c, s;
+        twiddle((long)(i >> 1) * (j >> 1), N, &c, &s);
+        if (inv) s = -s;
+        v = ((i & 1) == (j & 1)) ? c : ((i & 1) ? s : -s);
+    }
+    M[(long)i * Np + j] = v;
+}
+
+// rows of interleaved complex lines [nlines][2N] -> [Mp][Kp], zero padded
+__global__ void sp_dense_pack_kernel(const double *__restrict__ in, long nlines, long Mp, int N2, int Kp, double *__restrict__ A)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    const long r = blockIdx.y + (long)blockIdx.z * 65535;
+    if (c >= Kp || r >= Mp) return;
+    A[r * Kp + c] = (r < nlines && c < N2) ? in[r * N2 + c] : 0.0;
+}
+
+// C [Mp][Np] (row b N + y holds the transformed line) -> out[b][k][y]
+__global__ void sp_dense_transpose_kernel(const double *__restrict__ C, int N, int Np, cplx *__restrict__ out)
+{
+    __shared__ cplx tile[16][17];
+    const long b = blockIdx.z;
+    const int k0 = blockIdx.x * 16, y0 = blockIdx.y * 16, tx = threadIdx.x, ty = threadIdx.y;
+    if (y0 + ty < N && k0 + tx < N) {
+        const double *p = C + (b * N + y0 + ty) * Np + 2 * (k0 + tx);
+        tile[ty][tx] = make_double2(p[0], p[1]);
+    }
+    __syncthreads();
+    if (k0 + ty < N && y0 + tx < N) out[(b * N + k0 + ty) * N + y0 + tx] = tile[tx][ty];
+}
+
+// what one 2-D transform engine needs out of the workspace, and the engine itself
+struct SpFft {
+    int N = 0, route = 0, Kp = 0, Np = 0;
+    long Mp = 0;  // dense: padded line count of the largest batch
+    FftPlan pl;
+    cplx *tw = nullptr;
+    double *Mf = nullptr, *Mi = nullptr, *A = nullptr, *C = nullptr;
+};
+
+static void sp_fft_plan(SpFft &f, int N, long planes, WsPlan &plan)
+{
+    f.N = N;
+    f.route = splitpsf_route(N);
+    if (f.route == SPLITPSF_ROUTE_LINES) {
+        fft_line_plan(N, &f.pl);
+        plan.add((size_t)N * 16);
+    } else {
+        f.Kp = up(2 * N, 16);
+        f.Np = up(2 * N, NB);
+        f.Mp = (planes * N + NB - 1) / NB * NB;
+        plan.add((size_t)f.Kp * f.Np * 8);
+        plan.add((size_t)f.Kp * f.Np * 8);
+        plan.add((size_t)f.Mp * f.Kp * 8);
+        plan.add((size_t)f.Mp * f.Np * 8);
+    }
+}
+
+static int sp_fft_take(imcom_ctx *ctx, SpFft &f, const char *who)
+{
+    if (f.route == SPLITPSF_ROUTE_LINES) {
+        IMCOM_TRY(ws_take(ctx, (size_t)f.N, &f.tw, who));
+        IMCOM_TRY(fft_line_twiddles(ctx, f.pl, f.tw));
+        const size_t lds = ((size_t)f.pl.waves * f.pl.npad + f.pl.twn) * 16;
+        if (lds > 48 * 1024) {
+            IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)sp_lines_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)sp_lines_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
+        return IMCOM_OK;
+    }
+    IMCOM_TRY(ws_take(ctx, (size_t)f.Kp * f.Np, &f.Mf, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)f.Kp * f.Np, &f.Mi, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)f.Mp * f.Kp, &f.A, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)f.Mp * f.Np, &f.C, who));
+    hipLaunchKernelGGL(sp_dft_matrix_kernel, dim3((f.Np + 255) / 256, f.Kp), dim3(256), 0, ctx->stream, f.N, f.Kp, f.Np, 0, f.Mf);
+    hipLaunchKernelGGL(sp_dft_matrix_kernel, dim3((f.Np + 255) / 256, f.Kp), dim3(256), 0, ctx->stream, f.N, f.Kp, f.Np, 1, f.Mi);
+    return check_launch("sp_dft_matrix_kernel");
+}
+
+// one pass: the lines of `planes` planes of `in`, transformed, into `out` transposed
+static int sp_lines_T(imcom_ctx *ctx, const SpFft &f, const cplx *in, cplx *out, long planes, bool inv)
+{
+    const int N = f.N;
+    const long nlines = planes * N;
+    if (f.route == SPLITPSF_ROUTE_LINES) {
+        const int W = f.pl.waves;
+        const size_t lds = ((size_t)W * f.pl.npad + f.pl.twn) * 16;
+        const unsigned grid = (unsigned)((nlines + W - 1) / W);
+        if (inv) hipLaunchKernelGGL(sp_lines_kernel<true>, dim3(grid), dim3(64 * W), lds, ctx->stream, in, out, nlines, f.pl, (const cplx *)f.tw);
+        else hipLaunchKernelGGL(sp_lines_kernel<false>, dim3(grid), dim3(64 * W), lds, ctx->stream, in, out, nlines, f.pl, (const cplx *)f.tw);
+        return check_launch("sp_lines_kernel");
+    }
+    const long Mp = (nlines + NB - 1) / NB * NB;
+    IMCOM_REQUIRE(Mp <= f.Mp && Mp <= 0x7fffffffL, "internal: splitpsf dense batch of %ld lines", nlines);
+    hipLaunchKernelGGL(sp_dense_pack_kernel, dim3((f.Kp + 255) / 256, (unsigned)std::min<long>(Mp, 65535), (unsigned)((Mp + 65534) / 65535)), dim3(256), 0,
+                       ctx->stream, (const double *)in, nlines, Mp, 2 * N, f.Kp, f.A);
+    IMCOM_TRY(check_launch("sp_dense_pack_kernel"));
+    IMCOM_TRY(launch_gemm(ctx, false, true, (int)Mp, f.Np, f.Kp, 1, f.A, f.Kp, 0, inv ? f.Mi : f.Mf, f.Np, 0, f.C, f.Np, 0, 1.0, 0.0));
+    hipLaunchKernelGGL(sp_dense_transpose_kernel, dim3((N + 15) / 16, (N + 15) / 16, (unsigned)planes), dim3(16, 16), 0, ctx->stream, (const double *)f.C, N, f.Np,
+                       out);
+    return check_launch("sp_dense_transpose_kernel");
+}
+
+// the cyclic 2-D transform of `planes` planes: a -> a (b is scratch), natural order in and out, unnormalised
+static int sp_fft2(imcom_ctx *ctx, const SpFft &f, cplx *a, cplx *b, long planes, bool inv)
+{
+    IMCOM_TRY(sp_lines_T(ctx, f, a, b, planes, inv));
+    return sp_lines_T(ctx, f, b, a, planes, inv);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the tophat filter (splitpsf.py:131-154); planes 2j, 2j+1 of the cube ride as one complex plane (the filter is real and even)
+__global__ void sp_tophat_pack_kernel(const double *__restrict__ cube, int nplane, int n, int npad, int N, cplx *__restrict__ Z)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, j = blockIdx.z;
+    if (x >= N) return;
+    const int yy = y - npad, xx = x - npad;
+    cplx v = make_double2(0.0, 0.0);
+    if (yy >= 0 && yy < n && xx >= 0 && xx < n) {
+        const long o = (long)yy * n + xx, pl = (long)n * n;
+        v.x = cube[2L * j * pl + o];
+        if (2 * j + 1 < nplane) v.y = cube[(2L * j + 1) * pl + o];
+    }
+    Z[((long)j * N + y) * N + x] = v;
+}
+
+__device__ __forceinline__ double sp_sinc(double x) { return x == 0.0 ? 1.0 : sinpi(x) / (M_PI * x); }
+__device__ __forceinline__ double sp_freq(int k, int N)  // numpy: u = k / N, u - 1 where u > 0.5
+{
+    const double u = (double)k / (double)N;
+    return u > 0.5 ? u - 1.0 : u;
+}
+
+__global__ void sp_tophat_filter_kernel(cplx *__restrict__ Z, int N, double width)
+{
+    const int kx = blockIdx.x * blockDim.x + threadIdx.x, ky = blockIdx.y, j = blockIdx.z;
+    if (kx >= N) return;
+    const double s = sp_sinc(sp_freq(kx, N) * width) * sp_sinc(sp_freq(ky, N) * width);
+    cplx *p = Z + ((long)j * N + ky) * N + kx;
+    *p = make_double2(p->x * s, p->y * s);
+}
+
+__global__ void sp_tophat_crop_kernel(const cplx *__restrict__ Z, int nplane, int n, int npad, int N, double *__restrict__ out)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, p = blockIdx.z;
+    if (x >= n) return;
+    const cplx v = Z[((long)(p >> 1) * N + y + npad) * N + x + npad];
+    out[((long)p * n + y) * n + x] = ((p & 1) ? v.y : v.x) / ((double)N * (double)N);
+}
+
+int splitpsf_tophat_npad(double width)  // splitpsf.py:134-135
+{
+    const int npad = (int)std::ceil(width);
+    return npad + (4 - npad % 4) % 4;
+}
+
+static size_t tophat_ws(int nplane, int n, double width, SpFft *f_out)
+{
+    const int N = n + 2 * splitpsf_tophat_npad(width), npair = (nplane + 1) / 2;
+    SpFft f;
+    WsPlan plan;
+    sp_fft_plan(f, N, npair, plan);
+    plan.add((size_t)npair * N * N * 16);
+    plan.add((size_t)npair * N * N * 16);
+    if (f_out) *f_out = f;
+    return plan.total;
+}
+size_t splitpsf_tophat_ws(int nplane, int n, double width) { return tophat_ws(nplane, n, width, nullptr); }
+
+// cube, out [nplane][n][n] in device memory (out may be cube); the caller has reserved splitpsf_tophat_ws() for this
+int launch_splitpsf_tophat(imcom_ctx *ctx, const double *cube, int nplane, int n, double width, double *out)
+{
+    const int npad = splitpsf_tophat_npad(width), N = n + 2 * npad, npair = (nplane + 1) / 2;
+    SpFft f;
+    tophat_ws(nplane, n, width, &f);
+    IMCOM_TRY(sp_fft_take(ctx, f, __func__));
+    cplx *Z, *T;
+    IMCOM_TRY(ws_take(ctx, (size_t)npair * N * N, &Z, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)npair * N * N, &T, __func__));
+    ProfScope ps(ctx, "splitpsf_tophat");
+    const dim3 gN((N + 255) / 256, N, npair);
+    hipLaunchKernelGGL(sp_tophat_pack_kernel, gN, dim3(256), 0, ctx->stream, cube, nplane, n, npad, N, Z);
+    IMCOM_TRY(check_launch("sp_tophat_pack_kernel"));
+    IMCOM_TRY(sp_fft2(ctx, f, Z, T, npair, false));
+    hipLaunchKernelGGL(sp_tophat_filter_kernel, gN, dim3(256), 0, ctx->stream, Z, N, width);
+    IMCOM_TRY(check_launch("sp_tophat_filter_kernel"));
+    IMCOM_TRY(sp_fft2(ctx, f, Z, T, npair, true));
+    hipLaunchKernelGGL(sp_tophat_crop_kernel, dim3((n + 255) / 256, n, nplane), dim3(256), 0, ctx->stream, (const cplx *)Z, nplane, n, npad, N, out);
+    return check_launch("sp_tophat_crop_kernel");
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the windows and the split (splitpsf.py:71-128, 223-234)
+__device__ __forceinline__ double sp_blackman(double x)
+{
+    const double alpha = 0.08;
+    if (x >= 1.0) return 1.0;
+    if (x <= -1.0) return 0.0;
+    return 0.5 * (x + 1.0) + (0.5 * sinpi(x) + alpha / 4 * sinpi(2.0 * x)) / ((1.0 - alpha) * M_PI);
+}
+
+// trunc [n]: the 1-D factor of Truncate_2D_integratedBlackman (host); smallpsf [npoly][ns][ns], resid [npoly][n][n]
+__global__ void sp_split_kernel(const double *__restrict__ cube, int npoly, int n, int ns, double r1, double r2, const double *__restrict__ trunc,
+                                double *__restrict__ smallpsf, double *__restrict__ resid)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= n) return;
+    const double xx = (1 - n) / 2.0 + x, yy = (1 - n) / 2.0 + y, r = sqrt(xx * xx + yy * yy);
+    const double W = sp_blackman(-1.0 + 2.0 / (r2 - r1) * (r2 - r)), T = trunc[y] * trunc[x];
+    const int ntrim = (n - ns) / 2, ys = y - ntrim, xs = x - ntrim;
+    const bool in_small = ys >= 0 && ys < ns && xs >= 0 && xs < ns;
+    for (int a = 0; a < npoly; a++) {
+        const double c = cube[((long)a * n + y) * n + x];
+        if (in_small) smallpsf[((long)a * ns + ys) * ns + xs] = W * c;
+        resid[((long)a * n + y) * n + x] = c * (1.0 - W) * T;
+    }
+}
+
+int launch_splitpsf_split(imcom_ctx *ctx, const double *cube, int npoly, int n, int ns, double r1, double r2, const double *trunc_dev, double *smallpsf,
+                          double *resid)
+{
+    hipLaunchKernelGGL(sp_split_kernel, dim3((n + 255) / 256, n), dim3(256), 0, ctx->stream, cube, npoly, n, ns, r1, r2, trunc_dev, smallpsf, resid);
+    return check_launch("sp_split_kernel");
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// per grid point.  Plane p = sl * npts + il: SCA sl of the call, grid point i0 + il.
+// locLRP (splitpsf.py:267) in ascending plane order
+__global__ void sp_loc_kernel(const double *__restrict__ resid, int npoly, long npix, int npts, int i0, const double *__restrict__ lpw,
+                              double *__restrict__ loc)
+{
+    const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    const int p = blockIdx.y;
+    if (e >= npix) return;
+    const int sl = p / npts, i = i0 + p % npts;
+    const double *r = resid + (long)sl * npoly * npix + e, *w = lpw + (long)i * npoly;
+    double acc = 0.0;
+    for (int a = 0; a < npoly; a++) acc += w[a] * r[a * npix];
+    loc[(long)p * npix + e] = acc;
+}
+
+// gauss_deconv, 161-163: the plane zero padded to 2n x 2n, as a complex plane
+__global__ void sp_pad_real_kernel(const double *__restrict__ src, int n, int N, cplx *__restrict__ Z)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, p = blockIdx.z;
+    if (x >= N) return;
+    Z[((long)p * N + y) * N + x] = make_double2((y < n && x < n) ? src[((long)p * n + y) * n + x] : 0.0, 0.0);
+}
+
+// gauss_deconv, 164-168: u = k / 2n, minus one from k = n on; u along the last axis
+__global__ void sp_deconv_filter_kernel(cplx *__restrict__ Z, int n, int npoly, int npts, int i0, const double *__restrict__ cov, double eps)
+{
+    const int N = 2 * n, kx = blockIdx.x * blockDim.x + threadIdx.x, ky = blockIdx.y, p = blockIdx.z;
+    if (kx >= N) return;
+    const double *C = cov + ((long)(p / npts) * npoly + i0 + p % npts) * 4;
+    double u = (double)kx / (double)N, v = (double)ky / (double)N;
+    if (kx >= n) u -= 1.0;
+    if (ky >= n) v -= 1.0;
+    const double G = exp(-2.0 * (M_PI * M_PI) * (C[0] * (u * u) + C[3] * (v * v) + 2.0 * C[1] * u * v));
+    const double h = G / (G * G + eps * eps);
+    cplx *q = Z + ((long)p * N + ky) * N + kx;
+    *q = make_double2(q->x * h, q->y * h);
+}
+
+// gauss_deconv, 169-170: the real part of the inverse, [:n, :n]
+__global__ void sp_kreal_kernel(const cplx *__restrict__ Z, int n, double *__restrict__ kreal)
+{
+    const int N = 2 * n, x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, p = blockIdx.z;
+    if (x >= n) return;
+    kreal[((long)p * n + y) * n + x] = Z[((long)p * N + y) * N + x].x / ((double)N * (double)N);
+}
+
+// the operands of the linear convolution of 269-274 as ONE complex plane: K_real + i gauss_stamp (172-185), both zero padded to 2n
+__global__ void sp_zeta_pack_kernel(const double *__restrict__ kreal, int n, int npoly, int npts, int i0, const double *__restrict__ cov,
+                                    cplx *__restrict__ Z)
+{
+    const int N = 2 * n, x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, p = blockIdx.z;
+    if (x >= N) return;
+    cplx v = make_double2(0.0, 0.0);
+    if (x < n && y < n) {
+        const double *C = cov + ((long)(p / npts) * npoly + i0 + p % npts) * 4;
+        const double det = C[0] * C[3] - C[1] * C[1], i00 = C[3] / det, i01 = -C[1] / det, i11 = C[0] / det;
+        const double xx = (1 - n) / 2.0 + x, yy = (1 - n) / 2.0 + y;
+        v.x = kreal[((long)p * n + y) * n + x];
+        v.y = exp(-0.5 * (i00 * (xx * xx) + i11 * (yy * yy)) - i01 * xx * yy) / (2.0 * M_PI * sqrt(det));
+    }
+    Z[((long)p * N + y) * N + x] = v;
+}
+
+// Z = FFT(a + i b), a and b real: A_k = (Z_k + conj Z_-k) / 2, B_k = (Z_k - conj Z_-k) / (2 i); out = A_k B_k
+__global__ void sp_zeta_product_kernel(const cplx *__restrict__ Z, int N, cplx *__restrict__ out)
+{
+    const int kx = blockIdx.x * blockDim.x + threadIdx.x, ky = blockIdx.y, p = blockIdx.z;
+    if (kx >= N) return;
+    const cplx *pl = Z + (long)p * N * N;
+    const cplx z = pl[(long)ky * N + kx], m = pl[(long)((N - ky) % N) * N + (N - kx) % N];
+    const cplx A = make_double2(0.5 * (z.x + m.x), 0.5 * (z.y - m.y)), B = make_double2(0.5 * (z.y + m.y), -0.5 * (z.x - m.x));
+    out[((long)p * N + ky) * N + kx] = cmulf(A, B);
+}
+
+// zeta = locLRP - the "same" part of the convolution (offset (n - 1) / 2); the row's max |zeta| goes to part[p n + y]
+__global__ __launch_bounds__(256) void sp_zeta_kernel(const cplx *__restrict__ Z, const double *__restrict__ loc, int n, double *__restrict__ zeta,
+                                                      double *__restrict__ part)
+{
+    __shared__ double red[256];
+    const int N = 2 * n, y = blockIdx.x, p = blockIdx.y, off = (n - 1) / 2;
+    double mx = 0.0;
+    for (int x = threadIdx.x; x < n; x += 256) {
+        const long o = ((long)p * n + y) * n + x;
+        const double z = loc[o] - Z[((long)p * N + y + off) * N + x + off].x / ((double)N * (double)N);
+        if (zeta) zeta[o] = z;
+        mx = fmax(mx, fabs(z));
+    }
+    red[threadIdx.x] = mx;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[(long)p * n + y] = red[0];
+}
+
+// zmax[sl] = max(zmax[sl] unless this is the SCA's first grid point, the SCA's row maxima)
+__global__ __launch_bounds__(256) void sp_zmax_kernel(const double *__restrict__ part, long per_sca, int first, double *__restrict__ zmax)
+{
+    __shared__ double red[256];
+    const int sl = blockIdx.x;
+    double mx = first ? 0.0 : zmax[sl];
+    for (long e = threadIdx.x; e < per_sca; e += 256) mx = fmax(mx, part[(long)sl * per_sca + e]);
+    red[threadIdx.x] = mx;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) zmax[sl] = red[0];
+}
+
+// 277, 282-284: K_Legendre[a] += wg[i] * (lpw_i[a] * K_real_i), i ascending, every product and sum rounded on its own (as numpy does);
+// after the last grid point the (l_x + 1/2)(l_y + 1/2) normalisation.  One owner thread per element.
+__global__ void sp_accumulate_kernel(const double *__restrict__ kreal, int npoly, long npix, int npts, int i0, const double *__restrict__ lpw,
+                                     const double *__restrict__ wg, int lorder1, double *__restrict__ KL)
+{
+    const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    const int a = blockIdx.y, sl = blockIdx.z;
+    if (e >= npix) return;
+    double *dst = KL + ((long)sl * npoly + a) * npix + e;
+    double acc = i0 == 0 ? 0.0 : *dst;
+    for (int il = 0; il < npts; il++) {
+        const int i = i0 + il;
+        const double t = __dmul_rn(lpw[(long)i * npoly + a], kreal[((long)sl * npts + il) * npix + e]);
+        acc = __dadd_rn(acc, __dmul_rn(wg[i], t));
+    }
+    if (i0 + npts == npoly) acc = __dmul_rn(acc, __dmul_rn((a / lorder1) + 0.5, (a % lorder1) + 0.5));
+    *dst = acc;
+}
+
+static size_t points_ws(int n, int nsca, int npts, bool own_kreal, SpFft *f_out)
+{
+    const long P = (long)nsca * npts;
+    const int N = 2 * n;
+    SpFft f;
+    WsPlan plan;
+    sp_fft_plan(f, N, P, plan);
+    plan.add((size_t)P * N * N * 16);          // Z
+    plan.add((size_t)P * N * N * 16);          // T
+    plan.add((size_t)P * n * n * 8);           // locLRP
+    if (own_kreal) plan.add((size_t)P * n * n * 8);
+    plan.add((size_t)P * n * 8);               // row maxima of |zeta|
+    if (f_out) *f_out = f;
+    return plan.total;
+}
+size_t splitpsf_points_ws(int n, int nsca, int npts, bool own_kreal) { return points_ws(n, nsca, npts, own_kreal, nullptr); }
+
+// resid [nsca][npoly][n][n]; lpw [npoly][npoly], wg [npoly], cov [nsca][npoly][4] in device memory; K_real / zeta (may be null)
+// [nsca][npts][n][n]; KL [nsca][npoly][n][n]; zmax [nsca].  The caller has reserved splitpsf_points_ws() for this.
+int launch_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npoly, int n, int i0, int npts, const double *lpw, const double *wg,
+                           const double *cov, double eps, double *KL, double *K_real, double *zeta, double *zmax)
+{
+    const long P = (long)nsca * npts, npix = (long)n * n;
+    const int N = 2 * n;
+    int lorder1 = 1;
+    while (lorder1 * lorder1 < npoly) lorder1++;
+    SpFft f;
+    points_ws(n, nsca, npts, !K_real, &f);
+    IMCOM_TRY(sp_fft_take(ctx, f, __func__));
+    cplx *Z, *T;
+    double *loc, *kreal = K_real, *part;
+    IMCOM_TRY(ws_take(ctx, (size_t)P * N * N, &Z, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)P * N * N, &T, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)P * npix, &loc, __func__));
+    if (!kreal) IMCOM_TRY(ws_take(ctx, (size_t)P * npix, &kreal, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)P * n, &part, __func__));
+    ProfScope ps(ctx, "splitpsf_points");
+    hipStream_t st = ctx->stream;
+    const dim3 gN((N + 255) / 256, N, (unsigned)P), gn((n + 255) / 256, n, (unsigned)P);
+    hipLaunchKernelGGL(sp_loc_kernel, dim3((unsigned)((npix + 255) / 256), (unsigned)P), dim3(256), 0, st, resid, npoly, npix, npts, i0, lpw, loc);
+    hipLaunchKernelGGL(sp_pad_real_kernel, gN, dim3(256), 0, st, (const double *)loc, n, N, Z);
+    IMCOM_TRY(check_launch("sp_pad_real_kernel"));
+    IMCOM_TRY(sp_fft2(ctx, f, Z, T, P, false));
+    hipLaunchKernelGGL(sp_deconv_filter_kernel, gN, dim3(256), 0, st, Z, n, npoly, npts, i0, cov, eps);
+    IMCOM_TRY(check_launch("sp_deconv_filter_kernel"));
+    IMCOM_TRY(sp_fft2(ctx, f, Z, T, P, true));
+    hipLaunchKernelGGL(sp_kreal_kernel, gn, dim3(256), 0, st, (const cplx *)Z, n, kreal);
+    hipLaunchKernelGGL(sp_zeta_pack_kernel, gN, dim3(256), 0, st, (const double *)kreal, n, npoly, npts, i0, cov, Z);
+    IMCOM_TRY(check_launch("sp_zeta_pack_kernel"));
+    IMCOM_TRY(sp_fft2(ctx, f, Z, T, P, false));
+    hipLaunchKernelGGL(sp_zeta_product_kernel, gN, dim3(256), 0, st, (const cplx *)Z, N, T);
+    IMCOM_TRY(check_launch("sp_zeta_product_kernel"));
+    IMCOM_TRY(sp_fft2(ctx, f, T, Z, P, true));
+    hipLaunchKernelGGL(sp_zeta_kernel, dim3(n, (unsigned)P), dim3(256), 0, st, (const cplx *)T, (const double *)loc, n, zeta, part);
+    hipLaunchKernelGGL(sp_zmax_kernel, dim3(nsca), dim3(256), 0, st, (const double *)part, (long)npts * n, i0 == 0 ? 1 : 0, zmax);
+    hipLaunchKernelGGL(sp_accumulate_kernel, dim3((unsigned)((npix + 255) / 256), npoly, nsca), dim3(256), 0, st, (const double *)kreal, npoly, npix, npts, i0,
+                       lpw, wg, lorder1, KL);
+    return check_launch("sp_accumulate_kernel");
+}
+
+}  // namespace imcom
