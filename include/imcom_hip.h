@@ -420,6 +420,13 @@ int imcom_sample_psf(imcom_ctx *ctx, int n_psf, const double *psf, int ny, int n
  * SIP distortion up to order L - 1), 2 <= L <= 33.  lattice / yxco follow `memspace`. */
 int imcom_lattice_positions(imcom_ctx *ctx, int count, int L, const double *W, const double *lattice, int nsamp,
                             double *yxco, int memspace);
+/* The sampling positions yxco of imcom_sample_psf under PSFSPLIT (PSFGrp._sample_psf, psfutil.py:739-753): the reference evaluates
+ * outpix2world2inpix at the group's computation point +- oversamp output pixels along x and y only,
+ *   cardinal [count][4][2] = flip(outpix2world2inpix(p0 + [[1,0],[0,1],[-1,0],[0,-1]] * oversamp), axis=-1) / 2 * dscale   (y, x),
+ * and takes the map as affine over the PSF window: yxco[c][k][iy][ix] = (c0 - c2)[k] * yxo[1][iy][ix] + (c1 - c3)[k] * yxo[0][iy][ix]
+ * with yxo the unrotated grid (i - (nsamp - 1) / 2), two products and one sum per element as np.tensordot forms them.
+ * cardinal / yxco [count][2][nsamp][nsamp] follow `memspace`; 8 numbers per PSF group and exposure are uploaded. */
+int imcom_affine_positions(imcom_ctx *ctx, int count, const double *cardinal, int nsamp, double *yxco, int memspace);
 /* OutPSF.psf_gaussian psfutil.py:117-146 and OutPSF.psf_simple_airy 148-223 (n x n, row-major) */
 int imcom_psf_gaussian(imcom_ctx *ctx, int n, double sigmax, double sigmay, double *out, int memspace);
 int imcom_psf_simple_airy(imcom_ctx *ctx, int n, double ldp, double obsc, double tophat_conv, double sigma,
@@ -473,6 +480,20 @@ int imcom_psf_overlap_spectra_win(imcom_ctx *ctx, const double *spec1, int n1, c
 int imcom_psf_overlap_spectra_slots(imcom_ctx *ctx, const double *spec1, int n1, const double *spec2, int n2, int nsamp, int nfft,
                                     const int *pairs, int npairs, const double *amp_penalty, const int *win, const int *slots,
                                     int nslots, double *tables);
+/* PSFSPLIT (PSFGrp.setup(psfsplit=True), PSFOvl.setup psfutil.py:1087-1089): the overlap tables are wider than the PSFs --
+ * PSFOvl.nsamp = 2 * PSFGrp.nsamp + 1 = nfft - 1, PSFOvl.nc = PSFGrp.nsamp -- i.e. roll(irfft2(R1 conj R2), nc)[: 2 nc + 1, : 2 nc + 1]
+ * (1226-1227) is the whole cyclic correlation but one row and one column.  The entries below take the table side `ntab` (odd,
+ * nsamp <= ntab <= nfft - 1; rolled by ntab / 2) beside the PSF side `nsamp`; ntab == nsamp computes what the plain entries compute.
+ *   imcom_psf_overlap_wide          as imcom_psf_overlap (any nfft: butterfly plan or dense DFT): tables[npairs][ntab+12][ntab+12]
+ *   imcom_psf_overlap_spectra_wide  as imcom_psf_overlap_spectra_slots from the spectra of imcom_psf_spectra (which do not depend on the
+ *                            table side): win [npairs][4] in table coordinates 0..ntab or NULL, slots [npairs] or NULL (then pair t goes
+ *                            to tables[t]), tables of (ntab+12)^2 doubles each.  The intermediate of the two inverse transforms
+ *                            ((ntab + 1) x (nfft/2 + 1) complex per pair) is chunked against ~4 GB as for the plain entries. */
+int imcom_psf_overlap_wide(imcom_ctx *ctx, const double *psf1, int n1, const double *psf2, int n2, int nsamp, int ntab, int nfft,
+                           const int *pairs_host, int npairs, const double *amp_penalty, double *tables);
+int imcom_psf_overlap_spectra_wide(imcom_ctx *ctx, const double *spec1, int n1, const double *spec2, int n2, int nsamp, int ntab,
+                                   int nfft, const int *pairs, int npairs, const double *amp_penalty, const int *win, const int *slots,
+                                   int nslots, double *tables);
 
 /* pyimcom.meta.ginterp (reference src/pyimcom/meta/ginterp.py), the deconvolution-shear-reconvolution resampler of
  * MetaMosaic.shearimage (meta/distortimage.py:393-593).  Rsearch is served while the offsets number NN <= 320 and the corner

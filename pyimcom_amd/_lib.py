@@ -110,6 +110,7 @@ SIGNATURES = {
     "imcom_clamp_min_f32": [_vp, _vp, _l, C.c_float],
     "imcom_sample_psf": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i],
     "imcom_lattice_positions": [_vp, _i, _i, _vp, _vp, _i, _vp, _i],
+    "imcom_affine_positions": [_vp, _i, _vp, _i, _vp, _i],
     "imcom_psf_gaussian": [_vp, _i, _d, _d, _vp, _i],
     "imcom_psf_simple_airy": [_vp, _i, _d, _d, _d, _d, _vp, _i],
     "imcom_smooth_and_pad": [_vp, _i, _vp, _i, _i, _d, _d, _vp, _i],
@@ -118,6 +119,8 @@ SIGNATURES = {
     "imcom_psf_overlap_spectra": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp],
     "imcom_psf_overlap_spectra_win": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp],
     "imcom_psf_overlap_spectra_slots": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp],
+    "imcom_psf_overlap_wide": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp],
+    "imcom_psf_overlap_spectra_wide": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp],
     "imcom_block_accumulate": [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i],
     "imcom_solve_eigen_workspace": [_i, _i, _i, _i, _vp],
     "imcom_solve_chol_workspace": [_i, _i, _i, _i, _i, _vp],

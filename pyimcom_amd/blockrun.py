@@ -316,14 +316,15 @@ def tile_tables(h, w, n, n_out):
     return (h + 1) * (w + 1) * S + ((h + 1) * w + h * (w + 1) + 2 * h * w) * n * n
 
 
-def memory_plan(cfg, pool, n1P, n_psf, n_out=1, nfft=None, ctx=None, cap=256, kernel=None, nv=None):
+def memory_plan(cfg, pool, n1P, n_psf, n_out=1, nfft=None, ctx=None, cap=256, kernel=None, nv=None, ntab=None):
     """How a block's device memory is divided BEFORE its table arenas exist: {"capacity": overlap tables, "spec_capacity": spectra rows,
     "stamps": stamps per pass the rest holds}, to be handed to ``BlockTables(capacity=..., spec_capacity=...)``.  Stamps first: a pass is
     as large as memory allows up to ``cap`` provided the arenas still hold two passes' worth of tables and spectra (the pass on the device
     and the one being prepared); what is left beyond that goes to the arenas, up to the whole block (nothing is then computed twice).
     At cfg-2 size (0.15 GB per stamp) that is passes of 256 and every table of a 48 x 48 block resident; at the reference's production
     shape (1.2 GB per stamp: paper4) it is passes of ~160 and arenas of two passes -- where the fixed thirds of BlockTables' defaults
-    left the stamps passes of 32-40."""
+    left the stamps passes of 32-40.  ``ntab``: the side of the overlap tables when it differs from the PSF side (PSFSPLIT, BlockTables): a
+    table is then 8 (ntab + 12)^2 bytes, 3.9 times an unsplit one, and the capacity in tables shrinks accordingly."""
     import ctypes
 
     import torch
@@ -338,7 +339,7 @@ def memory_plan(cfg, pool, n1P, n_psf, n_out=1, nfft=None, ctx=None, cap=256, ke
     ldn = max(NB, (nmax + NB - 1) // NB * NB)
     ldm = (cfg.m + NB - 1) // NB * NB
     avail = int(fill_of(kernel) * available_bytes(pool.device, ctx)) - FIXED_RESERVE - block_maps_bytes(n1P, cfg.n2, cfg.fade, cfg.n_inframe, n_out, n_psf)
-    tb = 8 * (cfg.nsamp + 12) ** 2
+    tb = 8 * ((cfg.nsamp if ntab is None else int(ntab)) + 12) ** 2
     sb = 8 * int(lib.imcom_psf_spectra_size(cfg.nsamp, nfft)) or 1
     ng = (n1P + 3) // 2
     S = n_psf * (n_psf + 1) // 2 + n_out * n_psf

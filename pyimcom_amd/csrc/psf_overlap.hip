@@ -3,7 +3,10 @@
 // Replaces PSFGrp.accel_pad_and_rfft2 (reference src/pyimcom/psfutil.py:943-986) and
 // PSFOvl._build_psfovl / accel_irfft2_and_extract (1244-1294, 1178-1242):
 //     table[p,q] = roll(irfft2(rfft2(pad(psf1[p])) * conj(rfft2(pad(psf2[q])))), nc)[:nsamp, :nsamp]
-// written with the 6-pixel zero border the interpolators expect.
+// written with the 6-pixel zero border the interpolators expect.  Under PSFSPLIT the table is wider than the PSFs (PSFOvl.setup 1087-1089:
+// side 2 nsamp + 1 = nfft - 1, the whole cyclic correlation but one row and one column): the *_wide entries take the table side `ntab`
+// beside the PSF side.  Only the inverse knows about it -- the spectra are those of the PSF side, and the inverse transforms below keep
+// `ns` rows and columns, rolled by ns / 2, where ns is whatever table side their caller hands them (ns + 1 <= nfft).
 //
 // Two formulations.  (1) Butterfly path (default whenever nfft <= 1024 is a product of 16, 8, 4, 2, 3, 5): line FFTs with
 // one wavefront per line, butterflies in registers, the line exchanged through the wave's LDS slice without workgroup
@@ -553,7 +556,8 @@ static int fft_forward(imcom_ctx *ctx, const FftPlan &pl, const double *psf, int
     return check_launch("psf spectra (butterfly path)");
 }
 
-// tables[t] from spectra pairs (Ra[pairs[2t]], Rb[pairs[2t+1]]); the caller has reserved fft_inverse_ws()
+// tables[t] from spectra pairs (Ra[pairs[2t]], Rb[pairs[2t+1]]); the caller has reserved fft_inverse_ws().  nsamp: the TABLE side
+// (the PSF side for the plain entries, PSFOvl.nsamp = 2 nsamp + 1 for the wide ones): V and every launch below are sized by it.
 static int fft_inverse(imcom_ctx *ctx, const FftPlan &pl, const cplx *Ra, const cplx *Rb, const int *pairs_host, int npairs,
                        int nsamp, const double *amp_penalty, double *tables, const int *win_host = nullptr, const int *slots_host = nullptr)
 {
@@ -597,32 +601,27 @@ int fft_line_twiddles(imcom_ctx *ctx, const FftPlan &pl, cplx *tw)
 
 using namespace imcom;
 
-extern "C" int imcom_psf_overlap(imcom_ctx *ctx, const double *psf1, int n1, const double *psf2, int n2, int nsamp,
-                                 int nfft, const int *pairs_host, int npairs, const double *amp_penalty, double *tables)
+// Tables of side ntab (PSFs of side nsamp <= ntab <= nfft - 1, rolled by ntab / 2) from sampled PSFs: spectra + inverse on the butterfly
+// path, else the dense-DFT form.  ntab == nsamp is imcom_psf_overlap, ntab > nsamp imcom_psf_overlap_wide; the arguments have been checked.
+static int overlap_from_psfs(imcom_ctx *ctx, const double *psf1, int n1, const double *psf2, int n2, int nsamp, int ntab, int nfft,
+                             const int *pairs_host, int npairs, const double *amp_penalty, double *tables, const char *who)
 {
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(psf1 && psf2 && pairs_host && tables, "null pointer");
-    IMCOM_REQUIRE(n1 >= 1 && n2 >= 1 && npairs >= 1 && nsamp >= 1 && nfft >= 2 * nsamp && nfft % 2 == 0,
-                  "bad sizes (need nfft even and >= 2*nsamp)");
-    IMCOM_REQUIRE(nsamp % 2 == 1, "nsamp must be odd (PSFGrp.setup: nsamp = npixpsf*oversamp - 1)");
-    for (int t = 0; t < npairs; t++)
-        IMCOM_REQUIRE(pairs_host[2 * t] >= 0 && pairs_host[2 * t] < n1 && pairs_host[2 * t + 1] >= 0 && pairs_host[2 * t + 1] < n2,
-                      "pair %d out of range", t);
     FftPlan pl;
     if (!fft_force_gemm() && fft_plan(nfft, &pl)) {
         const int nh_ = nfft / 2 + 1;
         const bool same_ = (psf1 == psf2 && n1 == n2);
         const int npsf_ = same_ ? n1 : n1 + n2;
-        IMCOM_TRY(ws_reserve(ctx, fft_forward_ws(npsf_, nsamp, nfft) + (size_t)npsf_ * nfft * nh_ * 16 + fft_inverse_ws(npairs, nsamp, nfft) + (size_t)nfft * 64 + 65536));
+        IMCOM_TRY(ws_reserve(ctx, fft_forward_ws(npsf_, nsamp, nfft) + (size_t)npsf_ * nfft * nh_ * 16 + fft_inverse_ws(npairs, ntab, nfft) + (size_t)nfft * 64 + 65536));
         cplx *R = (cplx *)ws_take(ctx, (size_t)npsf_ * nfft * nh_ * 16);
-        if (!R) return ws_short(__func__);
+        if (!R) return ws_short(who);
         ProfScope ps(ctx, "psf_overlap");
         IMCOM_TRY(fft_forward(ctx, pl, psf1, n1, nsamp, R));
         if (!same_) IMCOM_TRY(fft_forward(ctx, pl, psf2, n2, nsamp, R + (long)n1 * nfft * nh_));
-        return fft_inverse(ctx, pl, R, same_ ? R : R + (long)n1 * nfft * nh_, pairs_host, npairs, nsamp, amp_penalty, tables);
+        return fft_inverse(ctx, pl, R, same_ ? R : R + (long)n1 * nfft * nh_, pairs_host, npairs, ntab, amp_penalty, tables);
     }
-    const int nh = nfft / 2 + 1, nc = nsamp / 2;
+    const int nh = nfft / 2 + 1, nc = ntab / 2;
     const int Sp = up(nsamp, NB);  // padded nsamp (as an M/N extent and as a K extent)
+    const int Tp = up(ntab, NB);   // padded table side (the kept rows / columns of the inverse)
     const int Hp = up(nh, NB);     // padded half-spectrum width
     const int Fp = up(nfft, NB);   // padded nfft
     const bool same = (psf1 == psf2 && n1 == n2);
@@ -632,29 +631,29 @@ extern "C" int imcom_psf_overlap(imcom_ctx *ctx, const double *psf1, int n1, con
     auto plan = [&](size_t b) { total = align_up(total, 256) + b; };
     plan(B8((long)Sp * Hp) * 2);        // FX
     plan(B8((long)Fp * Sp) * 2);        // FY
-    plan(B8((long)Sp * Fp) * 2);        // IY
-    plan(B8((long)Hp * Sp) * 2);        // IX
+    plan(B8((long)Tp * Fp) * 2);        // IY
+    plan(B8((long)Hp * Tp) * 2);        // IX
     const int npsf = same ? n1 : n1 + n2;
     plan(B8((long)npsf * Sp * Sp));     // padded PSFs
     plan(B8((long)npsf * Sp * Hp) * 2); // Y1 (x-transformed)
     plan(B8((long)npsf * plane) * 2);   // spectra
     plan(B8((long)npairs * plane) * 2); // Z
-    plan(B8((long)npairs * Sp * Hp) * 2); // U
-    plan(B8((long)npairs * Sp * Sp));   // windows
+    plan(B8((long)npairs * Tp * Hp) * 2); // U
+    plan(B8((long)npairs * Tp * Tp));   // windows
     plan((size_t)npairs * 8);
     IMCOM_TRY(ws_reserve(ctx, total + 8192));
     double *FXc = (double *)ws_take(ctx, B8((long)Sp * Hp) * 2), *FXs = FXc + (long)Sp * Hp;
     double *FYc = (double *)ws_take(ctx, B8((long)Fp * Sp) * 2), *FYs = FYc + (long)Fp * Sp;
-    double *IYc = (double *)ws_take(ctx, B8((long)Sp * Fp) * 2), *IYs = IYc + (long)Sp * Fp;
-    double *IXc = (double *)ws_take(ctx, B8((long)Hp * Sp) * 2), *IXs = IXc + (long)Hp * Sp;
+    double *IYc = (double *)ws_take(ctx, B8((long)Tp * Fp) * 2), *IYs = IYc + (long)Tp * Fp;
+    double *IXc = (double *)ws_take(ctx, B8((long)Hp * Tp) * 2), *IXs = IXc + (long)Hp * Tp;
     double *X = (double *)ws_take(ctx, B8((long)npsf * Sp * Sp));
     double *Y1 = (double *)ws_take(ctx, B8((long)npsf * Sp * Hp) * 2);
     double *R = (double *)ws_take(ctx, B8((long)npsf * plane) * 2);
     double *Z = (double *)ws_take(ctx, B8((long)npairs * plane) * 2);
-    double *U = (double *)ws_take(ctx, B8((long)npairs * Sp * Hp) * 2);
-    double *W = (double *)ws_take(ctx, B8((long)npairs * Sp * Sp));
+    double *U = (double *)ws_take(ctx, B8((long)npairs * Tp * Hp) * 2);
+    double *W = (double *)ws_take(ctx, B8((long)npairs * Tp * Tp));
     int *pairs_dev = (int *)ws_take(ctx, (size_t)npairs * 8);
-    if (!FXc || !FYc || !IYc || !IXc || !X || !Y1 || !R || !Z || !U || !W || !pairs_dev) return ws_short(__func__);
+    if (!FXc || !FYc || !IYc || !IXc || !X || !Y1 || !R || !Z || !U || !W || !pairs_dev) return ws_short(who);
     hipStream_t st = ctx->stream;
     ProfScope ps(ctx, "psf_overlap");
     // second group's PSFs are stored after the first's; remap q
@@ -667,8 +666,8 @@ extern "C" int imcom_psf_overlap(imcom_ctx *ctx, const double *psf1, int n1, con
     };
     dft(0, Sp, Hp, nsamp, nh, FXc, FXs);
     dft(1, Fp, Sp, nfft, nsamp, FYc, FYs);
-    dft(2, Sp, Fp, nsamp, nfft, IYc, IYs);
-    dft(3, Hp, Sp, nh, nsamp, IXc, IXs);
+    dft(2, Tp, Fp, ntab, nfft, IYc, IYs);
+    dft(3, Hp, Tp, nh, ntab, IXc, IXs);
     hipLaunchKernelGGL(pad_psf_kernel, dim3((Sp + 255) / 256, Sp, n1), dim3(256), 0, st, psf1, nsamp, X, Sp);
     if (!same) hipLaunchKernelGGL(pad_psf_kernel, dim3((Sp + 255) / 256, Sp, n2), dim3(256), 0, st, psf2, nsamp, X + (long)n1 * Sp * Sp, Sp);
     IMCOM_TRY(check_launch("psf_overlap prologue"));
@@ -687,18 +686,51 @@ extern "C" int imcom_psf_overlap(imcom_ctx *ctx, const double *psf1, int n1, con
                        nfft, amp_penalty ? amp_penalty[0] : 0.0, amp_penalty ? amp_penalty[1] : 0.0, Z);
     IMCOM_TRY(check_launch("cmul_conj_kernel"));
     // inverse along y on the kept rows: U = (IYc + i IYs) Z    [Sp x Fp] . [Fp x Hp]
-    const long sZ = 2L * plane, sU = 2L * Sp * Hp;
-    double *Zr = Z, *Zi = Z + plane, *Ur = U, *Ui = U + (long)Sp * Hp;
-    IMCOM_TRY(launch_gemm(ctx, false, true, Sp, Hp, Fp, npairs, IYc, Fp, 0, Zr, Hp, sZ, Ur, Hp, sU, 1.0, 0.0));
-    IMCOM_TRY(launch_gemm(ctx, false, true, Sp, Hp, Fp, npairs, IYs, Fp, 0, Zi, Hp, sZ, Ur, Hp, sU, -1.0, 1.0));
-    IMCOM_TRY(launch_gemm(ctx, false, true, Sp, Hp, Fp, npairs, IYc, Fp, 0, Zi, Hp, sZ, Ui, Hp, sU, 1.0, 0.0));
-    IMCOM_TRY(launch_gemm(ctx, false, true, Sp, Hp, Fp, npairs, IYs, Fp, 0, Zr, Hp, sZ, Ui, Hp, sU, 1.0, 1.0));
+    const long sZ = 2L * plane, sU = 2L * Tp * Hp;
+    double *Zr = Z, *Zi = Z + plane, *Ur = U, *Ui = U + (long)Tp * Hp;
+    IMCOM_TRY(launch_gemm(ctx, false, true, Tp, Hp, Fp, npairs, IYc, Fp, 0, Zr, Hp, sZ, Ur, Hp, sU, 1.0, 0.0));
+    IMCOM_TRY(launch_gemm(ctx, false, true, Tp, Hp, Fp, npairs, IYs, Fp, 0, Zi, Hp, sZ, Ur, Hp, sU, -1.0, 1.0));
+    IMCOM_TRY(launch_gemm(ctx, false, true, Tp, Hp, Fp, npairs, IYc, Fp, 0, Zi, Hp, sZ, Ui, Hp, sU, 1.0, 0.0));
+    IMCOM_TRY(launch_gemm(ctx, false, true, Tp, Hp, Fp, npairs, IYs, Fp, 0, Zr, Hp, sZ, Ui, Hp, sU, 1.0, 1.0));
     // inverse along x on the kept columns (Hermitian half-spectrum weights folded into IX)
-    IMCOM_TRY(launch_gemm(ctx, false, true, Sp, Sp, Hp, npairs, Ur, Hp, sU, IXc, Sp, 0, W, Sp, (long)Sp * Sp, 1.0, 0.0));
-    IMCOM_TRY(launch_gemm(ctx, false, true, Sp, Sp, Hp, npairs, Ui, Hp, sU, IXs, Sp, 0, W, Sp, (long)Sp * Sp, 1.0, 1.0));
-    const int ng = nsamp + 12;
-    hipLaunchKernelGGL(crop_table_kernel, dim3((ng + 255) / 256, ng, npairs), dim3(256), 0, st, W, Sp, nsamp, tables);
+    IMCOM_TRY(launch_gemm(ctx, false, true, Tp, Tp, Hp, npairs, Ur, Hp, sU, IXc, Tp, 0, W, Tp, (long)Tp * Tp, 1.0, 0.0));
+    IMCOM_TRY(launch_gemm(ctx, false, true, Tp, Tp, Hp, npairs, Ui, Hp, sU, IXs, Tp, 0, W, Tp, (long)Tp * Tp, 1.0, 1.0));
+    const int ng = ntab + 12;
+    hipLaunchKernelGGL(crop_table_kernel, dim3((ng + 255) / 256, ng, npairs), dim3(256), 0, st, W, Tp, ntab, tables);
     return check_launch("crop_table_kernel");
+}
+
+static int overlap_pairs_ok(const int *pairs_host, int npairs, int n1, int n2)
+{
+    for (int t = 0; t < npairs; t++)
+        IMCOM_REQUIRE(pairs_host[2 * t] >= 0 && pairs_host[2 * t] < n1 && pairs_host[2 * t + 1] >= 0 && pairs_host[2 * t + 1] < n2,
+                      "pair %d out of range", t);
+    return IMCOM_OK;
+}
+
+extern "C" int imcom_psf_overlap(imcom_ctx *ctx, const double *psf1, int n1, const double *psf2, int n2, int nsamp,
+                                 int nfft, const int *pairs_host, int npairs, const double *amp_penalty, double *tables)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(psf1 && psf2 && pairs_host && tables, "null pointer");
+    IMCOM_REQUIRE(n1 >= 1 && n2 >= 1 && npairs >= 1 && nsamp >= 1 && nfft >= 2 * nsamp && nfft % 2 == 0,
+                  "bad sizes (need nfft even and >= 2*nsamp)");
+    IMCOM_REQUIRE(nsamp % 2 == 1, "nsamp must be odd (PSFGrp.setup: nsamp = npixpsf*oversamp - 1)");
+    IMCOM_TRY(overlap_pairs_ok(pairs_host, npairs, n1, n2));
+    return overlap_from_psfs(ctx, psf1, n1, psf2, n2, nsamp, nsamp, nfft, pairs_host, npairs, amp_penalty, tables, __func__);
+}
+
+extern "C" int imcom_psf_overlap_wide(imcom_ctx *ctx, const double *psf1, int n1, const double *psf2, int n2, int nsamp, int ntab,
+                                      int nfft, const int *pairs_host, int npairs, const double *amp_penalty, double *tables)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(psf1 && psf2 && pairs_host && tables, "null pointer");
+    IMCOM_REQUIRE(n1 >= 1 && n2 >= 1 && npairs >= 1 && nsamp >= 1 && nfft >= 2 * nsamp && nfft % 2 == 0,
+                  "bad sizes (need nfft even and >= 2*nsamp)");
+    IMCOM_REQUIRE(nsamp % 2 == 1, "nsamp must be odd (PSFGrp.setup: nsamp = npixpsf*oversamp - 1)");
+    IMCOM_REQUIRE(ntab % 2 == 1 && ntab >= nsamp && ntab <= nfft - 1, "table side %d: need odd, nsamp <= ntab <= nfft - 1 (PSFOvl.setup: 2*nsamp + 1)", ntab);
+    IMCOM_TRY(overlap_pairs_ok(pairs_host, npairs, n1, n2));
+    return overlap_from_psfs(ctx, psf1, n1, psf2, n2, nsamp, ntab, nfft, pairs_host, npairs, amp_penalty, tables, __func__);
 }
 
 extern "C" long imcom_psf_spectra_size(int nsamp, int nfft)
@@ -720,6 +752,38 @@ extern "C" int imcom_psf_spectra(imcom_ctx *ctx, const double *psf, int n, int n
     return fft_forward(ctx, pl, psf, n, nsamp, (cplx *)spectra);
 }
 
+// Tables of side ntab from resident spectra (the inverse transforms keep ntab rows and columns whatever the PSF side was): ntab == nsamp
+// is imcom_psf_overlap_spectra_slots, ntab > nsamp imcom_psf_overlap_spectra_wide; sizes and pointers have been checked.
+static int overlap_from_spectra(imcom_ctx *ctx, const double *spec1, int n1, const double *spec2, int n2, int ntab, int nfft,
+                                const int *pairs_host, int npairs, const double *amp_penalty, const int *win_host, const int *slots_host,
+                                int nslots, double *tables)
+{
+    IMCOM_TRY(overlap_pairs_ok(pairs_host, npairs, n1, n2));
+    if (win_host)
+        for (int t = 0; t < npairs; t++) {
+            const int *w = win_host + 4 * (size_t)t;
+            IMCOM_REQUIRE(0 <= w[0] && w[0] < w[1] && w[1] <= ntab && 0 <= w[2] && w[2] < w[3] && w[3] <= ntab, "window %d out of range", t);
+        }
+    if (slots_host)
+        for (int t = 0; t < npairs; t++) IMCOM_REQUIRE(slots_host[t] >= 0 && slots_host[t] < nslots, "slot %d of pair %d outside the arena of %d tables", slots_host[t], t, nslots);
+    FftPlan pl;
+    fft_plan(nfft, &pl);
+    // in chunks of pairs, so that the intermediate (ntab x nh complex per pair) stays within ~4 GB however many
+    // tables a caller asks for at once; the chunks run back to back on the stream and reuse the workspace in order
+    const size_t per_pair = (size_t)(ntab + 1) * v_stride(nfft) * 16;
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)npairs, ((size_t)4 << 30) / per_pair));
+    IMCOM_TRY(ws_reserve(ctx, fft_inverse_ws(chunk, ntab, nfft) + 8192));
+    ProfScope ps(ctx, "psf_overlap");
+    const size_t tab = (size_t)(ntab + 12) * (ntab + 12);
+    for (int p0 = 0; p0 < npairs; p0 += chunk) {
+        ctx->ws_used = 0;
+        IMCOM_TRY(fft_inverse(ctx, pl, (const cplx *)spec1, (const cplx *)spec2, pairs_host + 2 * (size_t)p0, std::min(chunk, npairs - p0), ntab,
+                              amp_penalty, slots_host ? tables : tables + (size_t)p0 * tab, win_host ? win_host + 4 * (size_t)p0 : nullptr,
+                              slots_host ? slots_host + p0 : nullptr));
+    }
+    return IMCOM_OK;
+}
+
 extern "C" int imcom_psf_overlap_spectra_slots(imcom_ctx *ctx, const double *spec1, int n1, const double *spec2, int n2, int nsamp,
                                                int nfft, const int *pairs_host, int npairs, const double *amp_penalty,
                                                const int *win_host, const int *slots_host, int nslots, double *tables)
@@ -727,32 +791,19 @@ extern "C" int imcom_psf_overlap_spectra_slots(imcom_ctx *ctx, const double *spe
     IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(spec1 && spec2 && pairs_host && tables && npairs >= 1, "null pointer / no pairs");
     IMCOM_REQUIRE(imcom_psf_spectra_size(nsamp, nfft) > 0, "no butterfly plan for nfft=%d (use imcom_psf_overlap)", nfft);
-    for (int t = 0; t < npairs; t++)
-        IMCOM_REQUIRE(pairs_host[2 * t] >= 0 && pairs_host[2 * t] < n1 && pairs_host[2 * t + 1] >= 0 && pairs_host[2 * t + 1] < n2,
-                      "pair %d out of range", t);
-    if (win_host)
-        for (int t = 0; t < npairs; t++) {
-            const int *w = win_host + 4 * (size_t)t;
-            IMCOM_REQUIRE(0 <= w[0] && w[0] < w[1] && w[1] <= nsamp && 0 <= w[2] && w[2] < w[3] && w[3] <= nsamp, "window %d out of range", t);
-        }
-    if (slots_host)
-        for (int t = 0; t < npairs; t++) IMCOM_REQUIRE(slots_host[t] >= 0 && slots_host[t] < nslots, "slot %d of pair %d outside the arena of %d tables", slots_host[t], t, nslots);
-    FftPlan pl;
-    fft_plan(nfft, &pl);
-    // in chunks of pairs, so that the intermediate (nsamp x nh complex per pair) stays within ~4 GB however many
-    // tables a caller asks for at once; the chunks run back to back on the stream and reuse the workspace in order
-    const size_t per_pair = (size_t)(nsamp + 1) * v_stride(nfft) * 16;
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)npairs, ((size_t)4 << 30) / per_pair));
-    IMCOM_TRY(ws_reserve(ctx, fft_inverse_ws(chunk, nsamp, nfft) + 8192));
-    ProfScope ps(ctx, "psf_overlap");
-    const size_t tab = (size_t)(nsamp + 12) * (nsamp + 12);
-    for (int p0 = 0; p0 < npairs; p0 += chunk) {
-        ctx->ws_used = 0;
-        IMCOM_TRY(fft_inverse(ctx, pl, (const cplx *)spec1, (const cplx *)spec2, pairs_host + 2 * (size_t)p0, std::min(chunk, npairs - p0), nsamp,
-                              amp_penalty, slots_host ? tables : tables + (size_t)p0 * tab, win_host ? win_host + 4 * (size_t)p0 : nullptr,
-                              slots_host ? slots_host + p0 : nullptr));
-    }
-    return IMCOM_OK;
+    return overlap_from_spectra(ctx, spec1, n1, spec2, n2, nsamp, nfft, pairs_host, npairs, amp_penalty, win_host, slots_host, nslots, tables);
+}
+
+extern "C" int imcom_psf_overlap_spectra_wide(imcom_ctx *ctx, const double *spec1, int n1, const double *spec2, int n2, int nsamp,
+                                              int ntab, int nfft, const int *pairs_host, int npairs, const double *amp_penalty,
+                                              const int *win_host, const int *slots_host, int nslots, double *tables)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(spec1 && spec2 && pairs_host && tables && npairs >= 1, "null pointer / no pairs");
+    IMCOM_REQUIRE(imcom_psf_spectra_size(nsamp, nfft) > 0, "no butterfly plan for nfft=%d (use imcom_psf_overlap_wide)", nfft);
+    IMCOM_REQUIRE(ntab % 2 == 1 && ntab >= nsamp && ntab <= nfft - 1, "table side %d: need odd, nsamp <= ntab <= nfft - 1 (PSFOvl.setup: 2*nsamp + 1)", ntab);
+    // the spectra do not depend on the table side; from here on only the table side counts (rows kept, intermediate, windows, table stride)
+    return overlap_from_spectra(ctx, spec1, n1, spec2, n2, ntab, nfft, pairs_host, npairs, amp_penalty, win_host, slots_host, nslots, tables);
 }
 
 extern "C" int imcom_psf_overlap_spectra_win(imcom_ctx *ctx, const double *spec1, int n1, const double *spec2, int n2, int nsamp,

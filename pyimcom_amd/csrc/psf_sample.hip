@@ -209,6 +209,24 @@ __global__ __launch_bounds__(256) void lattice_positions_kernel(const double *__
     }
 }
 
+// Sampling positions under PSFSPLIT (psfutil.py:739-753): the reference evaluates outpix2world2inpix at the group's computation point
+// +- oversamp output pixels along x and y only and takes the map as affine over the PSF window,
+//   yxco = (c0 - c2) (x) yxo[1] + (c1 - c3) (x) yxo[0],   c = the four results flipped to (y, x), halved, times dscale,
+// yxo the unrotated sample grid (integers i - (nsamp - 1) / 2).  card [count][4][2]; one thread per sample, two products and one sum
+// per element as np.tensordot(..., axes=0) + np.tensordot(..., axes=0) forms them (no contraction into an fma).
+__global__ __launch_bounds__(256) void affine_positions_kernel(const double *__restrict__ card, int ns, double *__restrict__ out)
+{
+    const int c = blockIdx.z, iy = blockIdx.y, ix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ix >= ns) return;
+    const double *cd = card + (long)c * 8;
+    const double gx = (double)ix - 0.5 * (double)(ns - 1), gy = (double)iy - 0.5 * (double)(ns - 1);  // yxo[1], yxo[0]
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const double ax = __dsub_rn(cd[k], cd[4 + k]), ay = __dsub_rn(cd[2 + k], cd[6 + k]);  // (c0 - c2)[k], (c1 - c3)[k]
+        out[(((long)c * 2 + k) * ns + iy) * ns + ix] = __dadd_rn(__dmul_rn(ax, gx), __dmul_rn(ay, gy));
+    }
+}
+
 // imcom_smooth_and_pad's device work, shared with imcom_psf_from_cube (api.hip): the scratch is taken from the workspace the caller
 // has reserved (smooth_pad_ws_bytes counts it), src [n][ny][nx] and dst [n][ny + 2 npad][nx + 2 npad] are device memory.
 size_t smooth_pad_ws_bytes(int n, int ny, int nx, double tophatwidth, double gaussiansigma)
@@ -331,6 +349,29 @@ extern "C" int imcom_lattice_positions(imcom_ctx *ctx, int count, int L, const d
         hipLaunchKernelGGL(lattice_positions_kernel, dim3((nsamp + LAT_ROWS - 1) / LAT_ROWS, 2 * count), dim3(256), lds, ctx->stream, (const double *)W_d, lat_d,
                            L, nsamp, out_d);
         IMCOM_TRY(check_launch("lattice_positions_kernel"));
+    }
+    IMCOM_TRY(st.back(yxco, out_d, szO));
+    return st.done();
+}
+
+extern "C" int imcom_affine_positions(imcom_ctx *ctx, int count, const double *cardinal, int nsamp, double *yxco, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(count >= 1 && count <= 65535 && cardinal && yxco && nsamp >= 1 && nsamp <= 65535, "bad arguments (1 <= count, nsamp <= 65535)");
+    Stage st(ctx, memspace, __func__);
+    const size_t szC = (size_t)count * 8, szO = (size_t)count * 2 * nsamp * nsamp;
+    WsPlan plan;
+    plan.add(8192);
+    st.plan(plan, {szC * 8, szO * 8});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *card_d;
+    double *out_d;
+    IMCOM_TRY(st.in(cardinal, szC, &card_d));
+    IMCOM_TRY(st.out(yxco, szO, &out_d));
+    {
+        ProfScope ps(ctx, "psf_sample");
+        hipLaunchKernelGGL(affine_positions_kernel, dim3((nsamp + 255) / 256, nsamp, count), dim3(256), 0, ctx->stream, card_d, nsamp, out_d);
+        IMCOM_TRY(check_launch("affine_positions_kernel"));
     }
     IMCOM_TRY(st.back(yxco, out_d, szO));
     return st.done();

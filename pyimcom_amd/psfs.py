@@ -148,3 +148,30 @@ def lattice_positions(lattice, W, nsamp, ctx=None):
     out = _out((count, 2, nsamp, nsamp), "torch" if tor else "numpy", lattice.device if tor else None)
     check(lib.imcom_lattice_positions(ctx.handle, int(count), int(L), ptr(W), ptr(lattice), int(nsamp), ptr(out), MEM_DEVICE if tor else MEM_HOST))
     return out
+
+
+def affine_positions(cardinal, nsamp, ctx=None):
+    """The sampling positions yxco [count, 2, nsamp, nsamp] of ``sample_psf`` under PSFSPLIT (imcom_affine_positions; PSFGrp._sample_psf,
+    psfutil.py:739-753): ``cardinal`` [count, 4, 2] = ``outpix2world2inpix`` at the group's computation point +- oversamp output pixels
+    along x and y, flipped to (y, x), halved, times dscale (``cardinal_points``) -- the map is taken as affine over the PSF window.
+    numpy -> numpy out, torch device tensor -> device out."""
+    ctx = ctx or default_context()
+    tor = _is_torch(cardinal)
+    count, four, two = cardinal.shape
+    assert four == 4 and two == 2
+    if tor:
+        import torch
+
+        cardinal = cardinal.contiguous()
+        ctx.set_stream(torch.cuda.current_stream(cardinal.device).cuda_stream)
+    else:
+        cardinal = np.ascontiguousarray(cardinal, dtype=np.float64)
+    out = _out((count, 2, nsamp, nsamp), "torch" if tor else "numpy", cardinal.device if tor else None)
+    check(lib.imcom_affine_positions(ctx.handle, int(count), ptr(cardinal), int(nsamp), ptr(out), MEM_DEVICE if tor else MEM_HOST))
+    return out
+
+
+def cardinal_points(outpix2world2inpix, point, oversamp, dscale):
+    """``yx_cardinal`` of psfutil.py:739-749, [4, 2]: the host half of ``affine_positions`` (four evaluations of the WCS chain)."""
+    p = np.array(point, dtype=np.float64)[None, :] + np.array([[1, 0], [0, 1], [-1, 0], [0, -1]]) * oversamp
+    return np.flip(outpix2world2inpix(p), axis=-1) / 2.0 * dscale

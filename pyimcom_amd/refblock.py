@@ -23,7 +23,10 @@ PSF file broker and the WCS evaluation of the PSF sampling positions -- everythi
 
 Configurations this build cannot serve raise ``ImcomError`` with status IMCOM_ERR_UNSUPPORTED instead of silently taking
 another path: PSFINTERP "G4460" (the 8x8 interpolator of furry_parakeet: no source and no numerical test in the reference,
-SURVEY 8c) and PSF splitting (``psfsplit``, psfutil.py:594-606 -- a different table pipeline).
+SURVEY 8c).  PSF splitting (``cfg.psfsplit``, psfutil.py:594-606, 739-753, 1087-1089) is served on request only --
+``coadd_output_stamps(blk, PSFGrp, psfsplit=True)`` -- because it is one stage of three: the caller has cut the PSF cubes
+(``pyimcom_amd.splitpsf``), its ``get_psf_pos(point, use_shortrange=True)`` returns short-range PSFs, and it subtracts the long-range
+part afterwards (``pyimcom_amd.imsubtract``).  Without the keyword such a configuration is refused with IMCOM_ERR_UNSUPPORTED.
 """
 
 import numpy as np
@@ -35,14 +38,18 @@ IMCOM_ERR_UNSUPPORTED = -4
 ARCSEC = np.pi / 180.0 / 3600.0  # pyimcom.config.Settings.arcsec (config.py:85-98)
 
 
-def check_supported(cfg):
-    """Raise IMCOM_ERR_UNSUPPORTED for the reference configurations that have no device path."""
+def check_supported(cfg, psfsplit=False):
+    """Raise IMCOM_ERR_UNSUPPORTED for the reference configurations that have no device path.  ``psfsplit``: the caller asks for the
+    split-PSF coaddition (module docstring); a configuration and a keyword that disagree are an error either way."""
     interp = str(getattr(cfg, "psf_interp", "D5512") or "D5512").upper()
     if interp != "D5512":
         raise ImcomError(IMCOM_ERR_UNSUPPORTED, f"PSFINTERP = {interp!r}: only the D5512 (10x10) interpolator is built "
                          "(iG4460C has no in-tree source or numerical test to pin it against, coadd.py:1599-1601)")
-    if getattr(cfg, "psfsplit", None):
-        raise ImcomError(IMCOM_ERR_UNSUPPORTED, "PSFSPLIT is set: the split-PSF table pipeline (psfutil.py:594-606, 1178-1242) is not built")
+    if getattr(cfg, "psfsplit", None) and not psfsplit:
+        raise ImcomError(IMCOM_ERR_UNSUPPORTED, "PSFSPLIT is set: the split-PSF coaddition (psfutil.py:594-606, 739-753, 1087-1089) is served on "
+                         "request only -- pass psfsplit=True once the PSF broker returns short-range PSFs (pyimcom_amd.splitpsf)")
+    if psfsplit and not getattr(cfg, "psfsplit", None):
+        raise ValueError("psfsplit=True, but the configuration has no PSFSPLIT: the overlap tables would be twice as wide as the reference's")
     kernel = getattr(cfg, "linear_algebra", "Cholesky")
     if kernel not in ("Cholesky", "Eigen", "Iterative", "Empirical"):
         raise ImcomError(IMCOM_ERR_UNSUPPORTED, f"LAKERNEL = {kernel!r}")
@@ -107,7 +114,7 @@ class _HostAhead:
 LATTICE = 17  # nodes per axis of the lattice the sampling positions are evaluated on (positions="lattice")
 
 
-def input_psf_groups(blk, psfgrp, device, ctx=None, host_threads=1, positions="lattice"):
+def input_psf_groups(blk, psfgrp, device, ctx=None, host_threads=1, positions="lattice", psfsplit=False):
     """PSFGrp._build_inpsfgrp for the 2x2 groups of InStamps (psfutil.py:797-851), on demand: returns (count, expo, provider,
     ahead) with count[(gj, gi)] = number of exposures with pixels in the group, expo[(gj, gi)] = their block indices,
     ``provider(keys)`` -> device tensor [sum of the keys' counts, nsamp, nsamp] of sampled PSFs, and ``ahead`` the _HostAhead that
@@ -119,7 +126,9 @@ def input_psf_groups(blk, psfgrp, device, ctx=None, host_threads=1, positions="l
     exposure, as psfutil.py:751-771 does (2.3 MB uploaded each); "lattice" (default) -- at the 17 x 17 Chebyshev-Lobatto nodes spanning
     the same window, and the device forms the positions from them (psfs.lattice_positions: exact for maps of degree < 17 per axis; the
     real chain's deviation from that over the 5" window is below rounding -- tests/test_gpu_refblock.py bounds it at 1e-10 samples on
-    affine + distorted maps)."""
+    affine + distorted maps).  ``psfsplit=True``: the reference's own choice under PSFSPLIT (psfutil.py:739-753) -- four evaluations per
+    group and exposure, at the computation point +- oversamp output pixels along x and y, the map taken as affine over the PSF window
+    (psfs.cardinal_points, psfs.affine_positions: 8 numbers uploaded); ``positions`` is then ignored."""
     import torch
 
     from . import psfs
@@ -137,6 +146,7 @@ def input_psf_groups(blk, psfgrp, device, ctx=None, host_threads=1, positions="l
         lx, ly = np.meshgrid(nodes, nodes)  # [a][b]: node a along y, node b along x
         xy = np.stack([lx.ravel(), ly.ravel()], axis=1)
     npos = LATTICE if lattice else ns  # positions per axis the host evaluates
+    pos_shape = (4, 2) if psfsplit else (2, npos, npos)  # what the host hands over per exposure
     count, expo = {}, {}
     for gj in range(nst // 2):
         for gi in range(nst // 2):
@@ -162,22 +172,28 @@ def input_psf_groups(blk, psfgrp, device, ctx=None, host_threads=1, positions="l
         for e in expo[key]:
             im = blk.inimages[e]
             img = np.asarray(im.get_psf_pos(world, use_shortrange=True), dtype=np.float64)
-            d = (np.asarray(im.outpix2world2inpix(xy + p0)) - np.asarray(im.outpix2world2inpix(p0[None]))) * oversamp
+            if psfsplit:
+                d = np.asarray(psfs.cardinal_points(im.outpix2world2inpix, p0, psfgrp.oversamp, psfgrp.dscale), dtype=np.float64)
+            else:
+                d = (np.asarray(im.outpix2world2inpix(xy + p0)) - np.asarray(im.outpix2world2inpix(p0[None]))) * oversamp
+                d = np.stack([d[:, 1].reshape(npos, npos), d[:, 0].reshape(npos, npos)])
             out.append((img, d))
         # stacked into page-locked memory here, on the worker: the device loop's thread only queues the copies
         if len({img.shape for img, _ in out}) == 1:
             k = len(out)
             imgs = torch.empty((k,) + out[0][0].shape, dtype=torch.float64, pin_memory=True)
-            yx = torch.empty((k, 2, npos, npos), dtype=torch.float64, pin_memory=True)
+            yx = torch.empty((k,) + pos_shape, dtype=torch.float64, pin_memory=True)
             iv, yv = imgs.numpy(), yx.numpy()
             for q, (img, d) in enumerate(out):
                 iv[q] = img
-                yv[q, 0], yv[q, 1] = d[:, 1].reshape(npos, npos), d[:, 0].reshape(npos, npos)
+                yv[q] = d
             return imgs, yx
-        return [(img, np.stack([d[:, 1].reshape(npos, npos), d[:, 0].reshape(npos, npos)])) for img, d in out]
+        return out
 
     def full(yx):
         """device positions [k, 2, ns, ns] of what the host evaluated"""
+        if psfsplit:
+            return psfs.affine_positions(yx, ns, ctx)
         return psfs.lattice_positions(yx, W_lat, ns, ctx) if lattice else yx
 
     ahead = _HostAhead(host_half, host_threads)
@@ -234,7 +250,7 @@ _REPAIR_STATE = {}  # per context: the repair record of the last block's first p
                     # start from ITS first pass's record, never from another block's
 
 def coadd_output_stamps(blk, psfgrp, flat_penalty=None, batch=None, device="cuda:0", stamps=None, finalize=True, table_capacity=None, ctx=None,
-                        host_threads=1, positions="lattice"):
+                        host_threads=1, positions="lattice", psfsplit=False):
     """Run the stamp loop of ``blk`` on the GPU and fill its block maps (module docstring).  The stamps are those of the
     reference's loop: the window ``blk.j_st_min .. j_st_max, i_st_min .. i_st_max`` of Block._handle_postage_pad (coadd.py:1808-1838;
     default: all n1P x n1P) in cells of 2 x 2, stopping after ``blk.nrun`` stamps when the block carries one (cfg.stoptile,
@@ -247,13 +263,20 @@ def coadd_output_stamps(blk, psfgrp, flat_penalty=None, batch=None, device="cuda
     the coming batches is prepared on ``host_threads`` worker thread(s) while the GPU works on the current one (_HostAhead; one
     thread unless the block's ``inimages`` may be entered from several).  ``positions``: "lattice" (default) -- the WCS chain is evaluated
     at 17 x 17 nodes per PSF group and exposure and the device forms the nsamp^2 sampling positions from them; "exact" -- at all nsamp^2,
-    as the reference does (input_psf_groups).  Returns the ``BlockMaps``."""
+    as the reference does (input_psf_groups).  ``psfsplit=True``: the coaddition stage of the reference's PSFSPLIT pipeline (module docstring):
+    ``cfg.psfsplit`` must be set (and ``PSFGrp.psfsplit`` true where the class carries it), the overlap tables take PSFOvl's side
+    2 * PSFGrp.nsamp + 1 (psfutil.py:1087-1089), and the sampling positions are the reference's affine ones from four WCS evaluations per
+    group and exposure (psfutil.py:739-753) -- ``positions`` is ignored.  Everything else runs as without it.  Returns the ``BlockMaps``."""
     from .blockrun import coadd_block, plan_block, stamp_groups
     from .select import InStampPool
     from .stamps import BlockTables
 
     cfg = blk.cfg
-    check_supported(cfg)
+    psfsplit = bool(psfsplit)
+    check_supported(cfg, psfsplit=psfsplit)
+    if hasattr(psfgrp, "psfsplit") and bool(psfgrp.psfsplit) != psfsplit:
+        raise ValueError(f"psfsplit={psfsplit}, but PSFGrp.psfsplit = {psfgrp.psfsplit!r}: PSFGrp.setup and the call must agree")
+    ntab = 2 * int(psfgrp.nsamp) + 1 if psfsplit else None  # PSFOvl.setup, psfutil.py:1087-1089
     if flat_penalty is None:
         flat_penalty = getattr(cfg, "flat_penalty", 0.0)
     scfg = stamp_config(cfg, psfgrp, blk.n_inimage, flat_penalty)
@@ -261,7 +284,7 @@ def coadd_output_stamps(blk, psfgrp, flat_penalty=None, batch=None, device="cuda
         if hasattr(cfg, k):
             setattr(scfg, k, getattr(cfg, k))
     pool = InStampPool([(st.x_val, st.y_val, st.data, st.pix_cumsum) for row in blk.instamps for st in row], scfg.n_inframe, device=device)
-    count, expo, provider, ahead = input_psf_groups(blk, psfgrp, device, ctx, host_threads, positions)
+    count, expo, provider, ahead = input_psf_groups(blk, psfgrp, device, ctx, host_threads, positions, psfsplit)
     target = target_psfs(cfg, psfgrp, device, ctx)
     amp = getattr(cfg, "amp_penalty", None)
     amp = None if amp is None or 0.0 in tuple(amp) else (float(amp[0]), float(amp[1]) * float(psfgrp.oversamp))  # psfutil.py:661-671
@@ -270,12 +293,13 @@ def coadd_output_stamps(blk, psfgrp, flat_penalty=None, batch=None, device="cuda
     if table_capacity is None and count:
         from .blockrun import memory_plan
 
-        mp_ = memory_plan(scfg, pool, int(cfg.n1P), max(count.values()), n_out=int(target.shape[0]), nfft=int(psfgrp.nfft), ctx=ctx)
+        mp_ = memory_plan(scfg, pool, int(cfg.n1P), max(count.values()), n_out=int(target.shape[0]), nfft=int(psfgrp.nfft), ctx=ctx, ntab=ntab)
         table_capacity, spec_cap = mp_["capacity"], mp_["spec_capacity"]
     tables = BlockTables({k: None for k in count}, target, int(psfgrp.nfft), group_expo=expo, group_count=count, bulk_provider=provider,
                          capacity=None if table_capacity is None else int(table_capacity), spec_capacity=spec_cap, amp_penalty=amp, device=device, ctx=ctx,
                          cells=True,  # groups of 2 x 2 InStamps: cells of the block's grid (coadd.py:207, 329-358)
-                         provider_waits=True)  # the provider hands over what the worker threads have prepared
+                         provider_waits=True,  # the provider hands over what the worker threads have prepared
+                         ntab=ntab)
     n1P = int(cfg.n1P)
     window = [int(getattr(blk, k, d)) for k, d in (("j_st_min", 1), ("j_st_max", n1P), ("i_st_min", 1), ("i_st_max", n1P))]
     if stamps is None and (window != [1, n1P, 1, n1P] or getattr(blk, "nrun", None) not in (None, n1P * n1P)):

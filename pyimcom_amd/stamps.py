@@ -87,11 +87,15 @@ def psf_spectra(ctx, psf, nfft):
     return spec
 
 
-def overlap_tables(ctx, p1, s1, p2, s2, nsamp, nfft, pairs, amp, out, win=None, slots=None):
+def overlap_tables(ctx, p1, s1, p2, s2, nsamp, nfft, pairs, amp, out, win=None, slots=None, ntab=None):
     """Tables of the (i, j) `pairs` between two PSF sets, from their spectra when both are given (else from the
     sampled PSFs through imcom_psf_overlap).  ``win`` [npairs, 4] (spectra form only): the part of every table's window
     that will be read, imcom_psf_overlap_spectra_win.  ``slots`` [npairs] (spectra form only): pair t goes to table
-    ``out[slots[t]]`` of the arena ``out`` instead of ``out[t]``, imcom_psf_overlap_spectra_slots."""
+    ``out[slots[t]]`` of the arena ``out`` instead of ``out[t]``, imcom_psf_overlap_spectra_slots.  ``ntab``: a table side of its
+    own (PSFSPLIT: 2 * nsamp + 1, psfutil.py:1087-1089; ``out`` [.., ntab + 12, ntab + 12], windows in table coordinates) through
+    the *_wide entries; None or nsamp: the plain entries."""
+    wide = ntab is not None and int(ntab) != int(nsamp)
+    assert tuple(out.shape[1:]) == ((int(ntab) if wide else int(nsamp)) + 12,) * 2
     pairs = np.ascontiguousarray(pairs, dtype=np.int32)
     ampp = None if amp is None else ptr(amp)
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)
@@ -106,12 +110,20 @@ def overlap_tables(ctx, p1, s1, p2, s2, nsamp, nfft, pairs, amp, out, win=None, 
             slots = np.ascontiguousarray(slots, dtype=np.int32)
             assert slots.shape == (len(pairs),)
             slp = ptr(slots)
-        check(lib.imcom_psf_overlap_spectra_slots(ctx.handle, ptr(s1), s1.shape[0], ptr(s2), s2.shape[0], nsamp, nfft, ptr(pairs),
-                                                  len(pairs), ampp, winp, slp, out.shape[0], ptr(out)))
+        if wide:
+            check(lib.imcom_psf_overlap_spectra_wide(ctx.handle, ptr(s1), s1.shape[0], ptr(s2), s2.shape[0], nsamp, int(ntab), nfft, ptr(pairs),
+                                                     len(pairs), ampp, winp, slp, out.shape[0], ptr(out)))
+        else:
+            check(lib.imcom_psf_overlap_spectra_slots(ctx.handle, ptr(s1), s1.shape[0], ptr(s2), s2.shape[0], nsamp, nfft, ptr(pairs),
+                                                      len(pairs), ampp, winp, slp, out.shape[0], ptr(out)))
     else:
         assert slots is None
-        check(lib.imcom_psf_overlap(ctx.handle, ptr(p1), p1.shape[0], ptr(p2), p2.shape[0], nsamp, nfft, ptr(pairs), len(pairs),
-                                    ampp, ptr(out)))
+        if wide:
+            check(lib.imcom_psf_overlap_wide(ctx.handle, ptr(p1), p1.shape[0], ptr(p2), p2.shape[0], nsamp, int(ntab), nfft, ptr(pairs),
+                                             len(pairs), ampp, ptr(out)))
+        else:
+            check(lib.imcom_psf_overlap(ctx.handle, ptr(p1), p1.shape[0], ptr(p2), p2.shape[0], nsamp, nfft, ptr(pairs), len(pairs),
+                                        ampp, ptr(out)))
 
 
 class PSFGroupTables:
@@ -124,18 +136,20 @@ class PSFGroupTables:
     (lakernel.py:121-128, kappa = kappaC * C of that target); ``Cs`` [n_out], ``C`` = Cs[0].
     """
 
-    def __init__(self, psf_in, psf_out, nfft, ctx=None, device="cuda:0", amp_penalty=None):
-        """amp_penalty: None or (cfg.amp_penalty[0], cfg.amp_penalty[1] * oversamp) (psfutil.py:661-671)."""
+    def __init__(self, psf_in, psf_out, nfft, ctx=None, device="cuda:0", amp_penalty=None, ntab=None):
+        """amp_penalty: None or (cfg.amp_penalty[0], cfg.amp_penalty[1] * oversamp) (psfutil.py:661-671).  ntab: the table side when it
+        differs from the PSF side (PSFSPLIT: PSFOvl.nsamp = 2 * nsamp + 1, psfutil.py:1087-1089); default: the PSF side."""
         self.ctx = ctx or default_context()
         amp = None if amp_penalty is None or 0.0 in tuple(amp_penalty) else np.array(amp_penalty, dtype=np.float64)
         E, ns, _ = psf_in.shape
         self.n_psf, self.nsamp, self.nfft = E, ns, nfft
+        nt = self.ntab = ns if ntab is None else int(ntab)  # side of the tables: what the builders' geometry and every buffer follow
         dev = torch.device(device)
         as_dev = lambda a: (a.to(dev).contiguous() if torch.is_tensor(a)  # noqa: E731
                             else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev))
         pin, pout = as_dev(psf_in), as_dev(psf_out)
         O = self.n_out = pout.shape[0]
-        ng = ns + 12
+        ng = nt + 12
         self.ntri = E * (E + 1) // 2
         # one set of E + O PSFs: self pairs (triangle order), input-output pairs (target-major), output self pairs;
         # their spectra are computed once and every table comes from them in one call
@@ -144,16 +158,16 @@ class PSFGroupTables:
         pairs = ([(i, j) for i in range(E) for j in range(i, E)] + [(i, E + o) for o in range(O) for i in range(E)]
                  + [(E + o, E + o) for o in range(O)])
         full = torch.empty((len(pairs), ng, ng), dtype=torch.float64, device=dev)
-        overlap_tables(self.ctx, allp, spec, allp, spec, ns, nfft, pairs, amp, full)
+        overlap_tables(self.ctx, allp, spec, allp, spec, ns, nfft, pairs, amp, full, ntab=nt)
         self.tables = full[: self.ntri + O * E]
         cc = full[self.ntri + O * E :]
-        nc = ns // 2
+        nc = nt // 2
         self.Cs = cc[:, 6 + nc, 6 + nc].cpu().numpy().astype(np.float64)  # psfutil.py:1290
         self.C = float(self.Cs[0])
 
     @classmethod
     def from_images(cls, psf_images, yxco, target, nsamp, nfft, oversamp, psf_circ=False, psf_norm=False, ctx=None,
-                    device="cuda:0", amp_penalty=None):
+                    device="cuda:0", amp_penalty=None, ntab=None):
         """The whole PSF side of a 2x2 stamp group on the device (PSFGrp.__init__ for the input group and for the
         output group, psfutil.py:615-671, then PSFOvl): ``psf_images`` [E, ny, nx] as returned by
         ``InImage.get_psf_pos``, ``yxco`` [E, 2, nsamp, nsamp] their sampling positions (psfutil.py:751-771, the
@@ -168,7 +182,7 @@ class PSFGroupTables:
         targets = [target] if isinstance(target[0], str) else list(target)
         timg = torch.stack([psfs.get_outpsf(t[0], t[1], t[2], nsamp, oversamp, device=dev, ctx=ctx) for t in targets])
         psf_out = psfs.sample_psf(timg, nsamp, None, psf_circ, psf_norm, ctx)
-        return cls(psf_in, psf_out, nfft, ctx=ctx, device=device, amp_penalty=amp_penalty)
+        return cls(psf_in, psf_out, nfft, ctx=ctx, device=device, amp_penalty=amp_penalty, ntab=ntab)
 
     def _set_stream(self):
         self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
@@ -224,7 +238,7 @@ class BlockTables:
     ValueError (``blockrun.plan_batches`` sizes a block's batches by ``demand``)."""
 
     def __init__(self, group_psfs, psf_out, nfft, group_expo=None, capacity=None, amp_penalty=None, ctx=None, device="cuda:0", on_full="evict",
-                 group_count=None, bulk_provider=None, cells=False, spec_capacity=None, eager_groups=False, provider_waits=False):
+                 group_count=None, bulk_provider=None, cells=False, spec_capacity=None, eager_groups=False, provider_waits=False, ntab=None):
         assert on_full in ("evict", "raise")
         self.on_full, self.evictions, self.evicted_tables, self.computed_tables = on_full, 0, 0, 0
         self.ctx = ctx or default_context()
@@ -257,6 +271,10 @@ class BlockTables:
         self.expo = {k: (list(range(self._count_of[k])) if group_expo is None else [int(e) for e in group_expo[k]]) for k in self.psf}
         assert all(len(self.expo[k]) == self._count_of[k] for k in self.psf)
         self.nsamp, self.nfft = int(psf_out.shape[-1]), nfft
+        # ``ntab``: the side of the tables when it differs from the PSF side (PSFSPLIT: PSFOvl.nsamp = 2 * nsamp + 1, psfutil.py:1087-1089;
+        # 4.85 MB per table at production size instead of 1.25 MB): the arena, its capacity in tables, the windows of ``cells`` and the
+        # builders' geometry follow it; the spectra arena does not (the spectra are those of the PSF side)
+        self.ntab = self.nsamp if ntab is None else int(ntab)
         self.n_max = max(self._count_of.values())
         self.n_psf = self.n_max
         self.n_blk_expo = 1 + max(max(v) for v in self.expo.values())
@@ -265,7 +283,7 @@ class BlockTables:
         O = self.n_out = self.pout.shape[0]
         amp = None if amp_penalty is None or 0.0 in tuple(amp_penalty) else np.array(amp_penalty, dtype=np.float64)
         self._amp = amp
-        ng = self.nsamp + 12
+        ng = self.ntab + 12
         if capacity is None:
             third = int(free_device_bytes(dev) // 3 // (8 * ng * ng))
             capacity = max(min(self.block_demand(), third), 1)
@@ -300,7 +318,7 @@ class BlockTables:
             check(lib.imcom_psf_spectra(self.ctx.handle, ptr(self.pout), O, self.nsamp, self.nfft, ptr(self._spec_all[:O])))
         cc = torch.empty((O, ng, ng), dtype=torch.float64, device=dev)
         self._compute([(None, None, [(o, o) for o in range(O)])], cc)
-        nc = self.nsamp // 2
+        nc = self.ntab // 2
         self._Cs_dev, self._Cs = cc[:, 6 + nc, 6 + nc].contiguous(), None  # read back when first asked for: no host wait here
 
     @property
@@ -406,13 +424,13 @@ class BlockTables:
             off = 0
             for g1, g2, pairs in jobs:
                 dst = out[off : off + len(pairs)] if slots is None else torch.empty((len(pairs),) + tuple(out.shape[1:]), dtype=out.dtype, device=out.device)
-                overlap_tables(self.ctx, self._psf_of(g1), None, self._psf_of(g2), None, self.nsamp, self.nfft, pairs, self._amp, dst)
+                overlap_tables(self.ctx, self._psf_of(g1), None, self._psf_of(g2), None, self.nsamp, self.nfft, pairs, self._amp, dst, ntab=self.ntab)
                 if slots is not None:
                     out.index_copy_(0, h2d(slots[off : off + len(pairs)], out.device, np.int64), dst)
                 off += len(pairs)
             return
         allp, allw = [], []
-        ns, nc, margin = self.nsamp, self.nsamp // 2, 8  # ten-tap stencils reach 4 below / 5 above the cell of a separation
+        ns, nc, margin = self.ntab, self.ntab // 2, 8  # (table coordinates) ten-tap stencils reach 4 below / 5 above the cell of a separation
         rng = {-1: (0, min(ns, nc + margin)), 0: (0, ns), 1: (max(0, nc - margin), ns)}
         sgn = lambda a, b: (a > b) - (a < b)  # noqa: E731
         self._ensure_spectra([g for g1, g2, _ in jobs for g in (g1, g2)])
@@ -423,7 +441,7 @@ class BlockTables:
                 sy, sx = (0, 0) if g1 is None or g2 is None or g1 == g2 else (sgn(g1[0], g2[0]), sgn(g1[1], g2[1]))
                 allw.append(np.broadcast_to(np.array(rng[sy] + rng[sx], dtype=np.int32), (len(pairs), 4)))
         overlap_tables(self.ctx, None, self._spec_all, None, self._spec_all, self.nsamp, self.nfft, np.concatenate(allp), self._amp, out,
-                       win=np.concatenate(allw) if self.cells else None, slots=slots)
+                       win=np.concatenate(allw) if self.cells else None, slots=slots, ntab=self.ntab)
 
     def _n(self, g):
         return self._count_of[g]
@@ -663,7 +681,7 @@ class StampBatch:
         expo i32 [B, ldn], indata f32 [B, n_inframe, ldn] with ldn a multiple of 128 and zero padding; n, out_x0,
         out_y0 host arrays [B].  Stamps whose pixels belong to several PSF groups pass ``psf_slot`` (i32 [B, ldn],
         stamp-local PSF index of each pixel) and ``maps`` = (pair_tab [B,P,P] i32, pair_pen [B,P,P] f64, io_tab [B,P] i32)
-        as documented at imcom_build_A / imcom_build_B; ``tables`` then only needs .tables, .nsamp, .C, .ctx.  ``buffers``: a
+        as documented at imcom_build_A / imcom_build_B; ``tables`` then only needs .tables, .nsamp (or .ntab), .C, .ctx.  ``buffers``: a
         BatchBuffers the large arrays are taken from (they are then valid until its next use)."""
         self = cls.__new__(cls)
         ldn = x.shape[1]
@@ -708,7 +726,8 @@ class StampBatch:
             self.pair_tab = h2d(tab, dev, np.int32)
             self.pair_pen = h2d(pen, dev, np.float64)
         self.io_tab_o = h2d(io, dev, np.int32)  # [n_out, B, P]
-        self.geom = TableGeom(tables.nsamp, float(tables.nsamp // 2), float(cfg.dscale), float(cfg.flat_penalty))
+        nt = int(getattr(tables, "ntab", tables.nsamp))  # the tables' side: the PSF side unless the tables are PSFSPLIT's wide ones
+        self.geom = TableGeom(nt, float(nt // 2), float(cfg.dscale), float(cfg.flat_penalty))
         Cs = np.asarray(getattr(tables, "Cs", [tables.C]), dtype=np.float64)
         self.Cs_o = np.ascontiguousarray(np.broadcast_to(Cs[:, None], (O, B)))
         self.kappaC = np.ascontiguousarray(cfg.kappaC, dtype=np.float64)
