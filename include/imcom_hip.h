@@ -602,6 +602,55 @@ int imcom_splitpsf_split(imcom_ctx *ctx, const double *cube, int npoly, int n, i
 int imcom_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npoly, int n, int i0, int npts, const double *lpw, const double *wg,
                           const double *cov, double eps, double *K_Legendre, double *K_real, double *zeta_real, double *zetamax, int memspace);
 
+/* Destriping: the cost function and its gradient over a mosaic resident on the device (reference src/pyimcom/imdestripe.py).  Every
+ * array is DEVICE memory except the pair table (pair_a .. pair_lat, host arrays of npairs entries).  n_sca SCAs of side nside are stacked:
+ * image, g_eff float32 [n_sca][nside][nside], mask bytes (0 / 1), N_eff float64, psi float32; params and the residuals float64
+ * [n_sca][nbins], nbins = ds_rows + nside / amp_cols (amp_cols <= 0: rows only).  Ordered pair i gathers neighbour pair_b[i] onto target
+ * pair_a[i]; the table is sorted by (a, b) -- the order the sums of a target pixel are formed in, whatever order the caller learnt the pairs
+ * in.  The positions of a's pixels in b are pair_x[i], pair_y[i] (float64 [nside][nside]: column and row in b, the x_target, y_target of
+ * compareutils.map_sca2sca) or, with both NULL, pair_lat[i] = their values [2][L][L] (x plane, y plane) on the L x L Chebyshev-Lobatto
+ * lattice over a's pixel range (row node, column node) with W [nside][L] the Lagrange weights of the nodes at every pixel index: the
+ * kernels contract the row axis once per image row and spend L multiply-adds per pixel and coordinate, as imcom_lattice_positions does.
+ * The cell is floor; a target pixel whose cell is not wholly inside the source contributes nothing.
+ *   imcom_destripe_sizes     out[8] = {nbins, column blocks, resident bytes per SCA (image, mask, g_eff, N_eff, psi), bytes of a pair's
+ *                            position arrays, bytes of a pair's lattice, workspace bytes of imcom_destripe_cost, of imcom_destripe_residual,
+ *                            bytes of W}.  IMCOM_ERR_UNSUPPORTED: ds_rows != nside (the "linear" model's 2 ds_rows parameters cannot be
+ *                            broadcast by the reference's own forward_par, imdestripe.py:690-691), amp_cols that does not divide nside
+ *                            (643-648), L outside 2 .. 33, a shape whose bins do not fit a workgroup's LDS.
+ *   imcom_destripe_neff      N_eff[a] = sum_b Interp_{b->a}[mask_b] (Sca_img.make_interpolated 535-562; once per mosaic).
+ *   imcom_destripe_cost      make_interpolated 476-594, interpolate_image_bilinear 972-998, subtract_parameters 430-449, apply_all_mask
+ *                            421-427, Parameters.forward_par 670-703, cost_function_single 1546-1559, the cost models 875-887,
+ *                            compute_boundary_continuity_penalty 1413-1489:  J_a = sum_b Interp_{b->a}[(I_b - P_b) mask_b g_b] (NaN -> 0, the
+ *                            stripe image P_b never formed), new_mask = N_eff > neff_min, J_a = where(new_mask, J_a / N_eff, 0) / g_a,
+ *                            psi = where(new_mask mask_a, (I_a - P_a) mask_a - J_a, 0) rounded once to float32,
+ *                            eps[a] = sum f(psi) (+ col_boundary_const * penalty when amp_cols > 0 and col_boundary_const > 0; amp_cols < 50
+ *                            is then IMCOM_ERR_UNSUPPORTED) in float64, rows in a fixed tree, then in row order.
+ *   imcom_destripe_residual  residual_function 1311-1317, residual_function_single 1375-1403, transpose_interpolate 1001-1023,
+ *                            transpose_par 1026-1058, the derivatives 890-902:  g = f'(psi), term_1 = the row (and column-block) sums of g;
+ *                            g /= g_a N_eff where N_eff != 0, else 0; every target pixel adds its four weighted values times g_b at the
+ *                            corners to the bins of b (gradient_original is never formed).  resids = term_2 - term_1; resids1 = -term_1
+ *                            and resids2 = term_2 when not NULL.  term_2 is summed as fixed-point integers of one scale per call (2^e with
+ *                            n_sca nside^2 max|g| geff_max < 2^(62-e); geff_max >= max g_eff): exact sums of once-rounded terms, the same
+ *                            bits for every order of arrival.
+ *   imcom_destripe_interp / _transpose   the two routines on their own for float64 images: out[i] += the bilinear value of src * gsrc
+ *                            [rows][cols] at (x[i], y[i]); out [rows][cols] += the transposed scatter of image[i]. */
+#define IMCOM_DESTRIPE_QUADRATIC 0
+#define IMCOM_DESTRIPE_ABSOLUTE 1
+#define IMCOM_DESTRIPE_HUBER 2
+int imcom_destripe_sizes(int n_sca, int nside, int ds_rows, int amp_cols, int L, int max_np, int npairs, long *out);
+int imcom_destripe_neff(imcom_ctx *ctx, int n_sca, int nside, int L, const unsigned char *mask, int npairs, const int *pair_a, const int *pair_b,
+                        const void *const *pair_x, const void *const *pair_y, const void *const *pair_lat, const double *W, double *neff);
+int imcom_destripe_cost(imcom_ctx *ctx, int n_sca, int nside, int ds_rows, int amp_cols, int L, const float *image, const unsigned char *mask,
+                        const float *geff, const double *neff, const double *params, int npairs, const int *pair_a, const int *pair_b,
+                        const void *const *pair_x, const void *const *pair_y, const void *const *pair_lat, const double *W, int model, double thresh,
+                        double neff_min, double col_boundary_const, float *psi, double *eps);
+int imcom_destripe_residual(imcom_ctx *ctx, int n_sca, int nside, int ds_rows, int amp_cols, int L, const float *psi, const float *geff, const double *neff,
+                            int npairs, const int *pair_a, const int *pair_b, const void *const *pair_x, const void *const *pair_y,
+                            const void *const *pair_lat, const double *W, int model, double thresh, double geff_max, double *resids, double *resids1,
+                            double *resids2);
+int imcom_destripe_interp(imcom_ctx *ctx, const double *src, const double *gsrc, int rows, int cols, const double *x, const double *y, long npix, double *out);
+int imcom_destripe_interp_transpose(imcom_ctx *ctx, const double *image, const double *x, const double *y, long npix, int rows, int cols, double *out);
+
 #ifdef __cplusplus
 }
 #endif

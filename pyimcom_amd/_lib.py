@@ -141,6 +141,12 @@ SIGNATURES = {
     "imcom_splitpsf_tophat": [_vp, _vp, _i, _i, _d, _vp, _i],
     "imcom_splitpsf_split": [_vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _i],
     "imcom_splitpsf_points": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _i],
+    "imcom_destripe_sizes": [_i, _i, _i, _i, _i, _i, _i, _vp],
+    "imcom_destripe_neff": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "imcom_destripe_cost": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _d, _vp, _vp],
+    "imcom_destripe_residual": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _vp],
+    "imcom_destripe_interp": [_vp, _vp, _vp, _i, _i, _vp, _vp, _l, _vp],
+    "imcom_destripe_interp_transpose": [_vp, _vp, _vp, _vp, _l, _i, _i, _vp],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

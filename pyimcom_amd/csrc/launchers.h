@@ -146,6 +146,32 @@ int launch_imsub_convolve(imcom_ctx *ctx, const float *canvas, int A, long crow0
                           int nside, int first, int y0, int ny, float *image, double *kh);
 int launch_imsub_canvas_add(imcom_ctx *ctx, float *canvas, int A, const double *H, int hh, int hw, const float *area, int s, int row0, int col0);
 
+// destripe.hip
+struct DsPair {            // one ordered pair: neighbour b gathered onto / scattered from target a
+    const double *x, *y;   // positions of a's pixels in b [nside][nside] (column, row), or both null:
+    const double *lat;     // their values on the lattice [2][L][L] (x plane, y plane; row node, column node)
+    int a, b;
+};
+struct DsGeom {
+    int n_sca, nside, ds_rows, amp_cols, ncb, nbins;  // ncb column blocks (0: rows only), nbins = ds_rows + ncb
+    int L, max_np;                                    // lattice nodes per axis (0: no lattice pair), most neighbours of one target
+    int model;
+    double thresh, neff_min, lambda;
+};
+size_t destripe_forward_lds(const DsGeom &g);
+size_t destripe_prep_lds(const DsGeom &g);
+size_t destripe_scatter_lds(const DsGeom &g);
+int launch_destripe_forward(imcom_ctx *ctx, const DsGeom &g, bool make_neff, const float *img, const unsigned char *mask, const float *geff, const double *params,
+                            const DsPair *pairs, const int *start, const double *W, double *neff, float *psi, double *eps_rows);
+int launch_destripe_eps(imcom_ctx *ctx, const DsGeom &g, const float *img, const unsigned char *mask, const double *params, const double *eps_rows, double *pen,
+                        int nchunk, double *eps);
+int launch_destripe_gradient(imcom_ctx *ctx, const DsGeom &g, const float *psi, const float *geff, const double *neff, const DsPair *pairs, int npairs,
+                             const double *W, double gmax_all, double *term1, double *rowcb, unsigned long long *gmax_bits, double *scale,
+                             unsigned long long *bins, double *resids, double *r1, double *r2);
+int launch_destripe_interp(imcom_ctx *ctx, const double *src, const double *gsrc, int rows, int cols, const double *x, const double *y, long npix, double *out);
+int launch_destripe_transpose(imcom_ctx *ctx, const double *img, const double *x, const double *y, long npix, int rows, int cols, unsigned long long *acc,
+                              unsigned long long *bits, double *scale, double *out);
+
 
 // psf_overlap.hip: the plan of the wave-per-line transforms (fft_lines.h) and its stage tables (tw: pl.n complex values, device memory)
 struct FftPlan;

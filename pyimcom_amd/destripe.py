@@ -1,0 +1,315 @@
+"""Destriping on the device: the cost function of ``pyimcom.imdestripe`` and its gradient (reference src/pyimcom/imdestripe.py,
+``cost_function`` 1589-1670 and ``residual_function`` 1231-1327) over a mosaic whose SCAs all stay in device memory.
+
+    eng = DestripeEngine(nside, ds_rows, amp_cols=cfg.amp_cols, col_boundary_const=cfg.col_boundary_const)
+    for sca in all_scas:
+        eng.add_sca(image, mask, g_eff)                  # what Sca_img holds after its masks: float32, bool, float32
+    for a, nb in neighbors.items():
+        for b in nb:
+            eng.set_pair(a, b, x=x_target, y=y_target)   # compareutils.map_sca2sca(wcs_a, wcs_b): positions of a's pixels in b
+    eng.bind(imdestripe)                                 # imdestripe.cost_function / residual_function now run here
+    imdestripe.conjugate_gradient(...)                   # unchanged
+
+The host keeps the files, the masks' construction, the WCS chain, ``get_neighbors`` and the optimiser.  csrc/destripe.hip has the kernels;
+INTEGRATION.md, seam 8, the binding lines and the quirks that are kept."""
+
+import ctypes as C
+
+import numpy as np
+
+from ._lib import ImcomError, check, default_context, lib, ptr
+
+__all__ = ["DestripeEngine", "MODELS", "lattice_nodes", "interpolate_bilinear", "transpose_bilinear", "memory_plan"]
+
+IMCOM_ERR_NOMEM = -3
+IMCOM_ERR_UNSUPPORTED = -4
+MODELS = {"quadratic": 0, "absolute": 1, "huber_loss": 2}
+PRIMES = {"quad_prime": "quadratic", "abs_prime": "absolute", "huber_prime": "huber_loss"}
+FILL = 0.9  # share of the free device memory a mosaic may take
+MAX_L = 33
+
+
+def _is_torch(a):
+    return a is not None and type(a).__module__.startswith("torch")
+
+
+def _unsupported(msg):
+    return ImcomError(IMCOM_ERR_UNSUPPORTED, msg)
+
+
+def lattice_nodes(nside, L=17):
+    """(nodes [L], W [nside, L]): the Chebyshev-Lobatto nodes over the pixel range 0 .. nside - 1 at which a caller evaluates
+    ``map_sca2sca`` for ``set_pair(lattice=)`` (row node i, column node j -> pixel (x, y) = (nodes[j], nodes[i])), and the Lagrange weights
+    of every pixel index."""
+    from .psfs import lattice_nodes_and_weights
+
+    if not 2 <= int(L) <= MAX_L:
+        raise _unsupported(f"destripe: a lattice of {L} nodes per axis (2 <= L <= {MAX_L})")
+    return lattice_nodes_and_weights(np.arange(int(nside), dtype=np.float64), int(L))
+
+
+def model_name(f):
+    """The cost model a function of the reference stands for (``quadratic`` / ``quad_prime`` ...), by ``__name__``; names pass through."""
+    name = f if isinstance(f, str) else getattr(f, "__name__", None)
+    name = PRIMES.get(name, name)
+    if name not in MODELS:
+        raise ValueError(f"destripe: cost model {name!r} is none of {sorted(MODELS)} or their derivatives {sorted(PRIMES)}")
+    return name
+
+
+def memory_plan(n_sca, nside, ds_rows, amp_cols, n_full, n_lattice, L, max_np):
+    """Exact device bytes of a mosaic: n_sca SCAs, ``n_full`` ordered pairs with position arrays, ``n_lattice`` with lattices.  Two psi
+    stacks are counted: the one ``cost`` makes (in ``per_sca``) and one uploaded by ``residual`` when psi comes from the host; the bound
+    ``cost_function`` lets go of its previous psi before it makes the next."""
+    sz = np.zeros(8, dtype=np.int64)
+    check(lib.imcom_destripe_sizes(int(n_sca), int(nside), int(ds_rows), int(amp_cols or 0), int(L if n_lattice else 0), int(max_np),
+                                   int(n_full + n_lattice), ptr(sz)))
+    nbins = int(sz[0])
+    plan = {"nbins": nbins, "per_sca": int(sz[2]), "scas": int(sz[2]) * n_sca, "pairs_full": int(sz[3]) * n_full, "pairs_lattice": int(sz[4]) * n_lattice,
+            "weights": int(sz[7]) if n_lattice else 0, "params_and_resids": 8 * n_sca * nbins * 4 + 8 * n_sca, "workspace": int(max(sz[5], sz[6])),
+            "psi_upload": 4 * n_sca * int(nside) ** 2}  # a psi handed to residual() from the host sits beside the one cost() made
+    plan["total"] = sum(v for k, v in plan.items() if k not in ("nbins", "per_sca"))
+    return plan
+
+
+class DestripeEngine:
+    """The SCAs of one mosaic, their overlaps and the two functions the reference's optimiser calls."""
+
+    def __init__(self, nside, ds_rows, amp_cols=None, col_boundary_const=0, N_eff_min=0.5, context=None, device="cuda:0", ds_model="constant"):
+        self.nside, self.ds_rows = int(nside), int(ds_rows)
+        self.amp_cols = int(amp_cols) if amp_cols is not None and amp_cols > 0 else 0
+        self.col_boundary_const, self.N_eff_min = float(col_boundary_const), float(N_eff_min)
+        if ds_model != "constant":
+            raise _unsupported(f"destripe: ds_model={ds_model!r}: the reference's forward_par cannot broadcast its 2 * ds_rows parameters "
+                               "(imdestripe.py:690-691), there is nothing to be equal to")
+        sz = np.zeros(8, dtype=np.int64)
+        check(lib.imcom_destripe_sizes(1, self.nside, self.ds_rows, self.amp_cols, 0, 0, 0, ptr(sz)))  # the shape refusals
+        if self.amp_cols and self.col_boundary_const > 0 and self.amp_cols < 50:
+            raise _unsupported(f"destripe: the boundary penalty reads 50 columns either side of a boundary, amp_cols={self.amp_cols}")
+        self.nbins, self.n_col_blocks = int(sz[0]), int(sz[1])
+        self._ctx, self._device = context, device
+        self._scas, self._pairs, self.L = [], {}, 0
+        self._frozen = self._tables = None
+        self._last = None  # (host psi, device psi) of the last cost_function call
+
+    # ---- registration (host logic only) ----
+    @property
+    def n_sca(self):
+        return len(self._scas)
+
+    def add_sca(self, image, mask, g_eff):
+        if self._frozen is not None:
+            raise RuntimeError("destripe: the mosaic is already on the device")
+        for arr in (image, mask, g_eff):
+            if tuple(arr.shape) != (self.nside, self.nside):
+                raise ValueError(f"destripe: an array of shape {tuple(arr.shape)}, the SCA is {self.nside} x {self.nside}")
+        self._scas.append((image, mask, g_eff))
+        return len(self._scas) - 1
+
+    def set_pair(self, a, b, x=None, y=None, lattice=None, L=None):
+        a, b = int(a), int(b)
+        if a == b or min(a, b) < 0 or max(a, b) >= self.n_sca:
+            raise ValueError(f"destripe: pair ({a}, {b}) of {self.n_sca} SCAs")
+        if (x is None) != (y is None) or (x is None) == (lattice is None):
+            raise ValueError("destripe: a pair has x= and y=, or lattice=")
+        if lattice is not None:
+            L = int(L if L is not None else lattice.shape[-1])
+            if not 2 <= L <= MAX_L:
+                raise _unsupported(f"destripe: a lattice of {L} nodes per axis (2 <= L <= {MAX_L})")
+            if tuple(lattice.shape) != (2, L, L) or (self.L and L != self.L):
+                raise ValueError(f"destripe: lattice of shape {tuple(lattice.shape)}, expected (2, {self.L or L}, {self.L or L})")
+            self.L = L
+            self._pairs[(a, b)] = ("lattice", lattice)
+        else:
+            if int(np.prod(x.shape)) != self.nside ** 2 or int(np.prod(y.shape)) != self.nside ** 2:
+                raise ValueError(f"destripe: positions of {int(np.prod(x.shape))} pixels, the SCA has {self.nside ** 2}")
+            self._pairs[(a, b)] = ("full", x, y)
+        self._tables = None
+
+    @property
+    def n_pairs(self):
+        return len(self._pairs)
+
+    def neighbors(self):
+        nb = {a: [] for a in range(self.n_sca)}
+        for a, b in sorted(self._pairs):
+            nb[a].append(b)
+        return nb
+
+    def plan(self):
+        n_lat = sum(1 for p in self._pairs.values() if p[0] == "lattice")
+        nb = self.neighbors()
+        return memory_plan(max(self.n_sca, 1), self.nside, self.ds_rows, self.amp_cols, len(self._pairs) - n_lat, n_lat, self.L,
+                           max([len(v) for v in nb.values()] or [0]))
+
+    # ---- device ----
+    def _bind_stream(self):
+        import torch
+
+        self.dev = torch.device(self._device)
+        if self._ctx is None:
+            self._ctx = default_context(self.dev.index or 0)
+        self._ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+        return self._ctx
+
+    def _freeze(self):
+        import torch
+
+        ctx = self._bind_stream()
+        if self._frozen is None:
+            if not self._scas:
+                raise ValueError("destripe: no SCA registered")
+            from .stamps import free_device_bytes
+
+            plan, free = self.plan(), free_device_bytes(self.dev)
+            if plan["total"] > FILL * free:
+                raise ImcomError(IMCOM_ERR_NOMEM, f"destripe: the mosaic needs {plan['total']} bytes on the device, {free} are free "
+                                                   "(streaming SCAs from the host is not served)")
+            n, ns = self.n_sca, self.nside
+            img = torch.empty((n, ns, ns), dtype=torch.float32, device=self.dev)
+            msk = torch.empty((n, ns, ns), dtype=torch.uint8, device=self.dev)
+            gef = torch.empty((n, ns, ns), dtype=torch.float32, device=self.dev)
+            for i, (im, ma, ge) in enumerate(self._scas):
+                img[i].copy_(torch.as_tensor(im if _is_torch(im) else np.ascontiguousarray(im, dtype=np.float32)).to(torch.float32))
+                msk[i].copy_(torch.as_tensor(ma if _is_torch(ma) else np.ascontiguousarray(ma).astype(bool)).to(torch.bool))
+                gef[i].copy_(torch.as_tensor(ge if _is_torch(ge) else np.ascontiguousarray(ge, dtype=np.float32)).to(torch.float32))
+            self._frozen = {"image": img, "mask": msk, "geff": gef, "neff": torch.zeros((n, ns, ns), dtype=torch.float64, device=self.dev),
+                            "gmax": float(gef.abs().max().item())}  # set-up, once: the bound the fixed-point scale of the gradient needs
+            self._scas = [None] * n
+        if self._tables is None:
+            from .stamps import free_device_bytes
+
+            new = sum(sum(v.nbytes if not _is_torch(v) else 0 for v in p[1:]) for p in self._pairs.values())  # pairs not yet on the device
+            if new > FILL * free_device_bytes(self.dev):
+                raise ImcomError(IMCOM_ERR_NOMEM, f"destripe: the pairs registered since the last evaluation need {new} more bytes on the device")
+            keys = sorted(self._pairs)  # the order of the sums: (a, b) ascending, whatever the order of registration
+            keep, px, py, pl = [], [], [], []
+            for k in keys:
+                p = self._pairs[k]
+                if p[0] == "full":
+                    xs = [torch.as_tensor(v if _is_torch(v) else np.ascontiguousarray(v, dtype=np.float64)).to(self.dev, torch.float64).contiguous()
+                          for v in p[1:]]
+                    self._pairs[k] = ("full", xs[0], xs[1])
+                    keep += xs
+                    px.append(xs[0].data_ptr()), py.append(xs[1].data_ptr()), pl.append(0)
+                else:
+                    la = torch.as_tensor(p[1] if _is_torch(p[1]) else np.ascontiguousarray(p[1], dtype=np.float64)).to(self.dev, torch.float64).contiguous()
+                    self._pairs[k] = ("lattice", la)
+                    keep.append(la)
+                    px.append(0), py.append(0), pl.append(la.data_ptr())
+            W = torch.as_tensor(lattice_nodes(self.nside, self.L)[1], device=self.dev) if self.L else None
+            arr = lambda v: np.asarray(v, dtype=np.uint64)  # noqa: E731
+            self._tables = {"n": len(keys), "a": np.asarray([k[0] for k in keys], dtype=np.int32), "b": np.asarray([k[1] for k in keys], dtype=np.int32),
+                            "x": arr(px), "y": arr(py), "lat": arr(pl), "W": W, "keep": keep}
+            t, f = self._tables, self._frozen
+            check(lib.imcom_destripe_neff(ctx.handle, self.n_sca, self.nside, self.L, ptr(f["mask"]), t["n"], ptr(t["a"]), ptr(t["b"]), ptr(t["x"]),
+                                          ptr(t["y"]), ptr(t["lat"]), ptr(W), ptr(f["neff"])))
+        return self._frozen, self._tables
+
+    @property
+    def N_eff(self):
+        return self._freeze()[0]["neff"]
+
+    def _model(self, model, thresh):
+        name = model_name(model)
+        if name == "huber_loss" and thresh is None:
+            raise ValueError("destripe: huber_loss needs a threshold")
+        return MODELS[name], float(thresh) if thresh is not None else 0.0
+
+    def cost(self, params, model="quadratic", thresh=None):
+        """(epsilon, psi): psi a device tensor [n_sca, nside, nside] float32; epsilon the sum of the SCAs' costs in index order."""
+        import torch
+
+        m, th = self._model(model, thresh)
+        f, t = self._freeze()
+        params = torch.as_tensor(params if _is_torch(params) else np.ascontiguousarray(params, dtype=np.float64)).to(self.dev, torch.float64).contiguous()
+        if tuple(params.shape) != (self.n_sca, self.nbins):
+            raise ValueError(f"destripe: params of shape {tuple(params.shape)}, expected {(self.n_sca, self.nbins)}")
+        psi = torch.empty((self.n_sca, self.nside, self.nside), dtype=torch.float32, device=self.dev)
+        eps = torch.empty(self.n_sca, dtype=torch.float64, device=self.dev)
+        check(lib.imcom_destripe_cost(self._ctx.handle, self.n_sca, self.nside, self.ds_rows, self.amp_cols, self.L, ptr(f["image"]), ptr(f["mask"]),
+                                      ptr(f["geff"]), ptr(f["neff"]), ptr(params), t["n"], ptr(t["a"]), ptr(t["b"]), ptr(t["x"]), ptr(t["y"]), ptr(t["lat"]),
+                                      ptr(t["W"]), m, th, self.N_eff_min, self.col_boundary_const, ptr(psi), ptr(eps)))
+        epsilon = 0.0
+        for e in eps.cpu().numpy():  # (the copy waits for the stream: `params` may go)
+            epsilon += float(e)
+        return epsilon, psi
+
+    def residual(self, psi, model="quadratic", thresh=None, extrareturn=False):
+        """resids [n_sca, nbins] float64 (numpy) for the psi of ``cost``; with ``extrareturn`` also -term_1 and term_2 on their own."""
+        import torch
+
+        m, th = self._model(model, thresh)
+        f, t = self._freeze()
+        psi = torch.as_tensor(psi if _is_torch(psi) else np.ascontiguousarray(psi, dtype=np.float32)).to(self.dev, torch.float32).contiguous()
+        if tuple(psi.shape) != (self.n_sca, self.nside, self.nside):
+            raise ValueError(f"destripe: psi of shape {tuple(psi.shape)}")
+        out = torch.empty((3 if extrareturn else 1, self.n_sca, self.nbins), dtype=torch.float64, device=self.dev)
+        check(lib.imcom_destripe_residual(self._ctx.handle, self.n_sca, self.nside, self.ds_rows, self.amp_cols, self.L, ptr(psi), ptr(f["geff"]),
+                                          ptr(f["neff"]), t["n"], ptr(t["a"]), ptr(t["b"]), ptr(t["x"]), ptr(t["y"]), ptr(t["lat"]), ptr(t["W"]), m, th,
+                                          f["gmax"], ptr(out[0]), ptr(out[1]) if extrareturn else None, ptr(out[2]) if extrareturn else None))
+        res = out.cpu().numpy()
+        return (res[0], res[1], res[2]) if extrareturn else res[0]
+
+    # ---- the reference's two functions (signatures and return types of imdestripe.py:1589-1591, 1231-1243) ----
+    def _check_mosaic(self, scalist, neighbors):
+        if len(scalist) != self.n_sca:
+            raise ValueError(f"destripe: {len(scalist)} SCAs in scalist, {self.n_sca} on the device")
+        mine = self.neighbors()
+        if {k: sorted(v) for k, v in neighbors.items() if v} != {k: v for k, v in mine.items() if v}:
+            raise ValueError("destripe: `neighbors` is not the set of pairs registered with set_pair")
+
+    def cost_function(self, p, f, thresh, workers, scalist, neighbors, cfg, tempdir=None, of=None, indata_type="fits"):
+        self._check_mosaic(scalist, neighbors)
+        self._last = None  # the previous psi goes back to the allocator before the next one is made
+        epsilon, psi = self.cost(np.reshape(p.params, (self.n_sca, self.nbins)), model_name(f), thresh)
+        host = psi.cpu().numpy()
+        self._last = (host, psi)
+        return epsilon, host
+
+    def residual_function(self, psi, f_prime, scalist, wcslist, neighbors, thresh, workers, cfg, extrareturn=False, of=None, indata_type="fits"):
+        self._check_mosaic(scalist, neighbors)
+        if self._last is not None and psi is self._last[0]:
+            psi = self._last[1]  # the array cost_function handed out: its device copy is still here
+        return self.residual(psi, model_name(f_prime), thresh, extrareturn=extrareturn)
+
+    def bind(self, module):
+        """Replace ``module.cost_function`` and ``module.residual_function`` (pyimcom.imdestripe) by this engine's."""
+        module.cost_function = self.cost_function
+        module.residual_function = self.residual_function
+        return module
+
+
+def _f64(a, dev):
+    import torch
+
+    return torch.as_tensor(a if _is_torch(a) else np.ascontiguousarray(a, dtype=np.float64)).to(dev, torch.float64).contiguous()
+
+
+def interpolate_bilinear(image, g_eff, x, y, out=None, device="cuda:0", ctx=None):
+    """``bilinear_interpolation(image, g_eff, coords, out)`` as imdestripe.py:972-998 calls it, coords = (y, x) columns: out (flat order of
+    x, y) += the bilinear value of image * g_eff.  float64 in and out; returns a device tensor of x's shape."""
+    import torch
+
+    dev = torch.device(device)
+    ctx = ctx or default_context(dev.index or 0)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    src, gs, xs, ys = (_f64(v, dev) for v in (image, g_eff, x, y))
+    res = torch.zeros(xs.shape, dtype=torch.float64, device=dev) if out is None else _f64(out, dev).clone()
+    check(lib.imcom_destripe_interp(ctx.handle, ptr(src), ptr(gs), int(src.shape[0]), int(src.shape[1]), ptr(xs), ptr(ys), C.c_long(xs.numel()), ptr(res)))
+    torch.cuda.current_stream(dev).synchronize()
+    return res
+
+
+def transpose_bilinear(image, x, y, shape, device="cuda:0", ctx=None):
+    """``bilinear_transpose(image, coords, original_image)`` (imdestripe.py:1001-1023) into a zero image of ``shape``."""
+    import torch
+
+    dev = torch.device(device)
+    ctx = ctx or default_context(dev.index or 0)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    img, xs, ys = (_f64(v, dev) for v in (image, x, y))
+    res = torch.zeros(tuple(shape), dtype=torch.float64, device=dev)
+    check(lib.imcom_destripe_interp_transpose(ctx.handle, ptr(img), ptr(xs), ptr(ys), C.c_long(img.numel()), int(shape[0]), int(shape[1]), ptr(res)))
+    torch.cuda.current_stream(dev).synchronize()
+    return res
