@@ -651,6 +651,37 @@ int imcom_destripe_residual(imcom_ctx *ctx, int n_sca, int nside, int ds_rows, i
 int imcom_destripe_interp(imcom_ctx *ctx, const double *src, const double *gsrc, int rows, int cols, const double *x, const double *y, long npix, double *out);
 int imcom_destripe_interp_transpose(imcom_ctx *ctx, const double *image, const double *x, const double *y, long npix, int rows, int cols, double *out);
 
+/* Noise power spectra of coadded frames (reference src/pyimcom/analysis.py, NoiseAnal.__call__ 745-807 and the loop of
+ * _BlkGrp.get_noise_power_spectra 1270-1303; src/pyimcom/diagnostics/noise_diagnostics.py, NoiseReport.measure_power_spectrum 400-443 and
+ * azimuthal_average 472-506).  Frames are real, of even side L <= 4096, float32 or float64 (in_f64); the arithmetic is float64 throughout.
+ * A frame's result depends on that frame only (rows 2j, 2j+1 of ONE frame ride as a complex line), every output element has one owner
+ * thread and a fixed summation order: the same bits from run to run and however frames are grouped into calls.  Routes of the line
+ * transforms: 1 the wave-per-line butterflies (L <= 1024 a product of 2, 3, 5), 3 two-level (L = N1 N2, N1 a butterfly side, 2 <= N2 <= 16:
+ * 2560 = 640 x 4, 2688 = 384 x 7), 2 the dense DFT on the fp64 MFMA tile engine (every other side; IMCOM_NOISEPS_ROUTE=dense in the
+ * environment forces it).  IMCOM_ERR_ARG: L odd, L % 8 != 0 with bin8, L > 4096, a window that is not L x L, a route that does not serve L.
+ *   imcom_noiseps_route      the route of side L (0: not served).  Returns the route, not a status.
+ *   imcom_noiseps_sizes      out[4] = {route served (argument route = 0: the plan's choice), side of an output frame (L / 8 with bin8, else L),
+ *                            workspace bytes of imcom_noiseps_2d for nframe frames with device pointers, bytes of one frame's half spectrum}.
+ *   imcom_noiseps_2d         analysis.py:789-794 / noise_diagnostics.py:430-441: out[f][ky][kx] = |F_f[(ky - L/2) mod L][(kx - L/2) mod L]|^2
+ *                            / norm[f], F_f the 2-D transform of frame f times `window` (NULL: none; window_len = its element count, L L),
+ *                            i.e. the fftshift-ed full spectrum, its missing half by Hermitian symmetry; with bin8 the 8 x 8 averages (sum,
+ *                            then one division by 64), out [nframe][L/8][L/8], else [nframe][L][L].  Element (f, y, x) of `frames` is at
+ *                            f fstride + y rstride + x (in elements): a cropped view of a larger block is read in place.  norm [nframe] is a
+ *                            HOST array whatever `memspace` says; with a window the caller passes norm * mean(window^2) (432).
+ *   imcom_noiseps_radial     analysis.py:699-702 (ndimage.mean, standard_deviation, sum over labels): for index i = 1 .. nidx of the int32
+ *                            labels rbin [n][n], mean[f][i-1] over the pixels of image [nframe][n][n] with that label and err[f][i-1] =
+ *                            sqrt(sum (x - mean)^2 / npix) / sqrt(npix), two passes.  One pixel: err = 0 exactly; none: NaN (as ndimage).
+ *   imcom_noiseps_accumulate analysis.py:1278-1279 on the device, in call order: ps2d_all [nlayers][n][n] += ps2d [nlayers][n][n];
+ *                            ps1d_all [nlayers][bins][nrad][2] at coverage_bin += (mean, err) [nlayers][nrad].  DEVICE memory throughout.
+ *   frames, window, out, image, rbin, mean and err follow `memspace`. */
+int imcom_noiseps_route(int L);
+int imcom_noiseps_sizes(int L, int nframe, int bin8, int route, long *out);
+int imcom_noiseps_2d(imcom_ctx *ctx, const void *frames, int in_f64, int nframe, int L, long fstride, long rstride, const double *window, long window_len,
+                     const double *norm, int bin8, int route, double *out, int memspace);
+int imcom_noiseps_radial(imcom_ctx *ctx, const double *image, int nframe, int n, const int *rbin, int nidx, double *mean, double *err, int memspace);
+int imcom_noiseps_accumulate(imcom_ctx *ctx, const double *ps2d, const double *mean, const double *err, int nlayers, int n, int nrad, int bins, int coverage_bin,
+                             double *ps2d_all, double *ps1d_all);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,11 @@ SIGNATURES = {
     "imcom_destripe_residual": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _vp],
     "imcom_destripe_interp": [_vp, _vp, _vp, _i, _i, _vp, _vp, _l, _vp],
     "imcom_destripe_interp_transpose": [_vp, _vp, _vp, _vp, _l, _i, _i, _vp],
+    "imcom_noiseps_route": [_i],
+    "imcom_noiseps_sizes": [_i, _i, _i, _i, _vp],
+    "imcom_noiseps_2d": [_vp, _vp, _i, _i, _i, _l, _l, _vp, _l, _vp, _i, _i, _vp, _i],
+    "imcom_noiseps_radial": [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i],
+    "imcom_noiseps_accumulate": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

@@ -155,3 +155,22 @@ class BlockMaps:
         pads = [w * (s not in pad_sides) for s in "BTLR"]
         for m in self.maps.values():
             check(lib.imcom_trapezoid_recover_f32(h, ptr(m), self.n_out, self.nside, self.nside, self.fade, *pads))
+
+    def noise_spectrum(self, layer_indices, pad, norm, out=0, window=None, bin8=True):
+        """The noise power spectra of input layers of this block without a copy to the host (``pyimcom_amd.noisespec``; reference
+        analysis.py:776-794): layer ``i`` of ``layer_indices`` is ``out_map[out, i]`` cropped by the fade margin plus ``pad`` pixels (the
+        reference's ``n2 * postage_pad``; 0 keeps the padding stamps) and then to a multiple of 8, read in place.  ``norm``: a number or
+        one per layer; ``window``: float64 [Lcut, Lcut] or None.  Returns float64 [len(layer_indices), Lcut/8, Lcut/8] (``bin8``) on the
+        device.  Call it after ``finalize``."""
+        from .noisespec import power_spectrum_2d
+
+        idx = [int(i) for i in layer_indices]
+        c = self.fade + int(pad)
+        side = self.nside - 2 * c
+        lcut = side // 8 * 8 if bin8 else side // 2 * 2
+        norms = np.broadcast_to(np.asarray(norm, dtype=np.float64), (len(idx),))
+        view = self.out_map[out][:, c:c + lcut, c:c + lcut]
+        step = idx[1] - idx[0] if len(idx) > 1 else 1
+        if step > 0 and all(b - a == step for a, b in zip(idx, idx[1:])):  # one call: the layers are evenly strided frames of the view
+            return power_spectrum_2d(view[idx[0]:idx[-1] + 1:step], norms, window, bin8, ctx=self.ctx)
+        return torch.cat([power_spectrum_2d(view[i:i + 1], norms[k:k + 1], window, bin8, ctx=self.ctx) for k, i in enumerate(idx)])

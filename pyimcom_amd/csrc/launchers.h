@@ -190,5 +190,25 @@ int launch_splitpsf_split(imcom_ctx *ctx, const double *cube, int npoly, int n, 
 size_t splitpsf_points_ws(int n, int nsca, int npts, bool own_kreal);
 int launch_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npoly, int n, int i0, int npts, const double *lpw, const double *wg,
                            const double *cov, double eps, double *KL, double *K_real, double *zeta, double *zmax);
+// its dense-DFT line engine (route 2) for other callers: plan / take the DFT matrix (forward, and inverse if asked), the packed lines A and
+// the product C; after splitpsf_dense_product row l of d.C (stride d.Np doubles) holds the transform of line l of `in`, interleaved (re, im)
+struct SpDense {
+    int N = 0, Kp = 0, Np = 0;
+    long Mp = 0;  // padded line count of the largest batch
+    double *Mf = nullptr, *Mi = nullptr, *A = nullptr, *C = nullptr;
+};
+void splitpsf_dense_plan(SpDense &d, int N, long nlines, bool inverse, WsPlan &plan);
+int splitpsf_dense_take(imcom_ctx *ctx, SpDense &d, bool inverse, const char *who);
+int splitpsf_dense_product(imcom_ctx *ctx, const SpDense &d, const double2 *in, long nlines, bool inv);
+
+// noisespec.hip: noise power spectra of coadded frames
+constexpr int NOISEPS_ROUTE_NONE = 0, NOISEPS_ROUTE_LINES = 1, NOISEPS_ROUTE_DENSE = 2, NOISEPS_ROUTE_TWOLEVEL = 3;
+int noiseps_route(int L, bool force_dense);  // force_dense: IMCOM_NOISEPS_ROUTE=dense (the caller reads the environment)
+size_t noiseps_ws(int L, int nframe, int route);
+int launch_noiseps_2d(imcom_ctx *ctx, const void *frames, bool in_f64, int nframe, int L, long fstride, long rstride, const double *window,
+                      const double *norm_dev, bool bin8, int route, double *out);
+int launch_noiseps_radial(imcom_ctx *ctx, const double *image, int nframe, int n, const int *rbin, int nidx, double *mean, double *err);
+int launch_noiseps_accumulate(imcom_ctx *ctx, const double *ps2d, const double *mean, const double *err, int nlayers, long npix, int nrad, int bins,
+                              int coverage_bin, double *ps2d_all, double *ps1d_all);
 
 }  // namespace imcom

@@ -95,13 +95,47 @@ __global__ void sp_dense_transpose_kernel(const double *__restrict__ C, int N, i
     if (k0 + ty < N && y0 + tx < N) out[(b * N + k0 + ty) * N + y0 + tx] = tile[tx][ty];
 }
 
+// route 2 on its own (launchers.h: noisespec.hip runs its lines through it too): the tables and buffers of the dense DFT of lines of
+// length N, and the product -- row l of d.C (stride d.Np doubles) = the transform of line l, interleaved (re, im)
+void splitpsf_dense_plan(SpDense &d, int N, long nlines, bool inverse, WsPlan &plan)
+{
+    d.N = N;
+    d.Kp = up(2 * N, 16);
+    d.Np = up(2 * N, NB);
+    d.Mp = (nlines + NB - 1) / NB * NB;
+    plan.add((size_t)d.Kp * d.Np * 8);
+    if (inverse) plan.add((size_t)d.Kp * d.Np * 8);
+    plan.add((size_t)d.Mp * d.Kp * 8);
+    plan.add((size_t)d.Mp * d.Np * 8);
+}
+
+int splitpsf_dense_take(imcom_ctx *ctx, SpDense &d, bool inverse, const char *who)
+{
+    IMCOM_TRY(ws_take(ctx, (size_t)d.Kp * d.Np, &d.Mf, who));
+    if (inverse) IMCOM_TRY(ws_take(ctx, (size_t)d.Kp * d.Np, &d.Mi, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)d.Mp * d.Kp, &d.A, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)d.Mp * d.Np, &d.C, who));
+    hipLaunchKernelGGL(sp_dft_matrix_kernel, dim3((d.Np + 255) / 256, d.Kp), dim3(256), 0, ctx->stream, d.N, d.Kp, d.Np, 0, d.Mf);
+    if (inverse) hipLaunchKernelGGL(sp_dft_matrix_kernel, dim3((d.Np + 255) / 256, d.Kp), dim3(256), 0, ctx->stream, d.N, d.Kp, d.Np, 1, d.Mi);
+    return check_launch("sp_dft_matrix_kernel");
+}
+
+int splitpsf_dense_product(imcom_ctx *ctx, const SpDense &d, const cplx *in, long nlines, bool inv)
+{
+    const long Mp = (nlines + NB - 1) / NB * NB;
+    IMCOM_REQUIRE(Mp <= d.Mp && Mp <= 0x7fffffffL && (!inv || d.Mi), "internal: splitpsf dense batch of %ld lines", nlines);
+    hipLaunchKernelGGL(sp_dense_pack_kernel, dim3((d.Kp + 255) / 256, (unsigned)std::min<long>(Mp, 65535), (unsigned)((Mp + 65534) / 65535)), dim3(256), 0,
+                       ctx->stream, (const double *)in, nlines, Mp, 2 * d.N, d.Kp, d.A);
+    IMCOM_TRY(check_launch("sp_dense_pack_kernel"));
+    return launch_gemm(ctx, false, true, (int)Mp, d.Np, d.Kp, 1, d.A, d.Kp, 0, inv ? d.Mi : d.Mf, d.Np, 0, d.C, d.Np, 0, 1.0, 0.0);
+}
+
 // what one 2-D transform engine needs out of the workspace, and the engine itself
 struct SpFft {
-    int N = 0, route = 0, Kp = 0, Np = 0;
-    long Mp = 0;  // dense: padded line count of the largest batch
+    int N = 0, route = 0;
+    SpDense d;
     FftPlan pl;
     cplx *tw = nullptr;
-    double *Mf = nullptr, *Mi = nullptr, *A = nullptr, *C = nullptr;
 };
 
 static void sp_fft_plan(SpFft &f, int N, long planes, WsPlan &plan)
@@ -112,13 +146,7 @@ static void sp_fft_plan(SpFft &f, int N, long planes, WsPlan &plan)
         fft_line_plan(N, &f.pl);
         plan.add((size_t)N * 16);
     } else {
-        f.Kp = up(2 * N, 16);
-        f.Np = up(2 * N, NB);
-        f.Mp = (planes * N + NB - 1) / NB * NB;
-        plan.add((size_t)f.Kp * f.Np * 8);
-        plan.add((size_t)f.Kp * f.Np * 8);
-        plan.add((size_t)f.Mp * f.Kp * 8);
-        plan.add((size_t)f.Mp * f.Np * 8);
+        splitpsf_dense_plan(f.d, N, planes * N, true, plan);
     }
 }
 
@@ -134,13 +162,7 @@ static int sp_fft_take(imcom_ctx *ctx, SpFft &f, const char *who)
         }
         return IMCOM_OK;
     }
-    IMCOM_TRY(ws_take(ctx, (size_t)f.Kp * f.Np, &f.Mf, who));
-    IMCOM_TRY(ws_take(ctx, (size_t)f.Kp * f.Np, &f.Mi, who));
-    IMCOM_TRY(ws_take(ctx, (size_t)f.Mp * f.Kp, &f.A, who));
-    IMCOM_TRY(ws_take(ctx, (size_t)f.Mp * f.Np, &f.C, who));
-    hipLaunchKernelGGL(sp_dft_matrix_kernel, dim3((f.Np + 255) / 256, f.Kp), dim3(256), 0, ctx->stream, f.N, f.Kp, f.Np, 0, f.Mf);
-    hipLaunchKernelGGL(sp_dft_matrix_kernel, dim3((f.Np + 255) / 256, f.Kp), dim3(256), 0, ctx->stream, f.N, f.Kp, f.Np, 1, f.Mi);
-    return check_launch("sp_dft_matrix_kernel");
+    return splitpsf_dense_take(ctx, f.d, true, who);
 }
 
 // one pass: the lines of `planes` planes of `in`, transformed, into `out` transposed
@@ -156,13 +178,8 @@ static int sp_lines_T(imcom_ctx *ctx, const SpFft &f, const cplx *in, cplx *out,
         else hipLaunchKernelGGL(sp_lines_kernel<false>, dim3(grid), dim3(64 * W), lds, ctx->stream, in, out, nlines, f.pl, (const cplx *)f.tw);
         return check_launch("sp_lines_kernel");
     }
-    const long Mp = (nlines + NB - 1) / NB * NB;
-    IMCOM_REQUIRE(Mp <= f.Mp && Mp <= 0x7fffffffL, "internal: splitpsf dense batch of %ld lines", nlines);
-    hipLaunchKernelGGL(sp_dense_pack_kernel, dim3((f.Kp + 255) / 256, (unsigned)std::min<long>(Mp, 65535), (unsigned)((Mp + 65534) / 65535)), dim3(256), 0,
-                       ctx->stream, (const double *)in, nlines, Mp, 2 * N, f.Kp, f.A);
-    IMCOM_TRY(check_launch("sp_dense_pack_kernel"));
-    IMCOM_TRY(launch_gemm(ctx, false, true, (int)Mp, f.Np, f.Kp, 1, f.A, f.Kp, 0, inv ? f.Mi : f.Mf, f.Np, 0, f.C, f.Np, 0, 1.0, 0.0));
-    hipLaunchKernelGGL(sp_dense_transpose_kernel, dim3((N + 15) / 16, (N + 15) / 16, (unsigned)planes), dim3(16, 16), 0, ctx->stream, (const double *)f.C, N, f.Np,
+    IMCOM_TRY(splitpsf_dense_product(ctx, f.d, in, nlines, inv));
+    hipLaunchKernelGGL(sp_dense_transpose_kernel, dim3((N + 15) / 16, (N + 15) / 16, (unsigned)planes), dim3(16, 16), 0, ctx->stream, (const double *)f.d.C, N, f.d.Np,
                        out);
     return check_launch("sp_dense_transpose_kernel");
 }
