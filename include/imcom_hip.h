@@ -682,6 +682,31 @@ int imcom_noiseps_radial(imcom_ctx *ctx, const double *image, int nframe, int n,
 int imcom_noiseps_accumulate(imcom_ctx *ctx, const double *ps2d, const double *mean, const double *err, int nlayers, int n, int nrad, int bins, int coverage_bin,
                              double *ps2d_all, double *ps1d_all);
 
+/* Draws of numpy's PCG64 stream by position, and the simulated cosmic-ray mask made of them (reference src/pyimcom/layer.py:933-964,
+ * Mask.randmask; 1071-1077, the lab-noise threshold of Mask.load_cr_mask; 313-401, GalSimInject.subgen / subgen_multirow).  The stream is
+ * given as numpy reports it, np.random.PCG64(seed).state["state"]: `state` and `inc`, each as its low and high 64 bits; seeding stays
+ * numpy's.  U[k], k = 0, 1, ..., is the double that Generator.random() / uniform() returns as draw k + 1 from that state: the state moved
+ * k + 1 steps of s <- 0x2360ED051FC65DA44385DF649FCCF645 s + inc (mod 2^128), the output rotr64(hi ^ lo, s >> 122), and (output >> 11)
+ * 2^-53.  Integer arithmetic until that one exact conversion: every result equals numpy's bit for bit, whatever the count, the offset
+ * and the memspace.  Only draws that consume one 64-bit output each are served: normal, Poisson and bounded-integer draws are not.
+ *   imcom_pcg64_uniform     out[i] = U[offset + i], i < count; offset = offset_hi 2^64 + offset_lo.  IMCOM_ERR_ARG: count < 0.
+ *   imcom_pcg64_uniform_at  out[i] = U[pos[i]], i < count; pos int64 in any order (an entry below 0 counts as its value mod 2^64).
+ *   imcom_cr_mask           Mask.randmask: pixel (r, c) of slice `slice` (idsca[1] - 1) of the padded draw [n_slices][W][W], W = nside +
+ *                           2 pad (the reference: n_slices 18, pad 10, nside 4088), is U[slice W^2 + r W + c]; it is a hit when
+ *                           U < pcut (float64).  mask [nside][nside] uint8: 1 where none of the nine padded pixels around (y + pad,
+ *                           x + pad) is a hit, else 0.  With labnoise [nside][nside] float32 (NULL: none) also layer.py:1076: mask &=
+ *                           |labnoise| < threshold, compared in float64 (the caller rounds `threshold` to the type numpy would compare
+ *                           in; a NaN pixel is masked).  *ngood: the number of 1s.  No image of draws is formed: hits live in LDS.
+ *                           IMCOM_ERR_ARG: nside outside 1 .. 65536, pad outside 1 .. 4096, n_slices outside 1 .. 65536, slice outside
+ *                           0 .. n_slices - 1.
+ *   pos, out, labnoise, mask and ngood follow `memspace`. */
+int imcom_pcg64_uniform(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                        long count, double *out, int memspace);
+int imcom_pcg64_uniform_at(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, const long *pos, long count, double *out,
+                           int memspace);
+int imcom_cr_mask(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, int nside, int pad, int slice, int n_slices,
+                  double pcut, const float *labnoise, double threshold, unsigned char *mask, long *ngood, int memspace);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,7 @@ def ptr(a):
 
 _vp, _i, _l, _d = C.c_void_p, C.c_int, C.c_long, C.c_double
 _ip = C.POINTER(C.c_int)
+_u64 = C.c_uint64
 
 # name -> argtypes; every function returns int status except the two noted below
 SIGNATURES = {
@@ -152,6 +153,9 @@ SIGNATURES = {
     "imcom_noiseps_2d": [_vp, _vp, _i, _i, _i, _l, _l, _vp, _l, _vp, _i, _i, _vp, _i],
     "imcom_noiseps_radial": [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i],
     "imcom_noiseps_accumulate": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
+    "imcom_pcg64_uniform": [_vp, _u64, _u64, _u64, _u64, _u64, _u64, _l, _vp, _i],
+    "imcom_pcg64_uniform_at": [_vp, _u64, _u64, _u64, _u64, _vp, _l, _vp, _i],
+    "imcom_cr_mask": [_vp, _u64, _u64, _u64, _u64, _i, _i, _i, _i, _d, _vp, _d, _vp, _vp, _i],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

@@ -211,4 +211,13 @@ int launch_noiseps_radial(imcom_ctx *ctx, const double *image, int nframe, int n
 int launch_noiseps_accumulate(imcom_ctx *ctx, const double *ps2d, const double *mean, const double *err, int nlayers, long npix, int nrad, int bins,
                               int coverage_bin, double *ps2d_all, double *ps1d_all);
 
+// pcg64.hip: draws of numpy's PCG64 stream by position, and the cosmic-ray mask made of them.  state / offset: (low, high) halves;
+// jumps [PCG64_JUMPS][2][2]: the (low, high) halves of A_j and C_j, the affine map of 2^j steps for the stream's increment (device memory)
+constexpr int PCG64_JUMPS = 128;
+int launch_pcg64_uniform(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const unsigned long long offset[2], long count,
+                         double *out);
+int launch_pcg64_uniform_at(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const long *pos, long count, double *out);
+int launch_cr_mask(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, unsigned long long base, int nside, int pad, double pcut,
+                   const float *labnoise, double threshold, unsigned char *mask, unsigned long long *ngood);
+
 }  // namespace imcom
