@@ -707,6 +707,44 @@ int imcom_pcg64_uniform_at(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi,
 int imcom_cr_mask(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, int nside, int pad, int slice, int n_slices,
                   double pcut, const float *labnoise, double threshold, unsigned char *mask, long *ngood, int memspace);
 
+/* Bright-object masks of the destripe set-up (reference src/pyimcom/imdestripe.py:781-872, apply_object_mask; its caller
+ * Sca_img.__init__ 317-332; apply_jwst_mask 412-419 needs no entry).  Images are float32 or float64 (is_f64), masks and flags uint8 with
+ * one byte a pixel (0 / not 0 in, 0 / 1 out).  Every result is a boolean image, a count or an order statistic, formed from comparisons
+ * and integer sums: equal to numpy / scipy bit for bit and the same from run to run.  The scalar steps between the calls (817, 834, 845,
+ * 852-853, 863: thresholds, 1.4826 mad, the max() and the breaks) are the caller's, in numpy scalars.
+ *   imcom_select_kth      np.median / np.partition (817, 832-833, 842-843): order statistics k and min(k + 1, m - 1) of the m values whose
+ *                         flag is not 0 (flags NULL: all n), or with k < 0 the two middle ones, ranks (m - 1) / 2 and m / 2, whose mean in
+ *                         the array's type is the median.  use_abs: of |v - c| instead, formed in the array's type and never stored
+ *                         (the MAD, 833).  NaNs sort last; a rank among them gives NaN.  -0.0 and 0.0 are one value (0.0 is returned).
+ *                         out: two values of the array's type; info[2] = {m, number of NaNs among them}; m = 0 gives NaNs.
+ *                         Radix select on order-preserving integer keys, digits of 11 bits, histograms in LDS merged with integer adds.
+ *                         IMCOM_ERR_ARG: n < 1, k >= n.
+ *   imcom_mask_threshold  855-856 and 863: seed = ok && (v - bkg) >= t_seed, and with grow != NULL grow = ok && (v - bkg) >= t_grow in the
+ *                         same pass; ok = isfinite(v) with finite_only, else true (863 has no such test: bkg = 0 there).  v - bkg in the
+ *                         array's type; the comparison in float64, which is exact for either type (the caller rounds a threshold to
+ *                         the type numpy would compare in).
+ *   imcom_mask_clip       820 and 837-840: keep_out = keep_in && |v - bkg| < t, or with keep_in NULL keep_out = isfinite(v);
+ *                         *count = the number kept.  keep_out may be keep_in.  The reference's clip_vals[keep] is cumulative, so the
+ *                         flags of round i + 1 made from those of round i are its subset.
+ *   imcom_mask_propagate  857, scipy.ndimage.binary_propagation(seed, mask=grow), default structure (4-connectivity), border 0: out = seed
+ *                         plus every grow pixel joined to it by a 4-connected path of grow pixels.  Tiles of 62 x 62 pixels are grown to
+ *                         their own fixpoint in LDS; sweeps repeat while one of them changed (*sweeps, a HOST long or NULL: how many
+ *                         ran).  No workgroup waits for another; the fixpoint is unique.  out may be seed, not grow.
+ *   imcom_mask_dilate     858-860 and 865, binary_dilation with a (2 r + 1) x (2 r + 1) structure of ones, border 0.  3 x 3 twice and then
+ *                         5 x 5 is r = 4.  IMCOM_ERR_UNSUPPORTED: r outside 1 .. 8.  IMCOM_ERR_ARG: out == in.
+ *   imcom_mask_apply      867-872, out = mask ? 0 : in over n elements of dtype 0 float32, 1 float64, 2 uint8 (330-332: sca_mask &=
+ *                         ~object_mask is dtype 2 with in = out = the SCA's mask).  out may be in.
+ *   Every array follows `memspace`.  Workspace: the selection's state and histograms (33 KB); the second image of the propagation. */
+int imcom_select_kth(imcom_ctx *ctx, const void *values, int is_f64, long n, const unsigned char *flags, int use_abs, double c, long k, void *out, long *info,
+                     int memspace);
+int imcom_mask_threshold(imcom_ctx *ctx, const void *image, int is_f64, long n, double bkg, double t_seed, double t_grow, int finite_only, unsigned char *seed,
+                         unsigned char *grow, int memspace);
+int imcom_mask_clip(imcom_ctx *ctx, const void *image, int is_f64, long n, const unsigned char *keep_in, double bkg, double t, unsigned char *keep_out, long *count,
+                    int memspace);
+int imcom_mask_propagate(imcom_ctx *ctx, const unsigned char *seed, const unsigned char *grow, int rows, int cols, unsigned char *out, long *sweeps, int memspace);
+int imcom_mask_dilate(imcom_ctx *ctx, const unsigned char *in, int rows, int cols, int r, unsigned char *out, int memspace);
+int imcom_mask_apply(imcom_ctx *ctx, const void *in, int dtype, const unsigned char *mask, long n, void *out, int memspace);
+
 #ifdef __cplusplus
 }
 #endif

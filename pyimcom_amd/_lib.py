@@ -156,6 +156,12 @@ SIGNATURES = {
     "imcom_pcg64_uniform": [_vp, _u64, _u64, _u64, _u64, _u64, _u64, _l, _vp, _i],
     "imcom_pcg64_uniform_at": [_vp, _u64, _u64, _u64, _u64, _vp, _l, _vp, _i],
     "imcom_cr_mask": [_vp, _u64, _u64, _u64, _u64, _i, _i, _i, _i, _d, _vp, _d, _vp, _vp, _i],
+    "imcom_select_kth": [_vp, _vp, _i, _l, _vp, _i, _d, _l, _vp, _vp, _i],
+    "imcom_mask_threshold": [_vp, _vp, _i, _l, _d, _d, _d, _i, _vp, _vp, _i],
+    "imcom_mask_clip": [_vp, _vp, _i, _l, _vp, _d, _d, _vp, _vp, _i],
+    "imcom_mask_propagate": [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(_l), _i],
+    "imcom_mask_dilate": [_vp, _vp, _i, _i, _i, _vp, _i],
+    "imcom_mask_apply": [_vp, _vp, _i, _vp, _l, _vp, _i],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

@@ -220,4 +220,18 @@ int launch_pcg64_uniform_at(imcom_ctx *ctx, const unsigned long long state[2], c
 int launch_cr_mask(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, unsigned long long base, int nside, int pad, double pcut,
                    const float *labnoise, double threshold, unsigned char *mask, unsigned long long *ngood);
 
+// objmask.hip: exact order statistics, threshold / clipping flags, constrained propagation, box dilation and application of a mask
+constexpr int SELECT_BINS = 2048, SELECT_STATE = 8;  // histogram bins of a pass (two histograms); words of the selection state
+constexpr int MASK_DILATE_TX = 48, MASK_DILATE_TY = 32, MASK_DILATE_MAX_R = 8;  // output pixels of a dilation workgroup; largest radius
+constexpr int MASK_PROPAGATE_T = 62;                                            // side of a propagation tile
+int launch_select_kth(imcom_ctx *ctx, const void *vals, bool f64, const unsigned char *flags, long n, bool use_abs, double c, long k, unsigned long long *state,
+                      unsigned long long *hist, void *res, long *info);
+int launch_mask_threshold(imcom_ctx *ctx, const void *img, bool f64, long n, double bkg, double t1, double t2, bool finite_only, unsigned char *m1,
+                          unsigned char *m2);
+int launch_mask_clip(imcom_ctx *ctx, const void *img, bool f64, long n, const unsigned char *keep_in, double bkg, double t, unsigned char *keep_out,
+                     unsigned long long *count);
+int launch_mask_apply(imcom_ctx *ctx, const void *in, int dtype, const unsigned char *mask, long n, void *out);
+int launch_mask_dilate(imcom_ctx *ctx, const unsigned char *in, int H, int W, int r, unsigned char *out);
+int launch_mask_propagate(imcom_ctx *ctx, const unsigned char *grow, int H, int W, unsigned char *out, unsigned char *tmp, unsigned int *changed, long *sweeps);
+
 }  // namespace imcom

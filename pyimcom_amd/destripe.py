@@ -57,10 +57,11 @@ def model_name(f):
     return name
 
 
-def memory_plan(n_sca, nside, ds_rows, amp_cols, n_full, n_lattice, L, max_np):
+def memory_plan(n_sca, nside, ds_rows, amp_cols, n_full, n_lattice, L, max_np, objmask_setup=0):
     """Exact device bytes of a mosaic: n_sca SCAs, ``n_full`` ordered pairs with position arrays, ``n_lattice`` with lattices.  Two psi
     stacks are counted: the one ``cost`` makes (in ``per_sca``) and one uploaded by ``residual`` when psi comes from the host; the bound
-    ``cost_function`` lets go of its previous psi before it makes the next."""
+    ``cost_function`` lets go of its previous psi before it makes the next.  ``objmask_setup``: the temporaries of the object mask of ONE
+    SCA (``objmask.setup_bytes``), a peak during set-up that is not there per SCA; 0 when no SCA asks for one."""
     sz = np.zeros(8, dtype=np.int64)
     check(lib.imcom_destripe_sizes(int(n_sca), int(nside), int(ds_rows), int(amp_cols or 0), int(L if n_lattice else 0), int(max_np),
                                    int(n_full + n_lattice), ptr(sz)))
@@ -68,6 +69,8 @@ def memory_plan(n_sca, nside, ds_rows, amp_cols, n_full, n_lattice, L, max_np):
     plan = {"nbins": nbins, "per_sca": int(sz[2]), "scas": int(sz[2]) * n_sca, "pairs_full": int(sz[3]) * n_full, "pairs_lattice": int(sz[4]) * n_lattice,
             "weights": int(sz[7]) if n_lattice else 0, "params_and_resids": 8 * n_sca * nbins * 4 + 8 * n_sca, "workspace": int(max(sz[5], sz[6])),
             "psi_upload": 4 * n_sca * int(nside) ** 2}  # a psi handed to residual() from the host sits beside the one cost() made
+    if objmask_setup:
+        plan["objmask_setup"] = int(objmask_setup)
     plan["total"] = sum(v for k, v in plan.items() if k not in ("nbins", "per_sca"))
     return plan
 
@@ -97,13 +100,21 @@ class DestripeEngine:
     def n_sca(self):
         return len(self._scas)
 
-    def add_sca(self, image, mask, g_eff):
+    def add_sca(self, image, mask, g_eff, object_mask=None):
+        """``object_mask=(threshold_m, threshold_c, type)``: what ``Sca_img.__init__`` does after its masks (imdestripe.py:324-332) happens
+        on the device when the mosaic is uploaded -- ``apply_object_mask`` of the image in its own type (float32 or float64), its
+        complement and-ed into ``mask``.  The image itself is not zeroed: the reference discards ``image_out`` there."""
         if self._frozen is not None:
             raise RuntimeError("destripe: the mosaic is already on the device")
         for arr in (image, mask, g_eff):
             if tuple(arr.shape) != (self.nside, self.nside):
                 raise ValueError(f"destripe: an array of shape {tuple(arr.shape)}, the SCA is {self.nside} x {self.nside}")
-        self._scas.append((image, mask, g_eff))
+        if object_mask is not None:
+            threshold_m, threshold_c, kind = object_mask
+            if "float32" not in str(image.dtype) and "float64" not in str(image.dtype):
+                raise TypeError(f"destripe: the object mask is made of a float32 or float64 image, not {image.dtype}")
+            object_mask = (threshold_m, threshold_c, str(kind))
+        self._scas.append((image, mask, g_eff, object_mask))
         return len(self._scas) - 1
 
     def set_pair(self, a, b, x=None, y=None, lattice=None, L=None):
@@ -140,7 +151,15 @@ class DestripeEngine:
         n_lat = sum(1 for p in self._pairs.values() if p[0] == "lattice")
         nb = self.neighbors()
         return memory_plan(max(self.n_sca, 1), self.nside, self.ds_rows, self.amp_cols, len(self._pairs) - n_lat, n_lat, self.L,
-                           max([len(v) for v in nb.values()] or [0]))
+                           max([len(v) for v in nb.values()] or [0]), objmask_setup=self._objmask_setup)
+
+    @property
+    def _objmask_setup(self):
+        """Bytes of the largest object-mask set-up among the registered SCAs (0: none asks for one; nothing once they are uploaded)."""
+        from . import objmask
+
+        return max([objmask.setup_bytes(s[0].shape, str(s[0].dtype).replace("torch.", ""), s[3][2]) for s in self._scas if s is not None and s[3] is not None]
+                   or [0])
 
     # ---- device ----
     def _bind_stream(self):
@@ -169,9 +188,18 @@ class DestripeEngine:
             img = torch.empty((n, ns, ns), dtype=torch.float32, device=self.dev)
             msk = torch.empty((n, ns, ns), dtype=torch.uint8, device=self.dev)
             gef = torch.empty((n, ns, ns), dtype=torch.float32, device=self.dev)
-            for i, (im, ma, ge) in enumerate(self._scas):
-                img[i].copy_(torch.as_tensor(im if _is_torch(im) else np.ascontiguousarray(im, dtype=np.float32)).to(torch.float32))
+            for i, (im, ma, ge, om) in enumerate(self._scas):
                 msk[i].copy_(torch.as_tensor(ma if _is_torch(ma) else np.ascontiguousarray(ma).astype(bool)).to(torch.bool))
+                if om is None:
+                    img[i].copy_(torch.as_tensor(im if _is_torch(im) else np.ascontiguousarray(im, dtype=np.float32)).to(torch.float32))
+                else:  # imdestripe.py:324-332: self.mask *= ~object_mask, the image in its own type, image_out discarded
+                    from . import objmask
+
+                    own = (im if _is_torch(im) else torch.as_tensor(np.ascontiguousarray(im))).to(self.dev).contiguous()
+                    omask = objmask.object_mask(own, om[0], om[1], om[2])
+                    objmask._apply(ctx, msk[i], omask, msk[i])
+                    img[i].copy_(own.to(torch.float32))
+                    del own, omask
                 gef[i].copy_(torch.as_tensor(ge if _is_torch(ge) else np.ascontiguousarray(ge, dtype=np.float32)).to(torch.float32))
             self._frozen = {"image": img, "mask": msk, "geff": gef, "neff": torch.zeros((n, ns, ns), dtype=torch.float64, device=self.dev),
                             "gmax": float(gef.abs().max().item())}  # set-up, once: the bound the fixed-point scale of the gradient needs
