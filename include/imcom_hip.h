@@ -745,6 +745,53 @@ int imcom_mask_propagate(imcom_ctx *ctx, const unsigned char *seed, const unsign
 int imcom_mask_dilate(imcom_ctx *ctx, const unsigned char *in, int rows, int cols, int r, unsigned char *out, int memspace);
 int imcom_mask_apply(imcom_ctx *ctx, const void *in, int dtype, const unsigned char *mask, long n, void *out, int memspace);
 
+/* Validation-report statistics (reference src/pyimcom/diagnostics/layer_diagnostics.py:24-64 _percentiles_and_delete and 102-177, the
+ * gathering loop of LayerReport.build; src/pyimcom/diagnostics/dynrange.py:140-163, the SIGMA / EFFCOVER histograms, and 211-238, the ring
+ * profiles of gen_dynrange_data): exact order statistics of data that never sits in one place, for n_segments <= 64 segments and up to
+ * n_ranks <= 32 ranks per segment at once, and the histogram of a (u)int16-coded map.  The accumulator is a radix select on
+ * imcom_select_kth's keys and digits (float32: 3 passes of 11 / 11 / 10 bits, float64: 6) whose counters live in `state`, DEVICE memory
+ * of the caller (imcom_quant_sizes says how much) that must stay untouched until imcom_quant_free.  The caller feeds the SAME multiset of
+ * (segment, value) in every pass, in any chunking and order; all counts are 64-bit integers added with atomics, so every result is the
+ * same bits from run to run and for every chunking.  NaNs sort last, a rank among them is NaN, -0.0 and 0.0 are one value (0.0).
+ *   imcom_quant_sizes        out[4] = {bytes of `state`, passes, counters per group (2048), groups whose counters share a launch (8)}.
+ *   imcom_quant_begin        a new accumulator on `state`, ready for pass 1.  imcom_quant_reset: back to there.  imcom_quant_free.
+ *   imcom_quant_add_2d       layer_diagnostics.py:139-142: element (r, c) of a strided view, at values[r pitch + c] (in elements), read in
+ *                            place, all into `segment`: a block frame's [d:-d, d:-d] crop.  Counters in LDS, 8 live groups a launch.
+ *   imcom_quant_add_flat     n values with a segment id each (uint8, or int32 with ids_i32); an id outside 0 .. n_segments - 1 fails the pass.
+ *   imcom_quant_add_constant layer_diagnostics.py:114, 122, 133-134 (the zeros a missing block leaves): `count` copies of `value`, no data.
+ *   imcom_quant_add_rings    dynrange.py:216-228: for star k at (x[k], y[k]) (float64) every pixel of its clipped box (217-220) of the frame
+ *                            [n][n] goes to segment j = floor(sqrt((col - x)^2 + (row - y)^2)) when j < rpix <= n_segments, once per star
+ *                            whose box holds it; the radius in float64 as numpy forms it (no fused multiply-add, the correctly rounded
+ *                            root).  n <= 32767 and |x|, |y| < 32765 - rpix (the int16 of the reference), else the pass fails.
+ *   imcom_quant_end_pass     ends the pass that was fed; *passes_left (may be NULL).  IMCOM_ERR_ARG, reported here and nowhere earlier:
+ *                            a segment whose element or NaN count differs from pass 1's, a bad segment id or star position.  The failed
+ *                            pass has then not happened: its counters are zero again, it can be fed anew (or imcom_quant_reset).
+ *   imcom_quant_counts       after pass 1: total[s] and nans[s] (HOST arrays [n_segments]), NaNs included in total.
+ *   imcom_quant_set_ranks    between pass 1 and pass 2: ranks [n_segments][n_ranks] (HOST), 0-based ranks among the segment's elements in
+ *                            ascending order, -1 for a slot not used.  IMCOM_ERR_ARG: a rank >= the count of a segment that is not empty.
+ *   imcom_quant_results      after the last pass: out [n_segments][n_ranks] (HOST) of the accumulator's type, the order statistics; NaN
+ *                            for an unused slot, a rank among the NaNs, an empty segment.
+ *   imcom_codehist           dynrange.py:142-150, 155-163 for a map that is still (u)int16 codes (Block.compress_map): counts [nbins + 1]
+ *                            (int64): counts[table[code]] += 1 over the view codes[r pitch + c], the code's bit pattern indexing `table`
+ *                            [65536] uint8, which the caller makes by evaluating the reference's expression and comparisons on every
+ *                            code: t < 128 bin t (t = nbins: off scale high only), 128 <= t < 255 bin t - 128 and off scale high, 255
+ *                            neither.  nbins <= 127.  No power is taken on the device.
+ *   values, segment_ids, frame, x, y, codes, table and counts follow `memspace`. */
+typedef struct imcom_quant imcom_quant;
+int imcom_quant_sizes(int n_segments, int n_ranks, int is_f64, long *out);
+int imcom_quant_begin(imcom_ctx *ctx, int n_segments, int n_ranks, int is_f64, void *state, size_t state_bytes, imcom_quant **out);
+int imcom_quant_reset(imcom_ctx *ctx, imcom_quant *q);
+int imcom_quant_free(imcom_ctx *ctx, imcom_quant *q);
+int imcom_quant_add_2d(imcom_ctx *ctx, imcom_quant *q, int segment, const void *values, long rows, long cols, long pitch, int memspace);
+int imcom_quant_add_flat(imcom_ctx *ctx, imcom_quant *q, const void *values, const void *segment_ids, int ids_i32, long n, int memspace);
+int imcom_quant_add_constant(imcom_ctx *ctx, imcom_quant *q, int segment, double value, long count);
+int imcom_quant_add_rings(imcom_ctx *ctx, imcom_quant *q, const void *frame, int n, long pitch, const double *x, const double *y, int nstar, int rpix, int memspace);
+int imcom_quant_end_pass(imcom_ctx *ctx, imcom_quant *q, int *passes_left);
+int imcom_quant_counts(imcom_ctx *ctx, const imcom_quant *q, long *total, long *nans);
+int imcom_quant_set_ranks(imcom_ctx *ctx, imcom_quant *q, const long *ranks);
+int imcom_quant_results(imcom_ctx *ctx, const imcom_quant *q, void *out);
+int imcom_codehist(imcom_ctx *ctx, const void *codes, long rows, long cols, long pitch, const unsigned char *table, int nbins, long *counts, int memspace);
+
 #ifdef __cplusplus
 }
 #endif

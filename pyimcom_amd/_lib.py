@@ -162,6 +162,19 @@ SIGNATURES = {
     "imcom_mask_propagate": [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(_l), _i],
     "imcom_mask_dilate": [_vp, _vp, _i, _i, _i, _vp, _i],
     "imcom_mask_apply": [_vp, _vp, _i, _vp, _l, _vp, _i],
+    "imcom_quant_sizes": [_i, _i, _i, _vp],
+    "imcom_quant_begin": [_vp, _i, _i, _i, _vp, C.c_size_t, C.POINTER(_vp)],
+    "imcom_quant_reset": [_vp, _vp],
+    "imcom_quant_free": [_vp, _vp],
+    "imcom_quant_add_2d": [_vp, _vp, _i, _vp, _l, _l, _l, _i],
+    "imcom_quant_add_flat": [_vp, _vp, _vp, _vp, _i, _l, _i],
+    "imcom_quant_add_constant": [_vp, _vp, _i, _d, _l],
+    "imcom_quant_add_rings": [_vp, _vp, _vp, _i, _l, _vp, _vp, _i, _i, _i],
+    "imcom_quant_end_pass": [_vp, _vp, _ip],
+    "imcom_quant_counts": [_vp, _vp, _vp, _vp],
+    "imcom_quant_set_ranks": [_vp, _vp, _vp],
+    "imcom_quant_results": [_vp, _vp, _vp],
+    "imcom_codehist": [_vp, _vp, _l, _l, _l, _vp, _i, _vp, _i],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

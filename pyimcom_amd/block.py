@@ -174,3 +174,12 @@ class BlockMaps:
         if step > 0 and all(b - a == step for a, b in zip(idx, idx[1:])):  # one call: the layers are evenly strided frames of the view
             return power_spectrum_2d(view[idx[0]:idx[-1] + 1:step], norms, window, bin8, ctx=self.ctx)
         return torch.cat([power_spectrum_2d(view[i:i + 1], norms[k:k + 1], window, bin8, ctx=self.ctx) for k, i in enumerate(idx)])
+
+    def report_views(self, out=0, pad=0):
+        """The block's frames for the validation report's statistics (``pyimcom_amd.reportstats``) without a copy: ``out_map[out]``
+        cropped by the fade margin plus ``pad`` pixels on every side (the reference's ``postage_pad * n2``: the unique area that
+        layer_diagnostics.py:139-142 keeps), float32 [n_inframe, side, side], a view that ``layer_percentiles`` and ``add_star_rings``
+        read in place.  The coded SIGMA / EFFCOVER maps of ``coded_map_histogram`` are ``compress("Sigma")`` / ``compress("Neff")``.
+        Call it after ``finalize``."""
+        c = self.fade + int(pad)
+        return self.out_map[out][:, c:self.nside - c, c:self.nside - c]

@@ -234,4 +234,20 @@ int launch_mask_apply(imcom_ctx *ctx, const void *in, int dtype, const unsigned 
 int launch_mask_dilate(imcom_ctx *ctx, const unsigned char *in, int H, int W, int r, unsigned char *out);
 int launch_mask_propagate(imcom_ctx *ctx, const unsigned char *grow, int H, int W, unsigned char *out, unsigned char *tmp, unsigned int *changed, long *sweeps);
 
+// quantiles.hip: the counting passes of the streaming exact select and the coded-map histogram.  QtDev: the accumulator's device state
+// (all 64-bit words) -- per segment the elements and the NaNs the running pass has seen and the number of its live groups, `bad` one word
+// (segment ids out of range, star positions not served), the ascending prefixes of segment s's groups at gprefix[s R ..], the group's
+// counters at hist[(s R + g) QT_BINS ..].
+constexpr int QT_BINS = 2048, QT_TILE = 8, QT_THREADS = 512;  // counters of a group; groups whose counters share a workgroup's LDS; its threads
+struct QtDev {
+    unsigned long long *tot, *nan, *ng, *bad, *gprefix, *hist;
+    int S, R;
+};
+int launch_quant_dense(imcom_ctx *ctx, const QtDev &d, bool f64, int seg, int ng, const void *p, long rows, long cols, long pitch, int shift, int nbits);
+int launch_quant_ids(imcom_ctx *ctx, const QtDev &d, bool f64, const void *p, const void *ids, bool ids_i32, long n, int shift, int nbits);
+int launch_quant_rings(imcom_ctx *ctx, const QtDev &d, bool f64, const void *frame, int n, long pitch, const double *x, const double *y, int nstar, int rpix, int shift,
+                       int nbits);
+int launch_quant_constant(imcom_ctx *ctx, const QtDev &d, bool f64, int seg, double value, unsigned long long count, int shift, int nbits);
+int launch_codehist(imcom_ctx *ctx, const unsigned short *codes, long rows, long cols, long pitch, const unsigned char *table, int nbins, unsigned long long *counts);
+
 }  // namespace imcom
