@@ -688,7 +688,7 @@ int imcom_noiseps_accumulate(imcom_ctx *ctx, const double *ps2d, const double *m
  * numpy's.  U[k], k = 0, 1, ..., is the double that Generator.random() / uniform() returns as draw k + 1 from that state: the state moved
  * k + 1 steps of s <- 0x2360ED051FC65DA44385DF649FCCF645 s + inc (mod 2^128), the output rotr64(hi ^ lo, s >> 122), and (output >> 11)
  * 2^-53.  Integer arithmetic until that one exact conversion: every result equals numpy's bit for bit, whatever the count, the offset
- * and the memspace.  Only draws that consume one 64-bit output each are served: normal, Poisson and bounded-integer draws are not.
+ * and the memspace.  These entries serve draws that consume one 64-bit output each; normal draws are imcom_pcg64_normal's, below.
  *   imcom_pcg64_uniform     out[i] = U[offset + i], i < count; offset = offset_hi 2^64 + offset_lo.  IMCOM_ERR_ARG: count < 0.
  *   imcom_pcg64_uniform_at  out[i] = U[pos[i]], i < count; pos int64 in any order (an entry below 0 counts as its value mod 2^64).
  *   imcom_cr_mask           Mask.randmask: pixel (r, c) of slice `slice` (idsca[1] - 1) of the padded draw [n_slices][W][W], W = nside +
@@ -706,6 +706,50 @@ int imcom_pcg64_uniform_at(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi,
                            int memspace);
 int imcom_cr_mask(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, int nside, int pad, int slice, int n_slices,
                   double pcut, const float *labnoise, double threshold, unsigned char *mask, long *ngood, int memspace);
+
+/* numpy's float64 normal draws of a PCG64 stream (Generator.standard_normal / normal; reference src/pyimcom/layer.py:1303-1304, the
+ * white-noise layer drawn for every input image, and 899-900, the draws of CplxNoise.noise_1f_frame).  The stream is given as for
+ * imcom_pcg64_uniform.  A normal draw takes one stream output 99.3 % of the time and more otherwise (a ziggurat: csrc/ziggurat_core.h), so
+ * draw i has no stream position of its own; the draws are found as a chain through the stream, tile by tile (csrc/ziggurat.hip).
+ *   imcom_pcg64_normal_sizes  *tail_cap: the entries tail_idx must have room for (tail_raw: twice as many) for `count` draws.
+ *   imcom_pcg64_normal        out[i], i < count: the draws Generator.standard_normal(count) returns after bit_generator.advance(offset),
+ *                             bit for bit, EXCEPT the tail draws (|x| > 3.654, 2.7e-4 of all).  A tail draw's last bit depends on the
+ *                             libm numpy was built against, so for those out[i] is NOT final: it holds this library's log1p, which may
+ *                             differ from numpy's in the last bit, and nothing in `info` says whether it does.  A caller that wants
+ *                             numpy's bits must overwrite them: tail_idx[j] = i, tail_raw[2 j], tail_raw[2 j + 1], j < info[2], in no
+ *                             particular order, are the attempt's first output w0 and the output w1 whose logarithm the value holds,
+ *                             x = 3.6541528853610088 - 0.27366123732975828 log1p(-(w1 >> 11) 2^-53), negated if bit 17 of w0 is set,
+ *                             formed with the caller's libm.  A caller that ignores the list has normal draws that equal numpy's except
+ *                             possibly in the last bit of those entries.  info [4], host memory whatever the memspace: the stream
+ *                             outputs the count draws consume (the state numpy is left in is that many steps on), the consumed
+ *                             attempts that left the fast path, the tail draws, and 1 if the call is UNDECIDED: a comparison of the
+ *                             draw that depends on exp / log1p fell inside the guard band (relative 2^-46; two correct evaluations of
+ *                             a side differ by less than 2^-49), a tail loop ran over 8 pairs, or there were more than tail_cap tail
+ *                             draws.  Then `out` is not numpy's and the caller draws the request on the host: about one call in 7 10^5
+ *                             for 4088^2 draws, two thirds of them from the tail loop (csrc/ziggurat_core.h has the account).  The call
+ *                             waits for its work (once per chunk of tiles).  IMCOM_ERR_ARG: count < 0.
+ *   imcom_pcg64_normal_ex     the same with, for tests and measurements, the tile size (a power of two, 4 .. 1024), the tiles of one
+ *                             chunk (<= 2^20) and the guard band of this call; 0 is the default.  No result depends on the first two.
+ *                             IMCOM_ERR_ARG for values outside these ranges.
+ *   out, tail_idx and tail_raw follow `memspace`. */
+int imcom_pcg64_normal_sizes(long count, long *tail_cap);
+int imcom_pcg64_normal(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                       long count, double *out, long *tail_idx, uint64_t *tail_raw, uint64_t *info, int memspace);
+int imcom_pcg64_normal_ex(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                          long count, double *out, long *tail_idx, uint64_t *tail_raw, uint64_t *info, int memspace, int tile, long chunk_tiles,
+                          double guard_band);
+
+/* The transform of the 1/f noise layer (reference src/pyimcom/layer.py:896-913, the channel loop of CplxNoise.noise_1f_frame; the draws of
+ * 899-900 are imcom_pcg64_normal's, the amplitudes of 892-895 the caller's).  normals [2 nch][len]: rows 2c, 2c + 1 are the real and the
+ * imaginary draws of channel c; amp [len].  Per channel: the forward DFT of (re + i im) amp in float64 (a four-step transform, len = N1 N2),
+ * the real part of outputs k < len / 2, divided by sqrt(2), minus the channel mean (summed in float64 in a fixed order), cast to float32
+ * into columns c w .. c w + w - 1 of a [len / 2 / w][nch w] frame, the columns of odd channels reversed.  frame [len / 2 / w - 2 border]
+ * [nch w - 2 border] float32 is that frame without a border of `border` pixels (the reference: len 2^20, nch 32, w 128, border 4, the
+ * slice [4:4092, 4:4092]).  block (NULL: not wanted) [nch][len / 2] float64: the channels before the cast.  The same bits from run to run.
+ * IMCOM_ERR_UNSUPPORTED: len no power of two in 2^10 .. 2^20, or w no power of two <= len / 2.  IMCOM_ERR_ARG: nch outside 1 .. 4096, a
+ * border that leaves no pixel.  All arrays follow `memspace`. */
+int imcom_noise_1f(imcom_ctx *ctx, const double *normals, const double *amp, long len, int nch, int w, int border, float *frame, double *block,
+                   int memspace);
 
 /* Bright-object masks of the destripe set-up (reference src/pyimcom/imdestripe.py:781-872, apply_object_mask; its caller
  * Sca_img.__init__ 317-332; apply_jwst_mask 412-419 needs no entry).  Images are float32 or float64 (is_f64), masks and flags uint8 with

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "launchers.h"
 #include "quantiles_core.h"
+#include "ziggurat_core.h"
 
 namespace imcom {
 
@@ -2320,6 +2321,149 @@ int imcom_cr_mask(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t
     IMCOM_TRY(launch_cr_mask(ctx, state, jumps, (unsigned long long)slice * W * W, nside, pad, pcut, l_d, threshold, m_d, (unsigned long long *)n_d));
     IMCOM_TRY(st.back(mask, (const unsigned char *)m_d, npix));
     IMCOM_TRY(st.back(ngood, (const long *)n_d, (size_t)1));
+    return st.done();
+}
+
+// ---------------------------------------------------------------------------------------------
+// numpy's normal draws of a PCG64 stream (ziggurat.hip)
+namespace {
+constexpr int ZIG_TILE_DEFAULT = 1024, ZIG_TILE_MAX = 1024;  // (the LDS of zig_emit_kernel: 36 KB at 1024)
+constexpr long ZIG_CHUNK_TILES_DEFAULT = 1L << 16, ZIG_CHUNK_TILES_MAX = 1L << 20;
+constexpr double ZIG_GUARD_DEFAULT = ZIG_GUARD;
+// the tiles one chunk may need for `remaining` draws: 1.0145 outputs a draw on average, 3 % and a tile allowed for
+long zig_tiles_for(long remaining, int P) { return (remaining + remaining / 32 + P - 1) / P + 1; }
+}  // namespace
+
+int imcom_pcg64_normal_sizes(long count, long *tail_cap)
+{
+    IMCOM_REQUIRE(tail_cap, "null pointer");
+    IMCOM_REQUIRE(count >= 0 && count <= PCG64_MAX_COUNT, "pcg64: count %ld outside 0 .. 2^36", count);
+    *tail_cap = count / 1024 + 4096;  // the expected number is count / 3700
+    return IMCOM_OK;
+}
+
+int imcom_pcg64_normal(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                       long count, double *out, long *tail_idx, uint64_t *tail_raw, uint64_t *info, int memspace)
+{
+    return imcom_pcg64_normal_ex(ctx, state_lo, state_hi, inc_lo, inc_hi, offset_lo, offset_hi, count, out, tail_idx, tail_raw, info, memspace, 0, 0, 0.0);
+}
+
+int imcom_pcg64_normal_ex(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                          long count, double *out, long *tail_idx, uint64_t *tail_raw, uint64_t *info, int memspace, int tile, long chunk_tiles, double guard_band)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(count >= 0 && count <= PCG64_MAX_COUNT, "pcg64: count %ld outside 0 .. 2^36", count);
+    IMCOM_REQUIRE(info && (count == 0 || (out && tail_idx && tail_raw)), "null pointer");
+    IMCOM_REQUIRE(tile == 0 || (tile >= 4 && tile <= ZIG_TILE_MAX && (tile & (tile - 1)) == 0), "pcg64_normal: tile %d is no power of two in 4 .. %d", tile,
+                  ZIG_TILE_MAX);
+    IMCOM_REQUIRE(chunk_tiles >= 0 && chunk_tiles <= ZIG_CHUNK_TILES_MAX, "pcg64_normal: %ld tiles a chunk outside 1 .. 2^20", chunk_tiles);
+    IMCOM_REQUIRE(guard_band >= 0.0 && guard_band <= 1.0, "pcg64_normal: guard band %g outside 0 .. 1", guard_band);
+    for (int i = 0; i < 4; i++) info[i] = 0;
+    if (count == 0) return IMCOM_OK;
+    const int P = tile ? tile : ZIG_TILE_DEFAULT;
+    const long chunk_max = chunk_tiles ? chunk_tiles : ZIG_CHUNK_TILES_DEFAULT;
+    const double guard = guard_band > 0.0 ? guard_band : ZIG_GUARD_DEFAULT;
+    const long tail_cap = count / 1024 + 4096, tiles_max = std::min(chunk_max, zig_tiles_for(count, P));
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    plan.add((size_t)PCG64_JUMPS * 32);
+    plan.add((size_t)tiles_max * ZIG_ENTRIES);      // exit_t
+    plan.add((size_t)tiles_max * ZIG_ENTRIES * 2);  // count_t
+    plan.add((size_t)tiles_max);                    // entry_t
+    plan.add((size_t)tiles_max * 8);                // base_t
+    plan.add(2 * sizeof(long));                     // res
+    plan.add(4 * sizeof(unsigned long long));       // info
+    st.plan(plan, {(size_t)count * 8, (size_t)tail_cap * 8, (size_t)tail_cap * 16});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const unsigned long long *jumps, state[2] = {state_lo, state_hi};
+    unsigned char *exit_t, *entry_t;
+    unsigned short *count_t;
+    long *base_t, *res, *ti_d;
+    unsigned long long *info_d, *tr_d;
+    double *o_d;
+    IMCOM_TRY(pcg64_jumps(ctx, inc_lo, inc_hi, &jumps, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)tiles_max * ZIG_ENTRIES, &exit_t, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)tiles_max * ZIG_ENTRIES, &count_t, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)tiles_max, &entry_t, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)tiles_max, &base_t, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)2, &res, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)4, &info_d, __func__));
+    IMCOM_TRY(st.out(out, (size_t)count, &o_d));
+    IMCOM_TRY(st.out(tail_idx, (size_t)tail_cap, &ti_d));
+    IMCOM_TRY(st.out((unsigned long long *)tail_raw, (size_t)tail_cap * 2, &tr_d));
+    IMCOM_HIP_CHECK(hipMemsetAsync(info_d, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    // chunks in ascending order: a chunk's entry offset and output base are the exit of the chunk before
+    unsigned long long rel = 0;
+    long made = 0, entry = 0;
+    while (made < count) {
+        const long tiles = std::min(tiles_max, zig_tiles_for(count - made, P));
+        const unsigned long long lo = offset_lo + rel, start[2] = {lo, offset_hi + (lo < rel)};
+        long res_h[2];
+        IMCOM_TRY(launch_zig_chunk(ctx, state, jumps, start, rel, P, tiles, (int)entry, made, guard, exit_t, count_t, entry_t, base_t, res, count, o_d, ti_d,
+                                   tr_d, tail_cap, info_d));
+        IMCOM_HIP_CHECK(hipMemcpyAsync(res_h, res, sizeof(res_h), hipMemcpyDeviceToHost, ctx->stream));
+        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        entry = res_h[0];
+        made = res_h[1];
+        rel += (unsigned long long)tiles * P;
+    }
+    unsigned long long info_h[4];
+    IMCOM_HIP_CHECK(hipMemcpyAsync(info_h, info_d, sizeof(info_h), hipMemcpyDeviceToHost, ctx->stream));
+    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const long tails = (long)std::min<unsigned long long>(info_h[2], (unsigned long long)tail_cap);
+    IMCOM_TRY(st.back(out, (const double *)o_d, (size_t)count));
+    IMCOM_TRY(st.back(tail_idx, (const long *)ti_d, (size_t)tails));
+    IMCOM_TRY(st.back((unsigned long long *)tail_raw, (const unsigned long long *)tr_d, (size_t)tails * 2));
+    info[0] = info_h[0];
+    info[1] = info_h[1];
+    info[2] = info_h[2];
+    info[3] = info_h[3] != 0;
+    return st.done();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The transform of the 1/f noise layer (noise1f.hip)
+int imcom_noise_1f(imcom_ctx *ctx, const double *normals, const double *amp, long len, int nch, int w, int border, float *frame, double *block, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(len >= 2 && nch >= 1 && nch <= 4096 && w >= 1 && border >= 0, "noise_1f: len %ld, %d channels of width %d, border %d", len, nch, w, border);
+    int N1, N2;
+    if ((w & (w - 1)) || !noise1f_split(len, &N1, &N2) || (long)w > len / 2) {
+        set_error("noise_1f: the length (%ld) must be a power of two in 2^10 .. 2^20 and the channel width (%d) a power of two up to half of it", len, w);
+        return IMCOM_ERR_UNSUPPORTED;
+    }
+    IMCOM_REQUIRE(normals && amp && frame, "null pointer");
+    const long half = len / 2, rows = half / w, cols = (long)nch * w;
+    IMCOM_REQUIRE(2L * border < rows && 2L * border < cols, "noise_1f: a border of %d leaves nothing of %ld x %ld pixels", border, rows, cols);
+    const long npix = (rows - 2 * border) * (cols - 2 * border);
+    const int group = std::min(nch, NOISE1F_GROUP);
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    plan.add((size_t)N1 * 16);
+    plan.add((size_t)N2 * 16);
+    plan.add((size_t)group * len * 16);  // S
+    plan.add((size_t)nch * 8);           // sums
+    if (st.host || !block) plan.add((size_t)nch * half * 8);
+    st.plan(plan, {(size_t)2 * nch * len * 8, (size_t)len * 8, (size_t)npix * 4});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    double2 *tw1, *tw2, *S;
+    double *sum, *blk = block;
+    const double *g_d, *amp_d;
+    float *f_d;
+    IMCOM_TRY(ws_take(ctx, (size_t)N1, &tw1, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)N2, &tw2, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)group * len, &S, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)nch, &sum, __func__));
+    if (st.host || !block) IMCOM_TRY(ws_take(ctx, (size_t)nch * half, &blk, __func__));
+    IMCOM_TRY(st.in(normals, (size_t)2 * nch * len, &g_d));
+    IMCOM_TRY(st.in(amp, (size_t)len, &amp_d));
+    IMCOM_TRY(st.out(frame, (size_t)npix, &f_d));
+    IMCOM_TRY(noise1f_tables(ctx, len, tw1, tw2));
+    for (int ch0 = 0; ch0 < nch; ch0 += group)
+        IMCOM_TRY(launch_noise1f_group(ctx, g_d, amp_d, len, ch0, std::min(group, nch - ch0), tw1, tw2, S, blk));
+    IMCOM_TRY(launch_noise1f_place(ctx, blk, sum, len, nch, w, border, f_d));
+    IMCOM_TRY(st.back(frame, (const float *)f_d, (size_t)npix));
+    if (block) IMCOM_TRY(st.back(block, (const double *)blk, (size_t)nch * half));
     return st.done();
 }
 

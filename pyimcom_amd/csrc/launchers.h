@@ -217,6 +217,27 @@ constexpr int PCG64_JUMPS = 128;
 int launch_pcg64_uniform(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const unsigned long long offset[2], long count,
                          double *out);
 int launch_pcg64_uniform_at(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const long *pos, long count, double *out);
+
+// ziggurat.hip: numpy's normal draws of a PCG64 stream, one chunk of `tiles` tiles of P positions from stream position `start` (128 bits;
+// start_rel: the same counted from the call's offset).  The chain enters the chunk at offset entry0 with base0 draws made; res[2] = {entry
+// offset after the chunk, draws made by then}.  exit_t / count_t [tiles][ZIG_ENTRIES], entry_t / base_t [tiles]: the tile tables.
+// info [4] (device, zeroed by the caller): outputs consumed by `count` draws, slow attempts, tail draws, flags (1 undecided, 2 tail list full).
+size_t zig_lds_bytes(int P, int levels);
+int launch_zig_chunk(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const unsigned long long start[2],
+                     unsigned long long start_rel, int P, long tiles, int entry0, long base0, double guard, unsigned char *exit_t, unsigned short *count_t,
+                     unsigned char *entry_t, long *base_t, long *res, long count, double *out, long *tail_idx, unsigned long long *tail_raw, long tail_cap,
+                     unsigned long long *info);
+// noise1f.hip: the transform of the 1/f noise layer.  noise1f_split: len = N1 N2 for the four-step transform, false if len is no power of
+// two in 2^10 .. 2^20.  launch_noise1f_group: channels ch0 .. ch0 + nchg - 1 of g [2 nch][len] into blk [nch][len / 2] (Re DFT / sqrt 2), S
+// [nchg][len] complex scratch, tw1 [N1] / tw2 [N2] the stage tables of the line plans
+// (noise1f_tables).  launch_noise1f_place: the channel sums (sum
+// [nch]), blk minus its channel mean in place, and the float32 frame without its border.
+constexpr int NOISE1F_GROUP = 8;  // channels that share one pass (and the scratch S: 128 MB at len = 2^20)
+bool noise1f_split(long len, int *N1, int *N2);
+int noise1f_tables(imcom_ctx *ctx, long len, double2 *tw1, double2 *tw2);
+int launch_noise1f_group(imcom_ctx *ctx, const double *g, const double *amp, long len, int ch0, int nchg, const double2 *tw1, const double2 *tw2, double2 *S,
+                         double *blk);
+int launch_noise1f_place(imcom_ctx *ctx, double *blk, double *sum, long len, int nch, int w, int border, float *frame);
 int launch_cr_mask(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, unsigned long long base, int nside, int pad, double pcut,
                    const float *labnoise, double threshold, unsigned char *mask, unsigned long long *ngood);
 

@@ -1,0 +1,271 @@
+// ziggurat.hip -- numpy's float64 normal draws of a PCG64 stream (Generator.standard_normal; reference src/pyimcom/layer.py:1303-1304, the
+// white-noise layer, and 899-900, the draws of CplxNoise.noise_1f_frame).  The C-ABI entry imcom_pcg64_normal is in api.hip.
+//
+// A normal draw consumes a data-dependent number of outputs (ziggurat_core.h), so draw i has no position of its own; but every stream
+// position k has an "attempt starting at k" that consumes a(k) outputs, and the draws are the emitting attempts on the chain k -> k + a(k)
+// from the start: a list ranking.  The stream is cut into tiles of P positions:
+//   zig_map_kernel    (A, B) a workgroup per tile forms the tile's outputs from the closed form of pcg64_dev.h, every position's next and
+//                     emit flag, and by pointer doubling in LDS the exit offset and emit count for each of the ZIG_ENTRIES offsets at
+//                     which the chain can enter the tile.
+//   zig_chain_kernel  (C) entry offset and output base of every tile: one workgroup; a thread composes the maps of a run of tiles for all
+//                     entries, one thread chains the 256 run maps, every thread then walks its run from its entry.
+//   zig_emit_kernel   (D) a workgroup per tile forms the outputs again (cheaper than storing them), marks the on-chain positions by
+//                     doubling from the entry, ranks the emitting ones by a prefix sum and writes value -> out[base + rank]: one owner per
+//                     output, no atomics on values, the same bits for every tile size.
+// Only integer counters are summed with atomics.  Tail draws (2.7e-4 of all) are listed with their two words; the order of that list
+// is the only thing here that can differ from run to run, and the caller sorts it.
+#include "launchers.h"
+#include "pcg64_dev.h"
+#define ZIG_TABLE __device__ const
+#include "ziggurat_tables.h"
+#include "ziggurat_core.h"
+
+namespace imcom {
+
+namespace {
+
+typedef unsigned long long u64;
+
+// the outputs of stream positions start + tile P + [0, n) into raw[0 .. n): a thread forms a run, one jump and then steps
+__device__ __forceinline__ void tile_outputs(const U128 state, const U128 start, long tile, int P, int n, const U128 *tab, u64 *raw)
+{
+    const int per = (n + (int)blockDim.x - 1) / (int)blockDim.x, i0 = (int)threadIdx.x * per;
+    if (i0 >= n) return;
+    const u64 add = (u64)tile * (u64)P + (u64)i0, dlo = start.lo + add;
+    U128 s = jump(state, dlo, start.hi + (dlo < add), tab);
+    const int m = min(per, n - i0);
+    for (int q = 0; q < m; q++) raw[i0 + q] = step_output(s, tab);
+}
+
+// LDS of both tile kernels: the jump table, then the tile's outputs
+constexpr int ZIG_LDS_HEAD = 2 * PCG64_JUMPS * (int)sizeof(U128);
+
+__global__ __launch_bounds__(256) void zig_map_kernel(U128 state, const u64 *__restrict__ jumps, U128 start, int P, int levels, double guard,
+                                                      unsigned char *__restrict__ exit_t, unsigned short *__restrict__ count_t)
+{
+    extern __shared__ u64 lds[];
+    U128 *tab = (U128 *)lds;
+    u64 *raw = lds + ZIG_LDS_HEAD / 8;                            // [P + ZIG_HALO]
+    const int n = P + ZIG_ENTRIES;
+    unsigned short *nxt = (unsigned short *)(raw + P + ZIG_HALO);  // [2][n]
+    unsigned short *cnt = nxt + 2 * n;                             // [2][n]
+    const long tile = blockIdx.x;
+    load_jumps(tab, jumps);
+    __syncthreads();
+    tile_outputs(state, start, tile, P, P + ZIG_HALO, tab, raw);
+    __syncthreads();
+    for (int p = threadIdx.x; p < n; p += blockDim.x) {
+        int to = p, emits = 0;
+        if (p < P) {
+            const ZigAttempt a = zig_attempt((const uint64_t *)raw + p, ZIG_WI, (const uint64_t *)ZIG_KI, ZIG_FI, guard);
+            to = p + a.adv;
+            emits = zig_emits(a.kind) ? 1 : 0;
+        }
+        nxt[p] = (unsigned short)to;
+        cnt[p] = (unsigned short)emits;
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int l = 0; l <= levels; l++, cur ^= 1) {  // 2^(levels + 1) >= 2 P steps: every position has left the tile
+        const unsigned short *ni = nxt + cur * n, *ci = cnt + cur * n;
+        unsigned short *no = nxt + (cur ^ 1) * n, *co = cnt + (cur ^ 1) * n;
+        for (int p = threadIdx.x; p < n; p += blockDim.x) {
+            const int q = ni[p];
+            no[p] = ni[q];
+            co[p] = (unsigned short)(ci[p] + ci[q]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < ZIG_ENTRIES) {
+        exit_t[tile * ZIG_ENTRIES + threadIdx.x] = (unsigned char)(nxt[cur * n + threadIdx.x] - P);
+        count_t[tile * ZIG_ENTRIES + threadIdx.x] = cnt[cur * n + threadIdx.x];
+    }
+}
+
+// res[0] = the entry offset of the tile after the last, res[1] = the output base there
+__global__ __launch_bounds__(256) void zig_chain_kernel(const unsigned char *__restrict__ exit_t, const unsigned short *__restrict__ count_t, long tiles,
+                                                        int entry0, long base0, unsigned char *__restrict__ entry_t, long *__restrict__ base_t,
+                                                        long *__restrict__ res)
+{
+    __shared__ unsigned char run_exit[256][ZIG_ENTRIES];
+    __shared__ unsigned int run_count[256][ZIG_ENTRIES];
+    __shared__ unsigned char run_entry[256];
+    __shared__ long run_base[256];
+    const int t = threadIdx.x;
+    const long per = (tiles + 255) / 256, t0 = min(tiles, t * per), t1 = min(tiles, t0 + per);
+    {
+        unsigned char cur[ZIG_ENTRIES];
+        unsigned int acc[ZIG_ENTRIES];
+#pragma unroll
+        for (int e = 0; e < ZIG_ENTRIES; e++) {
+            cur[e] = (unsigned char)e;
+            acc[e] = 0;
+        }
+        for (long i = t0; i < t1; i++) {
+#pragma unroll
+            for (int e = 0; e < ZIG_ENTRIES; e++) {
+                const long at = i * ZIG_ENTRIES + cur[e];
+                acc[e] += count_t[at];
+                cur[e] = exit_t[at];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < ZIG_ENTRIES; e++) {
+            run_exit[t][e] = cur[e];
+            run_count[t][e] = acc[e];
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        int e = entry0;
+        long b = base0;
+        for (int j = 0; j < 256; j++) {
+            run_entry[j] = (unsigned char)e;
+            run_base[j] = b;
+            b += run_count[j][e];
+            e = run_exit[j][e];
+        }
+        res[0] = e;
+        res[1] = b;
+    }
+    __syncthreads();
+    int e = run_entry[t];
+    long b = run_base[t];
+    for (long i = t0; i < t1; i++) {
+        entry_t[i] = (unsigned char)e;
+        base_t[i] = b;
+        const long at = i * ZIG_ENTRIES + e;
+        b += count_t[at];
+        e = exit_t[at];
+    }
+}
+
+// info (device): [0] outputs the `count` draws consume (written by the owner of the last draw), [1] consumed attempts off the fast path,
+// [2] tail draws, [3] 1: a consumed attempt was undecided, 2: more tail draws than tail_cap
+__global__ __launch_bounds__(256) void zig_emit_kernel(U128 state, const u64 *__restrict__ jumps, U128 start, u64 start_rel, int P, int levels, double guard,
+                                                       const unsigned char *__restrict__ entry_t, const long *__restrict__ base_t, long count,
+                                                       double *__restrict__ out, long *__restrict__ tail_idx, u64 *__restrict__ tail_raw, long tail_cap,
+                                                       u64 *__restrict__ info)
+{
+    extern __shared__ u64 lds[];
+    const long tile = blockIdx.x;
+    const long base = base_t[tile];
+    if (base >= count) return;  // (the whole workgroup)
+    U128 *tab = (U128 *)lds;
+    u64 *raw = lds + ZIG_LDS_HEAD / 8;                            // [P + ZIG_HALO]
+    const int n = P + ZIG_ENTRIES;
+    unsigned short *lev = (unsigned short *)(raw + P + ZIG_HALO);  // [levels][n]: next^(2^l)
+    unsigned int *scan = (unsigned int *)(lev + (size_t)levels * n + ((size_t)levels * n & 1));  // [256]
+    unsigned char *kind = (unsigned char *)(scan + 256);           // [P]
+    unsigned char *mark = kind + P;                                // [P]
+    const int t = threadIdx.x;
+    load_jumps(tab, jumps);
+    __syncthreads();
+    tile_outputs(state, start, tile, P, P + ZIG_HALO, tab, raw);
+    __syncthreads();
+    for (int p = t; p < n; p += blockDim.x) {
+        int to = p;
+        if (p < P) {
+            const ZigAttempt a = zig_attempt((const uint64_t *)raw + p, ZIG_WI, (const uint64_t *)ZIG_KI, ZIG_FI, guard);
+            to = p + a.adv;
+            kind[p] = (unsigned char)a.kind;
+            mark[p] = 0;
+        }
+        lev[p] = (unsigned short)to;
+    }
+    __syncthreads();
+    for (int l = 1; l < levels; l++) {
+        const unsigned short *li = lev + (size_t)(l - 1) * n;
+        unsigned short *lo = lev + (size_t)l * n;
+        for (int p = t; p < n; p += blockDim.x) lo[p] = li[li[p]];
+        __syncthreads();
+    }
+    const int entry = entry_t[tile];
+    if (t == 0 && entry < P) mark[entry] = 1;
+    __syncthreads();
+    // level l: the marked positions are those at a chain index that is a multiple of 2^(l + 1); each marks the one 2^l further.  (A
+    // position marked in this very pass may act too: what it marks is 2^(l + 1) past a marked one, so marked already.)
+    for (int l = levels - 1; l >= 0; l--) {
+        const unsigned short *ll = lev + (size_t)l * n;
+        for (int p = t; p < P; p += blockDim.x)
+            if (mark[p]) {
+                const int q = ll[p];
+                if (q < P) mark[q] = 1;
+            }
+        __syncthreads();
+    }
+    // ranks: a thread owns `per` consecutive positions
+    const int per = (P + (int)blockDim.x - 1) / (int)blockDim.x, p0 = min(P, t * per), p1 = min(P, p0 + per);
+    unsigned int mine = 0;
+    for (int p = p0; p < p1; p++) mine += (mark[p] && zig_emits(kind[p])) ? 1u : 0u;
+    scan[t] = mine;
+    __syncthreads();
+    for (int off = 1; off < (int)blockDim.x; off <<= 1) {
+        const unsigned int v = t >= off ? scan[t - off] : 0u;
+        __syncthreads();
+        scan[t] += v;
+        __syncthreads();
+    }
+    long r = base + (long)(scan[t] - mine);
+    unsigned int slow = 0, flags = 0;
+    for (int p = p0; p < p1 && r < count; p++) {
+        if (!mark[p]) continue;
+        const int k = kind[p];
+        if (k != ZIG_FAST) slow++;
+        if (k == ZIG_UNDECIDED) flags |= 1u;
+        if (!zig_emits(k)) continue;
+        const ZigAttempt a = zig_attempt((const uint64_t *)raw + p, ZIG_WI, (const uint64_t *)ZIG_KI, ZIG_FI, guard);
+        out[r] = a.value;
+        if (k == ZIG_TAIL) {
+            const long slot = (long)atomicAdd(&info[2], 1ull);
+            if (slot < tail_cap) {
+                tail_idx[slot] = r;
+                tail_raw[2 * slot] = raw[p];
+                tail_raw[2 * slot + 1] = a.word;
+            } else {
+                flags |= 2u;
+            }
+        }
+        if (r == count - 1) info[0] = start_rel + (u64)tile * (u64)P + (u64)lev[p];
+        r++;
+    }
+    if (slow) atomicAdd(&info[1], (u64)slow);
+    if (flags) atomicOr(&info[3], (u64)flags);
+}
+
+}  // namespace
+
+size_t zig_lds_bytes(int P, int levels)
+{
+    const size_t n = (size_t)P + ZIG_ENTRIES, head = ZIG_LDS_HEAD + ((size_t)P + ZIG_HALO) * 8;
+    const size_t map = head + 4 * n * 2, emit = head + align_up((size_t)levels * n * 2, 4) + 256 * 4 + 2 * (size_t)P;
+    return map > emit ? map : emit;
+}
+
+int launch_zig_chunk(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const unsigned long long start[2],
+                     unsigned long long start_rel, int P, long tiles, int entry0, long base0, double guard, unsigned char *exit_t, unsigned short *count_t,
+                     unsigned char *entry_t, long *base_t, long *res, long count, double *out, long *tail_idx, unsigned long long *tail_raw, long tail_cap,
+                     unsigned long long *info)
+{
+    int levels = 0;
+    while ((1 << levels) < P) levels++;
+    const int emit_levels = levels > 0 ? levels : 1;
+    const unsigned lds = (unsigned)zig_lds_bytes(P, emit_levels);
+    const U128 s{state[0], state[1]}, st{start[0], start[1]};
+    {
+        ProfScope ps(ctx, "zig_map");
+        hipLaunchKernelGGL(zig_map_kernel, dim3((unsigned)tiles), dim3(256), lds, ctx->stream, s, jumps, st, P, levels, guard, exit_t, count_t);
+        IMCOM_TRY(check_launch("zig_map_kernel"));
+    }
+    {
+        ProfScope ps(ctx, "zig_chain");
+        hipLaunchKernelGGL(zig_chain_kernel, dim3(1), dim3(256), 0, ctx->stream, exit_t, count_t, tiles, entry0, base0, entry_t, base_t, res);
+        IMCOM_TRY(check_launch("zig_chain_kernel"));
+    }
+    ProfScope ps(ctx, "zig_emit");
+    hipLaunchKernelGGL(zig_emit_kernel, dim3((unsigned)tiles), dim3(256), lds, ctx->stream, s, jumps, st, start_rel, P, emit_levels, guard, entry_t, base_t,
+                       count, out, tail_idx, tail_raw, tail_cap, info);
+    return check_launch("zig_emit_kernel");
+}
+
+}  // namespace imcom
