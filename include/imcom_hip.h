@@ -836,6 +836,47 @@ int imcom_quant_set_ranks(imcom_ctx *ctx, imcom_quant *q, const long *ranks);
 int imcom_quant_results(imcom_ctx *ctx, const imcom_quant *q, void *out);
 int imcom_codehist(imcom_ctx *ctx, const void *codes, long rows, long cols, long pitch, const unsigned char *table, int nbins, long *counts, int memspace);
 
+/* The I24 layer codec (reference src/pyimcom/compress/i24.py: I24Cube.to_mode 367-437, i24compress 443-478, i24decompress 481-514, and the
+ * helpers lsbf_fwd / lsbf_rev 41-122, diff_fwd / diff_rev 128-181, smallnum_fwd / smallnum_rev 187-237) for a batch of L layers of ny x nx
+ * pixels with a parameter record each; scheme 0 is I24A (int32 codes), 1 is I24B (byte planes [nb][ny][nx], nb = (BITKEEP + 7) / 8, least
+ * significant first, with REORDER as bit streams).  Every result equals the reference's bit for bit, from run to run: one owner thread an
+ * output element, integer arithmetic, float32 steps rounded one by one, the float64 product and sum of 415 rounded separately.
+ * Served is ALPHA == 1 only (IMCOM_ERR_UNSUPPORTED otherwise: the power is numpy's float32 pow).  IMCOM_ERR_ARG: VMAX <= VMIN or either not
+ * finite, BITKEEP outside 1 .. 24, SOFTBIAS >= 2^24 (0 .. 2^24 - 1 and -1 are served, any other negative value does nothing, as in the
+ * reference), ny nx >= 2^31, L outside 1 .. 4096.  A NaN pixel gets code 0 and no table entry: numpy's cast of NaN to int32 on x86-64
+ * followed by the clip of 378.  +inf and -inf are overflow entries.
+ * EVERY array is DEVICE memory except pars and counts (HOST).  There is no memspace: a layer that has to cross to the host crosses as codes.
+ *   imcom_i24_sizes           no context: checks the parameters (the refusals above) and gives out[8] = {bytes of `state`, workspace bytes of
+ *                             a compress call, of a decompress call, bytes of one layer of compressed output (the largest nb of the batch),
+ *                             tiles a layer, pixels a tile, tile sums a step of the scan, 0}.
+ *   imcom_i24_compress        367-386 and 423-437.  frames: float32, pixel (l, y, x) at frames[l layer_stride + y row_stride + x] (in
+ *                             elements; a crop of a larger array is read in place).  Layer l of the result at (char *)out + l out_stride
+ *                             (bytes).  counts [L] (HOST): the overflow entries of every layer; the call waits for them.  `state` keeps
+ *                             what imcom_i24_overflow_fetch needs and must stay untouched until then.
+ *   imcom_i24_overflow_fetch  368-375, once the counts are known: the table of layer l, in ascending flat pixel order (np.where's), at
+ *                             entries sum(counts[:l]) .. of y / x (int32) and value (float32); frames, pars, state and counts as in the
+ *                             compress call, the frames unchanged since.  capacity: entries the three arrays hold; nothing is written at or
+ *                             beyond it, nor beyond a layer's count.  IMCOM_ERR_ARG: capacity < sum(counts).
+ *   imcom_i24_decompress      388-420.  Layer l of the input at (const char *)in + l in_stride; planes: the first axis of an I24B cube,
+ *                             IMCOM_ERR_ARG if it is not nb.  No bit is masked that the reference does not mask.  DIFF: an inclusive
+ *                             wrapping prefix sum over the flat image in three launches (tile sums, their scan, the sum inside the tiles);
+ *                             no workgroup waits for another.  The overflow table (counts NULL: none) as imcom_i24_overflow_fetch lays it
+ *                             out; out[l][y][x] = value.  A position outside the image is not stored and the call returns IMCOM_ERR_ARG
+ *                             (it waits for that answer whenever a table is given).  Positions of one layer are unique in tables this
+ *                             codec writes; with duplicates which value stays is unspecified.  out: float32 [L][ny][nx]. */
+typedef struct {
+    double vmin, vmax, alpha; /* float(pars["VMIN"]), float(pars["VMAX"]), float(pars["ALPHA"]) or 1 */
+    long softbias;            /* int(pars["SOFTBIAS"]) or 0 */
+    int bitkeep, diff, reorder; /* BITKEEP or 24; bool(pars["DIFF"]) or 0; bool(pars["REORDER"]) or 1 */
+} imcom_i24_pars;
+int imcom_i24_sizes(int L, long ny, long nx, const imcom_i24_pars *pars, int scheme, long *out);
+int imcom_i24_compress(imcom_ctx *ctx, const float *frames, long layer_stride, long row_stride, int L, int ny, int nx, const imcom_i24_pars *pars, int scheme,
+                       void *out, long out_stride, void *state, size_t state_bytes, long *counts);
+int imcom_i24_overflow_fetch(imcom_ctx *ctx, const float *frames, long layer_stride, long row_stride, int L, int ny, int nx, const imcom_i24_pars *pars,
+                             const void *state, size_t state_bytes, const long *counts, int *y, int *x, float *value, long capacity);
+int imcom_i24_decompress(imcom_ctx *ctx, const void *in, long in_stride, int planes, int scheme, int L, int ny, int nx, const imcom_i24_pars *pars, const int *y,
+                         const int *x, const float *value, const long *counts, float *out);
+
 #ifdef __cplusplus
 }
 #endif

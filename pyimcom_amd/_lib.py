@@ -31,6 +31,10 @@ class TableGeom(C.Structure):
     _fields_ = [("nsamp", C.c_int), ("nc", C.c_double), ("dscale", C.c_double), ("flat_penalty", C.c_double)]
 
 
+class I24Pars(C.Structure):  # imcom_i24_pars
+    _fields_ = [("vmin", C.c_double), ("vmax", C.c_double), ("alpha", C.c_double), ("softbias", C.c_long), ("bitkeep", C.c_int), ("diff", C.c_int), ("reorder", C.c_int)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -178,6 +182,10 @@ SIGNATURES = {
     "imcom_quant_set_ranks": [_vp, _vp, _vp],
     "imcom_quant_results": [_vp, _vp, _vp],
     "imcom_codehist": [_vp, _vp, _l, _l, _l, _vp, _i, _vp, _i],
+    "imcom_i24_sizes": [_i, _l, _l, _vp, _i, _vp],
+    "imcom_i24_compress": [_vp, _vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _l, _vp, C.c_size_t, _vp],
+    "imcom_i24_overflow_fetch": [_vp, _vp, _l, _l, _i, _i, _i, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _l],
+    "imcom_i24_decompress": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

@@ -175,6 +175,26 @@ class BlockMaps:
             return power_spectrum_2d(view[idx[0]:idx[-1] + 1:step], norms, window, bin8, ctx=self.ctx)
         return torch.cat([power_spectrum_2d(view[i:i + 1], norms[k:k + 1], window, bin8, ctx=self.ctx) for k, i in enumerate(idx)])
 
+    def compress_layers(self, layer_indices, pars_list, scheme="I24B", out=0, fk=0):
+        """The I24 codec (``pyimcom_amd.i24``; reference compress/compressutils.py ``CompressedOutput.compress_layer``) over input layers of
+        this block without a copy to the host: layer ``i`` of ``layer_indices`` is ``out_map[out, i]`` cropped by ``fk`` on every side, as
+        ``build_output_file`` crops, read in place, with the parameter dict ``pars_list[k]``.  Layer 0, the science layer, is refused as
+        ``compress_layer`` refuses it (238-239).  Returns (cubes, overflows) as ``i24.compress_layers`` does.  Call it after ``finalize``."""
+        from .i24 import compress_layers
+
+        idx = [int(i) for i in layer_indices]
+        pars_list = list(pars_list)
+        if len(pars_list) != len(idx):
+            raise ValueError(f"compress_layers: {len(idx)} layers and {len(pars_list)} parameter dicts")
+        if any(i == 0 for i in idx):
+            raise ValueError("compress_layers: layer 0 is the science layer and is not compressed")
+        view = self.out_map[out][:, fk:self.nside - fk, fk:self.nside - fk]
+        step = idx[1] - idx[0] if len(idx) > 1 else 1
+        if step > 0 and all(b - a == step for a, b in zip(idx, idx[1:])):  # one call: the layers are evenly strided frames of the view
+            return compress_layers(view[idx[0]:idx[-1] + 1:step], pars_list, scheme, ctx=self.ctx, device=self.device)
+        parts = [compress_layers(view[i:i + 1], [p], scheme, ctx=self.ctx, device=self.device) for i, p in zip(idx, pars_list)]
+        return [c for cs, _ in parts for c in cs], [o for _, os_ in parts for o in os_]
+
     def report_views(self, out=0, pad=0):
         """The block's frames for the validation report's statistics (``pyimcom_amd.reportstats``) without a copy: ``out_map[out]``
         cropped by the fade margin plus ``pad`` pixels on every side (the reference's ``postage_pad * n2``: the unique area that

@@ -7,6 +7,7 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "i24_core.h"
 #include "quantiles_core.h"
 #include "ziggurat_core.h"
 
@@ -2934,6 +2935,224 @@ int imcom_codehist(imcom_ctx *ctx, const void *codes, long rows, long cols, long
     IMCOM_TRY(launch_codehist(ctx, c_d, rows, cols, pitch, t_d, nbins, (unsigned long long *)n_d));
     IMCOM_TRY(st.back(counts, (const long *)n_d, (size_t)nbins + 1));
     return st.done();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The I24 layer codec (i24.hip, i24_core.h)
+}  // extern "C"
+
+namespace {
+constexpr int I24_MAX_LAYERS = 4096;
+
+// The refusals of the codec and the records the kernels read (rec may be NULL: check only).
+int i24_records(int L, long ny, long nx, const imcom_i24_pars *pars, I24Par *rec)
+{
+    IMCOM_REQUIRE(pars, "i24: null parameters");
+    IMCOM_REQUIRE(L >= 1 && L <= I24_MAX_LAYERS, "i24: %d layers, served are 1 .. %d", L, I24_MAX_LAYERS);
+    IMCOM_REQUIRE(ny >= 1 && nx >= 1 && ny <= 0x7fffffffL / nx, "i24: %ld x %ld pixels, served are 1 .. 2^31 - 1 a layer", ny, nx);
+    for (int l = 0; l < L; l++) {
+        const imcom_i24_pars &p = pars[l];
+        if (!(p.alpha == 1.0)) {
+            set_error("i24: layer %d has ALPHA = %g; only the linear codec (ALPHA absent or 1) is served: the power goes through numpy's float32 pow, whose last bit cannot be reproduced", l, p.alpha);
+            return IMCOM_ERR_UNSUPPORTED;
+        }
+        IMCOM_REQUIRE(std::isfinite(p.vmin) && std::isfinite(p.vmax) && p.vmax > p.vmin, "i24: layer %d has VMIN = %g, VMAX = %g; both must be finite and VMAX > VMIN", l, p.vmin,
+                      p.vmax);
+        IMCOM_REQUIRE(p.bitkeep >= 1 && p.bitkeep <= 24, "i24: layer %d has BITKEEP = %d outside 1 .. 24", l, p.bitkeep);
+        IMCOM_REQUIRE(p.softbias < (1L << 24), "i24: layer %d has SOFTBIAS = %ld; served are 0 .. 2^24 - 1 and -1", l, p.softbias);
+        if (!rec) continue;
+        I24Par &r = rec[l];
+        r.vmin = p.vmin;
+        r.range = p.vmax - p.vmin;
+        r.vmin_f = (float)p.vmin;
+        r.vmax_f = (float)p.vmax;
+        r.range_f = (float)r.range;
+        r.scale_f = (float)(1 << p.bitkeep);
+        r.bitkeep = p.bitkeep;
+        r.nb = (p.bitkeep + 7) / 8;
+        r.softbias = p.softbias > 0 ? (int)p.softbias : (p.softbias == -1 ? -1 : 0);  // (any other negative value does nothing, as in the reference)
+        r.diff = p.diff != 0;
+        r.reorder = p.reorder != 0;
+        r.pad = 0;
+    }
+    return IMCOM_OK;
+}
+
+long i24_layer_bytes(int L, long n, const imcom_i24_pars *pars, int scheme)
+{
+    int nb = 1;
+    for (int l = 0; l < L; l++) nb = std::max(nb, (pars[l].bitkeep + 7) / 8);
+    return scheme == I24_SCHEME_A ? 4 * n : (long)nb * n;
+}
+
+size_t i24_state_bytes(int L, long n) { return ((size_t)L * i24_tiles(n) + L) * 4; }
+
+int i24_scheme(int scheme)
+{
+    IMCOM_REQUIRE(scheme == I24_SCHEME_A || scheme == I24_SCHEME_B, "i24: scheme %d is neither 0 (I24A) nor 1 (I24B)", scheme);
+    return IMCOM_OK;
+}
+
+int i24_view(long layer_stride, long row_stride, int nx)
+{
+    IMCOM_REQUIRE(row_stride >= nx && layer_stride >= 0, "i24: a view of rows %ld and layers %ld elements apart for %d columns", row_stride, layer_stride, nx);
+    return IMCOM_OK;
+}
+
+// layer_off [L + 1] on the device from the host counts; *max_count, *total.
+int i24_offsets(imcom_ctx *ctx, int L, const long *counts, long *off_d, long *max_count, long *total)
+{
+    std::vector<long> off(L + 1, 0);
+    *max_count = 0;
+    for (int l = 0; l < L; l++) {
+        const long c = counts ? counts[l] : 0;
+        IMCOM_REQUIRE(c >= 0, "i24: %ld overflow entries for layer %d", c, l);
+        off[l + 1] = off[l] + c;
+        *max_count = std::max(*max_count, c);
+    }
+    *total = off[L];
+    return upload(ctx, off_d, off.data(), (size_t)L + 1);
+}
+}  // namespace
+
+extern "C" {
+
+int imcom_i24_sizes(int L, long ny, long nx, const imcom_i24_pars *pars, int scheme, long *out)
+{
+    IMCOM_REQUIRE(out, "null pointer");
+    IMCOM_TRY(i24_scheme(scheme));
+    IMCOM_TRY(i24_records(L, ny, nx, pars, nullptr));
+    const long n = ny * nx, tiles = i24_tiles(n);
+    WsPlan c, d;
+    c.add((size_t)L * sizeof(I24Par));
+    c.add((size_t)L * n * 4);
+    d.add((size_t)L * sizeof(I24Par));
+    d.add((size_t)L * n * 4);
+    d.add((size_t)L * tiles * 4);
+    d.add((size_t)L * 4);
+    d.add((size_t)(L + 1) * 8);
+    d.add(4);
+    out[0] = (long)i24_state_bytes(L, n);
+    out[1] = (long)c.total;
+    out[2] = (long)d.total;
+    out[3] = i24_layer_bytes(L, n, pars, scheme);
+    out[4] = tiles;
+    out[5] = I24_TILE;
+    out[6] = I24_SCAN_CHUNK;
+    out[7] = 0;
+    return IMCOM_OK;
+}
+
+int imcom_i24_compress(imcom_ctx *ctx, const float *frames, long layer_stride, long row_stride, int L, int ny, int nx, const imcom_i24_pars *pars, int scheme,
+                       void *out, long out_stride, void *state, size_t state_bytes, long *counts)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(frames && out && state && counts, "null pointer");
+    IMCOM_TRY(i24_scheme(scheme));
+    std::vector<I24Par> rec((size_t)std::max(L, 1));
+    IMCOM_TRY(i24_records(L, ny, nx, pars, rec.data()));
+    IMCOM_TRY(i24_view(layer_stride, row_stride, nx));
+    const long n = (long)ny * nx, tiles = i24_tiles(n);
+    IMCOM_REQUIRE(out_stride >= i24_layer_bytes(L, n, pars, scheme) && (scheme == I24_SCHEME_B || (out_stride % 4 == 0 && ((uintptr_t)out & 3) == 0)),
+                  "i24_compress: layers %ld bytes apart in the output, needed are %ld (I24A: int32-aligned)", out_stride, i24_layer_bytes(L, n, pars, scheme));
+    IMCOM_REQUIRE(state_bytes >= i24_state_bytes(L, n) && ((uintptr_t)state & 3) == 0, "i24_compress: state of %zu bytes, needed are %zu (4-byte aligned)", state_bytes,
+                  i24_state_bytes(L, n));
+    WsPlan plan;
+    plan.add((size_t)L * sizeof(I24Par));
+    plan.add((size_t)L * n * 4);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    I24Par *par_d;
+    int *codes;
+    IMCOM_TRY(ws_take(ctx, (size_t)L, &par_d, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)L * n, &codes, __func__));
+    IMCOM_TRY(upload(ctx, par_d, rec.data(), (size_t)L));
+    uint32_t *bases = (uint32_t *)state, *totals = bases + (size_t)L * tiles;
+    IMCOM_TRY(launch_i24_quantise(ctx, frames, layer_stride, row_stride, L, ny, nx, par_d, codes, bases, totals));
+    IMCOM_TRY(launch_i24_pack(ctx, codes, L, n, par_d, scheme, (unsigned char *)out, out_stride));
+    std::vector<uint32_t> tot((size_t)L);
+    IMCOM_HIP_CHECK(hipMemcpyAsync(tot.data(), totals, (size_t)L * 4, hipMemcpyDeviceToHost, ctx->stream));
+    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (int l = 0; l < L; l++) counts[l] = (long)tot[l];
+    return IMCOM_OK;
+}
+
+int imcom_i24_overflow_fetch(imcom_ctx *ctx, const float *frames, long layer_stride, long row_stride, int L, int ny, int nx, const imcom_i24_pars *pars,
+                             const void *state, size_t state_bytes, const long *counts, int *y, int *x, float *value, long capacity)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(frames && state && counts, "null pointer");
+    std::vector<I24Par> rec((size_t)std::max(L, 1));
+    IMCOM_TRY(i24_records(L, ny, nx, pars, rec.data()));
+    IMCOM_TRY(i24_view(layer_stride, row_stride, nx));
+    const long n = (long)ny * nx, tiles = i24_tiles(n);
+    IMCOM_REQUIRE(state_bytes >= i24_state_bytes(L, n) && ((uintptr_t)state & 3) == 0, "i24_overflow_fetch: state of %zu bytes, needed are %zu (4-byte aligned)", state_bytes,
+                  i24_state_bytes(L, n));
+    WsPlan plan;
+    plan.add((size_t)L * sizeof(I24Par));
+    plan.add((size_t)(L + 1) * 8);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    I24Par *par_d;
+    long *off_d, max_count, total;
+    IMCOM_TRY(ws_take(ctx, (size_t)L, &par_d, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)L + 1, &off_d, __func__));
+    IMCOM_TRY(i24_offsets(ctx, L, counts, off_d, &max_count, &total));
+    IMCOM_REQUIRE(capacity >= total, "i24_overflow_fetch: a table of %ld entries, the layers have %ld", capacity, total);
+    if (total == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(y && x && value, "null pointer");
+    IMCOM_TRY(upload(ctx, par_d, rec.data(), (size_t)L));
+    const uint32_t *bases = (const uint32_t *)state, *totals = bases + (size_t)L * tiles;
+    return launch_i24_overflow(ctx, frames, layer_stride, row_stride, L, ny, nx, par_d, bases, totals, off_d, capacity, y, x, value);
+}
+
+int imcom_i24_decompress(imcom_ctx *ctx, const void *in, long in_stride, int planes, int scheme, int L, int ny, int nx, const imcom_i24_pars *pars, const int *y,
+                         const int *x, const float *value, const long *counts, float *out)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(in && out, "null pointer");
+    IMCOM_TRY(i24_scheme(scheme));
+    std::vector<I24Par> rec((size_t)std::max(L, 1));
+    IMCOM_TRY(i24_records(L, ny, nx, pars, rec.data()));
+    const long n = (long)ny * nx, tiles = i24_tiles(n);
+    bool any_diff = false;
+    for (int l = 0; l < L; l++) {
+        any_diff = any_diff || rec[l].diff;
+        IMCOM_REQUIRE(scheme == I24_SCHEME_A || planes == rec[l].nb, "i24_decompress: a cube of %d byte planes for layer %d, BITKEEP = %d needs %d", planes, l, rec[l].bitkeep,
+                      rec[l].nb);
+    }
+    const long need = scheme == I24_SCHEME_A ? 4 * n : (long)planes * n;
+    IMCOM_REQUIRE(in_stride >= need && (scheme == I24_SCHEME_B || (in_stride % 4 == 0 && ((uintptr_t)in & 3) == 0)),
+                  "i24_decompress: layers %ld bytes apart in the input, needed are %ld (I24A: int32-aligned)", in_stride, need);
+    WsPlan plan;
+    plan.add((size_t)L * sizeof(I24Par));
+    plan.add((size_t)L * n * 4);
+    plan.add((size_t)L * tiles * 4);
+    plan.add((size_t)L * 4);
+    plan.add((size_t)(L + 1) * 8);
+    plan.add(4);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    I24Par *par_d;
+    int *codes;
+    uint32_t *sums, *totals;
+    long *off_d, max_count = 0, total = 0;
+    unsigned int *status;
+    IMCOM_TRY(ws_take(ctx, (size_t)L, &par_d, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)L * n, &codes, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)L * tiles, &sums, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)L, &totals, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)L + 1, &off_d, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)1, &status, __func__));
+    if (counts) IMCOM_TRY(i24_offsets(ctx, L, counts, off_d, &max_count, &total));
+    IMCOM_REQUIRE(total == 0 || (y && x && value), "i24_decompress: %ld overflow entries and no table", total);
+    IMCOM_TRY(upload(ctx, par_d, rec.data(), (size_t)L));
+    IMCOM_TRY(launch_i24_decode(ctx, (const unsigned char *)in, in_stride, scheme, L, n, par_d, any_diff, codes, sums, totals, out));
+    if (total == 0) return IMCOM_OK;
+    IMCOM_HIP_CHECK(hipMemsetAsync(status, 0, 4, ctx->stream));
+    IMCOM_TRY(launch_i24_patch(ctx, out, L, ny, nx, off_d, max_count, y, x, value, status));
+    unsigned int bad = 0;
+    IMCOM_HIP_CHECK(hipMemcpyAsync(&bad, status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    IMCOM_REQUIRE(bad == 0, "i24_decompress: the overflow table has a position outside the %d x %d image (it was not stored)", ny, nx);
+    return IMCOM_OK;
 }
 
 }  // extern "C"

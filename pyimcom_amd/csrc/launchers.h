@@ -271,4 +271,21 @@ int launch_quant_rings(imcom_ctx *ctx, const QtDev &d, bool f64, const void *fra
 int launch_quant_constant(imcom_ctx *ctx, const QtDev &d, bool f64, int seg, double value, unsigned long long count, int shift, int nbits);
 int launch_codehist(imcom_ctx *ctx, const unsigned short *codes, long rows, long cols, long pitch, const unsigned char *table, int nbins, unsigned long long *counts);
 
+// i24.hip: the I24 layer codec for a batch of L layers of ny x nx pixels (n = ny nx, tiles = i24_tiles(n) of I24_TILE pixels, i24_core.h).
+// pars [L] device records.  launch_i24_quantise: codes [L][n], counts [L][tiles] -> the exclusive prefix sums of the tiles' overflow hits,
+// totals [L].  launch_i24_pack: codes -> I24A int32 / I24B bytes, layer l at out + l out_stride (bytes).  launch_i24_overflow: the table
+// entries of layer l at layer_off[l] .. layer_off[l + 1] (device, [L + 1]) of oy / ox / ov, none at or beyond cap.  launch_i24_decode:
+// in -> codes (SOFTBIAS undone), sums [L][tiles] and totals [L] scratch of the prefix sum, out [L][n] float32.  launch_i24_patch: the
+// overflow entries into out; *status becomes non-zero if a position lies outside the image (it is not stored).
+struct I24Par;
+int launch_i24_quantise(imcom_ctx *ctx, const float *frames, long lstride, long rstride, int L, int ny, int nx, const I24Par *pars, int *codes, uint32_t *counts,
+                        uint32_t *totals);
+int launch_i24_pack(imcom_ctx *ctx, const int *codes, int L, long n, const I24Par *pars, int scheme, unsigned char *out, long out_stride);
+int launch_i24_overflow(imcom_ctx *ctx, const float *frames, long lstride, long rstride, int L, int ny, int nx, const I24Par *pars, const uint32_t *bases,
+                        const uint32_t *totals, const long *layer_off, long cap, int *oy, int *ox, float *ov);
+int launch_i24_decode(imcom_ctx *ctx, const unsigned char *in, long in_stride, int scheme, int L, long n, const I24Par *pars, bool any_diff, int *codes, uint32_t *sums,
+                      uint32_t *totals, float *out);
+int launch_i24_patch(imcom_ctx *ctx, float *out, int L, int ny, int nx, const long *layer_off, long max_count, const int *oy, const int *ox, const float *ov,
+                     unsigned int *status);
+
 }  // namespace imcom
