@@ -1,15 +1,12 @@
-// api.hip -- extern "C" entry points of libimcom_hip.so (see include/imcom_hip.h) and the host-side
-// orchestration of the batched blocked Cholesky solve.
+// api.hip -- the context, workspace and profiling helpers every source file calls (common.h), the extern "C" entries of the context and
+// the probes, the host-side orchestration of the batched blocked Cholesky solve with its entries, and the thin entries of interp.hip,
+// build_a.hip and la_kernels.hip.  Every other seam's entries (include/imcom_hip.h) end the file that holds its kernels.
 #include <chrono>
 #include <cmath>
-#include <cstdlib>
 #include <functional>
 
 #include "common.h"
 #include "launchers.h"
-#include "i24_core.h"
-#include "quantiles_core.h"
-#include "ziggurat_core.h"
 
 namespace imcom {
 
@@ -1594,1565 +1591,6 @@ int imcom_clamp_min_f32(imcom_ctx *ctx, float *maps, long count, float lo)
     IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(count >= 0 && (count == 0 || maps), "bad arguments");
     return launch_clamp_min_f32(ctx, maps, count, lo);
-}
-
-// ---------------------------------------------------------------------------------------------
-// injected star layers (inject.hip)
-int imcom_psf_from_cube(imcom_ctx *ctx, int na, const double *cube, int ny, int nx, int nstar, const double *lpoly, double tophatwidth,
-                        double gaussiansigma, double scale, double *out, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(na >= 1 && cube && ny >= 1 && nx >= 1 && nstar >= 0 && (nstar == 0 || (lpoly && out)), "bad arguments");
-    IMCOM_REQUIRE(tophatwidth >= 0.0 && gaussiansigma >= 0.0 && tophatwidth + 6.0 * gaussiansigma < 4096.0 && scale == scale,
-                  "bad smearing widths or scale");
-    if (nstar == 0) return IMCOM_OK;
-    Stage st(ctx, memspace, __func__);
-    const int npad = imcom_smooth_pad_width(tophatwidth, gaussiansigma), nyy = ny + 2 * npad, nxx = nx + 2 * npad;
-    const size_t szCube = (size_t)na * ny * nx, szL = (size_t)nstar * na, npix = (size_t)nyy * nxx, szOut = (size_t)nstar * npix;
-    WsPlan plan;
-    plan.add(smooth_pad_ws_bytes(na, ny, nx, tophatwidth, gaussiansigma));
-    plan.add((size_t)na * npix * 8);
-    st.plan(plan, {szCube * 8, szL * 8, szOut * 8});
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    SmoothPadWs w;
-    IMCOM_TRY(smooth_pad_take(ctx, na, ny, nx, tophatwidth, gaussiansigma, &w, __func__));
-    double *planes, *out_d;
-    IMCOM_TRY(ws_take(ctx, (size_t)na * npix, &planes, __func__));
-    const double *cube_d, *lpoly_d;
-    IMCOM_TRY(st.in(cube, szCube, &cube_d));
-    IMCOM_TRY(st.in(lpoly, szL, &lpoly_d));
-    IMCOM_TRY(st.out(out, szOut, &out_d));
-    IMCOM_TRY(smooth_pad_device(ctx, w, na, cube_d, ny, nx, tophatwidth, gaussiansigma, planes));
-    IMCOM_TRY(launch_cube_contract(ctx, planes, na, (long)npix, lpoly_d, nstar, scale, out_d));
-    IMCOM_TRY(st.back(out, out_d, szOut));
-    return st.done();
-}
-
-int imcom_draw_stars(imcom_ctx *ctx, int nstar, const double *psfs, int py, int px, const double *xsca, const double *ysca, double oversamp,
-                     int d, int nside, double *image, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(nstar >= 0 && image && (nstar == 0 || (psfs && xsca && ysca)), "null pointer");
-    IMCOM_REQUIRE(py >= 1 && px >= 1 && py <= 16384 && px <= 16384 && d >= 1 && d <= 65536 && nside >= 1 && nside <= 65536, "bad sizes");
-    IMCOM_REQUIRE(oversamp >= 1.0e-3 && oversamp <= 1.0e6, "oversamp %g out of range", oversamp);
-    if (nstar == 0) return IMCOM_OK;
-    Stage st(ctx, memspace, __func__);
-    const size_t szP = (size_t)nstar * py * px, szI = (size_t)nside * nside;
-    WsPlan plan;
-    st.plan(plan, {szP * 8, (size_t)nstar * 8, (size_t)nstar * 8, szI * 8});
-    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const double *p_d, *x_d, *y_d;
-    double *img_d;
-    IMCOM_TRY(st.in(psfs, szP, &p_d));
-    IMCOM_TRY(st.in(xsca, (size_t)nstar, &x_d));
-    IMCOM_TRY(st.in(ysca, (size_t)nstar, &y_d));
-    IMCOM_TRY(st.inout(image, szI, &img_d));  // the stars are added to what the image holds
-    IMCOM_TRY(launch_draw_stars(ctx, nstar, p_d, py, px, x_d, y_d, oversamp, d, nside, img_d));
-    IMCOM_TRY(st.back(image, img_d, szI));
-    return st.done();
-}
-
-// ---------------------------------------------------------------------------------------------
-// the long-range PSF part of an SCA image (imsubtract.hip)
-int imcom_imsub_sizes(int ax, int s, int nside, int Nl, long *out)
-{
-    IMCOM_REQUIRE(out, "null out");
-    IMCOM_REQUIRE(s >= 2 && s <= 64 && ax >= s && ax <= 16384 && nside >= 1 && nside <= 65536 && Nl >= 1 && Nl <= 16,
-                  "imsubtract: oversamp %d, axis_num %d, nside %d or Nl %d out of range", s, ax, nside, Nl);
-    IMCOM_REQUIRE(ax % (2 * s) == 0 || (s % 2 == 1 && ax % s == 0), "axis_num=%d must be a multiple of 2*oversamp, oversamp=%d", ax, s);
-    const long ipad = (ax + 2 * s - 1) / (2 * s), np = ax / s, npp = (np + 7) / 8 * 8;  // imsubtract.py:387-389, 451
-    out[0] = ipad;
-    out[1] = (s + 2 * s * ipad - ax) / 2;
-    out[2] = (long)s * (nside + 2 * ipad);
-    out[3] = np;
-    out[4] = npp;
-    out[5] = (long)Nl * Nl * s * s * np * npp;
-    return IMCOM_OK;
-}
-
-int imcom_imsub_prepare_kernel_f32(imcom_ctx *ctx, const float *K, int ncoeff, int ax, int Nl, int s, double *kf, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    long sz[6];
-    IMCOM_TRY(imcom_imsub_sizes(ax, s, 1, Nl, sz));
-    IMCOM_REQUIRE(K && kf, "null pointer");
-    IMCOM_REQUIRE(ncoeff >= 1 && Nl * Nl <= ncoeff, "imsubtract: Nl=%d needs %d kernel planes, the cube has %d", Nl, Nl * Nl, ncoeff);
-    Stage st(ctx, memspace, __func__);
-    const size_t szK = (size_t)Nl * Nl * ax * ax;
-    WsPlan plan;
-    st.plan(plan, {szK * 4});
-    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const float *K_d;
-    IMCOM_TRY(st.in(K, szK, &K_d));
-    IMCOM_TRY(launch_imsub_prepare(ctx, K_d, ax, s, Nl, kf));
-    return st.done();
-}
-
-int imcom_imsub_canvas_add_f32(imcom_ctx *ctx, float *canvas, int A, const double *H, int hh, int hw, const float *area, int s, int row0, int col0,
-                               int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(canvas && H && area, "null pointer");
-    IMCOM_REQUIRE(s >= 1 && A >= 1 && A <= 1 << 20 && hh >= 0 && hw >= 0 && hh % s == 0 && hw % s == 0, "imsubtract: the block is %d x %d, oversamp %d", hh,
-                  hw, s);
-    IMCOM_REQUIRE(row0 >= 0 && col0 >= 0 && (long)row0 + hh <= A && (long)col0 + hw <= A, "imsubtract: block %d x %d at (%d, %d) leaves the %d x %d canvas",
-                  hh, hw, row0, col0, A, A);
-    if (hh == 0 || hw == 0) return IMCOM_OK;
-    Stage st(ctx, memspace, __func__);
-    const size_t szC = (size_t)A * A, szH = (size_t)hh * hw, szA = szH / ((size_t)s * s);
-    WsPlan plan;
-    st.plan(plan, {szC * 4, szH * 8, szA * 4});
-    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
-    float *c_d;
-    const double *H_d;
-    const float *a_d;
-    IMCOM_TRY(st.inout(canvas, szC, &c_d));
-    IMCOM_TRY(st.in(H, szH, &H_d));
-    IMCOM_TRY(st.in(area, szA, &a_d));
-    IMCOM_TRY(launch_imsub_canvas_add(ctx, c_d, A, H_d, hh, hw, a_d, s, row0, col0));
-    IMCOM_TRY(st.back(canvas, (const float *)c_d, szC));
-    return st.done();
-}
-
-int imcom_imsub_convolve_subtract_f32(imcom_ctx *ctx, const float *canvas, int A, long crow0, long crows, const float *K, const double *kf, int ncoeff,
-                                      int ax, int Nl, int s, int nside, int y0, int ny, float *image, double *kh, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    long sz[6];
-    IMCOM_TRY(imcom_imsub_sizes(ax, s, nside, Nl, sz));
-    const long first = sz[1];
-    IMCOM_REQUIRE(canvas && image && (K || kf), "null pointer");
-    IMCOM_REQUIRE(ncoeff >= 1 && Nl * Nl <= ncoeff, "imsubtract: Nl=%d needs %d kernel planes, the cube has %d", Nl, Nl * Nl, ncoeff);
-    IMCOM_REQUIRE(A == sz[2], "imsubtract: the canvas is %d on a side, oversamp * (nside + 2 * I_pad) = %ld", A, sz[2]);
-    IMCOM_REQUIRE(y0 >= 0 && ny >= 0 && (long)y0 + ny <= nside, "imsubtract: rows %d .. %d of an image of %d", y0, y0 + ny, nside);
-    if (ny == 0) return IMCOM_OK;
-    IMCOM_REQUIRE(crow0 >= 0 && crows >= 1 && crow0 + crows <= A && crow0 <= first + (long)s * y0 && crow0 + crows >= first + (long)s * (y0 + ny - 1) + ax,
-                  "imsubtract: canvas rows %ld .. %ld do not cover rows %ld .. %ld", crow0, crow0 + crows, first + (long)s * y0,
-                  first + (long)s * (y0 + ny - 1) + ax);
-    Stage st(ctx, memspace, __func__);
-    const size_t szC = (size_t)crows * A, szK = (size_t)Nl * Nl * ax * ax, szI = (size_t)ny * nside, szL = (size_t)Nl * A;
-    WsPlan plan;
-    plan.add(szL * 4);
-    if (!kf) plan.add((size_t)sz[5] * 8);
-    st.plan(plan, {szC * 4, szI * 4});
-    if (st.host && !kf) plan.add(szK * 4);
-    if (st.host && kh) plan.add(szI * 8);
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-
-    // P_l(u) of the canvas coordinates, float64 rounded to float32 (imsubtract.py:487-488, 695-696)
-    std::vector<float> leg(szL);
-    {
-        const double ipad = (double)sz[0], a = -ipad - 0.5 + 0.5 / s, b = nside + ipad - 0.5 - 0.5 / s, step = (b - a) / (A - 1);
-        for (long i = 0; i < A; i++) {
-            double x = (double)i * step;  // numpy.linspace: arange * step, then + start; the last sample is the stop itself
-            x = x + a;
-            if (i == A - 1) x = b;
-            const double u = (x - (nside - 1) / 2.0) / (nside / 2.0);
-            double pm = 1.0, pc = u;
-            for (int l = 0; l < Nl; l++) {
-                leg[(size_t)l * A + i] = (float)(l == 0 ? 1.0 : pc);
-                if (l >= 1) {
-                    const double pn = ((2 * l + 1) * u * pc - l * pm) / (l + 1);
-                    pm = pc;
-                    pc = pn;
-                }
-            }
-        }
-    }
-    float *leg_d;
-    IMCOM_TRY(ws_take(ctx, szL, &leg_d, __func__));
-    IMCOM_TRY(upload(ctx, leg_d, leg.data(), szL));
-    double *kf_d = (double *)kf;
-    if (!kf) IMCOM_TRY(ws_take(ctx, (size_t)sz[5], &kf_d, __func__));
-    const float *c_d;
-    float *img_d;
-    IMCOM_TRY(st.in(canvas, szC, &c_d));
-    IMCOM_TRY(st.inout(image, szI, &img_d));
-    if (!kf) {
-        const float *K_d;
-        IMCOM_TRY(st.in(K, szK, &K_d));
-        IMCOM_TRY(launch_imsub_prepare(ctx, K_d, ax, s, Nl, kf_d));
-    }
-    double *kh_d = nullptr;
-    if (kh) IMCOM_TRY(st.out(kh, szI, &kh_d));
-    IMCOM_TRY(launch_imsub_convolve(ctx, c_d, A, crow0, crows, leg_d, kf_d, ax, Nl, s, nside, (int)first, y0, ny, img_d, kh_d));
-    IMCOM_TRY(st.back(image, (const float *)img_d, szI));
-    if (kh) IMCOM_TRY(st.back(kh, (const double *)kh_d, szI));
-    return st.done();
-}
-
-// ---------------------------------------------------------------------------------------------
-// the split of a PSF cube into its short- and long-range parts (splitpsf.hip)
-static int splitpsf_lorder1(int npoly)
-{
-    int l1 = 1;
-    while (l1 * l1 < npoly) l1++;
-    return l1 * l1 == npoly ? l1 : 0;
-}
-
-int imcom_splitpsf_sizes(int n, int npoly, double width, int nsca, int npts, long *out)
-{
-    IMCOM_REQUIRE(out, "null out");
-    IMCOM_REQUIRE(n >= 2 && n <= 65536 && npoly >= 1 && npoly <= 4096 && nsca >= 1 && npts >= 1 && npts <= npoly && width > 0.0 && width <= 4096.0,
-                  "splitpsf: side %d, %d planes, tophat width %g, %d SCAs or %d grid points out of range", n, npoly, width, nsca, npts);
-    const int npad = splitpsf_tophat_npad(width);
-    out[0] = npad;
-    out[1] = n + 2 * npad;
-    out[2] = splitpsf_route(n + 2 * npad);
-    out[3] = splitpsf_route(2 * n);
-    out[4] = out[2] ? (long)splitpsf_tophat_ws(npoly, n, width) + 4096 : 0;
-    out[5] = out[3] ? (long)splitpsf_points_ws(n, nsca, npts, true) + (long)(npoly * npoly + npoly + 4L * nsca * npoly) * 8 + 4096 : 0;
-    return IMCOM_OK;
-}
-
-int imcom_splitpsf_tophat(imcom_ctx *ctx, const double *cube, int nplane, int n, double width, double *out, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(cube && out, "null pointer");
-    IMCOM_REQUIRE(nplane >= 1 && nplane <= 65535 && n >= 1 && n <= SPLITPSF_MAXN && width > 0.0 && width <= 4096.0, "splitpsf tophat: %d planes of side %d, width %g",
-                  nplane, n, width);
-    if (!splitpsf_route(n + 2 * splitpsf_tophat_npad(width))) {
-        set_error("splitpsf tophat: a padded side of %d is beyond the %d this build transforms", n + 2 * splitpsf_tophat_npad(width), SPLITPSF_MAXN);
-        return IMCOM_ERR_UNSUPPORTED;
-    }
-    Stage st(ctx, memspace, __func__);
-    const size_t sz = (size_t)nplane * n * n;
-    WsPlan plan;
-    st.plan(plan, {sz * 8});
-    plan.add(splitpsf_tophat_ws(nplane, n, width));
-    IMCOM_TRY(ws_reserve(ctx, plan.total + 4096));
-    const double *c_d;
-    IMCOM_TRY(st.in(cube, sz, &c_d));
-    double *o_d = st.host ? (double *)c_d : out;  // the staged copy is filtered in place
-    IMCOM_TRY(launch_splitpsf_tophat(ctx, c_d, nplane, n, width, o_d));
-    IMCOM_TRY(st.back(out, (const double *)o_d, sz));
-    return st.done();
-}
-
-int imcom_splitpsf_split(imcom_ctx *ctx, const double *cube, int npoly, int n, int ns, double r_in, double r_out, int m_trunc, double *smallpsf,
-                         double *resid, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(cube && smallpsf && resid, "null pointer");
-    IMCOM_REQUIRE(npoly >= 1 && n >= 2 && n <= SPLITPSF_MAXN && n % 2 == 0 && ns >= 2 && ns <= n && ns % 2 == 0, "SplitPSF requires even dimension (%d, %d)", n, ns);
-    IMCOM_REQUIRE(std::isfinite(r_in) && std::isfinite(r_out) && r_in != r_out && m_trunc >= 0 && 2 * m_trunc <= n, "splitpsf: radii %g, %g, m_trunc %d", r_in,
-                  r_out, m_trunc);
-    // the 1-D factor of Truncate_2D_integratedBlackman (splitpsf.py:122-128), Window_integratedBlackman (79-89) on the host
-    std::vector<double> tr((size_t)n, 1.0);
-    for (int k = 0; k < m_trunc; k++) {
-        const double step = 2.0 / (m_trunc + 1), x = (k + 1) * step + -1.0, alpha = 0.08;
-        tr[k] = x >= 1 ? 1.0 : x <= -1 ? 0.0 : 0.5 * (x + 1) + (0.5 * std::sin(M_PI * x) + alpha / 4 * std::sin(2 * M_PI * x)) / ((1 - alpha) * M_PI);
-    }
-    for (int k = 0; k < m_trunc; k++) tr[n - m_trunc + k] = tr[m_trunc - 1 - k];
-    Stage st(ctx, memspace, __func__);
-    const size_t szC = (size_t)npoly * n * n, szS = (size_t)npoly * ns * ns;
-    WsPlan plan;
-    plan.add((size_t)n * 8);
-    st.plan(plan, {szC * 8, szS * 8, szC * 8});
-    IMCOM_TRY(ws_reserve(ctx, plan.total + 4096));
-    double *tr_d, *s_d, *r_d;
-    const double *c_d;
-    IMCOM_TRY(ws_take(ctx, (size_t)n, &tr_d, __func__));
-    IMCOM_TRY(upload(ctx, tr_d, tr.data(), (size_t)n));
-    IMCOM_TRY(st.in(cube, szC, &c_d));
-    IMCOM_TRY(st.out(smallpsf, szS, &s_d));
-    IMCOM_TRY(st.out(resid, szC, &r_d));
-    IMCOM_TRY(launch_splitpsf_split(ctx, c_d, npoly, n, ns, r_in, r_out, tr_d, s_d, r_d));
-    IMCOM_TRY(st.back(smallpsf, (const double *)s_d, szS));
-    IMCOM_TRY(st.back(resid, (const double *)r_d, szC));
-    return st.done();
-}
-
-int imcom_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npoly, int n, int i0, int npts, const double *lpw, const double *wg,
-                          const double *cov, double eps, double *K_Legendre, double *K_real, double *zeta_real, double *zetamax, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(resid && lpw && wg && cov && K_Legendre && zetamax, "null pointer");
-    IMCOM_REQUIRE(npoly >= 1 && npoly <= 4096 && splitpsf_lorder1(npoly), "SplitPSF Legendre polynomial dimension error (%d planes)", npoly);
-    IMCOM_REQUIRE(n >= 2 && n % 2 == 0, "SplitPSF requires even dimension (%d)", n);
-    IMCOM_REQUIRE(nsca >= 1 && i0 >= 0 && npts >= 1 && i0 + npts <= npoly && (long)nsca * npts <= 65535, "splitpsf: %d SCAs, grid points %d .. %d of %d", nsca, i0,
-                  i0 + npts, npoly);
-    IMCOM_REQUIRE(std::isfinite(eps) && eps >= 0.0, "splitpsf: eps = %g", eps);
-    for (long e = 0; e < (long)nsca * npoly; e++) {
-        const double *C = cov + 4 * e;
-        IMCOM_REQUIRE(C[0] > 0.0 && C[0] * C[3] - C[1] * C[1] > 0.0 && std::isfinite(C[0] + C[1] + C[3]),  // (C[1][0] is not read: 167, 181-182)
-                      "splitpsf: covariance %ld is not positive definite", e);
-    }
-    if (!splitpsf_route(2 * n)) {
-        set_error("splitpsf: a cube side of %d needs transforms of %d, beyond the %d this build transforms", n, 2 * n, SPLITPSF_MAXN);
-        return IMCOM_ERR_UNSUPPORTED;
-    }
-    Stage st(ctx, memspace, __func__);
-    const size_t szR = (size_t)nsca * npoly * n * n, szP = (size_t)nsca * npts * n * n, szL = (size_t)npoly * npoly, szC = (size_t)nsca * npoly * 4;
-    WsPlan plan;
-    plan.add(szL * 8);
-    plan.add((size_t)npoly * 8);
-    plan.add(szC * 8);
-    st.plan(plan, {szR * 8, szR * 8, (size_t)nsca * 8});
-    if (st.host && K_real) plan.add(szP * 8);
-    if (st.host && zeta_real) plan.add(szP * 8);
-    plan.add(splitpsf_points_ws(n, nsca, npts, !K_real));
-    IMCOM_TRY(ws_reserve(ctx, plan.total + 4096));
-    double *lpw_d, *wg_d, *cov_d, *KL_d, *zm_d, *kr_d = nullptr, *ze_d = nullptr;
-    const double *r_d;
-    IMCOM_TRY(ws_take(ctx, szL, &lpw_d, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)npoly, &wg_d, __func__));
-    IMCOM_TRY(ws_take(ctx, szC, &cov_d, __func__));
-    IMCOM_TRY(upload(ctx, lpw_d, lpw, szL));
-    IMCOM_TRY(upload(ctx, wg_d, wg, (size_t)npoly));
-    IMCOM_TRY(upload(ctx, cov_d, cov, szC));
-    IMCOM_TRY(st.in(resid, szR, &r_d));
-    IMCOM_TRY(st.inout(K_Legendre, szR, &KL_d));
-    IMCOM_TRY(st.inout(zetamax, (size_t)nsca, &zm_d));
-    if (K_real) IMCOM_TRY(st.out(K_real, szP, &kr_d));
-    if (zeta_real) IMCOM_TRY(st.out(zeta_real, szP, &ze_d));
-    IMCOM_TRY(launch_splitpsf_points(ctx, r_d, nsca, npoly, n, i0, npts, lpw_d, wg_d, cov_d, eps, KL_d, kr_d, ze_d, zm_d));
-    IMCOM_TRY(st.back(K_Legendre, (const double *)KL_d, szR));
-    IMCOM_TRY(st.back(zetamax, (const double *)zm_d, (size_t)nsca));
-    if (K_real) IMCOM_TRY(st.back(K_real, (const double *)kr_d, szP));
-    if (zeta_real) IMCOM_TRY(st.back(zeta_real, (const double *)ze_d, szP));
-    return st.done();
-}
-
-// ---------------------------------------------------------------------------------------------
-// destriping: cost and gradient over a resident mosaic (destripe.hip)
-namespace {
-using namespace imcom;
-
-int destripe_geom(int n_sca, int nside, int ds_rows, int amp_cols, int L, int max_np, DsGeom *g)
-{
-    IMCOM_REQUIRE(n_sca >= 1 && n_sca <= 65535 && nside >= 2 && nside <= 32768 && max_np >= 0, "destripe: %d SCAs of side %d", n_sca, nside);
-    if (ds_rows != nside) {
-        set_error("destripe: ds_rows=%d, the SCA has %d rows (forward_par, imdestripe.py:690-703, broadcasts one parameter per image row)", ds_rows, nside);
-        return IMCOM_ERR_UNSUPPORTED;
-    }
-    if (amp_cols > 0 && nside % amp_cols != 0) {
-        set_error("destripe: amp_cols=%d does not divide the %d image columns (imdestripe.py:643-648)", amp_cols, nside);
-        return IMCOM_ERR_UNSUPPORTED;
-    }
-    if (L != 0 && (L < 2 || L > 33)) {
-        set_error("destripe: a lattice of %d nodes per axis (2 <= L <= 33)", L);
-        return IMCOM_ERR_UNSUPPORTED;
-    }
-    g->n_sca = n_sca, g->nside = nside, g->ds_rows = ds_rows, g->amp_cols = amp_cols > 0 ? amp_cols : 0;
-    g->ncb = amp_cols > 0 ? nside / amp_cols : 0, g->nbins = ds_rows + g->ncb, g->L = L, g->max_np = max_np;
-    g->model = IMCOM_DESTRIPE_QUADRATIC, g->thresh = 0.0, g->neff_min = 0.5, g->lambda = 0.0;
-    if (destripe_forward_lds(*g) > 65536 || destripe_prep_lds(*g) > 65536 || destripe_scatter_lds(*g) > 65536) {
-        set_error("destripe: side %d with %d bins and %d neighbours of one SCA is beyond what a workgroup's LDS holds", nside, g->nbins, max_np);
-        return IMCOM_ERR_UNSUPPORTED;
-    }
-    return IMCOM_OK;
-}
-
-int destripe_model(int model, double thresh, DsGeom *g)
-{
-    IMCOM_REQUIRE(model == IMCOM_DESTRIPE_QUADRATIC || model == IMCOM_DESTRIPE_ABSOLUTE || model == IMCOM_DESTRIPE_HUBER, "destripe: cost model %d", model);
-    IMCOM_REQUIRE(model != IMCOM_DESTRIPE_HUBER || thresh == thresh, "destripe: huber_loss needs a threshold");
-    g->model = model, g->thresh = thresh;
-    return IMCOM_OK;
-}
-
-// the pair table: sorted by (a, b), no pair twice, a != b; *max_np = the most neighbours of one target
-int destripe_check_pairs(int n_sca, int L, int npairs, const int *pa, const int *pb, const void *const *px, const void *const *py, const void *const *pl,
-                         int *max_np)
-{
-    IMCOM_REQUIRE(npairs >= 0 && (npairs == 0 || (pa && pb && px && py && pl)), "destripe: null pair table");
-    int run = 0;
-    *max_np = 0;
-    for (int i = 0; i < npairs; i++) {
-        IMCOM_REQUIRE(pa[i] >= 0 && pa[i] < n_sca && pb[i] >= 0 && pb[i] < n_sca && pa[i] != pb[i], "destripe: pair %d is (%d, %d) of %d SCAs", i, pa[i], pb[i], n_sca);
-        IMCOM_REQUIRE(i == 0 || pa[i] > pa[i - 1] || (pa[i] == pa[i - 1] && pb[i] > pb[i - 1]), "destripe: the pair table is not sorted by (a, b) at %d", i);
-        IMCOM_REQUIRE((px[i] && py[i]) || (!px[i] && !py[i] && pl[i] && L >= 2), "destripe: pair %d has neither position arrays nor a lattice", i);
-        run = (i > 0 && pa[i] == pa[i - 1]) ? run + 1 : 1;
-        if (run > *max_np) *max_np = run;
-    }
-    return IMCOM_OK;
-}
-
-int destripe_upload_pairs(imcom_ctx *ctx, int n_sca, int npairs, const int *pa, const int *pb, const void *const *px, const void *const *py,
-                          const void *const *pl, DsPair **pairs_d, int **start_d, const char *who)
-{
-    std::vector<DsPair> tab((size_t)std::max(npairs, 1));
-    std::vector<int> start((size_t)n_sca + 1, 0);
-    for (int i = 0; i < npairs; i++) {
-        tab[i].x = (const double *)px[i], tab[i].y = (const double *)py[i], tab[i].lat = (const double *)pl[i], tab[i].a = pa[i], tab[i].b = pb[i];
-        start[pa[i] + 1]++;
-    }
-    for (int a = 0; a < n_sca; a++) start[a + 1] += start[a];
-    IMCOM_TRY(ws_take(ctx, tab.size(), pairs_d, who));
-    IMCOM_TRY(ws_take(ctx, start.size(), start_d, who));
-    IMCOM_TRY(upload(ctx, *pairs_d, tab.data(), tab.size()));
-    return upload(ctx, *start_d, start.data(), start.size());
-}
-
-size_t destripe_cost_ws(const DsGeom &g, int npairs, bool forward)
-{
-    WsPlan plan;
-    plan.add((size_t)std::max(npairs, 1) * sizeof(DsPair));
-    plan.add(((size_t)g.n_sca + 1) * sizeof(int));
-    if (forward) {
-        plan.add((size_t)g.n_sca * g.nside * 8);
-        plan.add((size_t)g.n_sca * std::max(g.ncb - 1, 1) * ((g.nside + 399) / 400) * 8);
-    }
-    return plan.total;
-}
-
-size_t destripe_resid_ws(const DsGeom &g, int npairs)
-{
-    WsPlan plan;
-    plan.add((size_t)std::max(npairs, 1) * sizeof(DsPair));
-    plan.add(((size_t)g.n_sca + 1) * sizeof(int));
-    plan.add((size_t)g.n_sca * g.nbins * 8);
-    plan.add((size_t)g.n_sca * g.nside * std::max(g.ncb, 1) * 8);
-    plan.add(8);
-    plan.add(16);
-    plan.add((size_t)g.n_sca * g.nbins * 8);
-    return plan.total;
-}
-}  // namespace
-
-int imcom_destripe_sizes(int n_sca, int nside, int ds_rows, int amp_cols, int L, int max_np, int npairs, long *out)
-{
-    IMCOM_REQUIRE(out && npairs >= 0, "null out");
-    DsGeom g;
-    IMCOM_TRY(destripe_geom(n_sca, nside, ds_rows, amp_cols, L, max_np, &g));
-    const long px = (long)nside * nside;
-    out[0] = g.nbins;
-    out[1] = g.ncb;
-    out[2] = px * (4 + 1 + 4 + 8 + 4);  // image, mask, g_eff, N_eff, psi
-    out[3] = px * 16;
-    out[4] = (long)L * L * 16;
-    out[5] = (long)destripe_cost_ws(g, npairs, true);
-    out[6] = (long)destripe_resid_ws(g, npairs);
-    out[7] = (long)nside * L * 8;  // the lattice weights W
-    return IMCOM_OK;
-}
-
-int imcom_destripe_neff(imcom_ctx *ctx, int n_sca, int nside, int L, const unsigned char *mask, int npairs, const int *pair_a, const int *pair_b,
-                        const void *const *pair_x, const void *const *pair_y, const void *const *pair_lat, const double *W, double *neff)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(mask && neff && (L == 0 || W), "null pointer");
-    int max_np;
-    IMCOM_TRY(destripe_check_pairs(n_sca, L, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &max_np));
-    DsGeom g;
-    IMCOM_TRY(destripe_geom(n_sca, nside, nside, 0, L, max_np, &g));
-    IMCOM_TRY(ws_reserve(ctx, destripe_cost_ws(g, npairs, false)));
-    DsPair *pairs_d;
-    int *start_d;
-    IMCOM_TRY(destripe_upload_pairs(ctx, n_sca, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &pairs_d, &start_d, __func__));
-    return launch_destripe_forward(ctx, g, true, nullptr, mask, nullptr, nullptr, pairs_d, start_d, W, neff, nullptr, nullptr);
-}
-
-int imcom_destripe_cost(imcom_ctx *ctx, int n_sca, int nside, int ds_rows, int amp_cols, int L, const float *image, const unsigned char *mask,
-                        const float *geff, const double *neff, const double *params, int npairs, const int *pair_a, const int *pair_b,
-                        const void *const *pair_x, const void *const *pair_y, const void *const *pair_lat, const double *W, int model, double thresh,
-                        double neff_min, double col_boundary_const, float *psi, double *eps)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(image && mask && geff && neff && params && psi && eps && (L == 0 || W), "null pointer");
-    int max_np;
-    IMCOM_TRY(destripe_check_pairs(n_sca, L, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &max_np));
-    DsGeom g;
-    IMCOM_TRY(destripe_geom(n_sca, nside, ds_rows, amp_cols, L, max_np, &g));
-    IMCOM_TRY(destripe_model(model, thresh, &g));
-    g.neff_min = neff_min, g.lambda = col_boundary_const;
-    if (g.ncb > 1 && g.lambda > 0.0 && g.amp_cols < 50) {
-        set_error("destripe: the boundary penalty reads 50 columns either side of a boundary, amp_cols=%d", g.amp_cols);
-        return IMCOM_ERR_UNSUPPORTED;
-    }
-    IMCOM_TRY(ws_reserve(ctx, destripe_cost_ws(g, npairs, true)));
-    DsPair *pairs_d;
-    int *start_d;
-    double *eps_rows, *pen;
-    const int nchunk = (nside + 399) / 400;
-    IMCOM_TRY(destripe_upload_pairs(ctx, n_sca, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &pairs_d, &start_d, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)n_sca * nside, &eps_rows, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)n_sca * std::max(g.ncb - 1, 1) * nchunk, &pen, __func__));
-    IMCOM_TRY(launch_destripe_forward(ctx, g, false, image, mask, geff, params, pairs_d, start_d, W, (double *)neff, psi, eps_rows));
-    return launch_destripe_eps(ctx, g, image, mask, params, eps_rows, pen, nchunk, eps);
-}
-
-int imcom_destripe_residual(imcom_ctx *ctx, int n_sca, int nside, int ds_rows, int amp_cols, int L, const float *psi, const float *geff, const double *neff,
-                            int npairs, const int *pair_a, const int *pair_b, const void *const *pair_x, const void *const *pair_y,
-                            const void *const *pair_lat, const double *W, int model, double thresh, double geff_max, double *resids, double *resids1,
-                            double *resids2)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(psi && geff && neff && resids && (L == 0 || W), "null pointer");
-    IMCOM_REQUIRE(geff_max >= 0.0 && geff_max < 1e300, "destripe: geff_max = %g", geff_max);
-    int max_np;
-    IMCOM_TRY(destripe_check_pairs(n_sca, L, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &max_np));
-    DsGeom g;
-    IMCOM_TRY(destripe_geom(n_sca, nside, ds_rows, amp_cols, L, max_np, &g));
-    IMCOM_TRY(destripe_model(model, thresh, &g));
-    IMCOM_TRY(ws_reserve(ctx, destripe_resid_ws(g, npairs)));
-    DsPair *pairs_d;
-    int *start_d;
-    double *term1, *rowcb, *scale;
-    unsigned long long *bits, *bins;
-    IMCOM_TRY(destripe_upload_pairs(ctx, n_sca, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &pairs_d, &start_d, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)n_sca * g.nbins, &term1, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)n_sca * nside * std::max(g.ncb, 1), &rowcb, __func__));
-    IMCOM_TRY(ws_take(ctx, 1, &bits, __func__));
-    IMCOM_TRY(ws_take(ctx, 2, &scale, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)n_sca * g.nbins, &bins, __func__));
-    return launch_destripe_gradient(ctx, g, psi, geff, neff, pairs_d, npairs, W, geff_max, term1, rowcb, bits, scale, bins, resids, resids1, resids2);
-}
-
-int imcom_destripe_interp(imcom_ctx *ctx, const double *src, const double *gsrc, int rows, int cols, const double *x, const double *y, long npix, double *out)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(src && gsrc && x && y && out && rows >= 2 && cols >= 2 && npix >= 0, "destripe: bad arguments of the interpolation");
-    if (npix == 0) return IMCOM_OK;
-    return launch_destripe_interp(ctx, src, gsrc, rows, cols, x, y, npix, out);
-}
-
-int imcom_destripe_interp_transpose(imcom_ctx *ctx, const double *image, const double *x, const double *y, long npix, int rows, int cols, double *out)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(image && x && y && out && rows >= 2 && cols >= 2 && npix >= 0, "destripe: bad arguments of the transposed interpolation");
-    if (npix == 0) return IMCOM_OK;
-    WsPlan plan;
-    plan.add((size_t)rows * cols * 8);
-    plan.add(8);
-    plan.add(16);
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    unsigned long long *acc, *bits;
-    double *scale;
-    IMCOM_TRY(ws_take(ctx, (size_t)rows * cols, &acc, __func__));
-    IMCOM_TRY(ws_take(ctx, 1, &bits, __func__));
-    IMCOM_TRY(ws_take(ctx, 2, &scale, __func__));
-    return launch_destripe_transpose(ctx, image, x, y, npix, rows, cols, acc, bits, scale, out);
-}
-
-// ---------------------------------------------------------------------------------------------
-// noise power spectra of coadded frames (noisespec.hip)
-static int noiseps_pick(int L, int route)  // route 0: the plan's own choice (IMCOM_NOISEPS_ROUTE=dense forces the dense DFT)
-{
-    const int best = noiseps_route(L, env_is("IMCOM_NOISEPS_ROUTE", "dense"));
-    if (route == 0 || best == NOISEPS_ROUTE_NONE) return best;
-    if (route == NOISEPS_ROUTE_DENSE) return route;
-    return route == noiseps_route(L, false) ? route : NOISEPS_ROUTE_NONE;
-}
-
-static int noiseps_check_side(int L, int bin8)
-{
-    IMCOM_REQUIRE(L >= 2 && L % 2 == 0, "noise spectra: the side %d is not even", L);
-    IMCOM_REQUIRE(!bin8 || L % 8 == 0, "noise spectra: the side %d is not a multiple of 8 (8 x 8 binning)", L);
-    IMCOM_REQUIRE(L <= SPLITPSF_MAXN, "noise spectra: a side of %d is beyond the %d this build transforms", L, SPLITPSF_MAXN);
-    return IMCOM_OK;
-}
-
-int imcom_noiseps_route(int L) { return noiseps_route(L, env_is("IMCOM_NOISEPS_ROUTE", "dense")); }
-
-int imcom_noiseps_sizes(int L, int nframe, int bin8, int route, long *out)
-{
-    IMCOM_REQUIRE(out, "null out");
-    IMCOM_TRY(noiseps_check_side(L, bin8));
-    IMCOM_REQUIRE(nframe >= 1 && nframe <= 65535 && route >= 0 && route <= 3, "noise spectra: %d frames, route %d", nframe, route);
-    const int r = noiseps_pick(L, route);
-    IMCOM_REQUIRE(r != NOISEPS_ROUTE_NONE, "noise spectra: route %d does not serve the side %d", route, L);
-    out[0] = r;
-    out[1] = bin8 ? L / 8 : L;
-    out[2] = (long)noiseps_ws(L, nframe, r) + (long)nframe * 8 + 4096;
-    out[3] = (long)(L / 2 + 1) * L * 16;
-    return IMCOM_OK;
-}
-
-int imcom_noiseps_2d(imcom_ctx *ctx, const void *frames, int in_f64, int nframe, int L, long fstride, long rstride, const double *window, long window_len,
-                     const double *norm, int bin8, int route, double *out, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(frames && norm && out, "null pointer");
-    IMCOM_TRY(noiseps_check_side(L, bin8));
-    IMCOM_REQUIRE(nframe >= 1 && nframe <= 65535 && route >= 0 && route <= 3, "noise spectra: %d frames, route %d", nframe, route);
-    IMCOM_REQUIRE(rstride >= L && (nframe == 1 || fstride >= (long)(L - 1) * rstride + L), "noise spectra: strides %ld, %ld of frames of side %d", fstride, rstride, L);
-    IMCOM_REQUIRE(!window || window_len == (long)L * L, "noise spectra: a window of %ld elements for frames of side %d", window_len, L);
-    for (int f = 0; f < nframe; f++) IMCOM_REQUIRE(std::isfinite(norm[f]) && norm[f] != 0.0, "noise spectra: norm[%d] = %g", f, norm[f]);
-    const int r = noiseps_pick(L, route);
-    IMCOM_REQUIRE(r != NOISEPS_ROUTE_NONE, "noise spectra: route %d does not serve the side %d", route, L);
-    Stage st(ctx, memspace, __func__);
-    const size_t esz = in_f64 ? 8 : 4, span = (size_t)(nframe - 1) * fstride + (size_t)(L - 1) * rstride + L, n = bin8 ? L / 8 : L, szO = (size_t)nframe * n * n;
-    WsPlan plan;
-    plan.add((size_t)nframe * 8);
-    st.plan(plan, {span * esz, szO * 8});
-    if (st.host && window) plan.add((size_t)L * L * 8);
-    plan.add(noiseps_ws(L, nframe, r));
-    IMCOM_TRY(ws_reserve(ctx, plan.total + 4096));
-    double *norm_d, *o_d;
-    const char *f_d;
-    const double *w_d;
-    IMCOM_TRY(ws_take(ctx, (size_t)nframe, &norm_d, __func__));
-    IMCOM_TRY(upload(ctx, norm_d, norm, (size_t)nframe));
-    IMCOM_TRY(st.in((const char *)frames, span * esz, &f_d));
-    IMCOM_TRY(st.out(out, szO, &o_d));
-    IMCOM_TRY(st.in(window, (size_t)L * L, &w_d));
-    IMCOM_TRY(launch_noiseps_2d(ctx, f_d, in_f64 != 0, nframe, L, fstride, rstride, w_d, norm_d, bin8 != 0, r, o_d));
-    IMCOM_TRY(st.back(out, (const double *)o_d, szO));
-    return st.done();
-}
-
-int imcom_noiseps_radial(imcom_ctx *ctx, const double *image, int nframe, int n, const int *rbin, int nidx, double *mean, double *err, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(image && rbin && mean && err, "null pointer");
-    IMCOM_REQUIRE(nframe >= 1 && nframe <= 65535 && n >= 1 && n <= SPLITPSF_MAXN && nidx >= 1 && nidx <= 65535, "noise spectra: %d frames of side %d, %d annuli", nframe,
-                  n, nidx);
-    Stage st(ctx, memspace, __func__);
-    const size_t npix = (size_t)n * n, szI = (size_t)nframe * npix, szR = (size_t)nframe * nidx;
-    WsPlan plan;
-    st.plan(plan, {szI * 8, npix * 4, szR * 8, szR * 8});
-    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total + 4096));
-    const double *i_d;
-    const int *r_d;
-    double *m_d, *e_d;
-    IMCOM_TRY(st.in(image, szI, &i_d));
-    IMCOM_TRY(st.in(rbin, npix, &r_d));
-    IMCOM_TRY(st.out(mean, szR, &m_d));
-    IMCOM_TRY(st.out(err, szR, &e_d));
-    IMCOM_TRY(launch_noiseps_radial(ctx, i_d, nframe, n, r_d, nidx, m_d, e_d));
-    IMCOM_TRY(st.back(mean, (const double *)m_d, szR));
-    IMCOM_TRY(st.back(err, (const double *)e_d, szR));
-    return st.done();
-}
-
-int imcom_noiseps_accumulate(imcom_ctx *ctx, const double *ps2d, const double *mean, const double *err, int nlayers, int n, int nrad, int bins, int coverage_bin,
-                             double *ps2d_all, double *ps1d_all)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(ps2d && mean && err && ps2d_all && ps1d_all, "null pointer");
-    IMCOM_REQUIRE(nlayers >= 1 && nlayers <= 65535 && n >= 1 && n <= SPLITPSF_MAXN && nrad >= 1 && bins >= 1 && coverage_bin >= 0 && coverage_bin < bins,
-                  "noise spectra: %d layers of side %d, %d annuli, coverage bin %d of %d", nlayers, n, nrad, coverage_bin, bins);
-    return launch_noiseps_accumulate(ctx, ps2d, mean, err, nlayers, (long)n * n, nrad, bins, coverage_bin, ps2d_all, ps1d_all);
-}
-
-// ---------------------------------------------------------------------------------------------
-// PCG64 draws by position and the cosmic-ray mask (pcg64.hip)
-namespace {
-// the affine maps of 2^j steps of s <- M s + inc, j < PCG64_JUMPS, into the workspace: (A_0, C_0) = (M, inc), A_{j+1} = A_j^2,
-// C_{j+1} = (A_j + 1) C_j (mod 2^128)
-int pcg64_jumps(imcom_ctx *ctx, uint64_t inc_lo, uint64_t inc_hi, const unsigned long long **jumps_d, const char *who)
-{
-    typedef unsigned __int128 u128;
-    unsigned long long tab[PCG64_JUMPS * 4], *d;
-    u128 A = ((u128)0x2360ED051FC65DA4ull << 64) | 0x4385DF649FCCF645ull, Cc = ((u128)inc_hi << 64) | inc_lo;
-    for (int j = 0; j < PCG64_JUMPS; j++) {
-        tab[4 * j] = (unsigned long long)A;
-        tab[4 * j + 1] = (unsigned long long)(A >> 64);
-        tab[4 * j + 2] = (unsigned long long)Cc;
-        tab[4 * j + 3] = (unsigned long long)(Cc >> 64);
-        Cc = (A + 1) * Cc;
-        A = A * A;
-    }
-    IMCOM_TRY(ws_take(ctx, (size_t)PCG64_JUMPS * 4, &d, who));
-    IMCOM_TRY(upload(ctx, d, tab, (size_t)PCG64_JUMPS * 4));
-    *jumps_d = d;
-    return IMCOM_OK;
-}
-constexpr long PCG64_MAX_COUNT = 1L << 36;
-}  // namespace
-
-int imcom_pcg64_uniform(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
-                        long count, double *out, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(count >= 0 && count <= PCG64_MAX_COUNT, "pcg64: count %ld outside 0 .. 2^36", count);
-    IMCOM_REQUIRE(count == 0 || out, "null pointer");
-    if (count == 0) return IMCOM_OK;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    plan.add((size_t)PCG64_JUMPS * 32);
-    st.plan(plan, {(size_t)count * 8});
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const unsigned long long *jumps, state[2] = {state_lo, state_hi}, offset[2] = {offset_lo, offset_hi};
-    double *o_d;
-    IMCOM_TRY(pcg64_jumps(ctx, inc_lo, inc_hi, &jumps, __func__));
-    IMCOM_TRY(st.out(out, (size_t)count, &o_d));
-    IMCOM_TRY(launch_pcg64_uniform(ctx, state, jumps, offset, count, o_d));
-    IMCOM_TRY(st.back(out, (const double *)o_d, (size_t)count));
-    return st.done();
-}
-
-int imcom_pcg64_uniform_at(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, const long *pos, long count, double *out,
-                           int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(count >= 0 && count <= PCG64_MAX_COUNT, "pcg64: count %ld outside 0 .. 2^36", count);
-    IMCOM_REQUIRE(count == 0 || (pos && out), "null pointer");
-    if (count == 0) return IMCOM_OK;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    plan.add((size_t)PCG64_JUMPS * 32);
-    st.plan(plan, {(size_t)count * 8, (size_t)count * 8});
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const unsigned long long *jumps, state[2] = {state_lo, state_hi};
-    const long *p_d;
-    double *o_d;
-    IMCOM_TRY(pcg64_jumps(ctx, inc_lo, inc_hi, &jumps, __func__));
-    IMCOM_TRY(st.in(pos, (size_t)count, &p_d));
-    IMCOM_TRY(st.out(out, (size_t)count, &o_d));
-    IMCOM_TRY(launch_pcg64_uniform_at(ctx, state, jumps, p_d, count, o_d));
-    IMCOM_TRY(st.back(out, (const double *)o_d, (size_t)count));
-    return st.done();
-}
-
-int imcom_cr_mask(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, int nside, int pad, int slice, int n_slices,
-                  double pcut, const float *labnoise, double threshold, unsigned char *mask, long *ngood, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(mask && ngood, "null pointer");
-    IMCOM_REQUIRE(nside >= 1 && nside <= 65536 && pad >= 1 && pad <= 4096, "cr_mask: nside %d outside 1 .. 65536 or pad %d outside 1 .. 4096", nside, pad);
-    IMCOM_REQUIRE(n_slices >= 1 && n_slices <= 65536 && slice >= 0 && slice < n_slices, "cr_mask: slice %d of %d", slice, n_slices);
-    Stage st(ctx, memspace, __func__);
-    const size_t npix = (size_t)nside * nside;
-    const unsigned long long W = (unsigned long long)nside + 2ull * pad;  // (slice W^2 + W^2 < 2^16 2^34)
-    WsPlan plan;
-    plan.add((size_t)PCG64_JUMPS * 32);
-    st.plan(plan, {labnoise ? npix * 4 : 0, npix, sizeof(long)});
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const unsigned long long *jumps, state[2] = {state_lo, state_hi};
-    const float *l_d;
-    unsigned char *m_d;
-    long *n_d;
-    IMCOM_TRY(pcg64_jumps(ctx, inc_lo, inc_hi, &jumps, __func__));
-    IMCOM_TRY(st.in(labnoise, npix, &l_d));
-    IMCOM_TRY(st.out(mask, npix, &m_d));
-    IMCOM_TRY(st.out(ngood, (size_t)1, &n_d));
-    IMCOM_TRY(launch_cr_mask(ctx, state, jumps, (unsigned long long)slice * W * W, nside, pad, pcut, l_d, threshold, m_d, (unsigned long long *)n_d));
-    IMCOM_TRY(st.back(mask, (const unsigned char *)m_d, npix));
-    IMCOM_TRY(st.back(ngood, (const long *)n_d, (size_t)1));
-    return st.done();
-}
-
-// ---------------------------------------------------------------------------------------------
-// numpy's normal draws of a PCG64 stream (ziggurat.hip)
-namespace {
-constexpr int ZIG_TILE_DEFAULT = 1024, ZIG_TILE_MAX = 1024;  // (the LDS of zig_emit_kernel: 36 KB at 1024)
-constexpr long ZIG_CHUNK_TILES_DEFAULT = 1L << 16, ZIG_CHUNK_TILES_MAX = 1L << 20;
-constexpr double ZIG_GUARD_DEFAULT = ZIG_GUARD;
-// the tiles one chunk may need for `remaining` draws: 1.0145 outputs a draw on average, 3 % and a tile allowed for
-long zig_tiles_for(long remaining, int P) { return (remaining + remaining / 32 + P - 1) / P + 1; }
-}  // namespace
-
-int imcom_pcg64_normal_sizes(long count, long *tail_cap)
-{
-    IMCOM_REQUIRE(tail_cap, "null pointer");
-    IMCOM_REQUIRE(count >= 0 && count <= PCG64_MAX_COUNT, "pcg64: count %ld outside 0 .. 2^36", count);
-    *tail_cap = count / 1024 + 4096;  // the expected number is count / 3700
-    return IMCOM_OK;
-}
-
-int imcom_pcg64_normal(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
-                       long count, double *out, long *tail_idx, uint64_t *tail_raw, uint64_t *info, int memspace)
-{
-    return imcom_pcg64_normal_ex(ctx, state_lo, state_hi, inc_lo, inc_hi, offset_lo, offset_hi, count, out, tail_idx, tail_raw, info, memspace, 0, 0, 0.0);
-}
-
-int imcom_pcg64_normal_ex(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
-                          long count, double *out, long *tail_idx, uint64_t *tail_raw, uint64_t *info, int memspace, int tile, long chunk_tiles, double guard_band)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(count >= 0 && count <= PCG64_MAX_COUNT, "pcg64: count %ld outside 0 .. 2^36", count);
-    IMCOM_REQUIRE(info && (count == 0 || (out && tail_idx && tail_raw)), "null pointer");
-    IMCOM_REQUIRE(tile == 0 || (tile >= 4 && tile <= ZIG_TILE_MAX && (tile & (tile - 1)) == 0), "pcg64_normal: tile %d is no power of two in 4 .. %d", tile,
-                  ZIG_TILE_MAX);
-    IMCOM_REQUIRE(chunk_tiles >= 0 && chunk_tiles <= ZIG_CHUNK_TILES_MAX, "pcg64_normal: %ld tiles a chunk outside 1 .. 2^20", chunk_tiles);
-    IMCOM_REQUIRE(guard_band >= 0.0 && guard_band <= 1.0, "pcg64_normal: guard band %g outside 0 .. 1", guard_band);
-    for (int i = 0; i < 4; i++) info[i] = 0;
-    if (count == 0) return IMCOM_OK;
-    const int P = tile ? tile : ZIG_TILE_DEFAULT;
-    const long chunk_max = chunk_tiles ? chunk_tiles : ZIG_CHUNK_TILES_DEFAULT;
-    const double guard = guard_band > 0.0 ? guard_band : ZIG_GUARD_DEFAULT;
-    const long tail_cap = count / 1024 + 4096, tiles_max = std::min(chunk_max, zig_tiles_for(count, P));
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    plan.add((size_t)PCG64_JUMPS * 32);
-    plan.add((size_t)tiles_max * ZIG_ENTRIES);      // exit_t
-    plan.add((size_t)tiles_max * ZIG_ENTRIES * 2);  // count_t
-    plan.add((size_t)tiles_max);                    // entry_t
-    plan.add((size_t)tiles_max * 8);                // base_t
-    plan.add(2 * sizeof(long));                     // res
-    plan.add(4 * sizeof(unsigned long long));       // info
-    st.plan(plan, {(size_t)count * 8, (size_t)tail_cap * 8, (size_t)tail_cap * 16});
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const unsigned long long *jumps, state[2] = {state_lo, state_hi};
-    unsigned char *exit_t, *entry_t;
-    unsigned short *count_t;
-    long *base_t, *res, *ti_d;
-    unsigned long long *info_d, *tr_d;
-    double *o_d;
-    IMCOM_TRY(pcg64_jumps(ctx, inc_lo, inc_hi, &jumps, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)tiles_max * ZIG_ENTRIES, &exit_t, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)tiles_max * ZIG_ENTRIES, &count_t, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)tiles_max, &entry_t, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)tiles_max, &base_t, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)2, &res, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)4, &info_d, __func__));
-    IMCOM_TRY(st.out(out, (size_t)count, &o_d));
-    IMCOM_TRY(st.out(tail_idx, (size_t)tail_cap, &ti_d));
-    IMCOM_TRY(st.out((unsigned long long *)tail_raw, (size_t)tail_cap * 2, &tr_d));
-    IMCOM_HIP_CHECK(hipMemsetAsync(info_d, 0, 4 * sizeof(unsigned long long), ctx->stream));
-    // chunks in ascending order: a chunk's entry offset and output base are the exit of the chunk before
-    unsigned long long rel = 0;
-    long made = 0, entry = 0;
-    while (made < count) {
-        const long tiles = std::min(tiles_max, zig_tiles_for(count - made, P));
-        const unsigned long long lo = offset_lo + rel, start[2] = {lo, offset_hi + (lo < rel)};
-        long res_h[2];
-        IMCOM_TRY(launch_zig_chunk(ctx, state, jumps, start, rel, P, tiles, (int)entry, made, guard, exit_t, count_t, entry_t, base_t, res, count, o_d, ti_d,
-                                   tr_d, tail_cap, info_d));
-        IMCOM_HIP_CHECK(hipMemcpyAsync(res_h, res, sizeof(res_h), hipMemcpyDeviceToHost, ctx->stream));
-        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        entry = res_h[0];
-        made = res_h[1];
-        rel += (unsigned long long)tiles * P;
-    }
-    unsigned long long info_h[4];
-    IMCOM_HIP_CHECK(hipMemcpyAsync(info_h, info_d, sizeof(info_h), hipMemcpyDeviceToHost, ctx->stream));
-    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    const long tails = (long)std::min<unsigned long long>(info_h[2], (unsigned long long)tail_cap);
-    IMCOM_TRY(st.back(out, (const double *)o_d, (size_t)count));
-    IMCOM_TRY(st.back(tail_idx, (const long *)ti_d, (size_t)tails));
-    IMCOM_TRY(st.back((unsigned long long *)tail_raw, (const unsigned long long *)tr_d, (size_t)tails * 2));
-    info[0] = info_h[0];
-    info[1] = info_h[1];
-    info[2] = info_h[2];
-    info[3] = info_h[3] != 0;
-    return st.done();
-}
-
-// ---------------------------------------------------------------------------------------------
-// The transform of the 1/f noise layer (noise1f.hip)
-int imcom_noise_1f(imcom_ctx *ctx, const double *normals, const double *amp, long len, int nch, int w, int border, float *frame, double *block, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(len >= 2 && nch >= 1 && nch <= 4096 && w >= 1 && border >= 0, "noise_1f: len %ld, %d channels of width %d, border %d", len, nch, w, border);
-    int N1, N2;
-    if ((w & (w - 1)) || !noise1f_split(len, &N1, &N2) || (long)w > len / 2) {
-        set_error("noise_1f: the length (%ld) must be a power of two in 2^10 .. 2^20 and the channel width (%d) a power of two up to half of it", len, w);
-        return IMCOM_ERR_UNSUPPORTED;
-    }
-    IMCOM_REQUIRE(normals && amp && frame, "null pointer");
-    const long half = len / 2, rows = half / w, cols = (long)nch * w;
-    IMCOM_REQUIRE(2L * border < rows && 2L * border < cols, "noise_1f: a border of %d leaves nothing of %ld x %ld pixels", border, rows, cols);
-    const long npix = (rows - 2 * border) * (cols - 2 * border);
-    const int group = std::min(nch, NOISE1F_GROUP);
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    plan.add((size_t)N1 * 16);
-    plan.add((size_t)N2 * 16);
-    plan.add((size_t)group * len * 16);  // S
-    plan.add((size_t)nch * 8);           // sums
-    if (st.host || !block) plan.add((size_t)nch * half * 8);
-    st.plan(plan, {(size_t)2 * nch * len * 8, (size_t)len * 8, (size_t)npix * 4});
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    double2 *tw1, *tw2, *S;
-    double *sum, *blk = block;
-    const double *g_d, *amp_d;
-    float *f_d;
-    IMCOM_TRY(ws_take(ctx, (size_t)N1, &tw1, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)N2, &tw2, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)group * len, &S, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)nch, &sum, __func__));
-    if (st.host || !block) IMCOM_TRY(ws_take(ctx, (size_t)nch * half, &blk, __func__));
-    IMCOM_TRY(st.in(normals, (size_t)2 * nch * len, &g_d));
-    IMCOM_TRY(st.in(amp, (size_t)len, &amp_d));
-    IMCOM_TRY(st.out(frame, (size_t)npix, &f_d));
-    IMCOM_TRY(noise1f_tables(ctx, len, tw1, tw2));
-    for (int ch0 = 0; ch0 < nch; ch0 += group)
-        IMCOM_TRY(launch_noise1f_group(ctx, g_d, amp_d, len, ch0, std::min(group, nch - ch0), tw1, tw2, S, blk));
-    IMCOM_TRY(launch_noise1f_place(ctx, blk, sum, len, nch, w, border, f_d));
-    IMCOM_TRY(st.back(frame, (const float *)f_d, (size_t)npix));
-    if (block) IMCOM_TRY(st.back(block, (const double *)blk, (size_t)nch * half));
-    return st.done();
-}
-
-// ---------------------------------------------------------------------------------------------
-// Bright-object masks of the destripe set-up (objmask.hip)
-namespace {
-constexpr long MASK_MAX_SIDE = 65536;
-}
-
-int imcom_select_kth(imcom_ctx *ctx, const void *values, int is_f64, long n, const unsigned char *flags, int use_abs, double c, long k, void *out, long *info,
-                     int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(values && out && info, "null pointer");
-    IMCOM_REQUIRE(n >= 1 && n <= MASK_MAX_SIDE * MASK_MAX_SIDE, "select_kth: n = %ld outside 1 .. 2^32", n);
-    IMCOM_REQUIRE(k < n, "select_kth: rank %ld of %ld values", k, n);
-    const size_t esz = is_f64 ? 8 : 4;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    plan.add(SELECT_STATE * sizeof(unsigned long long));
-    plan.add(2 * SELECT_BINS * sizeof(unsigned long long));
-    st.plan(plan, {(size_t)n * esz, flags ? (size_t)n : 0, 2 * esz, 2 * sizeof(long)});
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    unsigned long long *state, *hist;
-    const char *v_d;
-    const unsigned char *f_d;
-    char *o_d;
-    long *i_d;
-    IMCOM_TRY(ws_take(ctx, (size_t)SELECT_STATE, &state, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)2 * SELECT_BINS, &hist, __func__));
-    IMCOM_TRY(st.in((const char *)values, (size_t)n * esz, &v_d));
-    IMCOM_TRY(st.in(flags, (size_t)n, &f_d));
-    IMCOM_TRY(st.out((char *)out, 2 * esz, &o_d));
-    IMCOM_TRY(st.out(info, (size_t)2, &i_d));
-    IMCOM_TRY(launch_select_kth(ctx, v_d, is_f64 != 0, f_d, n, use_abs != 0, c, k, state, hist, o_d, i_d));
-    IMCOM_TRY(st.back((char *)out, (const char *)o_d, 2 * esz));
-    IMCOM_TRY(st.back(info, (const long *)i_d, (size_t)2));
-    return st.done();
-}
-
-int imcom_mask_threshold(imcom_ctx *ctx, const void *image, int is_f64, long n, double bkg, double t_seed, double t_grow, int finite_only, unsigned char *seed,
-                         unsigned char *grow, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(image && seed, "null pointer");
-    IMCOM_REQUIRE(n >= 1 && n <= MASK_MAX_SIDE * MASK_MAX_SIDE, "mask_threshold: n = %ld outside 1 .. 2^32", n);
-    const size_t esz = is_f64 ? 8 : 4;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    st.plan(plan, {(size_t)n * esz, (size_t)n, grow ? (size_t)n : 0});
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const char *v_d;
-    unsigned char *s_d, *g_d = nullptr;
-    IMCOM_TRY(st.in((const char *)image, (size_t)n * esz, &v_d));
-    IMCOM_TRY(st.out(seed, (size_t)n, &s_d));
-    if (grow) IMCOM_TRY(st.out(grow, (size_t)n, &g_d));
-    IMCOM_TRY(launch_mask_threshold(ctx, v_d, is_f64 != 0, n, bkg, t_seed, t_grow, finite_only != 0, s_d, g_d));
-    IMCOM_TRY(st.back(seed, (const unsigned char *)s_d, (size_t)n));
-    if (grow) IMCOM_TRY(st.back(grow, (const unsigned char *)g_d, (size_t)n));
-    return st.done();
-}
-
-int imcom_mask_clip(imcom_ctx *ctx, const void *image, int is_f64, long n, const unsigned char *keep_in, double bkg, double t, unsigned char *keep_out, long *count,
-                    int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(image && keep_out && count, "null pointer");
-    IMCOM_REQUIRE(n >= 1 && n <= MASK_MAX_SIDE * MASK_MAX_SIDE, "mask_clip: n = %ld outside 1 .. 2^32", n);
-    const size_t esz = is_f64 ? 8 : 4;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    st.plan(plan, {(size_t)n * esz, keep_in ? (size_t)n : 0, (size_t)n, sizeof(long)});
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const char *v_d;
-    const unsigned char *ki_d;
-    unsigned char *ko_d;
-    long *c_d;
-    IMCOM_TRY(st.in((const char *)image, (size_t)n * esz, &v_d));
-    IMCOM_TRY(st.in(keep_in, (size_t)n, &ki_d));
-    IMCOM_TRY(st.out(keep_out, (size_t)n, &ko_d));
-    IMCOM_TRY(st.out(count, (size_t)1, &c_d));
-    IMCOM_TRY(launch_mask_clip(ctx, v_d, is_f64 != 0, n, ki_d, bkg, t, ko_d, (unsigned long long *)c_d));
-    IMCOM_TRY(st.back(keep_out, (const unsigned char *)ko_d, (size_t)n));
-    IMCOM_TRY(st.back(count, (const long *)c_d, (size_t)1));
-    return st.done();
-}
-
-int imcom_mask_propagate(imcom_ctx *ctx, const unsigned char *seed, const unsigned char *grow, int rows, int cols, unsigned char *out, long *sweeps, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(seed && grow && out, "null pointer");
-    IMCOM_REQUIRE(rows >= 1 && rows <= MASK_MAX_SIDE && cols >= 1 && cols <= MASK_MAX_SIDE, "mask_propagate: %d x %d pixels, sides 1 .. 65536", rows, cols);
-    IMCOM_REQUIRE(out != grow, "mask_propagate: the result cannot overwrite the grow image");
-    const size_t npix = (size_t)rows * cols;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    plan.add(npix);
-    plan.add(sizeof(unsigned int));
-    st.plan(plan, {npix, npix, npix});
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    unsigned char *tmp, *o_d;
-    unsigned int *changed;
-    const unsigned char *s_d, *g_d;
-    IMCOM_TRY(ws_take(ctx, npix, &tmp, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)1, &changed, __func__));
-    IMCOM_TRY(st.in(seed, npix, &s_d));
-    IMCOM_TRY(st.in(grow, npix, &g_d));
-    IMCOM_TRY(st.out(out, npix, &o_d));
-    if (o_d != s_d) IMCOM_HIP_CHECK(hipMemcpyAsync(o_d, s_d, npix, hipMemcpyDeviceToDevice, ctx->stream));
-    long n_sweeps = 0;
-    IMCOM_TRY(launch_mask_propagate(ctx, g_d, rows, cols, o_d, tmp, changed, &n_sweeps));
-    if (sweeps) *sweeps = n_sweeps;
-    IMCOM_TRY(st.back(out, (const unsigned char *)o_d, npix));
-    return st.done();
-}
-
-int imcom_mask_dilate(imcom_ctx *ctx, const unsigned char *in, int rows, int cols, int r, unsigned char *out, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(in && out, "null pointer");
-    IMCOM_REQUIRE(rows >= 1 && rows <= MASK_MAX_SIDE && cols >= 1 && cols <= MASK_MAX_SIDE, "mask_dilate: %d x %d pixels, sides 1 .. 65536", rows, cols);
-    IMCOM_REQUIRE(in != out, "mask_dilate: not in place");
-    if (r < 1 || r > MASK_DILATE_MAX_R) {
-        set_error("mask_dilate: radius %d, served are 1 .. %d", r, MASK_DILATE_MAX_R);
-        return IMCOM_ERR_UNSUPPORTED;
-    }
-    const size_t npix = (size_t)rows * cols;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    st.plan(plan, {npix, npix});
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const unsigned char *i_d;
-    unsigned char *o_d;
-    IMCOM_TRY(st.in(in, npix, &i_d));
-    IMCOM_TRY(st.out(out, npix, &o_d));
-    IMCOM_TRY(launch_mask_dilate(ctx, i_d, rows, cols, r, o_d));
-    IMCOM_TRY(st.back(out, (const unsigned char *)o_d, npix));
-    return st.done();
-}
-
-int imcom_mask_apply(imcom_ctx *ctx, const void *in, int dtype, const unsigned char *mask, long n, void *out, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(in && mask && out, "null pointer");
-    IMCOM_REQUIRE(dtype >= 0 && dtype <= 2, "mask_apply: dtype %d is none of 0 (float32), 1 (float64), 2 (uint8)", dtype);
-    IMCOM_REQUIRE(n >= 1 && n <= MASK_MAX_SIDE * MASK_MAX_SIDE, "mask_apply: n = %ld outside 1 .. 2^32", n);
-    const size_t esz = dtype == 0 ? 4 : dtype == 1 ? 8 : 1;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    st.plan(plan, {(size_t)n * esz, (size_t)n, (size_t)n * esz});
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const char *i_d;
-    const unsigned char *m_d;
-    char *o_d;
-    IMCOM_TRY(st.in((const char *)in, (size_t)n * esz, &i_d));
-    IMCOM_TRY(st.in(mask, (size_t)n, &m_d));
-    IMCOM_TRY(st.out((char *)out, (size_t)n * esz, &o_d));
-    IMCOM_TRY(launch_mask_apply(ctx, i_d, dtype, m_d, n, o_d));
-    IMCOM_TRY(st.back((char *)out, (const char *)o_d, (size_t)n * esz));
-    return st.done();
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// Validation-report statistics: the streaming exact select and the coded-map histogram (quantiles.hip, quantiles_core.h)
-}  // extern "C"
-
-struct imcom_quant {
-    int S = 0, R = 0, keybits = 32, passes = 3, pass = 0;  // pass: the one being fed; == passes: the results are there
-    bool f64 = false, ranks_set = false;
-    QtDev d{};
-    std::vector<unsigned long long> total0, nan0, hist0;  // what pass 1 counted: elements and NaNs per segment, its histogram [S][QT_BINS]
-    std::vector<QtRank> ranks;                            // [S][R]
-    std::vector<std::vector<uint64_t>> groups;            // the running pass's live groups per segment
-};
-
-namespace {
-constexpr int QT_MAX_S = 64, QT_MAX_R = 32;
-constexpr long QT_MAX_CHUNK = 1L << 40;
-static_assert(QT_BINS == OM_BINS, "a group's counters are one digit's bins");
-
-size_t quant_words(int S, int R) { return (size_t)3 * S + 1 + (size_t)S * R + (size_t)S * R * QT_BINS; }
-
-void quant_digit(const imcom_quant *q, int *shift, int *nbits) { om_digit(q->keybits, q->pass, shift, nbits); }
-
-// zero the running pass's counters and hand the device the groups of q->groups
-int quant_arm(imcom_ctx *ctx, imcom_quant *q)
-{
-    const int S = q->S, R = q->R;
-    std::vector<unsigned long long> head((size_t)3 * S + 1 + (size_t)S * R, 0ull);  // tot, nan, ng, bad, gprefix
-    for (int s = 0; s < S; s++) {
-        head[2 * S + s] = q->groups[s].size();
-        for (size_t g = 0; g < q->groups[s].size(); g++) head[3 * S + 1 + (size_t)s * R + g] = q->groups[s][g];
-    }
-    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    IMCOM_HIP_CHECK(hipMemcpy(q->d.tot, head.data(), head.size() * 8, hipMemcpyHostToDevice));
-    for (int s = 0; s < S; s++)
-        if (!q->groups[s].empty()) IMCOM_HIP_CHECK(hipMemsetAsync(q->d.hist + (size_t)s * R * QT_BINS, 0, q->groups[s].size() * QT_BINS * 8, ctx->stream));
-    return IMCOM_OK;
-}
-
-int quant_restart(imcom_ctx *ctx, imcom_quant *q)
-{
-    q->pass = 0;
-    q->ranks_set = false;
-    q->groups.assign(q->S, std::vector<uint64_t>(1, 0ull));  // one group a segment holds every key
-    return quant_arm(ctx, q);
-}
-
-int quant_feedable(const imcom_quant *q, const char *who)
-{
-    IMCOM_REQUIRE(q, "%s: null accumulator", who);
-    IMCOM_REQUIRE(q->pass < q->passes, "%s: every pass has ended (imcom_quant_reset starts over)", who);
-    IMCOM_REQUIRE(q->pass == 0 || q->ranks_set, "%s: pass 2 needs the ranks (imcom_quant_set_ranks)", who);
-    return IMCOM_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int imcom_quant_sizes(int n_segments, int n_ranks, int is_f64, long *out)
-{
-    IMCOM_REQUIRE(out, "null pointer");
-    IMCOM_REQUIRE(n_segments >= 1 && n_segments <= QT_MAX_S && n_ranks >= 1 && n_ranks <= QT_MAX_R, "quant: %d segments of %d ranks, served are 1 .. %d of 1 .. %d",
-                  n_segments, n_ranks, QT_MAX_S, QT_MAX_R);
-    out[0] = (long)(quant_words(n_segments, n_ranks) * 8);
-    out[1] = om_passes(is_f64 ? 64 : 32);
-    out[2] = QT_BINS;
-    out[3] = QT_TILE;
-    return IMCOM_OK;
-}
-
-int imcom_quant_begin(imcom_ctx *ctx, int n_segments, int n_ranks, int is_f64, void *state, size_t state_bytes, imcom_quant **out)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(state && out, "null pointer");
-    long sz[4];
-    IMCOM_TRY(imcom_quant_sizes(n_segments, n_ranks, is_f64, sz));
-    IMCOM_REQUIRE(state_bytes >= (size_t)sz[0] && ((uintptr_t)state & 7) == 0, "quant_begin: state of %zu bytes, needed are %ld (8-byte aligned)", state_bytes, sz[0]);
-    imcom_quant *q = new imcom_quant;
-    const int S = q->S = n_segments, R = q->R = n_ranks;
-    q->f64 = is_f64 != 0;
-    q->keybits = q->f64 ? 64 : 32;
-    q->passes = om_passes(q->keybits);
-    unsigned long long *w = (unsigned long long *)state;
-    q->d = QtDev{w, w + S, w + 2 * S, w + 3 * S, w + 3 * S + 1, w + 3 * S + 1 + (size_t)S * R, S, R};
-    q->ranks.assign((size_t)S * R, QtRank());
-    q->hist0.assign((size_t)S * QT_BINS, 0ull);
-    const int rc = quant_restart(ctx, q);
-    if (rc != IMCOM_OK) {
-        delete q;
-        return rc;
-    }
-    *out = q;
-    return IMCOM_OK;
-}
-
-int imcom_quant_reset(imcom_ctx *ctx, imcom_quant *q)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(q, "quant_reset: null accumulator");
-    return quant_restart(ctx, q);
-}
-
-int imcom_quant_free(imcom_ctx *ctx, imcom_quant *q)
-{
-    IMCOM_TRY(enter(ctx));
-    if (q) IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    delete q;
-    return IMCOM_OK;
-}
-
-int imcom_quant_add_2d(imcom_ctx *ctx, imcom_quant *q, int segment, const void *values, long rows, long cols, long pitch, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_TRY(quant_feedable(q, __func__));
-    IMCOM_REQUIRE(segment >= 0 && segment < q->S, "quant_add_2d: segment %d of %d", segment, q->S);
-    IMCOM_REQUIRE(rows >= 0 && cols >= 0 && pitch >= cols && (rows == 0 || cols == 0 || rows <= QT_MAX_CHUNK / cols), "quant_add_2d: %ld x %ld elements, pitch %ld", rows, cols,
-                  pitch);
-    if (rows == 0 || cols == 0) return IMCOM_OK;
-    IMCOM_REQUIRE(values, "null pointer");
-    const size_t esz = q->f64 ? 8 : 4, span = (size_t)(rows - 1) * pitch + cols;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    st.plan(plan, {span * esz});
-    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const char *v_d;
-    IMCOM_TRY(st.in((const char *)values, span * esz, &v_d));
-    int shift, nbits;
-    quant_digit(q, &shift, &nbits);
-    IMCOM_TRY(launch_quant_dense(ctx, q->d, q->f64, segment, (int)q->groups[segment].size(), v_d, rows, cols, pitch, shift, nbits));
-    return st.done();
-}
-
-int imcom_quant_add_flat(imcom_ctx *ctx, imcom_quant *q, const void *values, const void *segment_ids, int ids_i32, long n, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_TRY(quant_feedable(q, __func__));
-    IMCOM_REQUIRE(n >= 0 && n <= QT_MAX_CHUNK, "quant_add_flat: n = %ld outside 0 .. 2^40", n);
-    if (n == 0) return IMCOM_OK;
-    IMCOM_REQUIRE(values && segment_ids, "null pointer");
-    const size_t esz = q->f64 ? 8 : 4, isz = ids_i32 ? 4 : 1;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    st.plan(plan, {(size_t)n * esz, (size_t)n * isz});
-    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const char *v_d, *i_d;
-    IMCOM_TRY(st.in((const char *)values, (size_t)n * esz, &v_d));
-    IMCOM_TRY(st.in((const char *)segment_ids, (size_t)n * isz, &i_d));
-    int shift, nbits;
-    quant_digit(q, &shift, &nbits);
-    IMCOM_TRY(launch_quant_ids(ctx, q->d, q->f64, v_d, i_d, ids_i32 != 0, n, shift, nbits));
-    return st.done();
-}
-
-int imcom_quant_add_constant(imcom_ctx *ctx, imcom_quant *q, int segment, double value, long count)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_TRY(quant_feedable(q, __func__));
-    IMCOM_REQUIRE(segment >= 0 && segment < q->S && count >= 0, "quant_add_constant: segment %d of %d, count %ld", segment, q->S, count);
-    if (count == 0) return IMCOM_OK;
-    int shift, nbits;
-    quant_digit(q, &shift, &nbits);
-    return launch_quant_constant(ctx, q->d, q->f64, segment, value, (unsigned long long)count, shift, nbits);
-}
-
-int imcom_quant_add_rings(imcom_ctx *ctx, imcom_quant *q, const void *frame, int n, long pitch, const double *x, const double *y, int nstar, int rpix, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_TRY(quant_feedable(q, __func__));
-    IMCOM_REQUIRE(n >= 1 && n <= 32767 && pitch >= n, "quant_add_rings: frame side %d outside 1 .. 32767 (the reference's int16) or pitch %ld below it", n, pitch);
-    IMCOM_REQUIRE(rpix >= 1 && rpix <= q->S && rpix <= 4096, "quant_add_rings: %d rings, the accumulator has %d segments", rpix, q->S);
-    IMCOM_REQUIRE(nstar >= 0, "quant_add_rings: %d stars", nstar);
-    if (nstar == 0) return IMCOM_OK;
-    IMCOM_REQUIRE(frame && x && y, "null pointer");
-    const size_t esz = q->f64 ? 8 : 4, span = (size_t)(n - 1) * pitch + n;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    st.plan(plan, {span * esz, (size_t)nstar * 8, (size_t)nstar * 8});
-    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const char *f_d;
-    const double *x_d, *y_d;
-    IMCOM_TRY(st.in((const char *)frame, span * esz, &f_d));
-    IMCOM_TRY(st.in(x, (size_t)nstar, &x_d));
-    IMCOM_TRY(st.in(y, (size_t)nstar, &y_d));
-    int shift, nbits;
-    quant_digit(q, &shift, &nbits);
-    IMCOM_TRY(launch_quant_rings(ctx, q->d, q->f64, f_d, n, pitch, x_d, y_d, nstar, rpix, shift, nbits));
-    return st.done();
-}
-
-int imcom_quant_end_pass(imcom_ctx *ctx, imcom_quant *q, int *passes_left)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_TRY(quant_feedable(q, __func__));
-    const int S = q->S, R = q->R;
-    std::vector<unsigned long long> head((size_t)3 * S + 1);
-    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    IMCOM_HIP_CHECK(hipMemcpy(head.data(), q->d.tot, head.size() * 8, hipMemcpyDeviceToHost));
-    const unsigned long long *tot = head.data(), *nan = tot + S, bad = head[3 * S];
-    int wrong = -1;
-    if (q->pass > 0)
-        for (int s = S - 1; s >= 0; s--)
-            if (tot[s] != q->total0[s] || nan[s] != q->nan0[s]) wrong = s;
-    if (bad || wrong >= 0) {  // the pass did not happen: its counters are zeroed, it can be fed again
-        IMCOM_TRY(quant_arm(ctx, q));
-        if (bad) set_error("quant_end_pass: %llu segment ids outside 0 .. %d or star positions that are not finite or beyond the int16 range", bad, S - 1);
-        else
-            set_error("quant_end_pass: pass %d fed segment %d %llu elements (%llu NaN), pass 1 fed it %llu (%llu NaN)", q->pass + 1, wrong, tot[wrong], nan[wrong],
-                      q->total0[wrong], q->nan0[wrong]);
-        return IMCOM_ERR_ARG;
-    }
-    std::vector<unsigned long long> hist;
-    for (int s = 0; s < S; s++) {
-        const size_t ng = q->groups[s].size();
-        if (ng == 0) continue;
-        hist.resize(ng * QT_BINS);
-        IMCOM_HIP_CHECK(hipMemcpy(hist.data(), q->d.hist + (size_t)s * R * QT_BINS, hist.size() * 8, hipMemcpyDeviceToHost));
-        if (q->pass == 0) std::copy(hist.begin(), hist.begin() + QT_BINS, q->hist0.begin() + (size_t)s * QT_BINS);
-        else qt_advance(q->ranks.data() + (size_t)s * R, R, q->groups[s], (const uint64_t *)hist.data(), q->keybits, q->pass);
-    }
-    if (q->pass == 0) {
-        q->total0.assign(tot, tot + S);
-        q->nan0.assign(nan, nan + S);
-        for (int s = 0; s < S; s++) q->groups[s].clear();  // until the ranks are set
-    }
-    q->pass++;
-    if (q->pass > 1 && q->pass < q->passes) {
-        int shift, nbits;
-        quant_digit(q, &shift, &nbits);
-        for (int s = 0; s < S; s++) q->groups[s] = qt_groups(q->ranks.data() + (size_t)s * R, R, shift + nbits);
-        IMCOM_TRY(quant_arm(ctx, q));
-    }
-    if (passes_left) *passes_left = q->passes - q->pass;
-    return IMCOM_OK;
-}
-
-int imcom_quant_counts(imcom_ctx *ctx, const imcom_quant *q, long *total, long *nans)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(q && total && nans, "null pointer");
-    IMCOM_REQUIRE(q->pass >= 1, "quant_counts: pass 1 has not ended");
-    for (int s = 0; s < q->S; s++) total[s] = (long)q->total0[s], nans[s] = (long)q->nan0[s];
-    return IMCOM_OK;
-}
-
-int imcom_quant_set_ranks(imcom_ctx *ctx, imcom_quant *q, const long *ranks)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(q && ranks, "null pointer");
-    IMCOM_REQUIRE(q->pass == 1, "quant_set_ranks: the ranks are set between pass 1 and pass 2");
-    const int S = q->S, R = q->R;
-    for (int s = 0; s < S; s++)
-        for (int r = 0; r < R; r++) {
-            const long k = ranks[(size_t)s * R + r];
-            IMCOM_REQUIRE(k >= -1 && (k < 0 || q->total0[s] == 0 || (unsigned long long)k < q->total0[s]), "quant_set_ranks: rank %ld of segment %d with %llu elements", k, s,
-                          q->total0[s]);
-        }
-    const std::vector<uint64_t> all(1, 0ull);
-    for (int s = 0; s < S; s++) {
-        QtRank *qr = q->ranks.data() + (size_t)s * R;
-        const unsigned long long real = q->total0[s] - q->nan0[s];
-        for (int r = 0; r < R; r++) {
-            const long k = ranks[(size_t)s * R + r];
-            qr[r] = QtRank();
-            qr[r].live = k >= 0 && (unsigned long long)k < real;
-            qr[r].rank = qr[r].live ? (uint64_t)k : 0;
-        }
-        qt_advance(qr, R, all, (const uint64_t *)q->hist0.data() + (size_t)s * QT_BINS, q->keybits, 0);
-    }
-    int shift, nbits;
-    quant_digit(q, &shift, &nbits);
-    for (int s = 0; s < S; s++) q->groups[s] = qt_groups(q->ranks.data() + (size_t)s * R, R, shift + nbits);
-    q->ranks_set = true;
-    return quant_arm(ctx, q);
-}
-
-int imcom_quant_results(imcom_ctx *ctx, const imcom_quant *q, void *out)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(q && out, "null pointer");
-    IMCOM_REQUIRE(q->pass == q->passes, "quant_results: %d of %d passes have ended", q->pass, q->passes);
-    for (size_t i = 0; i < (size_t)q->S * q->R; i++) {
-        const QtRank &r = q->ranks[i];
-        if (q->f64) ((double *)out)[i] = r.live ? om_value_f64(r.prefix) : std::nan("");
-        else ((float *)out)[i] = r.live ? om_value_f32(r.prefix) : std::nanf("");
-    }
-    return IMCOM_OK;
-}
-
-int imcom_codehist(imcom_ctx *ctx, const void *codes, long rows, long cols, long pitch, const unsigned char *table, int nbins, long *counts, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(codes && table && counts, "null pointer");
-    IMCOM_REQUIRE(nbins >= 1 && nbins <= 127, "codehist: %d bins outside 1 .. 127", nbins);
-    IMCOM_REQUIRE(rows >= 1 && cols >= 1 && pitch >= cols && rows <= QT_MAX_CHUNK / cols, "codehist: %ld x %ld codes, pitch %ld", rows, cols, pitch);
-    const size_t span = (size_t)(rows - 1) * pitch + cols;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    st.plan(plan, {span * 2, (size_t)65536, (size_t)(nbins + 1) * 8});
-    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const unsigned short *c_d;
-    const unsigned char *t_d;
-    long *n_d;
-    IMCOM_TRY(st.in((const unsigned short *)codes, span, &c_d));
-    IMCOM_TRY(st.in(table, (size_t)65536, &t_d));
-    IMCOM_TRY(st.out(counts, (size_t)nbins + 1, &n_d));
-    IMCOM_TRY(launch_codehist(ctx, c_d, rows, cols, pitch, t_d, nbins, (unsigned long long *)n_d));
-    IMCOM_TRY(st.back(counts, (const long *)n_d, (size_t)nbins + 1));
-    return st.done();
-}
-
-// ---------------------------------------------------------------------------------------------
-// The I24 layer codec (i24.hip, i24_core.h)
-}  // extern "C"
-
-namespace {
-constexpr int I24_MAX_LAYERS = 4096;
-
-// The refusals of the codec and the records the kernels read (rec may be NULL: check only).
-int i24_records(int L, long ny, long nx, const imcom_i24_pars *pars, I24Par *rec)
-{
-    IMCOM_REQUIRE(pars, "i24: null parameters");
-    IMCOM_REQUIRE(L >= 1 && L <= I24_MAX_LAYERS, "i24: %d layers, served are 1 .. %d", L, I24_MAX_LAYERS);
-    IMCOM_REQUIRE(ny >= 1 && nx >= 1 && ny <= 0x7fffffffL / nx, "i24: %ld x %ld pixels, served are 1 .. 2^31 - 1 a layer", ny, nx);
-    for (int l = 0; l < L; l++) {
-        const imcom_i24_pars &p = pars[l];
-        if (!(p.alpha == 1.0)) {
-            set_error("i24: layer %d has ALPHA = %g; only the linear codec (ALPHA absent or 1) is served: the power goes through numpy's float32 pow, whose last bit cannot be reproduced", l, p.alpha);
-            return IMCOM_ERR_UNSUPPORTED;
-        }
-        IMCOM_REQUIRE(std::isfinite(p.vmin) && std::isfinite(p.vmax) && p.vmax > p.vmin, "i24: layer %d has VMIN = %g, VMAX = %g; both must be finite and VMAX > VMIN", l, p.vmin,
-                      p.vmax);
-        IMCOM_REQUIRE(p.bitkeep >= 1 && p.bitkeep <= 24, "i24: layer %d has BITKEEP = %d outside 1 .. 24", l, p.bitkeep);
-        IMCOM_REQUIRE(p.softbias < (1L << 24), "i24: layer %d has SOFTBIAS = %ld; served are 0 .. 2^24 - 1 and -1", l, p.softbias);
-        if (!rec) continue;
-        I24Par &r = rec[l];
-        r.vmin = p.vmin;
-        r.range = p.vmax - p.vmin;
-        r.vmin_f = (float)p.vmin;
-        r.vmax_f = (float)p.vmax;
-        r.range_f = (float)r.range;
-        r.scale_f = (float)(1 << p.bitkeep);
-        r.bitkeep = p.bitkeep;
-        r.nb = (p.bitkeep + 7) / 8;
-        r.softbias = p.softbias > 0 ? (int)p.softbias : (p.softbias == -1 ? -1 : 0);  // (any other negative value does nothing, as in the reference)
-        r.diff = p.diff != 0;
-        r.reorder = p.reorder != 0;
-        r.pad = 0;
-    }
-    return IMCOM_OK;
-}
-
-long i24_layer_bytes(int L, long n, const imcom_i24_pars *pars, int scheme)
-{
-    int nb = 1;
-    for (int l = 0; l < L; l++) nb = std::max(nb, (pars[l].bitkeep + 7) / 8);
-    return scheme == I24_SCHEME_A ? 4 * n : (long)nb * n;
-}
-
-size_t i24_state_bytes(int L, long n) { return ((size_t)L * i24_tiles(n) + L) * 4; }
-
-int i24_scheme(int scheme)
-{
-    IMCOM_REQUIRE(scheme == I24_SCHEME_A || scheme == I24_SCHEME_B, "i24: scheme %d is neither 0 (I24A) nor 1 (I24B)", scheme);
-    return IMCOM_OK;
-}
-
-int i24_view(long layer_stride, long row_stride, int nx)
-{
-    IMCOM_REQUIRE(row_stride >= nx && layer_stride >= 0, "i24: a view of rows %ld and layers %ld elements apart for %d columns", row_stride, layer_stride, nx);
-    return IMCOM_OK;
-}
-
-// layer_off [L + 1] on the device from the host counts; *max_count, *total.
-int i24_offsets(imcom_ctx *ctx, int L, const long *counts, long *off_d, long *max_count, long *total)
-{
-    std::vector<long> off(L + 1, 0);
-    *max_count = 0;
-    for (int l = 0; l < L; l++) {
-        const long c = counts ? counts[l] : 0;
-        IMCOM_REQUIRE(c >= 0, "i24: %ld overflow entries for layer %d", c, l);
-        off[l + 1] = off[l] + c;
-        *max_count = std::max(*max_count, c);
-    }
-    *total = off[L];
-    return upload(ctx, off_d, off.data(), (size_t)L + 1);
-}
-}  // namespace
-
-extern "C" {
-
-int imcom_i24_sizes(int L, long ny, long nx, const imcom_i24_pars *pars, int scheme, long *out)
-{
-    IMCOM_REQUIRE(out, "null pointer");
-    IMCOM_TRY(i24_scheme(scheme));
-    IMCOM_TRY(i24_records(L, ny, nx, pars, nullptr));
-    const long n = ny * nx, tiles = i24_tiles(n);
-    WsPlan c, d;
-    c.add((size_t)L * sizeof(I24Par));
-    c.add((size_t)L * n * 4);
-    d.add((size_t)L * sizeof(I24Par));
-    d.add((size_t)L * n * 4);
-    d.add((size_t)L * tiles * 4);
-    d.add((size_t)L * 4);
-    d.add((size_t)(L + 1) * 8);
-    d.add(4);
-    out[0] = (long)i24_state_bytes(L, n);
-    out[1] = (long)c.total;
-    out[2] = (long)d.total;
-    out[3] = i24_layer_bytes(L, n, pars, scheme);
-    out[4] = tiles;
-    out[5] = I24_TILE;
-    out[6] = I24_SCAN_CHUNK;
-    out[7] = 0;
-    return IMCOM_OK;
-}
-
-int imcom_i24_compress(imcom_ctx *ctx, const float *frames, long layer_stride, long row_stride, int L, int ny, int nx, const imcom_i24_pars *pars, int scheme,
-                       void *out, long out_stride, void *state, size_t state_bytes, long *counts)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(frames && out && state && counts, "null pointer");
-    IMCOM_TRY(i24_scheme(scheme));
-    std::vector<I24Par> rec((size_t)std::max(L, 1));
-    IMCOM_TRY(i24_records(L, ny, nx, pars, rec.data()));
-    IMCOM_TRY(i24_view(layer_stride, row_stride, nx));
-    const long n = (long)ny * nx, tiles = i24_tiles(n);
-    IMCOM_REQUIRE(out_stride >= i24_layer_bytes(L, n, pars, scheme) && (scheme == I24_SCHEME_B || (out_stride % 4 == 0 && ((uintptr_t)out & 3) == 0)),
-                  "i24_compress: layers %ld bytes apart in the output, needed are %ld (I24A: int32-aligned)", out_stride, i24_layer_bytes(L, n, pars, scheme));
-    IMCOM_REQUIRE(state_bytes >= i24_state_bytes(L, n) && ((uintptr_t)state & 3) == 0, "i24_compress: state of %zu bytes, needed are %zu (4-byte aligned)", state_bytes,
-                  i24_state_bytes(L, n));
-    WsPlan plan;
-    plan.add((size_t)L * sizeof(I24Par));
-    plan.add((size_t)L * n * 4);
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    I24Par *par_d;
-    int *codes;
-    IMCOM_TRY(ws_take(ctx, (size_t)L, &par_d, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)L * n, &codes, __func__));
-    IMCOM_TRY(upload(ctx, par_d, rec.data(), (size_t)L));
-    uint32_t *bases = (uint32_t *)state, *totals = bases + (size_t)L * tiles;
-    IMCOM_TRY(launch_i24_quantise(ctx, frames, layer_stride, row_stride, L, ny, nx, par_d, codes, bases, totals));
-    IMCOM_TRY(launch_i24_pack(ctx, codes, L, n, par_d, scheme, (unsigned char *)out, out_stride));
-    std::vector<uint32_t> tot((size_t)L);
-    IMCOM_HIP_CHECK(hipMemcpyAsync(tot.data(), totals, (size_t)L * 4, hipMemcpyDeviceToHost, ctx->stream));
-    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (int l = 0; l < L; l++) counts[l] = (long)tot[l];
-    return IMCOM_OK;
-}
-
-int imcom_i24_overflow_fetch(imcom_ctx *ctx, const float *frames, long layer_stride, long row_stride, int L, int ny, int nx, const imcom_i24_pars *pars,
-                             const void *state, size_t state_bytes, const long *counts, int *y, int *x, float *value, long capacity)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(frames && state && counts, "null pointer");
-    std::vector<I24Par> rec((size_t)std::max(L, 1));
-    IMCOM_TRY(i24_records(L, ny, nx, pars, rec.data()));
-    IMCOM_TRY(i24_view(layer_stride, row_stride, nx));
-    const long n = (long)ny * nx, tiles = i24_tiles(n);
-    IMCOM_REQUIRE(state_bytes >= i24_state_bytes(L, n) && ((uintptr_t)state & 3) == 0, "i24_overflow_fetch: state of %zu bytes, needed are %zu (4-byte aligned)", state_bytes,
-                  i24_state_bytes(L, n));
-    WsPlan plan;
-    plan.add((size_t)L * sizeof(I24Par));
-    plan.add((size_t)(L + 1) * 8);
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    I24Par *par_d;
-    long *off_d, max_count, total;
-    IMCOM_TRY(ws_take(ctx, (size_t)L, &par_d, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)L + 1, &off_d, __func__));
-    IMCOM_TRY(i24_offsets(ctx, L, counts, off_d, &max_count, &total));
-    IMCOM_REQUIRE(capacity >= total, "i24_overflow_fetch: a table of %ld entries, the layers have %ld", capacity, total);
-    if (total == 0) return IMCOM_OK;
-    IMCOM_REQUIRE(y && x && value, "null pointer");
-    IMCOM_TRY(upload(ctx, par_d, rec.data(), (size_t)L));
-    const uint32_t *bases = (const uint32_t *)state, *totals = bases + (size_t)L * tiles;
-    return launch_i24_overflow(ctx, frames, layer_stride, row_stride, L, ny, nx, par_d, bases, totals, off_d, capacity, y, x, value);
-}
-
-int imcom_i24_decompress(imcom_ctx *ctx, const void *in, long in_stride, int planes, int scheme, int L, int ny, int nx, const imcom_i24_pars *pars, const int *y,
-                         const int *x, const float *value, const long *counts, float *out)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_REQUIRE(in && out, "null pointer");
-    IMCOM_TRY(i24_scheme(scheme));
-    std::vector<I24Par> rec((size_t)std::max(L, 1));
-    IMCOM_TRY(i24_records(L, ny, nx, pars, rec.data()));
-    const long n = (long)ny * nx, tiles = i24_tiles(n);
-    bool any_diff = false;
-    for (int l = 0; l < L; l++) {
-        any_diff = any_diff || rec[l].diff;
-        IMCOM_REQUIRE(scheme == I24_SCHEME_A || planes == rec[l].nb, "i24_decompress: a cube of %d byte planes for layer %d, BITKEEP = %d needs %d", planes, l, rec[l].bitkeep,
-                      rec[l].nb);
-    }
-    const long need = scheme == I24_SCHEME_A ? 4 * n : (long)planes * n;
-    IMCOM_REQUIRE(in_stride >= need && (scheme == I24_SCHEME_B || (in_stride % 4 == 0 && ((uintptr_t)in & 3) == 0)),
-                  "i24_decompress: layers %ld bytes apart in the input, needed are %ld (I24A: int32-aligned)", in_stride, need);
-    WsPlan plan;
-    plan.add((size_t)L * sizeof(I24Par));
-    plan.add((size_t)L * n * 4);
-    plan.add((size_t)L * tiles * 4);
-    plan.add((size_t)L * 4);
-    plan.add((size_t)(L + 1) * 8);
-    plan.add(4);
-    IMCOM_TRY(ws_reserve(ctx, plan.total));
-    I24Par *par_d;
-    int *codes;
-    uint32_t *sums, *totals;
-    long *off_d, max_count = 0, total = 0;
-    unsigned int *status;
-    IMCOM_TRY(ws_take(ctx, (size_t)L, &par_d, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)L * n, &codes, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)L * tiles, &sums, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)L, &totals, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)L + 1, &off_d, __func__));
-    IMCOM_TRY(ws_take(ctx, (size_t)1, &status, __func__));
-    if (counts) IMCOM_TRY(i24_offsets(ctx, L, counts, off_d, &max_count, &total));
-    IMCOM_REQUIRE(total == 0 || (y && x && value), "i24_decompress: %ld overflow entries and no table", total);
-    IMCOM_TRY(upload(ctx, par_d, rec.data(), (size_t)L));
-    IMCOM_TRY(launch_i24_decode(ctx, (const unsigned char *)in, in_stride, scheme, L, n, par_d, any_diff, codes, sums, totals, out));
-    if (total == 0) return IMCOM_OK;
-    IMCOM_HIP_CHECK(hipMemsetAsync(status, 0, 4, ctx->stream));
-    IMCOM_TRY(launch_i24_patch(ctx, out, L, ny, nx, off_d, max_count, y, x, value, status));
-    unsigned int bad = 0;
-    IMCOM_HIP_CHECK(hipMemcpyAsync(&bad, status, 4, hipMemcpyDeviceToHost, ctx->stream));
-    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    IMCOM_REQUIRE(bad == 0, "i24_decompress: the overflow table has a position outside the %d x %d image (it was not stored)", ny, nx);
-    return IMCOM_OK;
 }
 
 }  // extern "C"

@@ -2,15 +2,29 @@
 // neighbour B onto a target SCA A with the stripe parameters subtracted on the way (Sca_img.make_interpolated 476-594,
 // subtract_parameters 430-449, apply_all_mask 421-427, Parameters.forward_par 670-703), psi and its cost (cost_function_single
 // 1546-1551, 875-887, the boundary penalty 1413-1489) and the transposed scatter of f'(psi) into the parameter bins of every
-// neighbour (residual_function_single 1375-1403, transpose_par 1026-1058).  The C-ABI entries imcom_destripe_* are in api.hip.
+// neighbour (residual_function_single 1375-1403, transpose_par 1026-1058).  The C-ABI entries imcom_destripe_* end the file.
 //
 // The interpolation cell (the reference's tests/pyimcom/test_imdestripe.py 173-189, 240-256 on the C routine): positions are
 // (x, y) = (column, row) in the source, the cell is floor, a target pixel whose cell is not wholly inside the source contributes
 // nothing.  Sums that many threads feed (the parameter bins, the transposed image) are exact: every contribution is rounded once to
 // a fixed-point integer of a scale common to the call and added as an integer, so the order of arrival cannot change a bit.
+#include <algorithm>
+
 #include "launchers.h"
 
 namespace imcom {
+
+struct DsPair {            // one ordered pair: neighbour b gathered onto / scattered from target a
+    const double *x, *y;   // positions of a's pixels in b [nside][nside] (column, row), or both null:
+    const double *lat;     // their values on the lattice [2][L][L] (x plane, y plane; row node, column node)
+    int a, b;
+};
+struct DsGeom {
+    int n_sca, nside, ds_rows, amp_cols, ncb, nbins;  // ncb column blocks (0: rows only), nbins = ds_rows + ncb
+    int L, max_np;                                    // lattice nodes per axis (0: no lattice pair), most neighbours of one target
+    int model;
+    double thresh, neff_min, lambda;
+};
 
 constexpr int DS_T = 256;      // threads of a workgroup
 constexpr int DS_ROWS = 8;     // target rows a workgroup of the scatter serves before it flushes its bins
@@ -396,11 +410,11 @@ __global__ __launch_bounds__(DS_T) void destripe_unscale_kernel(const unsigned l
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
-size_t destripe_forward_lds(const DsGeom &g) { return ((size_t)g.max_np * 2 * g.L + DS_T) * sizeof(double); }
-size_t destripe_prep_lds(const DsGeom &g) { return ((size_t)g.nside + DS_T) * sizeof(double); }
-size_t destripe_scatter_lds(const DsGeom &g) { return ((size_t)2 * g.L + g.nbins) * sizeof(double); }
+static size_t destripe_forward_lds(const DsGeom &g) { return ((size_t)g.max_np * 2 * g.L + DS_T) * sizeof(double); }
+static size_t destripe_prep_lds(const DsGeom &g) { return ((size_t)g.nside + DS_T) * sizeof(double); }
+static size_t destripe_scatter_lds(const DsGeom &g) { return ((size_t)2 * g.L + g.nbins) * sizeof(double); }
 
-int launch_destripe_forward(imcom_ctx *ctx, const DsGeom &g, bool make_neff, const float *img, const unsigned char *mask, const float *geff, const double *params,
+static int launch_destripe_forward(imcom_ctx *ctx, const DsGeom &g, bool make_neff, const float *img, const unsigned char *mask, const float *geff, const double *params,
                             const DsPair *pairs, const int *start, const double *W, double *neff, float *psi, double *eps_rows)
 {
     ProfScope ps(ctx, make_neff ? "destripe_neff" : "destripe_forward");
@@ -416,7 +430,7 @@ int launch_destripe_forward(imcom_ctx *ctx, const DsGeom &g, bool make_neff, con
     return check_launch("destripe_forward_kernel");
 }
 
-int launch_destripe_eps(imcom_ctx *ctx, const DsGeom &g, const float *img, const unsigned char *mask, const double *params, const double *eps_rows, double *pen,
+static int launch_destripe_eps(imcom_ctx *ctx, const DsGeom &g, const float *img, const unsigned char *mask, const double *params, const double *eps_rows, double *pen,
                         int nchunk, double *eps)
 {
     ProfScope ps(ctx, "destripe_eps");
@@ -431,7 +445,7 @@ int launch_destripe_eps(imcom_ctx *ctx, const DsGeom &g, const float *img, const
     return check_launch("destripe_eps_kernel");
 }
 
-int launch_destripe_gradient(imcom_ctx *ctx, const DsGeom &g, const float *psi, const float *geff, const double *neff, const DsPair *pairs, int npairs,
+static int launch_destripe_gradient(imcom_ctx *ctx, const DsGeom &g, const float *psi, const float *geff, const double *neff, const DsPair *pairs, int npairs,
                              const double *W, double gmax_all, double *term1, double *rowcb, unsigned long long *gmax_bits, double *scale,
                              unsigned long long *bins, double *resids, double *r1, double *r2)
 {
@@ -463,14 +477,14 @@ int launch_destripe_gradient(imcom_ctx *ctx, const DsGeom &g, const float *psi, 
     return check_launch("destripe_resids_kernel");
 }
 
-int launch_destripe_interp(imcom_ctx *ctx, const double *src, const double *gsrc, int rows, int cols, const double *x, const double *y, long npix, double *out)
+static int launch_destripe_interp(imcom_ctx *ctx, const double *src, const double *gsrc, int rows, int cols, const double *x, const double *y, long npix, double *out)
 {
     ProfScope ps(ctx, "destripe_interp");
     hipLaunchKernelGGL(destripe_interp_kernel, dim3((unsigned)((npix + DS_T - 1) / DS_T)), dim3(DS_T), 0, ctx->stream, src, gsrc, rows, cols, x, y, npix, out);
     return check_launch("destripe_interp_kernel");
 }
 
-int launch_destripe_transpose(imcom_ctx *ctx, const double *img, const double *x, const double *y, long npix, int rows, int cols, unsigned long long *acc,
+static int launch_destripe_transpose(imcom_ctx *ctx, const double *img, const double *x, const double *y, long npix, int rows, int cols, unsigned long long *acc,
                               unsigned long long *bits, double *scale, double *out)
 {
     ProfScope ps(ctx, "destripe_transpose", 4);
@@ -490,3 +504,222 @@ int launch_destripe_transpose(imcom_ctx *ctx, const double *img, const double *x
 }
 
 }  // namespace imcom
+
+using namespace imcom;
+
+// ---------------------------------------------------------------------------------------------
+// C entries: destriping: cost and gradient over a resident mosaic
+
+namespace {
+using namespace imcom;
+
+int destripe_geom(int n_sca, int nside, int ds_rows, int amp_cols, int L, int max_np, DsGeom *g)
+{
+    IMCOM_REQUIRE(n_sca >= 1 && n_sca <= 65535 && nside >= 2 && nside <= 32768 && max_np >= 0, "destripe: %d SCAs of side %d", n_sca, nside);
+    if (ds_rows != nside) {
+        set_error("destripe: ds_rows=%d, the SCA has %d rows (forward_par, imdestripe.py:690-703, broadcasts one parameter per image row)", ds_rows, nside);
+        return IMCOM_ERR_UNSUPPORTED;
+    }
+    if (amp_cols > 0 && nside % amp_cols != 0) {
+        set_error("destripe: amp_cols=%d does not divide the %d image columns (imdestripe.py:643-648)", amp_cols, nside);
+        return IMCOM_ERR_UNSUPPORTED;
+    }
+    if (L != 0 && (L < 2 || L > 33)) {
+        set_error("destripe: a lattice of %d nodes per axis (2 <= L <= 33)", L);
+        return IMCOM_ERR_UNSUPPORTED;
+    }
+    g->n_sca = n_sca, g->nside = nside, g->ds_rows = ds_rows, g->amp_cols = amp_cols > 0 ? amp_cols : 0;
+    g->ncb = amp_cols > 0 ? nside / amp_cols : 0, g->nbins = ds_rows + g->ncb, g->L = L, g->max_np = max_np;
+    g->model = IMCOM_DESTRIPE_QUADRATIC, g->thresh = 0.0, g->neff_min = 0.5, g->lambda = 0.0;
+    if (destripe_forward_lds(*g) > 65536 || destripe_prep_lds(*g) > 65536 || destripe_scatter_lds(*g) > 65536) {
+        set_error("destripe: side %d with %d bins and %d neighbours of one SCA is beyond what a workgroup's LDS holds", nside, g->nbins, max_np);
+        return IMCOM_ERR_UNSUPPORTED;
+    }
+    return IMCOM_OK;
+}
+
+int destripe_model(int model, double thresh, DsGeom *g)
+{
+    IMCOM_REQUIRE(model == IMCOM_DESTRIPE_QUADRATIC || model == IMCOM_DESTRIPE_ABSOLUTE || model == IMCOM_DESTRIPE_HUBER, "destripe: cost model %d", model);
+    IMCOM_REQUIRE(model != IMCOM_DESTRIPE_HUBER || thresh == thresh, "destripe: huber_loss needs a threshold");
+    g->model = model, g->thresh = thresh;
+    return IMCOM_OK;
+}
+
+// the pair table: sorted by (a, b), no pair twice, a != b; *max_np = the most neighbours of one target
+int destripe_check_pairs(int n_sca, int L, int npairs, const int *pa, const int *pb, const void *const *px, const void *const *py, const void *const *pl,
+                         int *max_np)
+{
+    IMCOM_REQUIRE(npairs >= 0 && (npairs == 0 || (pa && pb && px && py && pl)), "destripe: null pair table");
+    int run = 0;
+    *max_np = 0;
+    for (int i = 0; i < npairs; i++) {
+        IMCOM_REQUIRE(pa[i] >= 0 && pa[i] < n_sca && pb[i] >= 0 && pb[i] < n_sca && pa[i] != pb[i], "destripe: pair %d is (%d, %d) of %d SCAs", i, pa[i], pb[i], n_sca);
+        IMCOM_REQUIRE(i == 0 || pa[i] > pa[i - 1] || (pa[i] == pa[i - 1] && pb[i] > pb[i - 1]), "destripe: the pair table is not sorted by (a, b) at %d", i);
+        IMCOM_REQUIRE((px[i] && py[i]) || (!px[i] && !py[i] && pl[i] && L >= 2), "destripe: pair %d has neither position arrays nor a lattice", i);
+        run = (i > 0 && pa[i] == pa[i - 1]) ? run + 1 : 1;
+        if (run > *max_np) *max_np = run;
+    }
+    return IMCOM_OK;
+}
+
+int destripe_upload_pairs(imcom_ctx *ctx, int n_sca, int npairs, const int *pa, const int *pb, const void *const *px, const void *const *py,
+                          const void *const *pl, DsPair **pairs_d, int **start_d, const char *who)
+{
+    std::vector<DsPair> tab((size_t)std::max(npairs, 1));
+    std::vector<int> start((size_t)n_sca + 1, 0);
+    for (int i = 0; i < npairs; i++) {
+        tab[i].x = (const double *)px[i], tab[i].y = (const double *)py[i], tab[i].lat = (const double *)pl[i], tab[i].a = pa[i], tab[i].b = pb[i];
+        start[pa[i] + 1]++;
+    }
+    for (int a = 0; a < n_sca; a++) start[a + 1] += start[a];
+    IMCOM_TRY(ws_take(ctx, tab.size(), pairs_d, who));
+    IMCOM_TRY(ws_take(ctx, start.size(), start_d, who));
+    IMCOM_TRY(upload(ctx, *pairs_d, tab.data(), tab.size()));
+    return upload(ctx, *start_d, start.data(), start.size());
+}
+
+size_t destripe_cost_ws(const DsGeom &g, int npairs, bool forward)
+{
+    WsPlan plan;
+    plan.add((size_t)std::max(npairs, 1) * sizeof(DsPair));
+    plan.add(((size_t)g.n_sca + 1) * sizeof(int));
+    if (forward) {
+        plan.add((size_t)g.n_sca * g.nside * 8);
+        plan.add((size_t)g.n_sca * std::max(g.ncb - 1, 1) * ((g.nside + 399) / 400) * 8);
+    }
+    return plan.total;
+}
+
+size_t destripe_resid_ws(const DsGeom &g, int npairs)
+{
+    WsPlan plan;
+    plan.add((size_t)std::max(npairs, 1) * sizeof(DsPair));
+    plan.add(((size_t)g.n_sca + 1) * sizeof(int));
+    plan.add((size_t)g.n_sca * g.nbins * 8);
+    plan.add((size_t)g.n_sca * g.nside * std::max(g.ncb, 1) * 8);
+    plan.add(8);
+    plan.add(16);
+    plan.add((size_t)g.n_sca * g.nbins * 8);
+    return plan.total;
+}
+}  // namespace
+
+extern "C" {
+
+int imcom_destripe_sizes(int n_sca, int nside, int ds_rows, int amp_cols, int L, int max_np, int npairs, long *out)
+{
+    IMCOM_REQUIRE(out && npairs >= 0, "null out");
+    DsGeom g;
+    IMCOM_TRY(destripe_geom(n_sca, nside, ds_rows, amp_cols, L, max_np, &g));
+    const long px = (long)nside * nside;
+    out[0] = g.nbins;
+    out[1] = g.ncb;
+    out[2] = px * (4 + 1 + 4 + 8 + 4);  // image, mask, g_eff, N_eff, psi
+    out[3] = px * 16;
+    out[4] = (long)L * L * 16;
+    out[5] = (long)destripe_cost_ws(g, npairs, true);
+    out[6] = (long)destripe_resid_ws(g, npairs);
+    out[7] = (long)nside * L * 8;  // the lattice weights W
+    return IMCOM_OK;
+}
+
+int imcom_destripe_neff(imcom_ctx *ctx, int n_sca, int nside, int L, const unsigned char *mask, int npairs, const int *pair_a, const int *pair_b,
+                        const void *const *pair_x, const void *const *pair_y, const void *const *pair_lat, const double *W, double *neff)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(mask && neff && (L == 0 || W), "null pointer");
+    int max_np;
+    IMCOM_TRY(destripe_check_pairs(n_sca, L, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &max_np));
+    DsGeom g;
+    IMCOM_TRY(destripe_geom(n_sca, nside, nside, 0, L, max_np, &g));
+    IMCOM_TRY(ws_reserve(ctx, destripe_cost_ws(g, npairs, false)));
+    DsPair *pairs_d;
+    int *start_d;
+    IMCOM_TRY(destripe_upload_pairs(ctx, n_sca, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &pairs_d, &start_d, __func__));
+    return launch_destripe_forward(ctx, g, true, nullptr, mask, nullptr, nullptr, pairs_d, start_d, W, neff, nullptr, nullptr);
+}
+
+int imcom_destripe_cost(imcom_ctx *ctx, int n_sca, int nside, int ds_rows, int amp_cols, int L, const float *image, const unsigned char *mask,
+                        const float *geff, const double *neff, const double *params, int npairs, const int *pair_a, const int *pair_b,
+                        const void *const *pair_x, const void *const *pair_y, const void *const *pair_lat, const double *W, int model, double thresh,
+                        double neff_min, double col_boundary_const, float *psi, double *eps)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(image && mask && geff && neff && params && psi && eps && (L == 0 || W), "null pointer");
+    int max_np;
+    IMCOM_TRY(destripe_check_pairs(n_sca, L, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &max_np));
+    DsGeom g;
+    IMCOM_TRY(destripe_geom(n_sca, nside, ds_rows, amp_cols, L, max_np, &g));
+    IMCOM_TRY(destripe_model(model, thresh, &g));
+    g.neff_min = neff_min, g.lambda = col_boundary_const;
+    if (g.ncb > 1 && g.lambda > 0.0 && g.amp_cols < 50) {
+        set_error("destripe: the boundary penalty reads 50 columns either side of a boundary, amp_cols=%d", g.amp_cols);
+        return IMCOM_ERR_UNSUPPORTED;
+    }
+    IMCOM_TRY(ws_reserve(ctx, destripe_cost_ws(g, npairs, true)));
+    DsPair *pairs_d;
+    int *start_d;
+    double *eps_rows, *pen;
+    const int nchunk = (nside + 399) / 400;
+    IMCOM_TRY(destripe_upload_pairs(ctx, n_sca, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &pairs_d, &start_d, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)n_sca * nside, &eps_rows, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)n_sca * std::max(g.ncb - 1, 1) * nchunk, &pen, __func__));
+    IMCOM_TRY(launch_destripe_forward(ctx, g, false, image, mask, geff, params, pairs_d, start_d, W, (double *)neff, psi, eps_rows));
+    return launch_destripe_eps(ctx, g, image, mask, params, eps_rows, pen, nchunk, eps);
+}
+
+int imcom_destripe_residual(imcom_ctx *ctx, int n_sca, int nside, int ds_rows, int amp_cols, int L, const float *psi, const float *geff, const double *neff,
+                            int npairs, const int *pair_a, const int *pair_b, const void *const *pair_x, const void *const *pair_y,
+                            const void *const *pair_lat, const double *W, int model, double thresh, double geff_max, double *resids, double *resids1,
+                            double *resids2)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(psi && geff && neff && resids && (L == 0 || W), "null pointer");
+    IMCOM_REQUIRE(geff_max >= 0.0 && geff_max < 1e300, "destripe: geff_max = %g", geff_max);
+    int max_np;
+    IMCOM_TRY(destripe_check_pairs(n_sca, L, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &max_np));
+    DsGeom g;
+    IMCOM_TRY(destripe_geom(n_sca, nside, ds_rows, amp_cols, L, max_np, &g));
+    IMCOM_TRY(destripe_model(model, thresh, &g));
+    IMCOM_TRY(ws_reserve(ctx, destripe_resid_ws(g, npairs)));
+    DsPair *pairs_d;
+    int *start_d;
+    double *term1, *rowcb, *scale;
+    unsigned long long *bits, *bins;
+    IMCOM_TRY(destripe_upload_pairs(ctx, n_sca, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &pairs_d, &start_d, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)n_sca * g.nbins, &term1, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)n_sca * nside * std::max(g.ncb, 1), &rowcb, __func__));
+    IMCOM_TRY(ws_take(ctx, 1, &bits, __func__));
+    IMCOM_TRY(ws_take(ctx, 2, &scale, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)n_sca * g.nbins, &bins, __func__));
+    return launch_destripe_gradient(ctx, g, psi, geff, neff, pairs_d, npairs, W, geff_max, term1, rowcb, bits, scale, bins, resids, resids1, resids2);
+}
+
+int imcom_destripe_interp(imcom_ctx *ctx, const double *src, const double *gsrc, int rows, int cols, const double *x, const double *y, long npix, double *out)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(src && gsrc && x && y && out && rows >= 2 && cols >= 2 && npix >= 0, "destripe: bad arguments of the interpolation");
+    if (npix == 0) return IMCOM_OK;
+    return launch_destripe_interp(ctx, src, gsrc, rows, cols, x, y, npix, out);
+}
+
+int imcom_destripe_interp_transpose(imcom_ctx *ctx, const double *image, const double *x, const double *y, long npix, int rows, int cols, double *out)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(image && x && y && out && rows >= 2 && cols >= 2 && npix >= 0, "destripe: bad arguments of the transposed interpolation");
+    if (npix == 0) return IMCOM_OK;
+    WsPlan plan;
+    plan.add((size_t)rows * cols * 8);
+    plan.add(8);
+    plan.add(16);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    unsigned long long *acc, *bits;
+    double *scale;
+    IMCOM_TRY(ws_take(ctx, (size_t)rows * cols, &acc, __func__));
+    IMCOM_TRY(ws_take(ctx, 1, &bits, __func__));
+    IMCOM_TRY(ws_take(ctx, 2, &scale, __func__));
+    return launch_destripe_transpose(ctx, image, x, y, npix, rows, cols, acc, bits, scale, out);
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // imsubtract.hip -- the long-range PSF part of an SCA image (reference src/pyimcom/splitpsf/imsubtract.py:658-707, run_imsubtract_single):
 // the canvas assembly  canvas[box] += H * area  and the Legendre-modulated convolution of the canvas with the kernel planes, evaluated
 // ONLY at the one sample in oversamp^2 that the reference keeps (imsubtract.py:707) and subtracted from the layer in the same launch.
-// The C-ABI entries imcom_imsub_* are in api.hip.
+// The C-ABI entries imcom_imsub_* are at the end of the file.
 //
 // With s = oversamp, np = ax / s and j = s j' + p, i = s i' + q the kept sample (Y, X) is
 //   KH[Y][X] = sum_c sum_{p,q < s} sum_{jj,ii < np} Kf[c][p][q][jj][ii] * arr_c[s (Y + Bp + jj) + rho_p][s (X + Bq + ii) + rho_q]
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void imsub_canvas_add_kernel(float *__restrict
     *dst = (float)__dadd_rn((double)*dst, __dmul_rn(H[idx], (double)area[(long)(j / s) * (hw / s) + i / s]));
 }
 
-int launch_imsub_prepare(imcom_ctx *ctx, const float *K, int ax, int s, int Nl, double *Kf)
+static int launch_imsub_prepare(imcom_ctx *ctx, const float *K, int ax, int s, int Nl, double *Kf)
 {
     ProfScope ps(ctx, "imsub_prepare");
     const int np = ax / s, npp = (np + 7) / 8 * 8;
@@ -132,7 +132,7 @@ int launch_imsub_prepare(imcom_ctx *ctx, const float *K, int ax, int s, int Nl, 
     return check_launch("imsub_prepare_kernel");
 }
 
-int launch_imsub_convolve(imcom_ctx *ctx, const float *canvas, int A, long crow0, long crows, const float *leg, const double *Kf, int ax, int Nl, int s,
+static int launch_imsub_convolve(imcom_ctx *ctx, const float *canvas, int A, long crow0, long crows, const float *leg, const double *Kf, int ax, int Nl, int s,
                           int nside, int first, int y0, int ny, float *image, double *kh)
 {
     ProfScope ps(ctx, "imsub_convolve");
@@ -144,7 +144,7 @@ int launch_imsub_convolve(imcom_ctx *ctx, const float *canvas, int A, long crow0
     return check_launch("imsub_convolve_kernel");
 }
 
-int launch_imsub_canvas_add(imcom_ctx *ctx, float *canvas, int A, const double *H, int hh, int hw, const float *area, int s, int row0, int col0)
+static int launch_imsub_canvas_add(imcom_ctx *ctx, float *canvas, int A, const double *H, int hh, int hw, const float *area, int s, int row0, int col0)
 {
     ProfScope ps(ctx, "imsub_canvas_add");
     const long total = (long)hh * hw;
@@ -153,3 +153,139 @@ int launch_imsub_canvas_add(imcom_ctx *ctx, float *canvas, int A, const double *
 }
 
 }  // namespace imcom
+
+using namespace imcom;
+
+// ---------------------------------------------------------------------------------------------
+// C entries: the long-range PSF part of an SCA image
+
+extern "C" {
+
+int imcom_imsub_sizes(int ax, int s, int nside, int Nl, long *out)
+{
+    IMCOM_REQUIRE(out, "null out");
+    IMCOM_REQUIRE(s >= 2 && s <= 64 && ax >= s && ax <= 16384 && nside >= 1 && nside <= 65536 && Nl >= 1 && Nl <= 16,
+                  "imsubtract: oversamp %d, axis_num %d, nside %d or Nl %d out of range", s, ax, nside, Nl);
+    IMCOM_REQUIRE(ax % (2 * s) == 0 || (s % 2 == 1 && ax % s == 0), "axis_num=%d must be a multiple of 2*oversamp, oversamp=%d", ax, s);
+    const long ipad = (ax + 2 * s - 1) / (2 * s), np = ax / s, npp = (np + 7) / 8 * 8;  // imsubtract.py:387-389, 451
+    out[0] = ipad;
+    out[1] = (s + 2 * s * ipad - ax) / 2;
+    out[2] = (long)s * (nside + 2 * ipad);
+    out[3] = np;
+    out[4] = npp;
+    out[5] = (long)Nl * Nl * s * s * np * npp;
+    return IMCOM_OK;
+}
+
+int imcom_imsub_prepare_kernel_f32(imcom_ctx *ctx, const float *K, int ncoeff, int ax, int Nl, int s, double *kf, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    long sz[6];
+    IMCOM_TRY(imcom_imsub_sizes(ax, s, 1, Nl, sz));
+    IMCOM_REQUIRE(K && kf, "null pointer");
+    IMCOM_REQUIRE(ncoeff >= 1 && Nl * Nl <= ncoeff, "imsubtract: Nl=%d needs %d kernel planes, the cube has %d", Nl, Nl * Nl, ncoeff);
+    Stage st(ctx, memspace, __func__);
+    const size_t szK = (size_t)Nl * Nl * ax * ax;
+    WsPlan plan;
+    st.plan(plan, {szK * 4});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const float *K_d;
+    IMCOM_TRY(st.in(K, szK, &K_d));
+    IMCOM_TRY(launch_imsub_prepare(ctx, K_d, ax, s, Nl, kf));
+    return st.done();
+}
+
+int imcom_imsub_canvas_add_f32(imcom_ctx *ctx, float *canvas, int A, const double *H, int hh, int hw, const float *area, int s, int row0, int col0,
+                               int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(canvas && H && area, "null pointer");
+    IMCOM_REQUIRE(s >= 1 && A >= 1 && A <= 1 << 20 && hh >= 0 && hw >= 0 && hh % s == 0 && hw % s == 0, "imsubtract: the block is %d x %d, oversamp %d", hh,
+                  hw, s);
+    IMCOM_REQUIRE(row0 >= 0 && col0 >= 0 && (long)row0 + hh <= A && (long)col0 + hw <= A, "imsubtract: block %d x %d at (%d, %d) leaves the %d x %d canvas",
+                  hh, hw, row0, col0, A, A);
+    if (hh == 0 || hw == 0) return IMCOM_OK;
+    Stage st(ctx, memspace, __func__);
+    const size_t szC = (size_t)A * A, szH = (size_t)hh * hw, szA = szH / ((size_t)s * s);
+    WsPlan plan;
+    st.plan(plan, {szC * 4, szH * 8, szA * 4});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    float *c_d;
+    const double *H_d;
+    const float *a_d;
+    IMCOM_TRY(st.inout(canvas, szC, &c_d));
+    IMCOM_TRY(st.in(H, szH, &H_d));
+    IMCOM_TRY(st.in(area, szA, &a_d));
+    IMCOM_TRY(launch_imsub_canvas_add(ctx, c_d, A, H_d, hh, hw, a_d, s, row0, col0));
+    IMCOM_TRY(st.back(canvas, (const float *)c_d, szC));
+    return st.done();
+}
+
+int imcom_imsub_convolve_subtract_f32(imcom_ctx *ctx, const float *canvas, int A, long crow0, long crows, const float *K, const double *kf, int ncoeff,
+                                      int ax, int Nl, int s, int nside, int y0, int ny, float *image, double *kh, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    long sz[6];
+    IMCOM_TRY(imcom_imsub_sizes(ax, s, nside, Nl, sz));
+    const long first = sz[1];
+    IMCOM_REQUIRE(canvas && image && (K || kf), "null pointer");
+    IMCOM_REQUIRE(ncoeff >= 1 && Nl * Nl <= ncoeff, "imsubtract: Nl=%d needs %d kernel planes, the cube has %d", Nl, Nl * Nl, ncoeff);
+    IMCOM_REQUIRE(A == sz[2], "imsubtract: the canvas is %d on a side, oversamp * (nside + 2 * I_pad) = %ld", A, sz[2]);
+    IMCOM_REQUIRE(y0 >= 0 && ny >= 0 && (long)y0 + ny <= nside, "imsubtract: rows %d .. %d of an image of %d", y0, y0 + ny, nside);
+    if (ny == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(crow0 >= 0 && crows >= 1 && crow0 + crows <= A && crow0 <= first + (long)s * y0 && crow0 + crows >= first + (long)s * (y0 + ny - 1) + ax,
+                  "imsubtract: canvas rows %ld .. %ld do not cover rows %ld .. %ld", crow0, crow0 + crows, first + (long)s * y0,
+                  first + (long)s * (y0 + ny - 1) + ax);
+    Stage st(ctx, memspace, __func__);
+    const size_t szC = (size_t)crows * A, szK = (size_t)Nl * Nl * ax * ax, szI = (size_t)ny * nside, szL = (size_t)Nl * A;
+    WsPlan plan;
+    plan.add(szL * 4);
+    if (!kf) plan.add((size_t)sz[5] * 8);
+    st.plan(plan, {szC * 4, szI * 4});
+    if (st.host && !kf) plan.add(szK * 4);
+    if (st.host && kh) plan.add(szI * 8);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+
+    // P_l(u) of the canvas coordinates, float64 rounded to float32 (imsubtract.py:487-488, 695-696)
+    std::vector<float> leg(szL);
+    {
+        const double ipad = (double)sz[0], a = -ipad - 0.5 + 0.5 / s, b = nside + ipad - 0.5 - 0.5 / s, step = (b - a) / (A - 1);
+        for (long i = 0; i < A; i++) {
+            double x = (double)i * step;  // numpy.linspace: arange * step, then + start; the last sample is the stop itself
+            x = x + a;
+            if (i == A - 1) x = b;
+            const double u = (x - (nside - 1) / 2.0) / (nside / 2.0);
+            double pm = 1.0, pc = u;
+            for (int l = 0; l < Nl; l++) {
+                leg[(size_t)l * A + i] = (float)(l == 0 ? 1.0 : pc);
+                if (l >= 1) {
+                    const double pn = ((2 * l + 1) * u * pc - l * pm) / (l + 1);
+                    pm = pc;
+                    pc = pn;
+                }
+            }
+        }
+    }
+    float *leg_d;
+    IMCOM_TRY(ws_take(ctx, szL, &leg_d, __func__));
+    IMCOM_TRY(upload(ctx, leg_d, leg.data(), szL));
+    double *kf_d = (double *)kf;
+    if (!kf) IMCOM_TRY(ws_take(ctx, (size_t)sz[5], &kf_d, __func__));
+    const float *c_d;
+    float *img_d;
+    IMCOM_TRY(st.in(canvas, szC, &c_d));
+    IMCOM_TRY(st.inout(image, szI, &img_d));
+    if (!kf) {
+        const float *K_d;
+        IMCOM_TRY(st.in(K, szK, &K_d));
+        IMCOM_TRY(launch_imsub_prepare(ctx, K_d, ax, s, Nl, kf_d));
+    }
+    double *kh_d = nullptr;
+    if (kh) IMCOM_TRY(st.out(kh, szI, &kh_d));
+    IMCOM_TRY(launch_imsub_convolve(ctx, c_d, A, crow0, crows, leg_d, kf_d, ax, Nl, s, nside, (int)first, y0, ny, img_d, kh_d));
+    IMCOM_TRY(st.back(image, (const float *)img_d, szI));
+    if (kh) IMCOM_TRY(st.back(kh, (const double *)kh_d, szI));
+    return st.done();
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // inject.hip -- injected point-source layers (reference src/pyimcom/layer.py:792-854, GridInject.make_image_from_grid): the PSF of
 // every grid star out of a Legendre cube (coadd.py:624-640) and the stars drawn into the SCA image with the D5512 interpolator.
-// The C-ABI entries imcom_psf_from_cube / imcom_draw_stars are in api.hip.
+// The C-ABI entries imcom_psf_from_cube / imcom_draw_stars are at the end of the file.
 #include "d5512.h"
 #include "launchers.h"
 
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void draw_stars_kernel(int nstar, const double
         if (touched[k]) image[(long)(y0 + tr + 8 * k) * nside + (x0 + tx)] = acc[k];  // (touched: the pixel is inside the image, star_span)
 }
 
-int launch_cube_contract(imcom_ctx *ctx, const double *planes, int na, long npix, const double *lpoly, int nstar, double scale, double *out)
+static int launch_cube_contract(imcom_ctx *ctx, const double *planes, int na, long npix, const double *lpoly, int nstar, double scale, double *out)
 {
     if (nstar == 0) return IMCOM_OK;
     ProfScope ps(ctx, "inject_psf");
@@ -169,7 +169,7 @@ int launch_cube_contract(imcom_ctx *ctx, const double *planes, int na, long npix
     return check_launch("cube_contract_kernel");
 }
 
-int launch_draw_stars(imcom_ctx *ctx, int nstar, const double *psfs, int py, int px, const double *xsca, const double *ysca, double oversamp,
+static int launch_draw_stars(imcom_ctx *ctx, int nstar, const double *psfs, int py, int px, const double *xsca, const double *ysca, double oversamp,
                       int d, int nside, double *image)
 {
     if (nstar == 0) return IMCOM_OK;
@@ -181,3 +181,66 @@ int launch_draw_stars(imcom_ctx *ctx, int nstar, const double *psfs, int py, int
 }
 
 }  // namespace imcom
+
+using namespace imcom;
+
+// ---------------------------------------------------------------------------------------------
+// C entries: injected star layers
+
+extern "C" {
+
+int imcom_psf_from_cube(imcom_ctx *ctx, int na, const double *cube, int ny, int nx, int nstar, const double *lpoly, double tophatwidth,
+                        double gaussiansigma, double scale, double *out, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(na >= 1 && cube && ny >= 1 && nx >= 1 && nstar >= 0 && (nstar == 0 || (lpoly && out)), "bad arguments");
+    IMCOM_REQUIRE(tophatwidth >= 0.0 && gaussiansigma >= 0.0 && tophatwidth + 6.0 * gaussiansigma < 4096.0 && scale == scale,
+                  "bad smearing widths or scale");
+    if (nstar == 0) return IMCOM_OK;
+    Stage st(ctx, memspace, __func__);
+    const int npad = imcom_smooth_pad_width(tophatwidth, gaussiansigma), nyy = ny + 2 * npad, nxx = nx + 2 * npad;
+    const size_t szCube = (size_t)na * ny * nx, szL = (size_t)nstar * na, npix = (size_t)nyy * nxx, szOut = (size_t)nstar * npix;
+    WsPlan plan;
+    plan.add(smooth_pad_ws_bytes(na, ny, nx, tophatwidth, gaussiansigma));
+    plan.add((size_t)na * npix * 8);
+    st.plan(plan, {szCube * 8, szL * 8, szOut * 8});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    SmoothPadWs w;
+    IMCOM_TRY(smooth_pad_take(ctx, na, ny, nx, tophatwidth, gaussiansigma, &w, __func__));
+    double *planes, *out_d;
+    IMCOM_TRY(ws_take(ctx, (size_t)na * npix, &planes, __func__));
+    const double *cube_d, *lpoly_d;
+    IMCOM_TRY(st.in(cube, szCube, &cube_d));
+    IMCOM_TRY(st.in(lpoly, szL, &lpoly_d));
+    IMCOM_TRY(st.out(out, szOut, &out_d));
+    IMCOM_TRY(smooth_pad_device(ctx, w, na, cube_d, ny, nx, tophatwidth, gaussiansigma, planes));
+    IMCOM_TRY(launch_cube_contract(ctx, planes, na, (long)npix, lpoly_d, nstar, scale, out_d));
+    IMCOM_TRY(st.back(out, out_d, szOut));
+    return st.done();
+}
+
+int imcom_draw_stars(imcom_ctx *ctx, int nstar, const double *psfs, int py, int px, const double *xsca, const double *ysca, double oversamp,
+                     int d, int nside, double *image, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(nstar >= 0 && image && (nstar == 0 || (psfs && xsca && ysca)), "null pointer");
+    IMCOM_REQUIRE(py >= 1 && px >= 1 && py <= 16384 && px <= 16384 && d >= 1 && d <= 65536 && nside >= 1 && nside <= 65536, "bad sizes");
+    IMCOM_REQUIRE(oversamp >= 1.0e-3 && oversamp <= 1.0e6, "oversamp %g out of range", oversamp);
+    if (nstar == 0) return IMCOM_OK;
+    Stage st(ctx, memspace, __func__);
+    const size_t szP = (size_t)nstar * py * px, szI = (size_t)nside * nside;
+    WsPlan plan;
+    st.plan(plan, {szP * 8, (size_t)nstar * 8, (size_t)nstar * 8, szI * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *p_d, *x_d, *y_d;
+    double *img_d;
+    IMCOM_TRY(st.in(psfs, szP, &p_d));
+    IMCOM_TRY(st.in(xsca, (size_t)nstar, &x_d));
+    IMCOM_TRY(st.in(ysca, (size_t)nstar, &y_d));
+    IMCOM_TRY(st.inout(image, szI, &img_d));  // the stars are added to what the image holds
+    IMCOM_TRY(launch_draw_stars(ctx, nstar, p_d, py, px, x_d, y_d, oversamp, d, nside, img_d));
+    IMCOM_TRY(st.back(image, img_d, szI));
+    return st.done();
+}
+
+}  // extern "C"

@@ -1,4 +1,5 @@
-// launchers.h -- host-side launch functions implemented next to their kernels.
+// launchers.h -- host-side functions, structs and constants that are used from ANOTHER source file than the one that defines them.  What only
+// its own file uses (a seam's launch functions, called by the C entries below them) is static there and has no line here.
 #pragma once
 #include <functional>
 
@@ -125,7 +126,6 @@ int launch_build_B(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, const d
                    const int *psf, const double *tables, int ng, double nc, double dscale, const int *io_tab,
                    int npsf_max, const double *out_x0, const double *out_y0, int n2f, int ldm, double *Bt);
 
-
 // psf_sample.hip: the device work of imcom_smooth_and_pad on its own (src, dst in device memory), its scratch out of the workspace
 struct SmoothPadWs {
     double *I, *Y, *Z, *Cy, *Cx, *ky, *kx;
@@ -135,44 +135,6 @@ int smooth_pad_take(imcom_ctx *ctx, int n, int ny, int nx, double tophatwidth, d
 int smooth_pad_device(imcom_ctx *ctx, const SmoothPadWs &w, int n, const double *src, int ny, int nx, double tophatwidth, double gaussiansigma,
                       double *dst);
 
-// inject.hip
-int launch_cube_contract(imcom_ctx *ctx, const double *planes, int na, long npix, const double *lpoly, int nstar, double scale, double *out);
-int launch_draw_stars(imcom_ctx *ctx, int nstar, const double *psfs, int py, int px, const double *xsca, const double *ysca, double oversamp,
-                      int d, int nside, double *image);
-
-// imsubtract.hip
-int launch_imsub_prepare(imcom_ctx *ctx, const float *K, int ax, int s, int Nl, double *Kf);
-int launch_imsub_convolve(imcom_ctx *ctx, const float *canvas, int A, long crow0, long crows, const float *leg, const double *Kf, int ax, int Nl, int s,
-                          int nside, int first, int y0, int ny, float *image, double *kh);
-int launch_imsub_canvas_add(imcom_ctx *ctx, float *canvas, int A, const double *H, int hh, int hw, const float *area, int s, int row0, int col0);
-
-// destripe.hip
-struct DsPair {            // one ordered pair: neighbour b gathered onto / scattered from target a
-    const double *x, *y;   // positions of a's pixels in b [nside][nside] (column, row), or both null:
-    const double *lat;     // their values on the lattice [2][L][L] (x plane, y plane; row node, column node)
-    int a, b;
-};
-struct DsGeom {
-    int n_sca, nside, ds_rows, amp_cols, ncb, nbins;  // ncb column blocks (0: rows only), nbins = ds_rows + ncb
-    int L, max_np;                                    // lattice nodes per axis (0: no lattice pair), most neighbours of one target
-    int model;
-    double thresh, neff_min, lambda;
-};
-size_t destripe_forward_lds(const DsGeom &g);
-size_t destripe_prep_lds(const DsGeom &g);
-size_t destripe_scatter_lds(const DsGeom &g);
-int launch_destripe_forward(imcom_ctx *ctx, const DsGeom &g, bool make_neff, const float *img, const unsigned char *mask, const float *geff, const double *params,
-                            const DsPair *pairs, const int *start, const double *W, double *neff, float *psi, double *eps_rows);
-int launch_destripe_eps(imcom_ctx *ctx, const DsGeom &g, const float *img, const unsigned char *mask, const double *params, const double *eps_rows, double *pen,
-                        int nchunk, double *eps);
-int launch_destripe_gradient(imcom_ctx *ctx, const DsGeom &g, const float *psi, const float *geff, const double *neff, const DsPair *pairs, int npairs,
-                             const double *W, double gmax_all, double *term1, double *rowcb, unsigned long long *gmax_bits, double *scale,
-                             unsigned long long *bins, double *resids, double *r1, double *r2);
-int launch_destripe_interp(imcom_ctx *ctx, const double *src, const double *gsrc, int rows, int cols, const double *x, const double *y, long npix, double *out);
-int launch_destripe_transpose(imcom_ctx *ctx, const double *img, const double *x, const double *y, long npix, int rows, int cols, unsigned long long *acc,
-                              unsigned long long *bits, double *scale, double *out);
-
-
 // psf_overlap.hip: the plan of the wave-per-line transforms (fft_lines.h) and its stage tables (tw: pl.n complex values, device memory)
 struct FftPlan;
 bool fft_line_plan(int n, FftPlan *pl);
@@ -180,17 +142,7 @@ int fft_line_twiddles(imcom_ctx *ctx, const FftPlan &pl, double2 *tw);
 
 // splitpsf.hip
 constexpr int SPLITPSF_MAXN = 4096;  // largest transform side (2 x the cube side)
-constexpr int SPLITPSF_ROUTE_NONE = 0, SPLITPSF_ROUTE_LINES = 1, SPLITPSF_ROUTE_DENSE = 2;
-int splitpsf_route(int nfft);
-int splitpsf_tophat_npad(double width);
-size_t splitpsf_tophat_ws(int nplane, int n, double width);
-int launch_splitpsf_tophat(imcom_ctx *ctx, const double *cube, int nplane, int n, double width, double *out);
-int launch_splitpsf_split(imcom_ctx *ctx, const double *cube, int npoly, int n, int ns, double r1, double r2, const double *trunc_dev, double *smallpsf,
-                          double *resid);
-size_t splitpsf_points_ws(int n, int nsca, int npts, bool own_kreal);
-int launch_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npoly, int n, int i0, int npts, const double *lpw, const double *wg,
-                           const double *cov, double eps, double *KL, double *K_real, double *zeta, double *zmax);
-// its dense-DFT line engine (route 2) for other callers: plan / take the DFT matrix (forward, and inverse if asked), the packed lines A and
+// the dense-DFT line engine (its route 2) for other callers: plan / take the DFT matrix (forward, and inverse if asked), the packed lines A and
 // the product C; after splitpsf_dense_product row l of d.C (stride d.Np doubles) holds the transform of line l of `in`, interleaved (re, im)
 struct SpDense {
     int N = 0, Kp = 0, Np = 0;
@@ -201,91 +153,10 @@ void splitpsf_dense_plan(SpDense &d, int N, long nlines, bool inverse, WsPlan &p
 int splitpsf_dense_take(imcom_ctx *ctx, SpDense &d, bool inverse, const char *who);
 int splitpsf_dense_product(imcom_ctx *ctx, const SpDense &d, const double2 *in, long nlines, bool inv);
 
-// noisespec.hip: noise power spectra of coadded frames
-constexpr int NOISEPS_ROUTE_NONE = 0, NOISEPS_ROUTE_LINES = 1, NOISEPS_ROUTE_DENSE = 2, NOISEPS_ROUTE_TWOLEVEL = 3;
-int noiseps_route(int L, bool force_dense);  // force_dense: IMCOM_NOISEPS_ROUTE=dense (the caller reads the environment)
-size_t noiseps_ws(int L, int nframe, int route);
-int launch_noiseps_2d(imcom_ctx *ctx, const void *frames, bool in_f64, int nframe, int L, long fstride, long rstride, const double *window,
-                      const double *norm_dev, bool bin8, int route, double *out);
-int launch_noiseps_radial(imcom_ctx *ctx, const double *image, int nframe, int n, const int *rbin, int nidx, double *mean, double *err);
-int launch_noiseps_accumulate(imcom_ctx *ctx, const double *ps2d, const double *mean, const double *err, int nlayers, long npix, int nrad, int bins,
-                              int coverage_bin, double *ps2d_all, double *ps1d_all);
-
-// pcg64.hip: draws of numpy's PCG64 stream by position, and the cosmic-ray mask made of them.  state / offset: (low, high) halves;
-// jumps [PCG64_JUMPS][2][2]: the (low, high) halves of A_j and C_j, the affine map of 2^j steps for the stream's increment (device memory)
+// pcg64.hip: jumps [PCG64_JUMPS][2][2] (device memory), the (low, high) halves of A_j and C_j, the affine map of 2^j steps of numpy's
+// PCG64 stream with the increment (inc_lo, inc_hi); pcg64_jumps forms them on the host and puts them into the workspace
 constexpr int PCG64_JUMPS = 128;
-int launch_pcg64_uniform(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const unsigned long long offset[2], long count,
-                         double *out);
-int launch_pcg64_uniform_at(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const long *pos, long count, double *out);
-
-// ziggurat.hip: numpy's normal draws of a PCG64 stream, one chunk of `tiles` tiles of P positions from stream position `start` (128 bits;
-// start_rel: the same counted from the call's offset).  The chain enters the chunk at offset entry0 with base0 draws made; res[2] = {entry
-// offset after the chunk, draws made by then}.  exit_t / count_t [tiles][ZIG_ENTRIES], entry_t / base_t [tiles]: the tile tables.
-// info [4] (device, zeroed by the caller): outputs consumed by `count` draws, slow attempts, tail draws, flags (1 undecided, 2 tail list full).
-size_t zig_lds_bytes(int P, int levels);
-int launch_zig_chunk(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const unsigned long long start[2],
-                     unsigned long long start_rel, int P, long tiles, int entry0, long base0, double guard, unsigned char *exit_t, unsigned short *count_t,
-                     unsigned char *entry_t, long *base_t, long *res, long count, double *out, long *tail_idx, unsigned long long *tail_raw, long tail_cap,
-                     unsigned long long *info);
-// noise1f.hip: the transform of the 1/f noise layer.  noise1f_split: len = N1 N2 for the four-step transform, false if len is no power of
-// two in 2^10 .. 2^20.  launch_noise1f_group: channels ch0 .. ch0 + nchg - 1 of g [2 nch][len] into blk [nch][len / 2] (Re DFT / sqrt 2), S
-// [nchg][len] complex scratch, tw1 [N1] / tw2 [N2] the stage tables of the line plans
-// (noise1f_tables).  launch_noise1f_place: the channel sums (sum
-// [nch]), blk minus its channel mean in place, and the float32 frame without its border.
-constexpr int NOISE1F_GROUP = 8;  // channels that share one pass (and the scratch S: 128 MB at len = 2^20)
-bool noise1f_split(long len, int *N1, int *N2);
-int noise1f_tables(imcom_ctx *ctx, long len, double2 *tw1, double2 *tw2);
-int launch_noise1f_group(imcom_ctx *ctx, const double *g, const double *amp, long len, int ch0, int nchg, const double2 *tw1, const double2 *tw2, double2 *S,
-                         double *blk);
-int launch_noise1f_place(imcom_ctx *ctx, double *blk, double *sum, long len, int nch, int w, int border, float *frame);
-int launch_cr_mask(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, unsigned long long base, int nside, int pad, double pcut,
-                   const float *labnoise, double threshold, unsigned char *mask, unsigned long long *ngood);
-
-// objmask.hip: exact order statistics, threshold / clipping flags, constrained propagation, box dilation and application of a mask
-constexpr int SELECT_BINS = 2048, SELECT_STATE = 8;  // histogram bins of a pass (two histograms); words of the selection state
-constexpr int MASK_DILATE_TX = 48, MASK_DILATE_TY = 32, MASK_DILATE_MAX_R = 8;  // output pixels of a dilation workgroup; largest radius
-constexpr int MASK_PROPAGATE_T = 62;                                            // side of a propagation tile
-int launch_select_kth(imcom_ctx *ctx, const void *vals, bool f64, const unsigned char *flags, long n, bool use_abs, double c, long k, unsigned long long *state,
-                      unsigned long long *hist, void *res, long *info);
-int launch_mask_threshold(imcom_ctx *ctx, const void *img, bool f64, long n, double bkg, double t1, double t2, bool finite_only, unsigned char *m1,
-                          unsigned char *m2);
-int launch_mask_clip(imcom_ctx *ctx, const void *img, bool f64, long n, const unsigned char *keep_in, double bkg, double t, unsigned char *keep_out,
-                     unsigned long long *count);
-int launch_mask_apply(imcom_ctx *ctx, const void *in, int dtype, const unsigned char *mask, long n, void *out);
-int launch_mask_dilate(imcom_ctx *ctx, const unsigned char *in, int H, int W, int r, unsigned char *out);
-int launch_mask_propagate(imcom_ctx *ctx, const unsigned char *grow, int H, int W, unsigned char *out, unsigned char *tmp, unsigned int *changed, long *sweeps);
-
-// quantiles.hip: the counting passes of the streaming exact select and the coded-map histogram.  QtDev: the accumulator's device state
-// (all 64-bit words) -- per segment the elements and the NaNs the running pass has seen and the number of its live groups, `bad` one word
-// (segment ids out of range, star positions not served), the ascending prefixes of segment s's groups at gprefix[s R ..], the group's
-// counters at hist[(s R + g) QT_BINS ..].
-constexpr int QT_BINS = 2048, QT_TILE = 8, QT_THREADS = 512;  // counters of a group; groups whose counters share a workgroup's LDS; its threads
-struct QtDev {
-    unsigned long long *tot, *nan, *ng, *bad, *gprefix, *hist;
-    int S, R;
-};
-int launch_quant_dense(imcom_ctx *ctx, const QtDev &d, bool f64, int seg, int ng, const void *p, long rows, long cols, long pitch, int shift, int nbits);
-int launch_quant_ids(imcom_ctx *ctx, const QtDev &d, bool f64, const void *p, const void *ids, bool ids_i32, long n, int shift, int nbits);
-int launch_quant_rings(imcom_ctx *ctx, const QtDev &d, bool f64, const void *frame, int n, long pitch, const double *x, const double *y, int nstar, int rpix, int shift,
-                       int nbits);
-int launch_quant_constant(imcom_ctx *ctx, const QtDev &d, bool f64, int seg, double value, unsigned long long count, int shift, int nbits);
-int launch_codehist(imcom_ctx *ctx, const unsigned short *codes, long rows, long cols, long pitch, const unsigned char *table, int nbins, unsigned long long *counts);
-
-// i24.hip: the I24 layer codec for a batch of L layers of ny x nx pixels (n = ny nx, tiles = i24_tiles(n) of I24_TILE pixels, i24_core.h).
-// pars [L] device records.  launch_i24_quantise: codes [L][n], counts [L][tiles] -> the exclusive prefix sums of the tiles' overflow hits,
-// totals [L].  launch_i24_pack: codes -> I24A int32 / I24B bytes, layer l at out + l out_stride (bytes).  launch_i24_overflow: the table
-// entries of layer l at layer_off[l] .. layer_off[l + 1] (device, [L + 1]) of oy / ox / ov, none at or beyond cap.  launch_i24_decode:
-// in -> codes (SOFTBIAS undone), sums [L][tiles] and totals [L] scratch of the prefix sum, out [L][n] float32.  launch_i24_patch: the
-// overflow entries into out; *status becomes non-zero if a position lies outside the image (it is not stored).
-struct I24Par;
-int launch_i24_quantise(imcom_ctx *ctx, const float *frames, long lstride, long rstride, int L, int ny, int nx, const I24Par *pars, int *codes, uint32_t *counts,
-                        uint32_t *totals);
-int launch_i24_pack(imcom_ctx *ctx, const int *codes, int L, long n, const I24Par *pars, int scheme, unsigned char *out, long out_stride);
-int launch_i24_overflow(imcom_ctx *ctx, const float *frames, long lstride, long rstride, int L, int ny, int nx, const I24Par *pars, const uint32_t *bases,
-                        const uint32_t *totals, const long *layer_off, long cap, int *oy, int *ox, float *ov);
-int launch_i24_decode(imcom_ctx *ctx, const unsigned char *in, long in_stride, int scheme, int L, long n, const I24Par *pars, bool any_diff, int *codes, uint32_t *sums,
-                      uint32_t *totals, float *out);
-int launch_i24_patch(imcom_ctx *ctx, float *out, int L, int ny, int nx, const long *layer_off, long max_count, const int *oy, const int *ox, const float *ov,
-                     unsigned int *status);
+constexpr long PCG64_MAX_COUNT = 1L << 36;  // most draws of one call
+int pcg64_jumps(imcom_ctx *ctx, uint64_t inc_lo, uint64_t inc_hi, const unsigned long long **jumps_d, const char *who);
 
 }  // namespace imcom

@@ -98,7 +98,8 @@ __global__ void n1f_place_kernel(double *__restrict__ blk, const double *__restr
     if (y >= 0 && y < rows - 2 * border && x >= 0 && x < cols - 2 * border) frame[y * (cols - 2 * border) + x] = (float)v;
 }
 
-bool noise1f_split(long len, int *N1, int *N2)
+// len = N1 N2 for the four-step transform, false if len is no power of two in 2^10 .. 2^20
+static bool noise1f_split(long len, int *N1, int *N2)
 {
     if (len < 1024 || len > (1L << 20) || (len & (len - 1))) return false;
     int lg = 0;
@@ -111,7 +112,7 @@ bool noise1f_split(long len, int *N1, int *N2)
 static size_t n1f_lds(const FftPlan &pl) { return ((size_t)pl.waves * pl.npad + pl.twn) * 16; }
 
 // the stage tables of the two line plans: tw1 [N1], tw2 [N2] complex values
-int noise1f_tables(imcom_ctx *ctx, long len, cplx *tw1, cplx *tw2)
+static int noise1f_tables(imcom_ctx *ctx, long len, cplx *tw1, cplx *tw2)
 {
     int N1, N2;
     FftPlan p1, p2;
@@ -122,7 +123,7 @@ int noise1f_tables(imcom_ctx *ctx, long len, cplx *tw1, cplx *tw2)
 
 // the channels ch0 .. ch0 + nchg - 1: g [2 nch][len] and blk [nch][len / 2] are the whole call's, S [nchg][len] the group's scratch; tw1 /
 // tw2: the stage tables of the N1 / N2 plans
-int launch_noise1f_group(imcom_ctx *ctx, const double *g, const double *amp, long len, int ch0, int nchg, const cplx *tw1, const cplx *tw2, cplx *S, double *blk)
+static int launch_noise1f_group(imcom_ctx *ctx, const double *g, const double *amp, long len, int ch0, int nchg, const cplx *tw1, const cplx *tw2, cplx *S, double *blk)
 {
     int N1, N2;
     FftPlan p1, p2;
@@ -140,7 +141,8 @@ int launch_noise1f_group(imcom_ctx *ctx, const double *g, const double *amp, lon
     return check_launch("n1f_step2_kernel");
 }
 
-int launch_noise1f_place(imcom_ctx *ctx, double *blk, double *sum, long len, int nch, int w, int border, float *frame)
+// the channel sums (sum [nch]), blk minus its channel mean in place, and the float32 frame without its border
+static int launch_noise1f_place(imcom_ctx *ctx, double *blk, double *sum, long len, int nch, int w, int border, float *frame)
 {
     const long half = len / 2;
     ProfScope ps(ctx, "n1f_place", 2);
@@ -151,3 +153,58 @@ int launch_noise1f_place(imcom_ctx *ctx, double *blk, double *sum, long len, int
 }
 
 }  // namespace imcom
+
+using namespace imcom;
+
+// ---------------------------------------------------------------------------------------------
+// C entries: The transform of the 1/f noise layer
+
+constexpr int NOISE1F_GROUP = 8;  // channels that share one pass (and the scratch S: 128 MB at len = 2^20)
+
+extern "C" {
+
+int imcom_noise_1f(imcom_ctx *ctx, const double *normals, const double *amp, long len, int nch, int w, int border, float *frame, double *block, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(len >= 2 && nch >= 1 && nch <= 4096 && w >= 1 && border >= 0, "noise_1f: len %ld, %d channels of width %d, border %d", len, nch, w, border);
+    int N1, N2;
+    if ((w & (w - 1)) || !noise1f_split(len, &N1, &N2) || (long)w > len / 2) {
+        set_error("noise_1f: the length (%ld) must be a power of two in 2^10 .. 2^20 and the channel width (%d) a power of two up to half of it", len, w);
+        return IMCOM_ERR_UNSUPPORTED;
+    }
+    IMCOM_REQUIRE(normals && amp && frame, "null pointer");
+    const long half = len / 2, rows = half / w, cols = (long)nch * w;
+    IMCOM_REQUIRE(2L * border < rows && 2L * border < cols, "noise_1f: a border of %d leaves nothing of %ld x %ld pixels", border, rows, cols);
+    const long npix = (rows - 2 * border) * (cols - 2 * border);
+    const int group = std::min(nch, NOISE1F_GROUP);
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    plan.add((size_t)N1 * 16);
+    plan.add((size_t)N2 * 16);
+    plan.add((size_t)group * len * 16);  // S
+    plan.add((size_t)nch * 8);           // sums
+    if (st.host || !block) plan.add((size_t)nch * half * 8);
+    st.plan(plan, {(size_t)2 * nch * len * 8, (size_t)len * 8, (size_t)npix * 4});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    double2 *tw1, *tw2, *S;
+    double *sum, *blk = block;
+    const double *g_d, *amp_d;
+    float *f_d;
+    IMCOM_TRY(ws_take(ctx, (size_t)N1, &tw1, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)N2, &tw2, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)group * len, &S, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)nch, &sum, __func__));
+    if (st.host || !block) IMCOM_TRY(ws_take(ctx, (size_t)nch * half, &blk, __func__));
+    IMCOM_TRY(st.in(normals, (size_t)2 * nch * len, &g_d));
+    IMCOM_TRY(st.in(amp, (size_t)len, &amp_d));
+    IMCOM_TRY(st.out(frame, (size_t)npix, &f_d));
+    IMCOM_TRY(noise1f_tables(ctx, len, tw1, tw2));
+    for (int ch0 = 0; ch0 < nch; ch0 += group)
+        IMCOM_TRY(launch_noise1f_group(ctx, g_d, amp_d, len, ch0, std::min(group, nch - ch0), tw1, tw2, S, blk));
+    IMCOM_TRY(launch_noise1f_place(ctx, blk, sum, len, nch, w, border, f_d));
+    IMCOM_TRY(st.back(frame, (const float *)f_d, (size_t)npix));
+    if (block) IMCOM_TRY(st.back(block, (const double *)blk, (size_t)nch * half));
+    return st.done();
+}
+
+}  // extern "C"

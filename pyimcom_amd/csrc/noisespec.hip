@@ -31,6 +31,7 @@
 
 namespace imcom {
 
+constexpr int NOISEPS_ROUTE_NONE = 0, NOISEPS_ROUTE_LINES = 1, NOISEPS_ROUTE_DENSE = 2, NOISEPS_ROUTE_TWOLEVEL = 3;
 constexpr int NS_MAXN2 = 16;
 constexpr int NS_MAXWAVES = 8;  // waves per workgroup: two per SIMD leave a wave 256 registers (a radix-16 butterfly with its twiddles needs ~140, the N2 column 64 more)
 
@@ -55,7 +56,8 @@ static bool ns_factor(int L, FftPlan *pl, int *N2)
     return false;
 }
 
-int noiseps_route(int L, bool force_dense)
+// force_dense: IMCOM_NOISEPS_ROUTE=dense (the caller reads the environment)
+static int noiseps_route(int L, bool force_dense)
 {
     if (L < 2 || L % 2 != 0 || L > SPLITPSF_MAXN) return NOISEPS_ROUTE_NONE;
     FftPlan pl;
@@ -342,7 +344,7 @@ static size_t ns_plan(NsPlan &p, int L, int nframe, int route, WsPlan &plan)
     return plan.total;
 }
 
-size_t noiseps_ws(int L, int nframe, int route)
+static size_t noiseps_ws(int L, int nframe, int route)
 {
     NsPlan p;
     WsPlan plan;
@@ -366,7 +368,7 @@ template <class T, bool ROWS> static int ns_launch_lines(imcom_ctx *ctx, const N
 
 // frames: nframe frames of side L, element (f, y, x) at f fstride + y rstride + x (device memory, float or double); window [L][L] or null;
 // norm_dev [nframe]; out [nframe][n][n], n = L / 8 (bin8) or L.  The caller has reserved noiseps_ws(L, nframe, route).
-int launch_noiseps_2d(imcom_ctx *ctx, const void *frames, bool in_f64, int nframe, int L, long fstride, long rstride, const double *window,
+static int launch_noiseps_2d(imcom_ctx *ctx, const void *frames, bool in_f64, int nframe, int L, long fstride, long rstride, const double *window,
                       const double *norm_dev, bool bin8, int route, double *out)
 {
     NsPlan p;
@@ -417,14 +419,14 @@ int launch_noiseps_2d(imcom_ctx *ctx, const void *frames, bool in_f64, int nfram
     return check_launch("ns_epilogue_kernel");
 }
 
-int launch_noiseps_radial(imcom_ctx *ctx, const double *image, int nframe, int n, const int *rbin, int nidx, double *mean, double *err)
+static int launch_noiseps_radial(imcom_ctx *ctx, const double *image, int nframe, int n, const int *rbin, int nidx, double *mean, double *err)
 {
     ProfScope ps(ctx, "noiseps_radial");
     hipLaunchKernelGGL(ns_radial_kernel, dim3(nidx, nframe), dim3(256), 0, ctx->stream, image, (long)n * n, rbin, nidx, mean, err);
     return check_launch("ns_radial_kernel");
 }
 
-int launch_noiseps_accumulate(imcom_ctx *ctx, const double *ps2d, const double *mean, const double *err, int nlayers, long npix, int nrad, int bins,
+static int launch_noiseps_accumulate(imcom_ctx *ctx, const double *ps2d, const double *mean, const double *err, int nlayers, long npix, int nrad, int bins,
                               int coverage_bin, double *ps2d_all, double *ps1d_all)
 {
     const long span = std::max<long>(npix, nrad);
@@ -434,3 +436,111 @@ int launch_noiseps_accumulate(imcom_ctx *ctx, const double *ps2d, const double *
 }
 
 }  // namespace imcom
+
+using namespace imcom;
+
+// ---------------------------------------------------------------------------------------------
+// C entries: noise power spectra of coadded frames
+
+static int noiseps_pick(int L, int route)  // route 0: the plan's own choice (IMCOM_NOISEPS_ROUTE=dense forces the dense DFT)
+{
+    const int best = noiseps_route(L, env_is("IMCOM_NOISEPS_ROUTE", "dense"));
+    if (route == 0 || best == NOISEPS_ROUTE_NONE) return best;
+    if (route == NOISEPS_ROUTE_DENSE) return route;
+    return route == noiseps_route(L, false) ? route : NOISEPS_ROUTE_NONE;
+}
+
+static int noiseps_check_side(int L, int bin8)
+{
+    IMCOM_REQUIRE(L >= 2 && L % 2 == 0, "noise spectra: the side %d is not even", L);
+    IMCOM_REQUIRE(!bin8 || L % 8 == 0, "noise spectra: the side %d is not a multiple of 8 (8 x 8 binning)", L);
+    IMCOM_REQUIRE(L <= SPLITPSF_MAXN, "noise spectra: a side of %d is beyond the %d this build transforms", L, SPLITPSF_MAXN);
+    return IMCOM_OK;
+}
+
+extern "C" {
+
+int imcom_noiseps_route(int L) { return noiseps_route(L, env_is("IMCOM_NOISEPS_ROUTE", "dense")); }
+
+int imcom_noiseps_sizes(int L, int nframe, int bin8, int route, long *out)
+{
+    IMCOM_REQUIRE(out, "null out");
+    IMCOM_TRY(noiseps_check_side(L, bin8));
+    IMCOM_REQUIRE(nframe >= 1 && nframe <= 65535 && route >= 0 && route <= 3, "noise spectra: %d frames, route %d", nframe, route);
+    const int r = noiseps_pick(L, route);
+    IMCOM_REQUIRE(r != NOISEPS_ROUTE_NONE, "noise spectra: route %d does not serve the side %d", route, L);
+    out[0] = r;
+    out[1] = bin8 ? L / 8 : L;
+    out[2] = (long)noiseps_ws(L, nframe, r) + (long)nframe * 8 + 4096;
+    out[3] = (long)(L / 2 + 1) * L * 16;
+    return IMCOM_OK;
+}
+
+int imcom_noiseps_2d(imcom_ctx *ctx, const void *frames, int in_f64, int nframe, int L, long fstride, long rstride, const double *window, long window_len,
+                     const double *norm, int bin8, int route, double *out, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(frames && norm && out, "null pointer");
+    IMCOM_TRY(noiseps_check_side(L, bin8));
+    IMCOM_REQUIRE(nframe >= 1 && nframe <= 65535 && route >= 0 && route <= 3, "noise spectra: %d frames, route %d", nframe, route);
+    IMCOM_REQUIRE(rstride >= L && (nframe == 1 || fstride >= (long)(L - 1) * rstride + L), "noise spectra: strides %ld, %ld of frames of side %d", fstride, rstride, L);
+    IMCOM_REQUIRE(!window || window_len == (long)L * L, "noise spectra: a window of %ld elements for frames of side %d", window_len, L);
+    for (int f = 0; f < nframe; f++) IMCOM_REQUIRE(std::isfinite(norm[f]) && norm[f] != 0.0, "noise spectra: norm[%d] = %g", f, norm[f]);
+    const int r = noiseps_pick(L, route);
+    IMCOM_REQUIRE(r != NOISEPS_ROUTE_NONE, "noise spectra: route %d does not serve the side %d", route, L);
+    Stage st(ctx, memspace, __func__);
+    const size_t esz = in_f64 ? 8 : 4, span = (size_t)(nframe - 1) * fstride + (size_t)(L - 1) * rstride + L, n = bin8 ? L / 8 : L, szO = (size_t)nframe * n * n;
+    WsPlan plan;
+    plan.add((size_t)nframe * 8);
+    st.plan(plan, {span * esz, szO * 8});
+    if (st.host && window) plan.add((size_t)L * L * 8);
+    plan.add(noiseps_ws(L, nframe, r));
+    IMCOM_TRY(ws_reserve(ctx, plan.total + 4096));
+    double *norm_d, *o_d;
+    const char *f_d;
+    const double *w_d;
+    IMCOM_TRY(ws_take(ctx, (size_t)nframe, &norm_d, __func__));
+    IMCOM_TRY(upload(ctx, norm_d, norm, (size_t)nframe));
+    IMCOM_TRY(st.in((const char *)frames, span * esz, &f_d));
+    IMCOM_TRY(st.out(out, szO, &o_d));
+    IMCOM_TRY(st.in(window, (size_t)L * L, &w_d));
+    IMCOM_TRY(launch_noiseps_2d(ctx, f_d, in_f64 != 0, nframe, L, fstride, rstride, w_d, norm_d, bin8 != 0, r, o_d));
+    IMCOM_TRY(st.back(out, (const double *)o_d, szO));
+    return st.done();
+}
+
+int imcom_noiseps_radial(imcom_ctx *ctx, const double *image, int nframe, int n, const int *rbin, int nidx, double *mean, double *err, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(image && rbin && mean && err, "null pointer");
+    IMCOM_REQUIRE(nframe >= 1 && nframe <= 65535 && n >= 1 && n <= SPLITPSF_MAXN && nidx >= 1 && nidx <= 65535, "noise spectra: %d frames of side %d, %d annuli", nframe,
+                  n, nidx);
+    Stage st(ctx, memspace, __func__);
+    const size_t npix = (size_t)n * n, szI = (size_t)nframe * npix, szR = (size_t)nframe * nidx;
+    WsPlan plan;
+    st.plan(plan, {szI * 8, npix * 4, szR * 8, szR * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total + 4096));
+    const double *i_d;
+    const int *r_d;
+    double *m_d, *e_d;
+    IMCOM_TRY(st.in(image, szI, &i_d));
+    IMCOM_TRY(st.in(rbin, npix, &r_d));
+    IMCOM_TRY(st.out(mean, szR, &m_d));
+    IMCOM_TRY(st.out(err, szR, &e_d));
+    IMCOM_TRY(launch_noiseps_radial(ctx, i_d, nframe, n, r_d, nidx, m_d, e_d));
+    IMCOM_TRY(st.back(mean, (const double *)m_d, szR));
+    IMCOM_TRY(st.back(err, (const double *)e_d, szR));
+    return st.done();
+}
+
+int imcom_noiseps_accumulate(imcom_ctx *ctx, const double *ps2d, const double *mean, const double *err, int nlayers, int n, int nrad, int bins, int coverage_bin,
+                             double *ps2d_all, double *ps1d_all)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(ps2d && mean && err && ps2d_all && ps1d_all, "null pointer");
+    IMCOM_REQUIRE(nlayers >= 1 && nlayers <= 65535 && n >= 1 && n <= SPLITPSF_MAXN && nrad >= 1 && bins >= 1 && coverage_bin >= 0 && coverage_bin < bins,
+                  "noise spectra: %d layers of side %d, %d annuli, coverage bin %d of %d", nlayers, n, nrad, coverage_bin, bins);
+    return launch_noiseps_accumulate(ctx, ps2d, mean, err, nlayers, (long)n * n, nrad, bins, coverage_bin, ps2d_all, ps1d_all);
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // objmask.hip -- the bright-object mask of the destripe set-up (reference src/pyimcom/imdestripe.py:781-872, apply_object_mask, and its
 // caller Sca_img.__init__ 317-332): exact order statistics of a device array, threshold and clipping flags, constrained propagation of a
 // binary image (scipy.ndimage.binary_propagation, 4-connectivity, border 0), box dilation (binary_dilation with (2r+1)^2 ones) and the
-// application of the mask.  The C-ABI entries imcom_select_kth / imcom_mask_* are in api.hip.
+// application of the mask.  The C-ABI entries imcom_select_kth / imcom_mask_* end the file.
 //
 // Every result is a boolean image, an integer count or an order statistic: integer arithmetic and comparisons only, so each has one right
 // value, whatever the cut into threads and workgroups and from run to run.  Masks are uint8 images, one byte a pixel, as everywhere in the
@@ -12,6 +12,10 @@
 #include "objmask_core.h"
 
 namespace imcom {
+
+constexpr int SELECT_BINS = 2048, SELECT_STATE = 8;  // histogram bins of a pass (two histograms); words of the selection state
+constexpr int MASK_DILATE_TX = 48, MASK_DILATE_TY = 32, MASK_DILATE_MAX_R = 8;  // output pixels of a dilation workgroup; largest radius
+constexpr int MASK_PROPAGATE_T = 62;                                            // side of a propagation tile
 
 __device__ __forceinline__ float om_abs(float v) { return fabsf(v); }
 __device__ __forceinline__ double om_abs(double v) { return fabs(v); }
@@ -265,7 +269,7 @@ static int select_kth_t(imcom_ctx *ctx, const T *vals, const unsigned char *flag
     return IMCOM_OK;
 }
 
-int launch_select_kth(imcom_ctx *ctx, const void *vals, bool f64, const unsigned char *flags, long n, bool use_abs, double c, long k, unsigned long long *state,
+static int launch_select_kth(imcom_ctx *ctx, const void *vals, bool f64, const unsigned char *flags, long n, bool use_abs, double c, long k, unsigned long long *state,
                       unsigned long long *hist, void *res, long *info)
 {
     ProfScope ps(ctx, "select_kth");
@@ -278,7 +282,7 @@ int launch_select_kth(imcom_ctx *ctx, const void *vals, bool f64, const unsigned
 
 static unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
 
-int launch_mask_threshold(imcom_ctx *ctx, const void *img, bool f64, long n, double bkg, double t1, double t2, bool finite_only, unsigned char *m1,
+static int launch_mask_threshold(imcom_ctx *ctx, const void *img, bool f64, long n, double bkg, double t1, double t2, bool finite_only, unsigned char *m1,
                           unsigned char *m2)
 {
     ProfScope ps(ctx, "mask_flags");
@@ -287,7 +291,7 @@ int launch_mask_threshold(imcom_ctx *ctx, const void *img, bool f64, long n, dou
     return check_launch("mask_threshold_kernel");
 }
 
-int launch_mask_clip(imcom_ctx *ctx, const void *img, bool f64, long n, const unsigned char *keep_in, double bkg, double t, unsigned char *keep_out,
+static int launch_mask_clip(imcom_ctx *ctx, const void *img, bool f64, long n, const unsigned char *keep_in, double bkg, double t, unsigned char *keep_out,
                      unsigned long long *count)
 {
     ProfScope ps(ctx, "mask_flags");
@@ -297,7 +301,7 @@ int launch_mask_clip(imcom_ctx *ctx, const void *img, bool f64, long n, const un
     return check_launch("mask_clip_kernel");
 }
 
-int launch_mask_apply(imcom_ctx *ctx, const void *in, int dtype, const unsigned char *mask, long n, void *out)
+static int launch_mask_apply(imcom_ctx *ctx, const void *in, int dtype, const unsigned char *mask, long n, void *out)
 {
     ProfScope ps(ctx, "mask_apply");
     if (dtype == 1) hipLaunchKernelGGL(mask_apply_kernel<double>, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, (const double *)in, mask, n, (double *)out);
@@ -306,7 +310,7 @@ int launch_mask_apply(imcom_ctx *ctx, const void *in, int dtype, const unsigned 
     return check_launch("mask_apply_kernel");
 }
 
-int launch_mask_dilate(imcom_ctx *ctx, const unsigned char *in, int H, int W, int r, unsigned char *out)
+static int launch_mask_dilate(imcom_ctx *ctx, const unsigned char *in, int H, int W, int r, unsigned char *out)
 {
     ProfScope ps(ctx, "mask_dilate");
     hipLaunchKernelGGL(mask_dilate_kernel, dim3((unsigned)((W + MASK_DILATE_TX - 1) / MASK_DILATE_TX), (unsigned)((H + MASK_DILATE_TY - 1) / MASK_DILATE_TY)), dim3(256),
@@ -317,7 +321,7 @@ int launch_mask_dilate(imcom_ctx *ctx, const unsigned char *in, int H, int W, in
 // out (already holding the seed) to the fixpoint; tmp: a second image.  Sweeps go in pairs, out -> tmp -> out, so the result is always in
 // `out`; a pair that changes nothing ends the loop (then out == tmp == the fixpoint).  A sweep that changes something sets at least one
 // pixel: H W / 2 + 1 pairs bound the loop.
-int launch_mask_propagate(imcom_ctx *ctx, const unsigned char *grow, int H, int W, unsigned char *out, unsigned char *tmp, unsigned int *changed, long *sweeps)
+static int launch_mask_propagate(imcom_ctx *ctx, const unsigned char *grow, int H, int W, unsigned char *out, unsigned char *tmp, unsigned int *changed, long *sweeps)
 {
     ProfScope ps(ctx, "mask_propagate");
     const dim3 grid((unsigned)((W + MASK_PROPAGATE_T - 1) / MASK_PROPAGATE_T), (unsigned)((H + MASK_PROPAGATE_T - 1) / MASK_PROPAGATE_T));
@@ -340,3 +344,169 @@ int launch_mask_propagate(imcom_ctx *ctx, const unsigned char *grow, int H, int 
 }
 
 }  // namespace imcom
+
+using namespace imcom;
+
+// ---------------------------------------------------------------------------------------------
+// C entries: Bright-object masks of the destripe set-up
+
+namespace {
+constexpr long MASK_MAX_SIDE = 65536;
+}
+
+extern "C" {
+
+int imcom_select_kth(imcom_ctx *ctx, const void *values, int is_f64, long n, const unsigned char *flags, int use_abs, double c, long k, void *out, long *info,
+                     int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(values && out && info, "null pointer");
+    IMCOM_REQUIRE(n >= 1 && n <= MASK_MAX_SIDE * MASK_MAX_SIDE, "select_kth: n = %ld outside 1 .. 2^32", n);
+    IMCOM_REQUIRE(k < n, "select_kth: rank %ld of %ld values", k, n);
+    const size_t esz = is_f64 ? 8 : 4;
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    plan.add(SELECT_STATE * sizeof(unsigned long long));
+    plan.add(2 * SELECT_BINS * sizeof(unsigned long long));
+    st.plan(plan, {(size_t)n * esz, flags ? (size_t)n : 0, 2 * esz, 2 * sizeof(long)});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    unsigned long long *state, *hist;
+    const char *v_d;
+    const unsigned char *f_d;
+    char *o_d;
+    long *i_d;
+    IMCOM_TRY(ws_take(ctx, (size_t)SELECT_STATE, &state, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)2 * SELECT_BINS, &hist, __func__));
+    IMCOM_TRY(st.in((const char *)values, (size_t)n * esz, &v_d));
+    IMCOM_TRY(st.in(flags, (size_t)n, &f_d));
+    IMCOM_TRY(st.out((char *)out, 2 * esz, &o_d));
+    IMCOM_TRY(st.out(info, (size_t)2, &i_d));
+    IMCOM_TRY(launch_select_kth(ctx, v_d, is_f64 != 0, f_d, n, use_abs != 0, c, k, state, hist, o_d, i_d));
+    IMCOM_TRY(st.back((char *)out, (const char *)o_d, 2 * esz));
+    IMCOM_TRY(st.back(info, (const long *)i_d, (size_t)2));
+    return st.done();
+}
+
+int imcom_mask_threshold(imcom_ctx *ctx, const void *image, int is_f64, long n, double bkg, double t_seed, double t_grow, int finite_only, unsigned char *seed,
+                         unsigned char *grow, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(image && seed, "null pointer");
+    IMCOM_REQUIRE(n >= 1 && n <= MASK_MAX_SIDE * MASK_MAX_SIDE, "mask_threshold: n = %ld outside 1 .. 2^32", n);
+    const size_t esz = is_f64 ? 8 : 4;
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    st.plan(plan, {(size_t)n * esz, (size_t)n, grow ? (size_t)n : 0});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const char *v_d;
+    unsigned char *s_d, *g_d = nullptr;
+    IMCOM_TRY(st.in((const char *)image, (size_t)n * esz, &v_d));
+    IMCOM_TRY(st.out(seed, (size_t)n, &s_d));
+    if (grow) IMCOM_TRY(st.out(grow, (size_t)n, &g_d));
+    IMCOM_TRY(launch_mask_threshold(ctx, v_d, is_f64 != 0, n, bkg, t_seed, t_grow, finite_only != 0, s_d, g_d));
+    IMCOM_TRY(st.back(seed, (const unsigned char *)s_d, (size_t)n));
+    if (grow) IMCOM_TRY(st.back(grow, (const unsigned char *)g_d, (size_t)n));
+    return st.done();
+}
+
+int imcom_mask_clip(imcom_ctx *ctx, const void *image, int is_f64, long n, const unsigned char *keep_in, double bkg, double t, unsigned char *keep_out, long *count,
+                    int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(image && keep_out && count, "null pointer");
+    IMCOM_REQUIRE(n >= 1 && n <= MASK_MAX_SIDE * MASK_MAX_SIDE, "mask_clip: n = %ld outside 1 .. 2^32", n);
+    const size_t esz = is_f64 ? 8 : 4;
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    st.plan(plan, {(size_t)n * esz, keep_in ? (size_t)n : 0, (size_t)n, sizeof(long)});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const char *v_d;
+    const unsigned char *ki_d;
+    unsigned char *ko_d;
+    long *c_d;
+    IMCOM_TRY(st.in((const char *)image, (size_t)n * esz, &v_d));
+    IMCOM_TRY(st.in(keep_in, (size_t)n, &ki_d));
+    IMCOM_TRY(st.out(keep_out, (size_t)n, &ko_d));
+    IMCOM_TRY(st.out(count, (size_t)1, &c_d));
+    IMCOM_TRY(launch_mask_clip(ctx, v_d, is_f64 != 0, n, ki_d, bkg, t, ko_d, (unsigned long long *)c_d));
+    IMCOM_TRY(st.back(keep_out, (const unsigned char *)ko_d, (size_t)n));
+    IMCOM_TRY(st.back(count, (const long *)c_d, (size_t)1));
+    return st.done();
+}
+
+int imcom_mask_propagate(imcom_ctx *ctx, const unsigned char *seed, const unsigned char *grow, int rows, int cols, unsigned char *out, long *sweeps, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(seed && grow && out, "null pointer");
+    IMCOM_REQUIRE(rows >= 1 && rows <= MASK_MAX_SIDE && cols >= 1 && cols <= MASK_MAX_SIDE, "mask_propagate: %d x %d pixels, sides 1 .. 65536", rows, cols);
+    IMCOM_REQUIRE(out != grow, "mask_propagate: the result cannot overwrite the grow image");
+    const size_t npix = (size_t)rows * cols;
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    plan.add(npix);
+    plan.add(sizeof(unsigned int));
+    st.plan(plan, {npix, npix, npix});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    unsigned char *tmp, *o_d;
+    unsigned int *changed;
+    const unsigned char *s_d, *g_d;
+    IMCOM_TRY(ws_take(ctx, npix, &tmp, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)1, &changed, __func__));
+    IMCOM_TRY(st.in(seed, npix, &s_d));
+    IMCOM_TRY(st.in(grow, npix, &g_d));
+    IMCOM_TRY(st.out(out, npix, &o_d));
+    if (o_d != s_d) IMCOM_HIP_CHECK(hipMemcpyAsync(o_d, s_d, npix, hipMemcpyDeviceToDevice, ctx->stream));
+    long n_sweeps = 0;
+    IMCOM_TRY(launch_mask_propagate(ctx, g_d, rows, cols, o_d, tmp, changed, &n_sweeps));
+    if (sweeps) *sweeps = n_sweeps;
+    IMCOM_TRY(st.back(out, (const unsigned char *)o_d, npix));
+    return st.done();
+}
+
+int imcom_mask_dilate(imcom_ctx *ctx, const unsigned char *in, int rows, int cols, int r, unsigned char *out, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(in && out, "null pointer");
+    IMCOM_REQUIRE(rows >= 1 && rows <= MASK_MAX_SIDE && cols >= 1 && cols <= MASK_MAX_SIDE, "mask_dilate: %d x %d pixels, sides 1 .. 65536", rows, cols);
+    IMCOM_REQUIRE(in != out, "mask_dilate: not in place");
+    if (r < 1 || r > MASK_DILATE_MAX_R) {
+        set_error("mask_dilate: radius %d, served are 1 .. %d", r, MASK_DILATE_MAX_R);
+        return IMCOM_ERR_UNSUPPORTED;
+    }
+    const size_t npix = (size_t)rows * cols;
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    st.plan(plan, {npix, npix});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const unsigned char *i_d;
+    unsigned char *o_d;
+    IMCOM_TRY(st.in(in, npix, &i_d));
+    IMCOM_TRY(st.out(out, npix, &o_d));
+    IMCOM_TRY(launch_mask_dilate(ctx, i_d, rows, cols, r, o_d));
+    IMCOM_TRY(st.back(out, (const unsigned char *)o_d, npix));
+    return st.done();
+}
+
+int imcom_mask_apply(imcom_ctx *ctx, const void *in, int dtype, const unsigned char *mask, long n, void *out, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(in && mask && out, "null pointer");
+    IMCOM_REQUIRE(dtype >= 0 && dtype <= 2, "mask_apply: dtype %d is none of 0 (float32), 1 (float64), 2 (uint8)", dtype);
+    IMCOM_REQUIRE(n >= 1 && n <= MASK_MAX_SIDE * MASK_MAX_SIDE, "mask_apply: n = %ld outside 1 .. 2^32", n);
+    const size_t esz = dtype == 0 ? 4 : dtype == 1 ? 8 : 1;
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    st.plan(plan, {(size_t)n * esz, (size_t)n, (size_t)n * esz});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const char *i_d;
+    const unsigned char *m_d;
+    char *o_d;
+    IMCOM_TRY(st.in((const char *)in, (size_t)n * esz, &i_d));
+    IMCOM_TRY(st.in(mask, (size_t)n, &m_d));
+    IMCOM_TRY(st.out((char *)out, (size_t)n * esz, &o_d));
+    IMCOM_TRY(launch_mask_apply(ctx, i_d, dtype, m_d, n, o_d));
+    IMCOM_TRY(st.back((char *)out, (const char *)o_d, (size_t)n * esz));
+    return st.done();
+}
+
+}  // extern "C"

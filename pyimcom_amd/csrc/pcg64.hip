@@ -1,6 +1,6 @@
 // pcg64.hip -- counter-based draws of numpy's PCG64 stream and the simulated cosmic-ray mask built from them (reference
 // src/pyimcom/layer.py:933-964, Mask.randmask; 1071-1077, the lab-noise threshold of Mask.load_cr_mask; 313-401, GalSimInject.subgen /
-// subgen_multirow).  The C-ABI entries imcom_pcg64_uniform / imcom_pcg64_uniform_at / imcom_cr_mask are in api.hip.
+// subgen_multirow).  The C-ABI entries imcom_pcg64_uniform / imcom_pcg64_uniform_at / imcom_cr_mask are at the end of the file.
 //
 // PCG64 (XSL-RR 128/64) is the 128-bit LCG s <- PCG64_MULT s + inc (mod 2^128) with the output rotr64(hi ^ lo, s >> 122), taken AFTER the
 // step.  Draw k (from 0) of Generator.random() / uniform() is (out_k >> 11) 2^-53 with out_k the output of the state after k + 1 steps.
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void cr_mask_kernel(U128 state, const unsigned
     if (t == 0 && good_lds) atomicAdd(ngood, (unsigned long long)good_lds);  // (integer: the same total in any order)
 }
 
-int launch_pcg64_uniform(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const unsigned long long offset[2], long count,
+static int launch_pcg64_uniform(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const unsigned long long offset[2], long count,
                          double *out)
 {
     if (count == 0) return IMCOM_OK;
@@ -109,7 +109,7 @@ int launch_pcg64_uniform(imcom_ctx *ctx, const unsigned long long state[2], cons
     return check_launch("pcg64_uniform_kernel");
 }
 
-int launch_pcg64_uniform_at(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const long *pos, long count, double *out)
+static int launch_pcg64_uniform_at(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const long *pos, long count, double *out)
 {
     if (count == 0) return IMCOM_OK;
     ProfScope ps(ctx, "pcg64_uniform");
@@ -118,7 +118,7 @@ int launch_pcg64_uniform_at(imcom_ctx *ctx, const unsigned long long state[2], c
     return check_launch("pcg64_uniform_at_kernel");
 }
 
-int launch_cr_mask(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, unsigned long long base, int nside, int pad, double pcut,
+static int launch_cr_mask(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, unsigned long long base, int nside, int pad, double pcut,
                    const float *labnoise, double threshold, unsigned char *mask, unsigned long long *ngood)
 {
     ProfScope ps(ctx, "cr_mask");
@@ -128,4 +128,106 @@ int launch_cr_mask(imcom_ctx *ctx, const unsigned long long state[2], const unsi
     return check_launch("cr_mask_kernel");
 }
 
+// the affine maps of 2^j steps of s <- M s + inc, j < PCG64_JUMPS, into the workspace: (A_0, C_0) = (M, inc), A_{j+1} = A_j^2,
+// C_{j+1} = (A_j + 1) C_j (mod 2^128)
+int pcg64_jumps(imcom_ctx *ctx, uint64_t inc_lo, uint64_t inc_hi, const unsigned long long **jumps_d, const char *who)
+{
+    typedef unsigned __int128 u128;
+    unsigned long long tab[PCG64_JUMPS * 4], *d;
+    u128 A = ((u128)0x2360ED051FC65DA4ull << 64) | 0x4385DF649FCCF645ull, Cc = ((u128)inc_hi << 64) | inc_lo;
+    for (int j = 0; j < PCG64_JUMPS; j++) {
+        tab[4 * j] = (unsigned long long)A;
+        tab[4 * j + 1] = (unsigned long long)(A >> 64);
+        tab[4 * j + 2] = (unsigned long long)Cc;
+        tab[4 * j + 3] = (unsigned long long)(Cc >> 64);
+        Cc = (A + 1) * Cc;
+        A = A * A;
+    }
+    IMCOM_TRY(ws_take(ctx, (size_t)PCG64_JUMPS * 4, &d, who));
+    IMCOM_TRY(upload(ctx, d, tab, (size_t)PCG64_JUMPS * 4));
+    *jumps_d = d;
+    return IMCOM_OK;
+}
+
 }  // namespace imcom
+
+using namespace imcom;
+
+// ---------------------------------------------------------------------------------------------
+// C entries: PCG64 draws by position and the cosmic-ray mask
+
+extern "C" {
+
+int imcom_pcg64_uniform(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                        long count, double *out, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(count >= 0 && count <= PCG64_MAX_COUNT, "pcg64: count %ld outside 0 .. 2^36", count);
+    IMCOM_REQUIRE(count == 0 || out, "null pointer");
+    if (count == 0) return IMCOM_OK;
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    plan.add((size_t)PCG64_JUMPS * 32);
+    st.plan(plan, {(size_t)count * 8});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const unsigned long long *jumps, state[2] = {state_lo, state_hi}, offset[2] = {offset_lo, offset_hi};
+    double *o_d;
+    IMCOM_TRY(pcg64_jumps(ctx, inc_lo, inc_hi, &jumps, __func__));
+    IMCOM_TRY(st.out(out, (size_t)count, &o_d));
+    IMCOM_TRY(launch_pcg64_uniform(ctx, state, jumps, offset, count, o_d));
+    IMCOM_TRY(st.back(out, (const double *)o_d, (size_t)count));
+    return st.done();
+}
+
+int imcom_pcg64_uniform_at(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, const long *pos, long count, double *out,
+                           int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(count >= 0 && count <= PCG64_MAX_COUNT, "pcg64: count %ld outside 0 .. 2^36", count);
+    IMCOM_REQUIRE(count == 0 || (pos && out), "null pointer");
+    if (count == 0) return IMCOM_OK;
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    plan.add((size_t)PCG64_JUMPS * 32);
+    st.plan(plan, {(size_t)count * 8, (size_t)count * 8});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const unsigned long long *jumps, state[2] = {state_lo, state_hi};
+    const long *p_d;
+    double *o_d;
+    IMCOM_TRY(pcg64_jumps(ctx, inc_lo, inc_hi, &jumps, __func__));
+    IMCOM_TRY(st.in(pos, (size_t)count, &p_d));
+    IMCOM_TRY(st.out(out, (size_t)count, &o_d));
+    IMCOM_TRY(launch_pcg64_uniform_at(ctx, state, jumps, p_d, count, o_d));
+    IMCOM_TRY(st.back(out, (const double *)o_d, (size_t)count));
+    return st.done();
+}
+
+int imcom_cr_mask(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, int nside, int pad, int slice, int n_slices,
+                  double pcut, const float *labnoise, double threshold, unsigned char *mask, long *ngood, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(mask && ngood, "null pointer");
+    IMCOM_REQUIRE(nside >= 1 && nside <= 65536 && pad >= 1 && pad <= 4096, "cr_mask: nside %d outside 1 .. 65536 or pad %d outside 1 .. 4096", nside, pad);
+    IMCOM_REQUIRE(n_slices >= 1 && n_slices <= 65536 && slice >= 0 && slice < n_slices, "cr_mask: slice %d of %d", slice, n_slices);
+    Stage st(ctx, memspace, __func__);
+    const size_t npix = (size_t)nside * nside;
+    const unsigned long long W = (unsigned long long)nside + 2ull * pad;  // (slice W^2 + W^2 < 2^16 2^34)
+    WsPlan plan;
+    plan.add((size_t)PCG64_JUMPS * 32);
+    st.plan(plan, {labnoise ? npix * 4 : 0, npix, sizeof(long)});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const unsigned long long *jumps, state[2] = {state_lo, state_hi};
+    const float *l_d;
+    unsigned char *m_d;
+    long *n_d;
+    IMCOM_TRY(pcg64_jumps(ctx, inc_lo, inc_hi, &jumps, __func__));
+    IMCOM_TRY(st.in(labnoise, npix, &l_d));
+    IMCOM_TRY(st.out(mask, npix, &m_d));
+    IMCOM_TRY(st.out(ngood, (size_t)1, &n_d));
+    IMCOM_TRY(launch_cr_mask(ctx, state, jumps, (unsigned long long)slice * W * W, nside, pad, pcut, l_d, threshold, m_d, (unsigned long long *)n_d));
+    IMCOM_TRY(st.back(mask, (const unsigned char *)m_d, npix));
+    IMCOM_TRY(st.back(ngood, (const long *)n_d, (size_t)1));
+    return st.done();
+}
+
+}  // extern "C"

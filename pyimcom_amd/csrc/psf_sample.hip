@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256) void affine_positions_kernel(const double *__r
     }
 }
 
-// imcom_smooth_and_pad's device work, shared with imcom_psf_from_cube (api.hip): the scratch is taken from the workspace the caller
+// imcom_smooth_and_pad's device work, shared with imcom_psf_from_cube (inject.hip): the scratch is taken from the workspace the caller
 // has reserved (smooth_pad_ws_bytes counts it), src [n][ny][nx] and dst [n][ny + 2 npad][nx + 2 npad] are device memory.
 size_t smooth_pad_ws_bytes(int n, int ny, int nx, double tophatwidth, double gaussiansigma)
 {

@@ -26,7 +26,9 @@ namespace imcom {
 
 static int up(int v, int a) { return (v + a - 1) / a * a; }
 
-int splitpsf_route(int nfft)
+constexpr int SPLITPSF_ROUTE_NONE = 0, SPLITPSF_ROUTE_LINES = 1, SPLITPSF_ROUTE_DENSE = 2;
+
+static int splitpsf_route(int nfft)
 {
     if (nfft < 2 || nfft > SPLITPSF_MAXN) return SPLITPSF_ROUTE_NONE;
     FftPlan pl;
@@ -231,7 +233,7 @@ __global__ void sp_tophat_crop_kernel(const cplx *__restrict__ Z, int nplane, in
     out[((long)p * n + y) * n + x] = ((p & 1) ? v.y : v.x) / ((double)N * (double)N);
 }
 
-int splitpsf_tophat_npad(double width)  // splitpsf.py:134-135
+static int splitpsf_tophat_npad(double width)  // splitpsf.py:134-135
 {
     const int npad = (int)std::ceil(width);
     return npad + (4 - npad % 4) % 4;
@@ -248,10 +250,10 @@ static size_t tophat_ws(int nplane, int n, double width, SpFft *f_out)
     if (f_out) *f_out = f;
     return plan.total;
 }
-size_t splitpsf_tophat_ws(int nplane, int n, double width) { return tophat_ws(nplane, n, width, nullptr); }
+static size_t splitpsf_tophat_ws(int nplane, int n, double width) { return tophat_ws(nplane, n, width, nullptr); }
 
 // cube, out [nplane][n][n] in device memory (out may be cube); the caller has reserved splitpsf_tophat_ws() for this
-int launch_splitpsf_tophat(imcom_ctx *ctx, const double *cube, int nplane, int n, double width, double *out)
+static int launch_splitpsf_tophat(imcom_ctx *ctx, const double *cube, int nplane, int n, double width, double *out)
 {
     const int npad = splitpsf_tophat_npad(width), N = n + 2 * npad, npair = (nplane + 1) / 2;
     SpFft f;
@@ -299,7 +301,7 @@ __global__ void sp_split_kernel(const double *__restrict__ cube, int npoly, int 
     }
 }
 
-int launch_splitpsf_split(imcom_ctx *ctx, const double *cube, int npoly, int n, int ns, double r1, double r2, const double *trunc_dev, double *smallpsf,
+static int launch_splitpsf_split(imcom_ctx *ctx, const double *cube, int npoly, int n, int ns, double r1, double r2, const double *trunc_dev, double *smallpsf,
                           double *resid)
 {
     hipLaunchKernelGGL(sp_split_kernel, dim3((n + 255) / 256, n), dim3(256), 0, ctx->stream, cube, npoly, n, ns, r1, r2, trunc_dev, smallpsf, resid);
@@ -453,11 +455,11 @@ static size_t points_ws(int n, int nsca, int npts, bool own_kreal, SpFft *f_out)
     if (f_out) *f_out = f;
     return plan.total;
 }
-size_t splitpsf_points_ws(int n, int nsca, int npts, bool own_kreal) { return points_ws(n, nsca, npts, own_kreal, nullptr); }
+static size_t splitpsf_points_ws(int n, int nsca, int npts, bool own_kreal) { return points_ws(n, nsca, npts, own_kreal, nullptr); }
 
 // resid [nsca][npoly][n][n]; lpw [npoly][npoly], wg [npoly], cov [nsca][npoly][4] in device memory; K_real / zeta (may be null)
 // [nsca][npts][n][n]; KL [nsca][npoly][n][n]; zmax [nsca].  The caller has reserved splitpsf_points_ws() for this.
-int launch_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npoly, int n, int i0, int npts, const double *lpw, const double *wg,
+static int launch_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npoly, int n, int i0, int npts, const double *lpw, const double *wg,
                            const double *cov, double eps, double *KL, double *K_real, double *zeta, double *zmax)
 {
     const long P = (long)nsca * npts, npix = (long)n * n;
@@ -499,3 +501,143 @@ int launch_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int np
 }
 
 }  // namespace imcom
+
+using namespace imcom;
+
+// ---------------------------------------------------------------------------------------------
+// C entries: the split of a PSF cube into its short- and long-range parts
+
+static int splitpsf_lorder1(int npoly)
+{
+    int l1 = 1;
+    while (l1 * l1 < npoly) l1++;
+    return l1 * l1 == npoly ? l1 : 0;
+}
+
+extern "C" {
+
+int imcom_splitpsf_sizes(int n, int npoly, double width, int nsca, int npts, long *out)
+{
+    IMCOM_REQUIRE(out, "null out");
+    IMCOM_REQUIRE(n >= 2 && n <= 65536 && npoly >= 1 && npoly <= 4096 && nsca >= 1 && npts >= 1 && npts <= npoly && width > 0.0 && width <= 4096.0,
+                  "splitpsf: side %d, %d planes, tophat width %g, %d SCAs or %d grid points out of range", n, npoly, width, nsca, npts);
+    const int npad = splitpsf_tophat_npad(width);
+    out[0] = npad;
+    out[1] = n + 2 * npad;
+    out[2] = splitpsf_route(n + 2 * npad);
+    out[3] = splitpsf_route(2 * n);
+    out[4] = out[2] ? (long)splitpsf_tophat_ws(npoly, n, width) + 4096 : 0;
+    out[5] = out[3] ? (long)splitpsf_points_ws(n, nsca, npts, true) + (long)(npoly * npoly + npoly + 4L * nsca * npoly) * 8 + 4096 : 0;
+    return IMCOM_OK;
+}
+
+int imcom_splitpsf_tophat(imcom_ctx *ctx, const double *cube, int nplane, int n, double width, double *out, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(cube && out, "null pointer");
+    IMCOM_REQUIRE(nplane >= 1 && nplane <= 65535 && n >= 1 && n <= SPLITPSF_MAXN && width > 0.0 && width <= 4096.0, "splitpsf tophat: %d planes of side %d, width %g",
+                  nplane, n, width);
+    if (!splitpsf_route(n + 2 * splitpsf_tophat_npad(width))) {
+        set_error("splitpsf tophat: a padded side of %d is beyond the %d this build transforms", n + 2 * splitpsf_tophat_npad(width), SPLITPSF_MAXN);
+        return IMCOM_ERR_UNSUPPORTED;
+    }
+    Stage st(ctx, memspace, __func__);
+    const size_t sz = (size_t)nplane * n * n;
+    WsPlan plan;
+    st.plan(plan, {sz * 8});
+    plan.add(splitpsf_tophat_ws(nplane, n, width));
+    IMCOM_TRY(ws_reserve(ctx, plan.total + 4096));
+    const double *c_d;
+    IMCOM_TRY(st.in(cube, sz, &c_d));
+    double *o_d = st.host ? (double *)c_d : out;  // the staged copy is filtered in place
+    IMCOM_TRY(launch_splitpsf_tophat(ctx, c_d, nplane, n, width, o_d));
+    IMCOM_TRY(st.back(out, (const double *)o_d, sz));
+    return st.done();
+}
+
+int imcom_splitpsf_split(imcom_ctx *ctx, const double *cube, int npoly, int n, int ns, double r_in, double r_out, int m_trunc, double *smallpsf,
+                         double *resid, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(cube && smallpsf && resid, "null pointer");
+    IMCOM_REQUIRE(npoly >= 1 && n >= 2 && n <= SPLITPSF_MAXN && n % 2 == 0 && ns >= 2 && ns <= n && ns % 2 == 0, "SplitPSF requires even dimension (%d, %d)", n, ns);
+    IMCOM_REQUIRE(std::isfinite(r_in) && std::isfinite(r_out) && r_in != r_out && m_trunc >= 0 && 2 * m_trunc <= n, "splitpsf: radii %g, %g, m_trunc %d", r_in,
+                  r_out, m_trunc);
+    // the 1-D factor of Truncate_2D_integratedBlackman (splitpsf.py:122-128), Window_integratedBlackman (79-89) on the host
+    std::vector<double> tr((size_t)n, 1.0);
+    for (int k = 0; k < m_trunc; k++) {
+        const double step = 2.0 / (m_trunc + 1), x = (k + 1) * step + -1.0, alpha = 0.08;
+        tr[k] = x >= 1 ? 1.0 : x <= -1 ? 0.0 : 0.5 * (x + 1) + (0.5 * std::sin(M_PI * x) + alpha / 4 * std::sin(2 * M_PI * x)) / ((1 - alpha) * M_PI);
+    }
+    for (int k = 0; k < m_trunc; k++) tr[n - m_trunc + k] = tr[m_trunc - 1 - k];
+    Stage st(ctx, memspace, __func__);
+    const size_t szC = (size_t)npoly * n * n, szS = (size_t)npoly * ns * ns;
+    WsPlan plan;
+    plan.add((size_t)n * 8);
+    st.plan(plan, {szC * 8, szS * 8, szC * 8});
+    IMCOM_TRY(ws_reserve(ctx, plan.total + 4096));
+    double *tr_d, *s_d, *r_d;
+    const double *c_d;
+    IMCOM_TRY(ws_take(ctx, (size_t)n, &tr_d, __func__));
+    IMCOM_TRY(upload(ctx, tr_d, tr.data(), (size_t)n));
+    IMCOM_TRY(st.in(cube, szC, &c_d));
+    IMCOM_TRY(st.out(smallpsf, szS, &s_d));
+    IMCOM_TRY(st.out(resid, szC, &r_d));
+    IMCOM_TRY(launch_splitpsf_split(ctx, c_d, npoly, n, ns, r_in, r_out, tr_d, s_d, r_d));
+    IMCOM_TRY(st.back(smallpsf, (const double *)s_d, szS));
+    IMCOM_TRY(st.back(resid, (const double *)r_d, szC));
+    return st.done();
+}
+
+int imcom_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npoly, int n, int i0, int npts, const double *lpw, const double *wg,
+                          const double *cov, double eps, double *K_Legendre, double *K_real, double *zeta_real, double *zetamax, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(resid && lpw && wg && cov && K_Legendre && zetamax, "null pointer");
+    IMCOM_REQUIRE(npoly >= 1 && npoly <= 4096 && splitpsf_lorder1(npoly), "SplitPSF Legendre polynomial dimension error (%d planes)", npoly);
+    IMCOM_REQUIRE(n >= 2 && n % 2 == 0, "SplitPSF requires even dimension (%d)", n);
+    IMCOM_REQUIRE(nsca >= 1 && i0 >= 0 && npts >= 1 && i0 + npts <= npoly && (long)nsca * npts <= 65535, "splitpsf: %d SCAs, grid points %d .. %d of %d", nsca, i0,
+                  i0 + npts, npoly);
+    IMCOM_REQUIRE(std::isfinite(eps) && eps >= 0.0, "splitpsf: eps = %g", eps);
+    for (long e = 0; e < (long)nsca * npoly; e++) {
+        const double *C = cov + 4 * e;
+        IMCOM_REQUIRE(C[0] > 0.0 && C[0] * C[3] - C[1] * C[1] > 0.0 && std::isfinite(C[0] + C[1] + C[3]),  // (C[1][0] is not read: 167, 181-182)
+                      "splitpsf: covariance %ld is not positive definite", e);
+    }
+    if (!splitpsf_route(2 * n)) {
+        set_error("splitpsf: a cube side of %d needs transforms of %d, beyond the %d this build transforms", n, 2 * n, SPLITPSF_MAXN);
+        return IMCOM_ERR_UNSUPPORTED;
+    }
+    Stage st(ctx, memspace, __func__);
+    const size_t szR = (size_t)nsca * npoly * n * n, szP = (size_t)nsca * npts * n * n, szL = (size_t)npoly * npoly, szC = (size_t)nsca * npoly * 4;
+    WsPlan plan;
+    plan.add(szL * 8);
+    plan.add((size_t)npoly * 8);
+    plan.add(szC * 8);
+    st.plan(plan, {szR * 8, szR * 8, (size_t)nsca * 8});
+    if (st.host && K_real) plan.add(szP * 8);
+    if (st.host && zeta_real) plan.add(szP * 8);
+    plan.add(splitpsf_points_ws(n, nsca, npts, !K_real));
+    IMCOM_TRY(ws_reserve(ctx, plan.total + 4096));
+    double *lpw_d, *wg_d, *cov_d, *KL_d, *zm_d, *kr_d = nullptr, *ze_d = nullptr;
+    const double *r_d;
+    IMCOM_TRY(ws_take(ctx, szL, &lpw_d, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)npoly, &wg_d, __func__));
+    IMCOM_TRY(ws_take(ctx, szC, &cov_d, __func__));
+    IMCOM_TRY(upload(ctx, lpw_d, lpw, szL));
+    IMCOM_TRY(upload(ctx, wg_d, wg, (size_t)npoly));
+    IMCOM_TRY(upload(ctx, cov_d, cov, szC));
+    IMCOM_TRY(st.in(resid, szR, &r_d));
+    IMCOM_TRY(st.inout(K_Legendre, szR, &KL_d));
+    IMCOM_TRY(st.inout(zetamax, (size_t)nsca, &zm_d));
+    if (K_real) IMCOM_TRY(st.out(K_real, szP, &kr_d));
+    if (zeta_real) IMCOM_TRY(st.out(zeta_real, szP, &ze_d));
+    IMCOM_TRY(launch_splitpsf_points(ctx, r_d, nsca, npoly, n, i0, npts, lpw_d, wg_d, cov_d, eps, KL_d, kr_d, ze_d, zm_d));
+    IMCOM_TRY(st.back(K_Legendre, (const double *)KL_d, szR));
+    IMCOM_TRY(st.back(zetamax, (const double *)zm_d, (size_t)nsca));
+    if (K_real) IMCOM_TRY(st.back(K_real, (const double *)kr_d, szP));
+    if (zeta_real) IMCOM_TRY(st.back(zeta_real, (const double *)ze_d, szP));
+    return st.done();
+}
+
+}  // extern "C"

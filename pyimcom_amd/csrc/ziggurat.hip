@@ -1,5 +1,5 @@
 // ziggurat.hip -- numpy's float64 normal draws of a PCG64 stream (Generator.standard_normal; reference src/pyimcom/layer.py:1303-1304, the
-// white-noise layer, and 899-900, the draws of CplxNoise.noise_1f_frame).  The C-ABI entry imcom_pcg64_normal is in api.hip.
+// white-noise layer, and 899-900, the draws of CplxNoise.noise_1f_frame).  The C-ABI entries imcom_pcg64_normal* end the file.
 //
 // A normal draw consumes a data-dependent number of outputs (ziggurat_core.h), so draw i has no position of its own; but every stream
 // position k has an "attempt starting at k" that consumes a(k) outputs, and the draws are the emitting attempts on the chain k -> k + a(k)
@@ -14,6 +14,8 @@
 //                     output, no atomics on values, the same bits for every tile size.
 // Only integer counters are summed with atomics.  Tail draws (2.7e-4 of all) are listed with their two words; the order of that list
 // is the only thing here that can differ from run to run, and the caller sorts it.
+#include <algorithm>
+
 #include "launchers.h"
 #include "pcg64_dev.h"
 #define ZIG_TABLE __device__ const
@@ -235,14 +237,18 @@ __global__ __launch_bounds__(256) void zig_emit_kernel(U128 state, const u64 *__
 
 }  // namespace
 
-size_t zig_lds_bytes(int P, int levels)
+static size_t zig_lds_bytes(int P, int levels)
 {
     const size_t n = (size_t)P + ZIG_ENTRIES, head = ZIG_LDS_HEAD + ((size_t)P + ZIG_HALO) * 8;
     const size_t map = head + 4 * n * 2, emit = head + align_up((size_t)levels * n * 2, 4) + 256 * 4 + 2 * (size_t)P;
     return map > emit ? map : emit;
 }
 
-int launch_zig_chunk(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const unsigned long long start[2],
+// One chunk of `tiles` tiles of P positions from stream position `start` (128 bits; start_rel: the same counted from the call's offset).
+// The chain enters the chunk at offset entry0 with base0 draws made; res[2] = {entry offset after the chunk, draws made by then}.
+// exit_t / count_t [tiles][ZIG_ENTRIES], entry_t / base_t [tiles]: the tile tables.  info [4] (device, zeroed by the caller): outputs
+// consumed by `count` draws, slow attempts, tail draws, flags (1 undecided, 2 tail list full).
+static int launch_zig_chunk(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long *jumps, const unsigned long long start[2],
                      unsigned long long start_rel, int P, long tiles, int entry0, long base0, double guard, unsigned char *exit_t, unsigned short *count_t,
                      unsigned char *entry_t, long *base_t, long *res, long count, double *out, long *tail_idx, unsigned long long *tail_raw, long tail_cap,
                      unsigned long long *info)
@@ -269,3 +275,107 @@ int launch_zig_chunk(imcom_ctx *ctx, const unsigned long long state[2], const un
 }
 
 }  // namespace imcom
+
+using namespace imcom;
+
+// ---------------------------------------------------------------------------------------------
+// C entries: numpy's normal draws of a PCG64 stream
+
+namespace {
+constexpr int ZIG_TILE_DEFAULT = 1024, ZIG_TILE_MAX = 1024;  // (the LDS of zig_emit_kernel: 36 KB at 1024)
+constexpr long ZIG_CHUNK_TILES_DEFAULT = 1L << 16, ZIG_CHUNK_TILES_MAX = 1L << 20;
+constexpr double ZIG_GUARD_DEFAULT = ZIG_GUARD;
+// the tiles one chunk may need for `remaining` draws: 1.0145 outputs a draw on average, 3 % and a tile allowed for
+long zig_tiles_for(long remaining, int P) { return (remaining + remaining / 32 + P - 1) / P + 1; }
+}  // namespace
+
+extern "C" {
+
+int imcom_pcg64_normal_sizes(long count, long *tail_cap)
+{
+    IMCOM_REQUIRE(tail_cap, "null pointer");
+    IMCOM_REQUIRE(count >= 0 && count <= PCG64_MAX_COUNT, "pcg64: count %ld outside 0 .. 2^36", count);
+    *tail_cap = count / 1024 + 4096;  // the expected number is count / 3700
+    return IMCOM_OK;
+}
+
+int imcom_pcg64_normal(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                       long count, double *out, long *tail_idx, uint64_t *tail_raw, uint64_t *info, int memspace)
+{
+    return imcom_pcg64_normal_ex(ctx, state_lo, state_hi, inc_lo, inc_hi, offset_lo, offset_hi, count, out, tail_idx, tail_raw, info, memspace, 0, 0, 0.0);
+}
+
+int imcom_pcg64_normal_ex(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                          long count, double *out, long *tail_idx, uint64_t *tail_raw, uint64_t *info, int memspace, int tile, long chunk_tiles, double guard_band)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(count >= 0 && count <= PCG64_MAX_COUNT, "pcg64: count %ld outside 0 .. 2^36", count);
+    IMCOM_REQUIRE(info && (count == 0 || (out && tail_idx && tail_raw)), "null pointer");
+    IMCOM_REQUIRE(tile == 0 || (tile >= 4 && tile <= ZIG_TILE_MAX && (tile & (tile - 1)) == 0), "pcg64_normal: tile %d is no power of two in 4 .. %d", tile,
+                  ZIG_TILE_MAX);
+    IMCOM_REQUIRE(chunk_tiles >= 0 && chunk_tiles <= ZIG_CHUNK_TILES_MAX, "pcg64_normal: %ld tiles a chunk outside 1 .. 2^20", chunk_tiles);
+    IMCOM_REQUIRE(guard_band >= 0.0 && guard_band <= 1.0, "pcg64_normal: guard band %g outside 0 .. 1", guard_band);
+    for (int i = 0; i < 4; i++) info[i] = 0;
+    if (count == 0) return IMCOM_OK;
+    const int P = tile ? tile : ZIG_TILE_DEFAULT;
+    const long chunk_max = chunk_tiles ? chunk_tiles : ZIG_CHUNK_TILES_DEFAULT;
+    const double guard = guard_band > 0.0 ? guard_band : ZIG_GUARD_DEFAULT;
+    const long tail_cap = count / 1024 + 4096, tiles_max = std::min(chunk_max, zig_tiles_for(count, P));
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    plan.add((size_t)PCG64_JUMPS * 32);
+    plan.add((size_t)tiles_max * ZIG_ENTRIES);      // exit_t
+    plan.add((size_t)tiles_max * ZIG_ENTRIES * 2);  // count_t
+    plan.add((size_t)tiles_max);                    // entry_t
+    plan.add((size_t)tiles_max * 8);                // base_t
+    plan.add(2 * sizeof(long));                     // res
+    plan.add(4 * sizeof(unsigned long long));       // info
+    st.plan(plan, {(size_t)count * 8, (size_t)tail_cap * 8, (size_t)tail_cap * 16});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const unsigned long long *jumps, state[2] = {state_lo, state_hi};
+    unsigned char *exit_t, *entry_t;
+    unsigned short *count_t;
+    long *base_t, *res, *ti_d;
+    unsigned long long *info_d, *tr_d;
+    double *o_d;
+    IMCOM_TRY(pcg64_jumps(ctx, inc_lo, inc_hi, &jumps, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)tiles_max * ZIG_ENTRIES, &exit_t, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)tiles_max * ZIG_ENTRIES, &count_t, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)tiles_max, &entry_t, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)tiles_max, &base_t, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)2, &res, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)4, &info_d, __func__));
+    IMCOM_TRY(st.out(out, (size_t)count, &o_d));
+    IMCOM_TRY(st.out(tail_idx, (size_t)tail_cap, &ti_d));
+    IMCOM_TRY(st.out((unsigned long long *)tail_raw, (size_t)tail_cap * 2, &tr_d));
+    IMCOM_HIP_CHECK(hipMemsetAsync(info_d, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    // chunks in ascending order: a chunk's entry offset and output base are the exit of the chunk before
+    unsigned long long rel = 0;
+    long made = 0, entry = 0;
+    while (made < count) {
+        const long tiles = std::min(tiles_max, zig_tiles_for(count - made, P));
+        const unsigned long long lo = offset_lo + rel, start[2] = {lo, offset_hi + (lo < rel)};
+        long res_h[2];
+        IMCOM_TRY(launch_zig_chunk(ctx, state, jumps, start, rel, P, tiles, (int)entry, made, guard, exit_t, count_t, entry_t, base_t, res, count, o_d, ti_d,
+                                   tr_d, tail_cap, info_d));
+        IMCOM_HIP_CHECK(hipMemcpyAsync(res_h, res, sizeof(res_h), hipMemcpyDeviceToHost, ctx->stream));
+        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        entry = res_h[0];
+        made = res_h[1];
+        rel += (unsigned long long)tiles * P;
+    }
+    unsigned long long info_h[4];
+    IMCOM_HIP_CHECK(hipMemcpyAsync(info_h, info_d, sizeof(info_h), hipMemcpyDeviceToHost, ctx->stream));
+    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const long tails = (long)std::min<unsigned long long>(info_h[2], (unsigned long long)tail_cap);
+    IMCOM_TRY(st.back(out, (const double *)o_d, (size_t)count));
+    IMCOM_TRY(st.back(tail_idx, (const long *)ti_d, (size_t)tails));
+    IMCOM_TRY(st.back((unsigned long long *)tail_raw, (const unsigned long long *)tr_d, (size_t)tails * 2));
+    info[0] = info_h[0];
+    info[1] = info_h[1];
+    info[2] = info_h[2];
+    info[3] = info_h[3] != 0;
+    return st.done();
+}
+
+}  // extern "C"

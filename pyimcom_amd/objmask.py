@@ -28,7 +28,7 @@ from ._lib import MEM_DEVICE, ImcomError, check, default_context, lib, ptr
 __all__ = ["apply_object_mask", "object_mask", "median", "order_statistics", "propagate", "dilate", "jwst_valid", "setup_bytes", "DILATE_TILE",
            "PROPAGATE_TILE", "DILATE_MAX_R"]
 
-DILATE_TILE = (32, 48)  # rows, columns of output pixels of a dilation workgroup (csrc/launchers.h)
+DILATE_TILE = (32, 48)  # rows, columns of output pixels of a dilation workgroup (csrc/objmask.hip)
 PROPAGATE_TILE = 62  # side of a propagation tile
 DILATE_MAX_R = 8
 DEVICE = "cuda:0"  # where a numpy image is worked on

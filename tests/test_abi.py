@@ -98,17 +98,37 @@ NULL_CTX_ENTRIES = {
     "psf_overlap.hip": "imcom_psf_overlap",
     "psf_sample.hip": "imcom_sample_psf",
     "select.hip": "imcom_select_pixels",
+    "inject.hip": "imcom_draw_stars",
+    "imsubtract.hip": "imcom_imsub_canvas_add_f32",
+    "splitpsf.hip": "imcom_splitpsf_tophat",
+    "destripe.hip": "imcom_destripe_interp",
+    "noisespec.hip": "imcom_noiseps_radial",
+    "pcg64.hip": "imcom_cr_mask",
+    "ziggurat.hip": "imcom_pcg64_normal",
+    "noise1f.hip": "imcom_noise_1f",
+    "objmask.hip": "imcom_mask_dilate",
+    "quantiles.hip": "imcom_codehist",
+    "i24.hip": "imcom_i24_decompress",
 }
+
+
+def _null_argument(t):
+    """0.0 for a ctypes float scalar, 0 for an integer scalar, None (a null pointer) for everything else."""
+    import ctypes as C
+
+    if t in (C.c_double, C.c_float):
+        return 0.0
+    if isinstance(t, type) and issubclass(t, C._SimpleCData) and t._type_ in "bBhHiIlLqQ":
+        return 0
+    return None
 
 
 @pytest.mark.parametrize("source", sorted(NULL_CTX_ENTRIES))
 def test_null_context_is_refused(source):
-    import ctypes as C
-
     from pyimcom_amd import _lib
 
     name = NULL_CTX_ENTRIES[source]
-    args = [0.0 if t is C.c_double else 0 if t in (C.c_int, C.c_long) else None for t in _lib.SIGNATURES[name]]
+    args = [_null_argument(t) for t in _lib.SIGNATURES[name]]
     assert getattr(_lib.lib, name)(*args) == -1  # IMCOM_ERR_ARG
     assert "null context" in _lib.lib.imcom_last_error().decode()
 
