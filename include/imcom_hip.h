@@ -877,6 +877,42 @@ int imcom_i24_overflow_fetch(imcom_ctx *ctx, const float *frames, long layer_str
 int imcom_i24_decompress(imcom_ctx *ctx, const void *in, long in_stride, int planes, int scheme, int L, int ny, int nx, const imcom_i24_pars *pars, const int *y,
                          const int *x, const float *value, const long *counts, float *out);
 
+/* The catalog of injected stars (reference src/pyimcom/analysis.py:1000-1057, StarsAnal.__call__; src/pyimcom/diagnostics/
+ * starcube_nonoise.py:186-237, gen_starcube_nonoise; psfutil.py:516): per star a cut of a frame, the adaptive-moment iteration on it (the
+ * iteration behind GalSim's FindAdaptiveMom -- restated from the published algorithm, not compared with an installed GalSim), the fourth
+ * moments and the forced-scale moments over the same cut, and the means of small windows of the maps.  All sums are float64, reduced in a
+ * fixed order that does not depend on the number of stars: a star's numbers are the same bits alone and in any batch, run after run.
+ * `frame` / `map`: rows x cols elements, `pitch` elements from row to row.  ox, oy (int32 [nstar]): frame column and row of the cut's first
+ * pixel, which may lie outside the frame; pixels outside the frame are zero (np.pad).  memspace covers every array but `par`.
+ *   imcom_star_sizes         no context: out[4] = {workspace bytes of an imcom_star_moments call with host arrays, the largest side of a
+ *                            cut, the result columns a star, LDS bytes of a moments workgroup}.  IMCOM_ERR_UNSUPPORTED: w or h above 127.
+ *   imcom_star_moments       out [nstar][22] float64: amp, x, y (1-based cut coordinates, as galsim.Image has them), sigma, e1, e2, g1, g2,
+ *                            rho4, iterations, status (0 ok, 1 not positive definite, 2 empty bounds, 3 moment or shift too large, 4 too
+ *                            many iterations, 5 NaN), the last convergence factor; then, for status 0 and forced_scale > 0: sum wti, sum wti
+ *                            (u^4 - v^4), sum wti (u^3 v + u v^3), sum wti2, sum wti2 (x^2 - y^2), sum wti2 2xy, M42_REAL, M42_IMAG,
+ *                            FORCED_PLUS, FORCED_CROSS (1016-1041).  forced_scale <= 0: columns 12-21 stay zero.  par NULL: the defaults.
+ *   imcom_star_window_stats  out [nstar][2]: mean and population standard deviation of map[yi+1-bd2 : yi+bd2, xi+1-bd2 : xi+bd2] as numpy
+ *                            slices it (clipped at the far edges; NaN for an empty window).  kind 0: float32, 1: float64, 2: 16-bit codes
+ *                            looked up in table (int16 [65536], indexed by the code's bit pattern) and summed as integers.
+ *   imcom_star_cuts          out float32 [nstar][h][w]: the cuts themselves, zero outside the frame. */
+typedef struct {
+    double convergence_threshold; /* 1e-6 */
+    double bound_correct_wt;      /* 0.25 */
+    double max_amoment;           /* 8000 */
+    double max_ashift;            /* 15 */
+    double max_moment_nsig2;      /* 25 */
+    double guess_sig;             /* 5 */
+    int max_mom2_iter;            /* 400 */
+    int reserved;
+} imcom_star_params;
+int imcom_star_sizes(int nstar, int w, int h, int is_f64, long *out);
+int imcom_star_moments(imcom_ctx *ctx, const void *frame, int is_f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h,
+                       const imcom_star_params *par, double forced_scale, double *out, int memspace);
+int imcom_star_window_stats(imcom_ctx *ctx, const void *map, int kind, long rows, long cols, long pitch, const short *table, const int *xi, const int *yi, int nstar,
+                            int bd2, double *out, int memspace);
+int imcom_star_cuts(imcom_ctx *ctx, const void *frame, int is_f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h, float *out,
+                    int memspace);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,11 @@ class I24Pars(C.Structure):  # imcom_i24_pars
     _fields_ = [("vmin", C.c_double), ("vmax", C.c_double), ("alpha", C.c_double), ("softbias", C.c_long), ("bitkeep", C.c_int), ("diff", C.c_int), ("reorder", C.c_int)]
 
 
+class StarParams(C.Structure):  # imcom_star_params
+    _fields_ = [("convergence_threshold", C.c_double), ("bound_correct_wt", C.c_double), ("max_amoment", C.c_double), ("max_ashift", C.c_double),
+                ("max_moment_nsig2", C.c_double), ("guess_sig", C.c_double), ("max_mom2_iter", C.c_int), ("reserved", C.c_int)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -182,6 +187,10 @@ SIGNATURES = {
     "imcom_quant_set_ranks": [_vp, _vp, _vp],
     "imcom_quant_results": [_vp, _vp, _vp],
     "imcom_codehist": [_vp, _vp, _l, _l, _l, _vp, _i, _vp, _i],
+    "imcom_star_sizes": [_i, _i, _i, _i, _vp],
+    "imcom_star_moments": [_vp, _vp, _i, _l, _l, _l, _vp, _vp, _i, _i, _i, _vp, _d, _vp, _i],
+    "imcom_star_window_stats": [_vp, _vp, _i, _l, _l, _l, _vp, _vp, _vp, _i, _i, _vp, _i],
+    "imcom_star_cuts": [_vp, _vp, _i, _l, _l, _l, _vp, _vp, _i, _i, _i, _vp, _i],
     "imcom_i24_sizes": [_i, _l, _l, _vp, _i, _vp],
     "imcom_i24_compress": [_vp, _vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _l, _vp, C.c_size_t, _vp],
     "imcom_i24_overflow_fetch": [_vp, _vp, _l, _l, _i, _i, _i, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _l],

@@ -159,4 +159,12 @@ constexpr int PCG64_JUMPS = 128;
 constexpr long PCG64_MAX_COUNT = 1L << 36;  // most draws of one call
 int pcg64_jumps(imcom_ctx *ctx, uint64_t inc_lo, uint64_t inc_hi, const unsigned long long **jumps_d, const char *who);
 
+// starmom.hip: the star catalog's kernels (every pointer device memory; their C entries end quantiles.hip).  kind: 0 float32, 1 float64, 2 codes
+size_t star_moments_lds(int w, int h, bool f64);  // LDS bytes of a workgroup
+int launch_star_moments(imcom_ctx *ctx, const void *frame, bool f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h,
+                        const imcom_star_params &par, double forced_scale, double *out);
+int launch_star_window_stats(imcom_ctx *ctx, const void *map, int kind, long rows, long cols, long pitch, const short *table, const int *xi, const int *yi, int nstar,
+                             int bd2, double *out);
+int launch_star_cuts(imcom_ctx *ctx, const void *frame, bool f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h, float *out);
+
 }  // namespace imcom
