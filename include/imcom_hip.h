@@ -913,6 +913,53 @@ int imcom_star_window_stats(imcom_ctx *ctx, const void *map, int kind, long rows
 int imcom_star_cuts(imcom_ctx *ctx, const void *frame, int is_f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h, float *out,
                     int memspace);
 
+/* World coordinate systems (reference src/pyimcom/wcsutil.py:419-634, PyIMCOM_WCS: a FITS TAN-SIP header, or for gwcs input -- type
+ * "ASTROPY+" -- a fitted TAN-SIP plus a bilinear error map; src/pyimcom/utils/compareutils.py:63-106, map_sca2sca; wcsutil.py:688-788,
+ * get_pix_area).  The arithmetic is that of the published definitions (FITS WCS papers I / II, the SIP convention), evaluated per point in
+ * float64; it has not been compared with astropy / wcslib.  One owner thread a point, integer counts only: the same bits for every run.
+ * A WCS is a caller-packed descriptor `wcs` of 130 doubles in HOST memory, whatever `memspace` says:
+ *   [0] projection: 0 TAN (with or without SIP), 1 STG      [1] CRPIX1  [2] CRPIX2      [3..6] CD1_1 CD1_2 CD2_1 CD2_2, degrees a pixel
+ *   [7..15] R, row-major: native unit vector = R (celestial unit vector) -- Paper II eq. (2) with the native pole at CRVAL and
+ *           phi_p = LONPOLE, formed by the caller once and rounded once
+ *   [16] A_ORDER  [17] B_ORDER (0: no polynomial; at most 9)      [18] niter, the fixed-point steps of the inverse's error map (0 .. 16)
+ *   [19] 0      [20 + i(p, q)] A_p_q   [75 + i(p, q)] B_p_q with i(p, q) = 10 p - p (p - 1) / 2 + q, p + q <= 9
+ * Anything else -- another projection, PV terms, look-up distortions, more than two axes -- cannot be packed; a projection code other than
+ * 0 / 1 or an order above 9 is IMCOM_ERR_UNSUPPORTED.  The optional error table (tab NULL: none) is passed beside it: tab [2][n2][n2] of
+ * float32 (tab_f64 0) or float64 (1), plane 0 the x offset and plane 1 the y offset, axes (y, x), n2 = N + 2 nodes an axis at tab_lo, 0, 1,
+ * .., N - 1, tab_hi -- the padded grid and values of LocWCS.err_interp (wcsutil.py:364-413); bilinear inside, linear beyond both ends,
+ * accumulated in float64.  Each point takes its OWN correction (the reference's pos[::-1, :] of lines 516 / 589 takes another point's).
+ * origin: 0 or 1, the index of the first pixel.  Points written NaN (and counted): the far hemisphere of TAN, the antipode of STG, input
+ * that is not finite, a SIP inverse whose Newton iteration (analytic Jacobian, from the linear solution) has not stopped after 12 steps; it
+ * stops at steps below 2^-40 pixel in both components, or -- more than 4096 pixels from CRPIX, where an ulp of the coordinate exceeds
+ * 2^-40 pixel -- below 2^-52 of the coordinate.
+ *   imcom_wcs_sizes      no context: out[4] = {workspace bytes of a list or map call with device arrays, of imcom_wcs_pix_area with device
+ *                        arrays for a W x H frame, doubles of a descriptor, the largest SIP order}.
+ *   imcom_wcs_pix2world  524-560: pix [n][2] -> world [n][2] = (ra in [0, 360), dec) in degrees; with a table world(pos + dp(pos)).
+ *                        *nbad (may be NULL; not NULL: the call waits for it): points written NaN.
+ *   imcom_wcs_world2pix  598-634: world [n][2] -> pix [n][2]; with a table pos2 = inverse(world), then niter times pos1 = pos2 - dp(pos1)
+ *                        from pos1 = pos2 (583-591).
+ *   imcom_wcs_pix2pix    compareutils.py:94-106: pixels of `from` -> pixels of `to` through the unit vector alone (no ra, no dec, no
+ *                        trigonometric function).  The points are a list points [n][2], or (points NULL) the grid {lo_x, step_x, count_x,
+ *                        lo_y, step_y, count_y} (six doubles in HOST memory, whatever `memspace` says), row-major over (y, x):
+ *                        map_sca2sca's meshgrid with pad and subsamp.  At most 2^40 points a call; nside and pad finite.  x, y [n] (both or
+ *                        neither): float64, or float32 with out_f32.  is_in_ref (uint8 [n], may be NULL): lines 103-105 with `nside` and
+ *                        `pad`, strict in x and not in y, from the float64 positions before any cast.  counts (HOST long [2], may be
+ *                        NULL; not NULL: the call waits): {points in the reference, points written NaN}.  With x, y, is_in_ref all NULL
+ *                        only the counts are formed (get_overlap_matrix, 161-167).
+ *   imcom_wcs_pix_area   wcsutil.py:729-786 in two launches: ra, dec of the frame (xs [W], ys [H]: the two linspaces of 718-726) with the
+ *                        exact extrema of ra; the host decides the turn of 740-749 (*rotated, may be NULL); then the centred differences
+ *                        over op = ovsamp pad points, / 2 / pad, the determinant and cos(dec): area [H - 2 op][W - 2 op], square degrees. */
+int imcom_wcs_sizes(long n, int W, int H, long *out);
+int imcom_wcs_pix2world(imcom_ctx *ctx, const double *wcs, const void *tab, int tab_f64, int tab_n2, double tab_lo, double tab_hi, const double *pix, long n, int origin,
+                        double *world, long *nbad, int memspace);
+int imcom_wcs_world2pix(imcom_ctx *ctx, const double *wcs, const void *tab, int tab_f64, int tab_n2, double tab_lo, double tab_hi, const double *world, long n, int origin,
+                        double *pix, long *nbad, int memspace);
+int imcom_wcs_pix2pix(imcom_ctx *ctx, const double *from, const void *ftab, int ftab_f64, int ftab_n2, double ftab_lo, double ftab_hi, const double *to, const void *ttab,
+                      int ttab_f64, int ttab_n2, double ttab_lo, double ttab_hi, const double *points, const double *grid, long n, int origin, double nside, double pad,
+                      void *x, void *y, int out_f32, unsigned char *is_in_ref, long *counts, int memspace);
+int imcom_wcs_pix_area(imcom_ctx *ctx, const double *wcs, const void *tab, int tab_f64, int tab_n2, double tab_lo, double tab_hi, const double *xs, int W, const double *ys,
+                       int H, int op, double pad, double *area, int *rotated, int memspace);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,11 @@ SIGNATURES = {
     "imcom_i24_compress": [_vp, _vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _l, _vp, C.c_size_t, _vp],
     "imcom_i24_overflow_fetch": [_vp, _vp, _l, _l, _i, _i, _i, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _l],
     "imcom_i24_decompress": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "imcom_wcs_sizes": [_l, _i, _i, _vp],
+    "imcom_wcs_pix2world": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _l, _i, _vp, C.POINTER(_l), _i],
+    "imcom_wcs_world2pix": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _l, _i, _vp, C.POINTER(_l), _i],
+    "imcom_wcs_pix2pix": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _l, _i, _d, _d, _vp, _vp, _i, _vp, _vp, _i],
+    "imcom_wcs_pix_area": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _i, _vp, _i, _i, _d, _vp, _ip, _i],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

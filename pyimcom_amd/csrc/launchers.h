@@ -167,4 +167,17 @@ int launch_star_window_stats(imcom_ctx *ctx, const void *map, int kind, long row
                              int bd2, double *out);
 int launch_star_cuts(imcom_ctx *ctx, const void *frame, bool f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h, float *out);
 
+// wcs.hip: world coordinate systems (wcs_core.h; every pointer device memory; their C entries end destripe.hip).  counts: {points inside
+// the reference, points written NaN}, added to; null: not counted
+struct WcsDesc;
+struct WcsTab;
+constexpr long WCS_MAX_POINTS = 1L << 40;  // most points of one call (the workgroups of 1024 points fit the launch's unsigned count)
+int launch_wcs_list(imcom_ctx *ctx, const WcsDesc &w, const WcsTab &t, int inverse, const double *in, long n, int origin, double *out, unsigned long long *counts);
+int launch_wcs_pix2pix(imcom_ctx *ctx, const WcsDesc &from, const WcsTab &tf, const WcsDesc &to, const WcsTab &tt, const double *M, const double *pts, const double *grid,
+                       long n, int origin, double nside, double pad, void *xo, void *yo, int f32, unsigned char *mask, unsigned long long *counts);
+int launch_wcs_area_frame(imcom_ctx *ctx, const WcsDesc &w, const WcsTab &t, const double *xs, int W, const double *ys, int H, double *ra, double *dec,
+                          unsigned long long *ext);  // ext: order keys of the smallest and largest ra (wcs_key_value)
+int launch_wcs_area_finish(imcom_ctx *ctx, const double *ra, const double *dec, int W, int H, int op, double pad, int rotate, double *area);
+double wcs_key_value(unsigned long long key);
+
 }  // namespace imcom
