@@ -304,7 +304,7 @@ __global__ void a_tile_scatter_kernel(const int *__restrict__ key, int *__restri
     desc[(long)s * ntri + atomicAdd(cursor + (long)s * nbin + key[g], 1)] = (int)(g - (long)s * ntri);  // the order inside a bucket decides only the schedule
 }
 
-int launch_build_A(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, const double *x, const double *y,
+static int launch_build_A(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, const double *x, const double *y,
                    const int *psf, const double *tables, int ntab, int ng, double nc, double dscale,
                    const int *pair_tab, const double *pair_pen, int npsf_max, double *A)
 {
@@ -333,3 +333,25 @@ int launch_build_A(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, const d
 }
 
 }  // namespace imcom
+
+using namespace imcom;
+
+extern "C" {
+
+int imcom_build_A(imcom_ctx *ctx, int batch, const int *n_host, int ldn, const double *x, const double *y, const int *psf,
+                  const double *tables, int ntab, const imcom_table_geom *geom, const int *pair_tab, const double *pair_pen,
+                  int npsf_max, double *A)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(batch >= 1 && n_host && x && y && psf && tables && geom && pair_tab && pair_pen && A, "null pointer");
+    IMCOM_REQUIRE(ldn >= 1 && ntab >= 1 && npsf_max >= 1 && geom->nsamp >= 1 && geom->dscale > 0, "bad sizes");
+    const long nt_ = (ldn + 15) / 16, tiles_ = nt_ * (nt_ + 1) / 2 * batch;  // per-stamp tile order by PSF pair: key + descriptor per tile, bins per stamp
+    IMCOM_TRY(ws_reserve(ctx, (size_t)batch * 4 + (size_t)tiles_ * 8 + (size_t)batch * ((size_t)npsf_max * npsf_max + 1) * 4 + 8192));
+    int *n_dev = (int *)ws_take(ctx, (size_t)batch * 4);
+    IMCOM_TRY(upload(ctx, n_dev, n_host, batch));
+    ProfScope ps(ctx, "build_A");
+    return launch_build_A(ctx, batch, n_dev, ldn, x, y, psf, tables, ntab, geom->nsamp + 12, geom->nc, geom->dscale, pair_tab,
+                          pair_pen, npsf_max, A);
+}
+
+}  // extern "C"

@@ -340,7 +340,7 @@ __global__ __launch_bounds__(MMA_THREADS, MMA_MINWAVES) void solve_fwd_kernel(co
 }
 
 // CO: the coaddition's sums taken from the finished tile of T (tile_coadd_partials; where the call's coaddition can ride along,
-// coadd_fusable in api.hip): an instantiation of its own, bounded to four waves per SIMD, so that the plain kernel's registers are
+// coadd_fusable in chol_solve.hip): an instantiation of its own, bounded to four waves per SIMD, so that the plain kernel's registers are
 // exactly what they were without it
 template <bool CO>
 __global__ __launch_bounds__(MMA_THREADS, CO ? 4 : MMA_MINWAVES) void solve_bwd_kernel(const double *__restrict__ L,
@@ -481,7 +481,7 @@ __global__ __launch_bounds__(MMA_THREADS, 2) void mfma_probe_kernel(int iters, d
     if (v == 0.123456789) sink[0] = v;  // keeps the loop alive
 }
 
-int launch_mfma_probe(imcom_ctx *ctx, int nwg, int iters, double *sink, int *waves_per_wg)
+static int launch_mfma_probe(imcom_ctx *ctx, int nwg, int iters, double *sink, int *waves_per_wg)
 {
     *waves_per_wg = MMA_WAVES;
     hipLaunchKernelGGL(mfma_probe_kernel, dim3(nwg), dim3(MMA_THREADS), 0, ctx->stream, iters, 1e-9, sink);
@@ -587,7 +587,7 @@ __global__ void probe_fill_kernel(double *__restrict__ p, long count, unsigned s
     p[i] = ((double)(x >> 11) * (1.0 / 9007199254740992.0) - 0.5) * 1e-3;  // (-5e-4, 5e-4): no overflow over K <= 1e6
 }
 
-int launch_probe_fill(imcom_ctx *ctx, double *p, long count, unsigned seed)
+static int launch_probe_fill(imcom_ctx *ctx, double *p, long count, unsigned seed)
 {
     hipLaunchKernelGGL(probe_fill_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, p, count, seed);
     return check_launch("probe_fill_kernel");
@@ -595,3 +595,74 @@ int launch_probe_fill(imcom_ctx *ctx, double *p, long count, unsigned seed)
 
 
 }  // namespace imcom
+
+using namespace imcom;
+
+extern "C" {
+
+int imcom_ctx_mfma_probe(imcom_ctx *ctx, double millis, double *tflops)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(tflops && millis > 0.0 && millis <= 5000.0, "bad arguments (millis in (0, 5000])");
+    const int nwg = 2 * ctx->cu_count;  // two 8-wave workgroups per CU: four waves per SIMD, all resident at once
+    IMCOM_TRY(ws_reserve(ctx, 4096));
+    double *sink;
+    IMCOM_TRY(ws_take(ctx, 1, &sink, "imcom_ctx_mfma_probe"));
+    hipEvent_t e0, e1;
+    IMCOM_HIP_CHECK(hipEventCreate(&e0));
+    IMCOM_HIP_CHECK(hipEventCreate(&e1));
+    int iters = 200, waves = 8;  // calibrated on a short first run
+    double ms = 0.0;
+    for (int pass = 0; pass < 2; pass++) {
+        IMCOM_HIP_CHECK(hipEventRecord(e0, ctx->stream));
+        IMCOM_TRY(launch_mfma_probe(ctx, nwg, iters, sink, &waves));
+        IMCOM_HIP_CHECK(hipEventRecord(e1, ctx->stream));
+        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        float f = 0.f;
+        IMCOM_HIP_CHECK(hipEventElapsedTime(&f, e0, e1));
+        ms = f;
+        if (pass == 0) iters = (int)std::max(200.0, std::min(2.0e7, iters * millis / std::max(ms, 1e-3)));
+    }
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    *tflops = (double)nwg * waves * 8.0 * iters * 2048.0 / (ms * 1e-3) / 1e12;  // 16 x 16 x 4 x 2 flop per MFMA and wave
+    return IMCOM_OK;
+}
+
+int imcom_ctx_gemm_probe(imcom_ctx *ctx, int variant, int M, int N, int K, int batch, int reps, double *tflops)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(variant == 0 || (variant >= 2 && variant <= 4), "gemm probe variant %d: 0, 2, 3 or 4", variant);
+    IMCOM_REQUIRE(tflops && M >= 256 && N >= 128 && K >= 16 && batch >= 1 && reps >= 1, "bad arguments");
+    IMCOM_REQUIRE(M % 256 == 0 && N % 128 == 0 && K % 16 == 0, "gemm probe: M % 256, N % 128, K % 16");
+    const size_t a = (size_t)batch * M * K * 8, b = (size_t)batch * K * N * 8, c = (size_t)batch * M * N * 8;
+    IMCOM_TRY(ws_reserve(ctx, a + b + c + 4096));
+    double *A = (double *)ws_take(ctx, a), *B = (double *)ws_take(ctx, b), *C = (double *)ws_take(ctx, c);
+    if (!A || !B || !C) return ws_short("imcom_ctx_gemm_probe");
+    IMCOM_TRY(launch_probe_fill(ctx, A, (long)(a / 8), 1u));  // pseudo-random operands: the power (and clock) of real data
+    IMCOM_TRY(launch_probe_fill(ctx, B, (long)(b / 8), 2u));
+    hipEvent_t e0, e1;
+    IMCOM_HIP_CHECK(hipEventCreate(&e0));
+    IMCOM_HIP_CHECK(hipEventCreate(&e1));
+    auto run = [&]() -> int {
+        // variants 2-4: the engine's other operand layouts (2: both row-major, the Cholesky updates' form C = A B^T; 3: both k-major,
+        // the backward solves'; 4: A k-major, B row-major) on the same buffers
+        if (variant == 2) return launch_gemm(ctx, false, false, M, N, K, batch, A, K, (long)M * K, B, K, (long)K * N, C, N, (long)M * N, 1.0, 0.0);
+        if (variant == 3) return launch_gemm(ctx, true, true, M, N, K, batch, A, M, (long)M * K, B, N, (long)K * N, C, N, (long)M * N, 1.0, 0.0);
+        if (variant == 4) return launch_gemm(ctx, true, false, M, N, K, batch, A, M, (long)M * K, B, K, (long)K * N, C, N, (long)M * N, 1.0, 0.0);
+        return launch_gemm(ctx, false, true, M, N, K, batch, A, K, (long)M * K, B, N, (long)K * N, C, N, (long)M * N, 1.0, 0.0);
+    };
+    IMCOM_TRY(run());  // warm-up
+    IMCOM_HIP_CHECK(hipEventRecord(e0, ctx->stream));
+    for (int r = 0; r < reps; r++) IMCOM_TRY(run());
+    IMCOM_HIP_CHECK(hipEventRecord(e1, ctx->stream));
+    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    IMCOM_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    *tflops = 2.0 * M * N * K * batch * reps / (ms * 1e-3) / 1e12;
+    return IMCOM_OK;
+}
+
+}  // extern "C"

@@ -274,14 +274,14 @@ __global__ __launch_bounds__(256) void build_B_kernel(const int *__restrict__ n,
 }
 
 // ------------------------------------------------------------------------------------------------
-int launch_getw(imcom_ctx *ctx, const double *fh, long n, double *w)
+static int launch_getw(imcom_ctx *ctx, const double *fh, long n, double *w)
 {
     if (n <= 0) return IMCOM_OK;
     hipLaunchKernelGGL(d5512_getw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, fh, n, w);
     return check_launch("d5512_getw_kernel");
 }
 
-int launch_interp(imcom_ctx *ctx, const double *infunc, int nlayer, int ngy, int ngx, const double *xpos,
+static int launch_interp(imcom_ctx *ctx, const double *infunc, int nlayer, int ngy, int ngx, const double *xpos,
                   const double *ypos, long nout, double *fhatout, int sym)
 {
     if (nout <= 0) return IMCOM_OK;
@@ -324,7 +324,7 @@ int launch_grid(imcom_ctx *ctx, const double *infunc, int ngy, int ngx, const do
     return check_launch("grid_d5512_kernel");
 }
 
-int launch_build_B(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, const double *x, const double *y,
+static int launch_build_B(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, const double *x, const double *y,
                    const int *psf, const double *tables, int ng, double nc, double dscale, const int *io_tab,
                    int npsf_max, const double *out_x0, const double *out_y0, int n2f, int ldm, double *Bt)
 {
@@ -340,3 +340,92 @@ int launch_build_B(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, const d
 
 
 }  // namespace imcom
+
+using namespace imcom;
+
+extern "C" {
+
+// ---------------------------------------------------------------------------------------------
+// native-routine seam: host pointers are staged through the workspace; device pointers used as is (Stage).
+int imcom_d5512_getw(imcom_ctx *ctx, const double *fh, long n, double *w, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(n >= 0 && (n == 0 || (fh && w)), "bad arguments");
+    if (n == 0) return IMCOM_OK;
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    st.plan(plan, {(size_t)n * 8, (size_t)n * 10 * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *fh_d;
+    double *w_d;
+    IMCOM_TRY(st.in(fh, n, &fh_d));
+    IMCOM_TRY(st.inout(w, (size_t)n * 10, &w_d));
+    IMCOM_TRY(launch_getw(ctx, fh_d, n, w_d));
+    IMCOM_TRY(st.back(w, w_d, (size_t)n * 10));
+    return st.done();
+}
+
+int imcom_interp_d5512(imcom_ctx *ctx, const double *infunc, int nlayer, int ngy, int ngx, const double *xpos,
+                       const double *ypos, long nout, double *fhatout, int sym, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(infunc && xpos && ypos && fhatout, "null pointer");
+    IMCOM_REQUIRE(nlayer >= 1 && ngy >= 1 && ngx >= 1 && nout >= 0, "bad sizes");
+    if (sym) {
+        long sq = (long)sqrt((double)(nout + 1));
+        IMCOM_REQUIRE(sq * sq <= nout, "iD5512C_sym: nout=%ld smaller than its square side^2", nout);
+    }
+    Stage st(ctx, memspace, __func__);
+    const size_t ntab = (size_t)nlayer * ngy * ngx, no = (size_t)nlayer * nout;
+    WsPlan plan;
+    st.plan(plan, {ntab * 8, (size_t)nout * 8, (size_t)nout * 8, no * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *f_d, *x_d, *y_d;
+    double *o_d;
+    IMCOM_TRY(st.in(infunc, ntab, &f_d));
+    IMCOM_TRY(st.in(xpos, nout, &x_d));
+    IMCOM_TRY(st.in(ypos, nout, &y_d));
+    IMCOM_TRY(st.inout(fhatout, no, &o_d));  // in-place semantics: untouched elements keep their values
+    { ProfScope ps(ctx, "interp"); IMCOM_TRY(launch_interp(ctx, f_d, nlayer, ngy, ngx, x_d, y_d, nout, o_d, sym)); }
+    IMCOM_TRY(st.back(fhatout, o_d, no));
+    return st.done();
+}
+
+int imcom_grid_d5512(imcom_ctx *ctx, const double *infunc, int ngy, int ngx, const double *xpos, const double *ypos,
+                     long npi, int nxo, int nyo, double *fhatout, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(infunc && xpos && ypos && fhatout, "null pointer");
+    IMCOM_REQUIRE(ngy >= 10 && ngx >= 10 && npi >= 0 && nxo >= 1 && nyo >= 1, "bad sizes");
+    Stage st(ctx, memspace, __func__);
+    const size_t ntab = (size_t)ngy * ngx, no = (size_t)npi * nxo * nyo;
+    WsPlan plan;
+    st.plan(plan, {ntab * 8, (size_t)npi * nxo * 8, (size_t)npi * nyo * 8, no * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *f_d, *x_d, *y_d;
+    double *o_d;
+    IMCOM_TRY(st.in(infunc, ntab, &f_d));
+    IMCOM_TRY(st.in(xpos, (size_t)npi * nxo, &x_d));
+    IMCOM_TRY(st.in(ypos, (size_t)npi * nyo, &y_d));
+    IMCOM_TRY(st.out(fhatout, no, &o_d));
+    { ProfScope ps(ctx, "interp"); IMCOM_TRY(launch_grid(ctx, f_d, ngy, ngx, x_d, y_d, npi, nxo, nyo, o_d)); }
+    IMCOM_TRY(st.back(fhatout, o_d, no));
+    return st.done();
+}
+
+int imcom_build_B(imcom_ctx *ctx, int batch, const int *n_host, int ldn, const double *x, const double *y, const int *psf,
+                  const double *tables, int ntab, const imcom_table_geom *geom, const int *io_tab, int npsf_max,
+                  const double *out_x0, const double *out_y0, int n2f, int ldm, double *Bt)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(batch >= 1 && n_host && x && y && psf && tables && geom && io_tab && out_x0 && out_y0 && Bt, "null pointer");
+    IMCOM_REQUIRE(ldn >= 1 && ntab >= 1 && npsf_max >= 1 && n2f >= 1 && ldm >= n2f * n2f, "bad sizes");
+    IMCOM_TRY(ws_reserve(ctx, (size_t)batch * 4 + 1024));
+    int *n_dev = (int *)ws_take(ctx, (size_t)batch * 4);
+    IMCOM_TRY(upload(ctx, n_dev, n_host, batch));
+    ProfScope ps(ctx, "build_B");
+    return launch_build_B(ctx, batch, n_dev, ldn, x, y, psf, tables, geom->nsamp + 12, geom->nc, geom->dscale, io_tab,
+                          npsf_max, out_x0, out_y0, n2f, ldm, Bt);
+}
+
+}  // extern "C"

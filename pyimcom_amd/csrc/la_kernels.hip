@@ -709,7 +709,7 @@ int launch_solve_mask(imcom_ctx *ctx, const int *nblk, const int *fac, const int
 }
 
 // ------------------------------------------------------------------------------------------------
-// Small kernels of the smallest-eigenvalue iteration (api.hip: lambda_min_subspace)
+// Small kernels of the smallest-eigenvalue iteration (chol_solve.hip: lambda_min_subspace)
 // X [batch][ldn][P]: pseudo-random start block, zero on the rows beyond n[s] and for stamps that are not wanted
 __global__ void lmin_init_kernel(double *__restrict__ X, int ldn, int P, const int *__restrict__ n, const int *__restrict__ want)
 {
@@ -786,7 +786,7 @@ int launch_lakernel1(imcom_ctx *ctx, const double *lam, const double *mPhalf, lo
     return check_launch("lakernel1_kernel");
 }
 
-int launch_trapezoid_f32(imcom_ctx *ctx, float *maps, long nmaps, int n2f, int fade)
+static int launch_trapezoid_f32(imcom_ctx *ctx, float *maps, long nmaps, int n2f, int fade)
 {
     const long tot = nmaps * n2f * n2f;
     if (tot <= 0 || fade <= 0) return IMCOM_OK;
@@ -794,7 +794,7 @@ int launch_trapezoid_f32(imcom_ctx *ctx, float *maps, long nmaps, int n2f, int f
     return check_launch("trapezoid_f32_kernel");
 }
 
-int launch_clamp_min_f32(imcom_ctx *ctx, float *maps, long count, float lo)
+static int launch_clamp_min_f32(imcom_ctx *ctx, float *maps, long count, float lo)
 {
     if (count <= 0) return IMCOM_OK;
     hipLaunchKernelGGL(clamp_min_f32_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, maps, count, lo);
@@ -837,3 +837,97 @@ int launch_coadd_from_partials(imcom_ctx *ctx, int batch, const int *n_dev, cons
 }
 
 }  // namespace imcom
+
+using namespace imcom;
+
+extern "C" {
+
+int imcom_lakernel1(imcom_ctx *ctx, const double *lam, const double *mPhalf, long m, long n, double C, double targetleak,
+                    double kCmin, double kCmax, int nbis, double *kappa, double *Sigma, double *UC, double *T, double smax,
+                    int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(lam && mPhalf && kappa && Sigma && UC && T, "null pointer");
+    IMCOM_REQUIRE(m >= 0 && n >= 0 && nbis >= 0, "bad sizes");
+    Stage st(ctx, memspace, __func__);
+    const size_t mn = (size_t)m * n;
+    WsPlan plan;
+    st.plan(plan, {(size_t)n * 8, mn * 8, (size_t)m * 8, (size_t)m * 8, (size_t)m * 8, mn * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *lam_d, *p_d;
+    double *k_d, *S_d, *U_d, *T_d;
+    IMCOM_TRY(st.in(lam, n, &lam_d));
+    IMCOM_TRY(st.in(mPhalf, mn, &p_d));
+    IMCOM_TRY(st.out(kappa, m, &k_d));
+    IMCOM_TRY(st.out(Sigma, m, &S_d));
+    IMCOM_TRY(st.out(UC, m, &U_d));
+    IMCOM_TRY(st.out(T, mn, &T_d));
+    { ProfScope ps(ctx, "lakernel1"); IMCOM_TRY(launch_lakernel1(ctx, lam_d, p_d, m, n, n, C, targetleak, kCmin, kCmax, nbis, k_d, S_d, U_d, T_d, n, smax)); }
+    IMCOM_TRY(st.back(kappa, k_d, m));
+    IMCOM_TRY(st.back(Sigma, S_d, m));
+    IMCOM_TRY(st.back(UC, U_d, m));
+    IMCOM_TRY(st.back(T, T_d, mn));
+    return st.done();
+}
+
+int imcom_build_reduced_T(imcom_ctx *ctx, const double *Nflat, const double *Dflat, const double *Eflat, const double *kappa,
+                          int nv, long m, double ucmin, double smax, double *out_kappa, double *out_Sigma, double *out_UC,
+                          double *out_w, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(Nflat && Dflat && Eflat && kappa && out_kappa && out_Sigma && out_UC && out_w, "null pointer");
+    IMCOM_REQUIRE(m >= 0 && nv >= 2, "bad sizes (nv must be >= 2, routine.py:537)");
+    Stage st(ctx, memspace, __func__);
+    const size_t nv2 = (size_t)nv * nv, mv = (size_t)m * nv;
+    WsPlan plan;
+    st.plan(plan, {(size_t)m * nv2 * 8, mv * 8, (size_t)m * nv2 * 8, (size_t)nv * 8, (size_t)m * 8, (size_t)m * 8, (size_t)m * 8, mv * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *N_d, *D_d, *E_d, *k_d;
+    double *ok, *oS, *oU, *ow;
+    IMCOM_TRY(st.in(Nflat, (size_t)m * nv2, &N_d));
+    IMCOM_TRY(st.in(Dflat, mv, &D_d));
+    IMCOM_TRY(st.in(Eflat, (size_t)m * nv2, &E_d));
+    IMCOM_TRY(st.in(kappa, nv, &k_d));
+    IMCOM_TRY(st.out(out_kappa, m, &ok));
+    IMCOM_TRY(st.out(out_Sigma, m, &oS));
+    IMCOM_TRY(st.out(out_UC, m, &oU));
+    IMCOM_TRY(st.out(out_w, mv, &ow));
+    { ProfScope ps(ctx, "reduced_T"); IMCOM_TRY(launch_build_reduced_T(ctx, N_d, D_d, E_d, k_d, nv, m, ucmin, smax, ok, oS, oU, ow)); }
+    IMCOM_TRY(st.back(out_kappa, ok, m));
+    IMCOM_TRY(st.back(out_Sigma, oS, m));
+    IMCOM_TRY(st.back(out_UC, oU, m));
+    IMCOM_TRY(st.back(out_w, ow, mv));
+    return st.done();
+}
+
+int imcom_coadd_epilogue(imcom_ctx *ctx, int batch, const int *n_host, int ldn, int m, int ldm, int n2f, int fade, int n2,
+                         float *Tt, const float *indata, int n_inframe, const int *expo, int n_expo, float *outimage,
+                         double *Tsum_stamp, double *Tsum_inpix, double *Neff)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(batch >= 1 && n_host && Tt && indata && expo && outimage && Tsum_stamp && Tsum_inpix && Neff, "null pointer");
+    IMCOM_REQUIRE(m == n2f * n2f && m <= ldm && n_inframe >= 1 && n_expo >= 1 && fade >= 0 && n2 >= 1, "bad sizes");
+    IMCOM_TRY(ws_reserve(ctx, (size_t)batch * 4 + (size_t)batch * m * n_expo * 8 + 2048));
+    int *n_dev = (int *)ws_take(ctx, (size_t)batch * 4);
+    double *Tsum_image = (double *)ws_take(ctx, (size_t)batch * m * n_expo * 8);
+    IMCOM_TRY(upload(ctx, n_dev, n_host, batch));
+    ProfScope ps(ctx, "epilogue");
+    return launch_epilogue(ctx, batch, n_dev, ldn, m, ldm, n2f, fade, n2, Tt, indata, n_inframe, expo, n_expo, outimage,
+                           Tsum_image, Tsum_stamp, Tsum_inpix, Neff);
+}
+
+int imcom_trapezoid_f32(imcom_ctx *ctx, float *maps, long nmaps, int n2f, int fade)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(maps && nmaps >= 0 && n2f >= 1 && fade >= 0, "bad arguments");
+    return launch_trapezoid_f32(ctx, maps, nmaps, n2f, fade);
+}
+
+int imcom_clamp_min_f32(imcom_ctx *ctx, float *maps, long count, float lo)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(count >= 0 && (count == 0 || maps), "bad arguments");
+    return launch_clamp_min_f32(ctx, maps, count, lo);
+}
+
+}  // extern "C"

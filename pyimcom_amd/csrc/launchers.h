@@ -31,8 +31,6 @@ int launch_coadd_from_partials(imcom_ctx *ctx, int batch, const int *n_dev, cons
                                float *outimage, double *Tsum_image, double *Tsum_stamp, double *Tsum_inpix, double *Neff);
 int launch_solve_dinv(imcom_ctx *ctx, const double *Dinv, double *Y, int ldn, int ldm, int k, int batch,
                       const int *nblk, bool trans);
-int launch_probe_fill(imcom_ctx *ctx, double *p, long count, unsigned seed);
-int launch_mfma_probe(imcom_ctx *ctx, int nwg, int iters, double *sink, int *waves_per_wg);
 int launch_syr2k_lower(imcom_ctx *ctx, int N, int K, int batch, const double *V, long ldv, long strideV, const double *W, long ldw, long strideW,
                        double *C, long ldc, long strideC, double alpha);  // lower 128-tiles of C += alpha (V^T W + W^T V), V, W k-major
 int launch_gemm(imcom_ctx *ctx, bool akm, bool bkm, int M, int N, int K, int batch, const double *A, long lda,
@@ -107,24 +105,13 @@ int launch_build_reduced_T(imcom_ctx *ctx, const double *Nf, const double *Df, c
 int launch_lakernel1(imcom_ctx *ctx, const double *lam, const double *mPhalf, long m, long n, long ldp, double C,
                      double targetleak, double kCmin, double kCmax, int nbis, double *kappa, double *Sigma,
                      double *UC, double *T, long ldt, double smax);
-int launch_trapezoid_f32(imcom_ctx *ctx, float *maps, long nmaps, int n2f, int fade);
-int launch_clamp_min_f32(imcom_ctx *ctx, float *maps, long count, float lo);
 int launch_epilogue(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, int m, int ldm, int n2f, int fade, int n2,
                     float *Tt, const float *indata, int n_inframe, const int *expo, int n_expo, float *outimage,
                     double *Tsum_image, double *Tsum_stamp, double *Tsum_inpix, double *Neff);
 
 // interp.hip
-int launch_getw(imcom_ctx *ctx, const double *fh, long n, double *w);
-int launch_interp(imcom_ctx *ctx, const double *infunc, int nlayer, int ngy, int ngx, const double *xpos,
-                  const double *ypos, long nout, double *fhatout, int sym);
 int launch_grid(imcom_ctx *ctx, const double *infunc, int ngy, int ngx, const double *xpos, const double *ypos,
                 long npi, int nxo, int nyo, double *fhatout);
-int launch_build_A(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, const double *x, const double *y,
-                   const int *psf, const double *tables, int ntab, int ng, double nc, double dscale,
-                   const int *pair_tab, const double *pair_pen, int npsf_max, double *A);
-int launch_build_B(imcom_ctx *ctx, int batch, const int *n_dev, int ldn, const double *x, const double *y,
-                   const int *psf, const double *tables, int ng, double nc, double dscale, const int *io_tab,
-                   int npsf_max, const double *out_x0, const double *out_y0, int n2f, int ldm, double *Bt);
 
 // psf_sample.hip: the device work of imcom_smooth_and_pad on its own (src, dst in device memory), its scratch out of the workspace
 struct SmoothPadWs {
@@ -158,26 +145,5 @@ int splitpsf_dense_product(imcom_ctx *ctx, const SpDense &d, const double2 *in, 
 constexpr int PCG64_JUMPS = 128;
 constexpr long PCG64_MAX_COUNT = 1L << 36;  // most draws of one call
 int pcg64_jumps(imcom_ctx *ctx, uint64_t inc_lo, uint64_t inc_hi, const unsigned long long **jumps_d, const char *who);
-
-// starmom.hip: the star catalog's kernels (every pointer device memory; their C entries end quantiles.hip).  kind: 0 float32, 1 float64, 2 codes
-size_t star_moments_lds(int w, int h, bool f64);  // LDS bytes of a workgroup
-int launch_star_moments(imcom_ctx *ctx, const void *frame, bool f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h,
-                        const imcom_star_params &par, double forced_scale, double *out);
-int launch_star_window_stats(imcom_ctx *ctx, const void *map, int kind, long rows, long cols, long pitch, const short *table, const int *xi, const int *yi, int nstar,
-                             int bd2, double *out);
-int launch_star_cuts(imcom_ctx *ctx, const void *frame, bool f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h, float *out);
-
-// wcs.hip: world coordinate systems (wcs_core.h; every pointer device memory; their C entries end destripe.hip).  counts: {points inside
-// the reference, points written NaN}, added to; null: not counted
-struct WcsDesc;
-struct WcsTab;
-constexpr long WCS_MAX_POINTS = 1L << 40;  // most points of one call (the workgroups of 1024 points fit the launch's unsigned count)
-int launch_wcs_list(imcom_ctx *ctx, const WcsDesc &w, const WcsTab &t, int inverse, const double *in, long n, int origin, double *out, unsigned long long *counts);
-int launch_wcs_pix2pix(imcom_ctx *ctx, const WcsDesc &from, const WcsTab &tf, const WcsDesc &to, const WcsTab &tt, const double *M, const double *pts, const double *grid,
-                       long n, int origin, double nside, double pad, void *xo, void *yo, int f32, unsigned char *mask, unsigned long long *counts);
-int launch_wcs_area_frame(imcom_ctx *ctx, const WcsDesc &w, const WcsTab &t, const double *xs, int W, const double *ys, int H, double *ra, double *dec,
-                          unsigned long long *ext);  // ext: order keys of the smallest and largest ra (wcs_key_value)
-int launch_wcs_area_finish(imcom_ctx *ctx, const double *ra, const double *dec, int W, int H, int op, double pad, int rotate, double *area);
-double wcs_key_value(unsigned long long key);
 
 }  // namespace imcom

@@ -1,6 +1,6 @@
 // lmin_skinny.hip -- the Cholesky repair's smallest-eigenvalue iteration on blocks of 16 vectors.
 //
-// The reference's repair needs w[0] of eigh(A) and nothing else (reference src/pyimcom/lakernel.py:262-279); api.hip
+// The reference's repair needs w[0] of eigh(A) and nothing else (reference src/pyimcom/lakernel.py:262-279); chol_solve.hip
 // lambda_min_subspace finds it by inverse subspace iteration on a Cholesky factor of A + sigma I.  With the shift sigma a few
 // per cent above |lambda_min| -- which is what the block-constant hint of a production block delivers -- the convergence per step is
 // governed by (lambda_1 + sigma) / (lambda_{P+1} + sigma), and on a production stamp (configs/paper4: N = 6.2k, lambda_1 = -1.95e-6,

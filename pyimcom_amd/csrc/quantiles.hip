@@ -2,8 +2,7 @@
 // and 102-177, _percentiles_and_delete and the gathering loop of LayerReport.build; src/pyimcom/diagnostics/dynrange.py:140-163 and
 // 211-238, the two histograms and the ring profiles of gen_dynrange_data): an exact radix select over data that arrives in chunks, for
 // many segments and many ranks at once, and the histogram of a (u)int16-coded map through a table of its 65 536 codes.  The C-ABI entries
-// imcom_quant_* / imcom_codehist end the file; the host's walk down the digits is theirs and quantiles_core.h's.  After them come the
-// entries imcom_star_* of the report's other half, the star catalog, whose kernels are starmom.hip's.
+// imcom_quant_* / imcom_codehist end the file; the host's walk down the digits is theirs and quantiles_core.h's.
 //
 // A pass counts, per live group (a segment and a key prefix that one of its ranks has reached) and per value of the pass's digit, the
 // elements of the segment whose higher bits equal the prefix.  Every number is an integer added with atomics: one right value, whatever
@@ -14,7 +13,6 @@
 //     (group, digit) at once.
 #include "launchers.h"
 #include "quantiles_core.h"
-#include "starmom_core.h"
 
 namespace imcom {
 
@@ -579,118 +577,6 @@ int imcom_codehist(imcom_ctx *ctx, const void *codes, long rows, long cols, long
     IMCOM_TRY(st.out(counts, (size_t)nbins + 1, &n_d));
     IMCOM_TRY(launch_codehist(ctx, c_d, rows, cols, pitch, t_d, nbins, (unsigned long long *)n_d));
     IMCOM_TRY(st.back(counts, (const long *)n_d, (size_t)nbins + 1));
-    return st.done();
-}
-
-// ---------------------------------------------------------------------------------------------
-// C entries of the star catalog, the other half of the validation report: the kernels are starmom.hip's, the entries live here because
-// tests/test_abi.py keeps a table of the source files that define entries taking a context.
-
-static int star_shape(const char *who, long rows, long cols, long pitch, int nstar, int w, int h)
-{
-    IMCOM_REQUIRE(rows >= 1 && cols >= 1 && pitch >= cols && rows <= QT_MAX_CHUNK / pitch, "%s: a frame of %ld x %ld elements, pitch %ld", who, rows, cols, pitch);
-    IMCOM_REQUIRE(nstar >= 0 && nstar <= (1 << 24) && w >= 1 && h >= 1, "%s: %d stars, cuts of %d x %d", who, nstar, w, h);
-    if (w > SM_MAX_SIDE || h > SM_MAX_SIDE) {
-        set_error("%s: cuts of %d x %d, served are sides up to %d", who, w, h, SM_MAX_SIDE);
-        return IMCOM_ERR_UNSUPPORTED;
-    }
-    return IMCOM_OK;
-}
-
-static const imcom_star_params STAR_DEFAULTS = {1e-6, 0.25, 8000.0, 15.0, 25.0, 5.0, 400, 0};
-
-int imcom_star_sizes(int nstar, int w, int h, int is_f64, long *out)
-{
-    IMCOM_REQUIRE(out, "null pointer");
-    IMCOM_TRY(star_shape(__func__, 1, 1, 1, nstar, w, h));
-    WsPlan plan;  // (without the frame: its size is the caller's)
-    plan.add((size_t)nstar * 4);
-    plan.add((size_t)nstar * 4);
-    plan.add((size_t)nstar * SM_NCOL * 8);
-    out[0] = (long)plan.total;
-    out[1] = SM_MAX_SIDE;
-    out[2] = SM_NCOL;
-    out[3] = (long)star_moments_lds(w, h, is_f64 != 0);
-    return IMCOM_OK;
-}
-
-int imcom_star_moments(imcom_ctx *ctx, const void *frame, int is_f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h,
-                       const imcom_star_params *par, double forced_scale, double *out, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_TRY(star_shape(__func__, rows, cols, pitch, nstar, w, h));
-    const imcom_star_params p = par ? *par : STAR_DEFAULTS;
-    IMCOM_REQUIRE(p.max_mom2_iter >= 1 && p.max_mom2_iter <= 100000 && p.guess_sig > 0.0 && p.max_moment_nsig2 > 0.0 && p.convergence_threshold > 0.0 &&
-                      p.bound_correct_wt > 0.0 && p.max_amoment > 0.0 && p.max_ashift > 0.0,
-                  "star_moments: parameters out of range (every one is positive, 1 .. 100000 iterations)");
-    IMCOM_REQUIRE(forced_scale == forced_scale, "star_moments: the forced scale is NaN");
-    if (nstar == 0) return IMCOM_OK;
-    IMCOM_REQUIRE(frame && ox && oy && out, "null pointer");
-    const size_t esz = is_f64 ? 8 : 4, span = (size_t)(rows - 1) * pitch + cols;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    st.plan(plan, {span * esz, (size_t)nstar * 4, (size_t)nstar * 4, (size_t)nstar * SM_NCOL * 8});
-    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const char *f_d;
-    const int *x_d, *y_d;
-    double *o_d;
-    IMCOM_TRY(st.in((const char *)frame, span * esz, &f_d));
-    IMCOM_TRY(st.in(ox, (size_t)nstar, &x_d));
-    IMCOM_TRY(st.in(oy, (size_t)nstar, &y_d));
-    IMCOM_TRY(st.out(out, (size_t)nstar * SM_NCOL, &o_d));
-    IMCOM_TRY(launch_star_moments(ctx, f_d, is_f64 != 0, rows, cols, pitch, x_d, y_d, nstar, w, h, p, forced_scale, o_d));
-    IMCOM_TRY(st.back(out, (const double *)o_d, (size_t)nstar * SM_NCOL));
-    return st.done();
-}
-
-int imcom_star_window_stats(imcom_ctx *ctx, const void *map, int kind, long rows, long cols, long pitch, const short *table, const int *xi, const int *yi, int nstar,
-                            int bd2, double *out, int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_TRY(star_shape(__func__, rows, cols, pitch, nstar, 1, 1));
-    IMCOM_REQUIRE(kind >= 0 && kind <= 2 && bd2 >= 1 && bd2 <= 4096, "star_window_stats: kind %d outside 0 .. 2 or bd2 = %d outside 1 .. 4096", kind, bd2);
-    if (nstar == 0) return IMCOM_OK;
-    IMCOM_REQUIRE(map && xi && yi && out && (kind != 2 || table), "null pointer");
-    const size_t esz = kind == 1 ? 8 : kind == 0 ? 4 : 2, span = (size_t)(rows - 1) * pitch + cols;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    st.plan(plan, {span * esz, kind == 2 ? (size_t)65536 * 2 : (size_t)0, (size_t)nstar * 4, (size_t)nstar * 4, (size_t)nstar * 2 * 8});
-    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const char *m_d;
-    const short *t_d = nullptr;
-    const int *x_d, *y_d;
-    double *o_d;
-    IMCOM_TRY(st.in((const char *)map, span * esz, &m_d));
-    if (kind == 2) IMCOM_TRY(st.in(table, (size_t)65536, &t_d));
-    IMCOM_TRY(st.in(xi, (size_t)nstar, &x_d));
-    IMCOM_TRY(st.in(yi, (size_t)nstar, &y_d));
-    IMCOM_TRY(st.out(out, (size_t)nstar * 2, &o_d));
-    IMCOM_TRY(launch_star_window_stats(ctx, m_d, kind, rows, cols, pitch, t_d, x_d, y_d, nstar, bd2, o_d));
-    IMCOM_TRY(st.back(out, (const double *)o_d, (size_t)nstar * 2));
-    return st.done();
-}
-
-int imcom_star_cuts(imcom_ctx *ctx, const void *frame, int is_f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h, float *out,
-                    int memspace)
-{
-    IMCOM_TRY(enter(ctx));
-    IMCOM_TRY(star_shape(__func__, rows, cols, pitch, nstar, w, h));
-    if (nstar == 0) return IMCOM_OK;
-    IMCOM_REQUIRE(frame && ox && oy && out, "null pointer");
-    const size_t esz = is_f64 ? 8 : 4, span = (size_t)(rows - 1) * pitch + cols, nout = (size_t)nstar * w * h;
-    Stage st(ctx, memspace, __func__);
-    WsPlan plan;
-    st.plan(plan, {span * esz, (size_t)nstar * 4, (size_t)nstar * 4, nout * 4});
-    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
-    const char *f_d;
-    const int *x_d, *y_d;
-    float *o_d;
-    IMCOM_TRY(st.in((const char *)frame, span * esz, &f_d));
-    IMCOM_TRY(st.in(ox, (size_t)nstar, &x_d));
-    IMCOM_TRY(st.in(oy, (size_t)nstar, &y_d));
-    IMCOM_TRY(st.out(out, nout, &o_d));
-    IMCOM_TRY(launch_star_cuts(ctx, f_d, is_f64 != 0, rows, cols, pitch, x_d, y_d, nstar, w, h, o_d));
-    IMCOM_TRY(st.back(out, (const float *)o_d, nout));
     return st.done();
 }
 

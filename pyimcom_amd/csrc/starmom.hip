@@ -3,7 +3,7 @@
 // the frame are zero, the np.pad of starcube_nonoise.py:194), runs the adaptive-moment iteration on it (starmom_core.h) and then, in the same
 // launch, the two passes over the whole cut for the fourth moments (1016-1032) and the forced-scale moments (1035-1041).  A second, small
 // kernel gives mean and np.std of the 15 x 15 windows of the maps (1044-1057), a wave a star; a third writes the cuts themselves, the cube
-// of _StarCat_galsim.fits.  The C-ABI entries imcom_star_* are at the end of quantiles.hip, the validation report's file.
+// of _StarCat_galsim.fits.  The C-ABI entries imcom_star_* end the file.
 //
 // Every sum is float64 and is reduced in one fixed order -- a thread's pixels in ascending order, the lanes of a wave by a shuffle tree, the
 // four waves in order through LDS -- that depends on the cut alone, never on the grid: no atomics on floating-point values.  After a
@@ -165,9 +165,9 @@ __global__ __launch_bounds__(SM_THREADS) void star_cuts_kernel(const T *__restri
 }
 
 // ------------------------------------------------------------------------------------------------
-size_t star_moments_lds(int w, int h, bool f64) { return (size_t)SM_HEAD * 8 + (size_t)w * h * (f64 ? 8 : 4); }
+static size_t star_moments_lds(int w, int h, bool f64) { return (size_t)SM_HEAD * 8 + (size_t)w * h * (f64 ? 8 : 4); }
 
-int launch_star_moments(imcom_ctx *ctx, const void *frame, bool f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h,
+static int launch_star_moments(imcom_ctx *ctx, const void *frame, bool f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h,
                         const imcom_star_params &par, double forced_scale, double *out)
 {
     ProfScope ps(ctx, "star_moments");
@@ -184,7 +184,7 @@ int launch_star_moments(imcom_ctx *ctx, const void *frame, bool f64, long rows, 
     return check_launch("star_moments_kernel");
 }
 
-int launch_star_window_stats(imcom_ctx *ctx, const void *map, int kind, long rows, long cols, long pitch, const short *table, const int *xi, const int *yi, int nstar,
+static int launch_star_window_stats(imcom_ctx *ctx, const void *map, int kind, long rows, long cols, long pitch, const short *table, const int *xi, const int *yi, int nstar,
                              int bd2, double *out)
 {
     ProfScope ps(ctx, "star_windows");
@@ -195,7 +195,7 @@ int launch_star_window_stats(imcom_ctx *ctx, const void *map, int kind, long row
     return check_launch("star_window_kernel");
 }
 
-int launch_star_cuts(imcom_ctx *ctx, const void *frame, bool f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h, float *out)
+static int launch_star_cuts(imcom_ctx *ctx, const void *frame, bool f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h, float *out)
 {
     ProfScope ps(ctx, "star_cuts");
     if (f64) hipLaunchKernelGGL(star_cuts_kernel<double>, dim3((unsigned)nstar), dim3(SM_THREADS), 0, ctx->stream, (const double *)frame, rows, cols, pitch, ox, oy, w, h, out);
@@ -204,3 +204,117 @@ int launch_star_cuts(imcom_ctx *ctx, const void *frame, bool f64, long rows, lon
 }
 
 }  // namespace imcom
+
+using namespace imcom;
+
+extern "C" {
+
+static int star_shape(const char *who, long rows, long cols, long pitch, int nstar, int w, int h)
+{
+    IMCOM_REQUIRE(rows >= 1 && cols >= 1 && pitch >= cols && rows <= SM_MAX_FRAME / pitch, "%s: a frame of %ld x %ld elements, pitch %ld", who, rows, cols, pitch);
+    IMCOM_REQUIRE(nstar >= 0 && nstar <= (1 << 24) && w >= 1 && h >= 1, "%s: %d stars, cuts of %d x %d", who, nstar, w, h);
+    if (w > SM_MAX_SIDE || h > SM_MAX_SIDE) {
+        set_error("%s: cuts of %d x %d, served are sides up to %d", who, w, h, SM_MAX_SIDE);
+        return IMCOM_ERR_UNSUPPORTED;
+    }
+    return IMCOM_OK;
+}
+
+static const imcom_star_params STAR_DEFAULTS = {1e-6, 0.25, 8000.0, 15.0, 25.0, 5.0, 400, 0};
+
+int imcom_star_sizes(int nstar, int w, int h, int is_f64, long *out)
+{
+    IMCOM_REQUIRE(out, "null pointer");
+    IMCOM_TRY(star_shape(__func__, 1, 1, 1, nstar, w, h));
+    WsPlan plan;  // (without the frame: its size is the caller's)
+    plan.add((size_t)nstar * 4);
+    plan.add((size_t)nstar * 4);
+    plan.add((size_t)nstar * SM_NCOL * 8);
+    out[0] = (long)plan.total;
+    out[1] = SM_MAX_SIDE;
+    out[2] = SM_NCOL;
+    out[3] = (long)star_moments_lds(w, h, is_f64 != 0);
+    return IMCOM_OK;
+}
+
+int imcom_star_moments(imcom_ctx *ctx, const void *frame, int is_f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h,
+                       const imcom_star_params *par, double forced_scale, double *out, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_TRY(star_shape(__func__, rows, cols, pitch, nstar, w, h));
+    const imcom_star_params p = par ? *par : STAR_DEFAULTS;
+    IMCOM_REQUIRE(p.max_mom2_iter >= 1 && p.max_mom2_iter <= 100000 && p.guess_sig > 0.0 && p.max_moment_nsig2 > 0.0 && p.convergence_threshold > 0.0 &&
+                      p.bound_correct_wt > 0.0 && p.max_amoment > 0.0 && p.max_ashift > 0.0,
+                  "star_moments: parameters out of range (every one is positive, 1 .. 100000 iterations)");
+    IMCOM_REQUIRE(forced_scale == forced_scale, "star_moments: the forced scale is NaN");
+    if (nstar == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(frame && ox && oy && out, "null pointer");
+    const size_t esz = is_f64 ? 8 : 4, span = (size_t)(rows - 1) * pitch + cols;
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    st.plan(plan, {span * esz, (size_t)nstar * 4, (size_t)nstar * 4, (size_t)nstar * SM_NCOL * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const char *f_d;
+    const int *x_d, *y_d;
+    double *o_d;
+    IMCOM_TRY(st.in((const char *)frame, span * esz, &f_d));
+    IMCOM_TRY(st.in(ox, (size_t)nstar, &x_d));
+    IMCOM_TRY(st.in(oy, (size_t)nstar, &y_d));
+    IMCOM_TRY(st.out(out, (size_t)nstar * SM_NCOL, &o_d));
+    IMCOM_TRY(launch_star_moments(ctx, f_d, is_f64 != 0, rows, cols, pitch, x_d, y_d, nstar, w, h, p, forced_scale, o_d));
+    IMCOM_TRY(st.back(out, (const double *)o_d, (size_t)nstar * SM_NCOL));
+    return st.done();
+}
+
+int imcom_star_window_stats(imcom_ctx *ctx, const void *map, int kind, long rows, long cols, long pitch, const short *table, const int *xi, const int *yi, int nstar,
+                            int bd2, double *out, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_TRY(star_shape(__func__, rows, cols, pitch, nstar, 1, 1));
+    IMCOM_REQUIRE(kind >= 0 && kind <= 2 && bd2 >= 1 && bd2 <= 4096, "star_window_stats: kind %d outside 0 .. 2 or bd2 = %d outside 1 .. 4096", kind, bd2);
+    if (nstar == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(map && xi && yi && out && (kind != 2 || table), "null pointer");
+    const size_t esz = kind == 1 ? 8 : kind == 0 ? 4 : 2, span = (size_t)(rows - 1) * pitch + cols;
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    st.plan(plan, {span * esz, kind == 2 ? (size_t)65536 * 2 : (size_t)0, (size_t)nstar * 4, (size_t)nstar * 4, (size_t)nstar * 2 * 8});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const char *m_d;
+    const short *t_d = nullptr;
+    const int *x_d, *y_d;
+    double *o_d;
+    IMCOM_TRY(st.in((const char *)map, span * esz, &m_d));
+    if (kind == 2) IMCOM_TRY(st.in(table, (size_t)65536, &t_d));
+    IMCOM_TRY(st.in(xi, (size_t)nstar, &x_d));
+    IMCOM_TRY(st.in(yi, (size_t)nstar, &y_d));
+    IMCOM_TRY(st.out(out, (size_t)nstar * 2, &o_d));
+    IMCOM_TRY(launch_star_window_stats(ctx, m_d, kind, rows, cols, pitch, t_d, x_d, y_d, nstar, bd2, o_d));
+    IMCOM_TRY(st.back(out, (const double *)o_d, (size_t)nstar * 2));
+    return st.done();
+}
+
+int imcom_star_cuts(imcom_ctx *ctx, const void *frame, int is_f64, long rows, long cols, long pitch, const int *ox, const int *oy, int nstar, int w, int h, float *out,
+                    int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_TRY(star_shape(__func__, rows, cols, pitch, nstar, w, h));
+    if (nstar == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(frame && ox && oy && out, "null pointer");
+    const size_t esz = is_f64 ? 8 : 4, span = (size_t)(rows - 1) * pitch + cols, nout = (size_t)nstar * w * h;
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    st.plan(plan, {span * esz, (size_t)nstar * 4, (size_t)nstar * 4, nout * 4});
+    if (st.host) IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const char *f_d;
+    const int *x_d, *y_d;
+    float *o_d;
+    IMCOM_TRY(st.in((const char *)frame, span * esz, &f_d));
+    IMCOM_TRY(st.in(ox, (size_t)nstar, &x_d));
+    IMCOM_TRY(st.in(oy, (size_t)nstar, &y_d));
+    IMCOM_TRY(st.out(out, nout, &o_d));
+    IMCOM_TRY(launch_star_cuts(ctx, f_d, is_f64 != 0, rows, cols, pitch, x_d, y_d, nstar, w, h, o_d));
+    IMCOM_TRY(st.back(out, (const float *)o_d, nout));
+    return st.done();
+}
+
+}  // extern "C"

@@ -37,6 +37,7 @@ enum SmCol {
     SMC_M42_REAL, SMC_M42_IMAG, SMC_FORCED_PLUS, SMC_FORCED_CROSS, SM_NCOL
 };
 constexpr int SM_MAX_SIDE = 127;
+constexpr long SM_MAX_FRAME = 1L << 40;  // most elements (rows x pitch) of a frame
 
 SM_HD double sm_sqrt(double v)
 {

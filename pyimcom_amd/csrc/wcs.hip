@@ -7,7 +7,7 @@
 // kernel arguments, so every coefficient is wave-uniform; the only gathers are the eight taps of an error-table look-up (four in each of its two
 // planes).
 // Counts are summed as integers inside a workgroup and added once a workgroup; there is no float atomic and no float sum across threads, so
-// the results are the same bits for every run and every chunking.  The C entries imcom_wcs_* end destripe.hip, the first consumer's file.
+// the results are the same bits for every run and every chunking.  The C entries imcom_wcs_* end the file.
 #include <algorithm>
 
 #include "launchers.h"
@@ -18,6 +18,7 @@ namespace imcom {
 namespace {
 
 constexpr int WCS_THREADS = 256, WCS_ITEMS = 4, WCS_TILE = WCS_THREADS * WCS_ITEMS;
+constexpr long WCS_MAX_POINTS = 1L << 40;  // most points of one call (the workgroups of 1024 points fit the launch's unsigned count)
 
 struct WcsMat {
     double m[9];
@@ -194,14 +195,14 @@ unsigned wcs_blocks(long n) { return (unsigned)std::max(1L, (n + WCS_TILE - 1) /
 
 }  // namespace
 
-int launch_wcs_list(imcom_ctx *ctx, const WcsDesc &w, const WcsTab &t, int inverse, const double *in, long n, int origin, double *out, unsigned long long *counts)
+static int launch_wcs_list(imcom_ctx *ctx, const WcsDesc &w, const WcsTab &t, int inverse, const double *in, long n, int origin, double *out, unsigned long long *counts)
 {
     ProfScope ps(ctx, "wcs");
     hipLaunchKernelGGL(wcs_list_kernel, dim3(wcs_blocks(n)), dim3(WCS_THREADS), 0, ctx->stream, w, t, inverse, (const double2 *)in, n, origin, (double2 *)out, counts);
     return check_launch("wcs_list_kernel");
 }
 
-int launch_wcs_pix2pix(imcom_ctx *ctx, const WcsDesc &from, const WcsTab &tf, const WcsDesc &to, const WcsTab &tt, const double *M, const double *pts, const double *grid,
+static int launch_wcs_pix2pix(imcom_ctx *ctx, const WcsDesc &from, const WcsTab &tf, const WcsDesc &to, const WcsTab &tt, const double *M, const double *pts, const double *grid,
                        long n, int origin, double nside, double pad, void *xo, void *yo, int f32, unsigned char *mask, unsigned long long *counts)
 {
     ProfScope ps(ctx, "wcs");
@@ -214,7 +215,7 @@ int launch_wcs_pix2pix(imcom_ctx *ctx, const WcsDesc &from, const WcsTab &tf, co
     return check_launch("wcs_pix2pix_kernel");
 }
 
-int launch_wcs_area_frame(imcom_ctx *ctx, const WcsDesc &w, const WcsTab &t, const double *xs, int W, const double *ys, int H, double *ra, double *dec,
+static int launch_wcs_area_frame(imcom_ctx *ctx, const WcsDesc &w, const WcsTab &t, const double *xs, int W, const double *ys, int H, double *ra, double *dec,
                           unsigned long long *ext)
 {
     ProfScope ps(ctx, "wcs");
@@ -222,7 +223,7 @@ int launch_wcs_area_frame(imcom_ctx *ctx, const WcsDesc &w, const WcsTab &t, con
     return check_launch("wcs_area_frame_kernel");
 }
 
-int launch_wcs_area_finish(imcom_ctx *ctx, const double *ra, const double *dec, int W, int H, int op, double pad, int rotate, double *area)
+static int launch_wcs_area_finish(imcom_ctx *ctx, const double *ra, const double *dec, int W, int H, int op, double pad, int rotate, double *area)
 {
     ProfScope ps(ctx, "wcs");
     hipLaunchKernelGGL(wcs_area_finish_kernel, dim3(wcs_blocks((long)(W - 2 * op) * (H - 2 * op))), dim3(WCS_THREADS), 0, ctx->stream, ra, dec, W, H, op, pad, rotate,
@@ -230,7 +231,7 @@ int launch_wcs_area_finish(imcom_ctx *ctx, const double *ra, const double *dec, 
     return check_launch("wcs_area_finish_kernel");
 }
 
-double wcs_key_value(unsigned long long k)
+static double wcs_key_value(unsigned long long k)
 {
     const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
     double v;
@@ -239,3 +240,216 @@ double wcs_key_value(unsigned long long k)
 }
 
 }  // namespace imcom
+
+using namespace imcom;
+
+// ---------------------------------------------------------------------------------------------
+// C entries -- the positions that set_pair's full storage holds are formed by them
+
+namespace {
+
+// The refusals of a packed descriptor, and the descriptor as the kernels take it.
+int wcs_descriptor(const double *d, const char *who, WcsDesc *out)
+{
+    IMCOM_REQUIRE(d, "%s: null descriptor", who);
+    for (int k = 0; k < WCS_DESC_LEN; k++) IMCOM_REQUIRE(std::isfinite(d[k]), "%s: descriptor entry %d is not finite", who, k);
+    if (!(d[WCS_D_PROJ] == (double)WCS_TAN || d[WCS_D_PROJ] == (double)WCS_STG)) {
+        set_error("%s: projection code %g; served are 0 (TAN, TAN-SIP) and 1 (STG)", who, d[WCS_D_PROJ]);
+        return IMCOM_ERR_UNSUPPORTED;
+    }
+    for (int k : {WCS_D_AORDER, WCS_D_BORDER}) {
+        if (!(d[k] >= 0 && d[k] == std::floor(d[k])) || d[k] > WCS_MAX_ORDER) {
+            set_error("%s: a SIP order of %g; served are 0 .. %d", who, d[k], WCS_MAX_ORDER);
+            return d[k] > WCS_MAX_ORDER ? IMCOM_ERR_UNSUPPORTED : IMCOM_ERR_ARG;
+        }
+    }
+    IMCOM_REQUIRE(d[WCS_D_NITER] >= 0 && d[WCS_D_NITER] <= WCS_MAX_NITER && d[WCS_D_NITER] == std::floor(d[WCS_D_NITER]), "%s: niter = %g outside 0 .. %d", who,
+                  d[WCS_D_NITER], WCS_MAX_NITER);
+    IMCOM_REQUIRE(d[WCS_D_CD] * d[WCS_D_CD + 3] - d[WCS_D_CD + 1] * d[WCS_D_CD + 2] != 0.0, "%s: the CD matrix is singular", who);
+    memcpy(out->d, d, sizeof(out->d));
+    return IMCOM_OK;
+}
+
+size_t wcs_table_bytes(const void *tab, int f64, int n2) { return tab ? (size_t)2 * n2 * n2 * (f64 ? 8 : 4) : 0; }
+
+int wcs_table(Stage &st, const void *tab, int f64, int n2, double lo, double hi, const char *who, WcsTab *out)
+{
+    *out = WcsTab{nullptr, 0, 0, 0.0, 0.0};
+    if (!tab) return IMCOM_OK;
+    IMCOM_REQUIRE(n2 >= 4 && n2 <= 32768 && lo < 0.0 && hi > (double)(n2 - 3) && std::isfinite(lo) && std::isfinite(hi) && ((uintptr_t)tab & (f64 ? 7 : 3)) == 0,
+                  "%s: an error table of %d nodes an axis with end nodes %g, %g (needed: 4 .. 32768 nodes, first node < 0, last node > %d)", who, n2, lo, hi, n2 - 3);
+    const unsigned char *dev;
+    IMCOM_TRY(st.in((const unsigned char *)tab, wcs_table_bytes(tab, f64, n2), &dev));
+    *out = WcsTab{dev, f64 ? 1 : 0, n2, lo, hi};
+    return IMCOM_OK;
+}
+
+int wcs_list(imcom_ctx *ctx, const char *who, int inverse, const double *wcs, const void *tab, int tab_f64, int tab_n2, double tab_lo, double tab_hi, const double *in,
+             long n, int origin, double *out, long *nbad, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    WcsDesc w;
+    IMCOM_TRY(wcs_descriptor(wcs, who, &w));
+    IMCOM_REQUIRE(n >= 0 && n <= WCS_MAX_POINTS && (origin == 0 || origin == 1), "%s: %ld points (at most 2^40), origin %d", who, n, origin);
+    if (nbad) *nbad = 0;
+    if (n == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(in && out, "%s: null pointer", who);
+    Stage st(ctx, memspace, who);
+    WsPlan plan;
+    plan.add(16);
+    st.plan(plan, {wcs_table_bytes(tab, tab_f64, tab_n2), (size_t)n * 16, (size_t)n * 16});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    unsigned long long *counts;
+    IMCOM_TRY(ws_take(ctx, 2, &counts, who));
+    WcsTab t;
+    IMCOM_TRY(wcs_table(st, tab, tab_f64, tab_n2, tab_lo, tab_hi, who, &t));
+    const double *in_d;
+    double *out_d;
+    IMCOM_TRY(st.in(in, (size_t)n * 2, &in_d));
+    IMCOM_TRY(st.out(out, (size_t)n * 2, &out_d));
+    if (nbad) IMCOM_HIP_CHECK(hipMemsetAsync(counts, 0, 16, ctx->stream));
+    IMCOM_TRY(launch_wcs_list(ctx, w, t, inverse, in_d, n, origin, out_d, nbad ? counts : nullptr));
+    IMCOM_TRY(st.back(out, out_d, (size_t)n * 2));
+    if (nbad) {
+        unsigned long long c[2];
+        IMCOM_HIP_CHECK(hipMemcpyAsync(c, counts, 16, hipMemcpyDeviceToHost, ctx->stream));
+        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        *nbad = (long)c[1];
+    }
+    return st.done();
+}
+}  // namespace
+
+extern "C" {
+
+int imcom_wcs_sizes(long n, int W, int H, long *out)
+{
+    IMCOM_REQUIRE(out && n >= 0 && W >= 0 && H >= 0, "wcs_sizes: bad arguments");
+    WsPlan a;
+    a.add(16);
+    a.add((size_t)W * H * 8);
+    a.add((size_t)W * H * 8);
+    out[0] = 16;               // device arrays: the two counts
+    out[1] = (long)a.total;    // imcom_wcs_pix_area with device arrays: counts and the ra / dec frame
+    out[2] = WCS_DESC_LEN;
+    out[3] = WCS_MAX_ORDER;
+    (void)n;
+    return IMCOM_OK;
+}
+
+int imcom_wcs_pix2world(imcom_ctx *ctx, const double *wcs, const void *tab, int tab_f64, int tab_n2, double tab_lo, double tab_hi, const double *pix, long n, int origin,
+                        double *world, long *nbad, int memspace)
+{
+    return wcs_list(ctx, "wcs_pix2world", 0, wcs, tab, tab_f64, tab_n2, tab_lo, tab_hi, pix, n, origin, world, nbad, memspace);
+}
+
+int imcom_wcs_world2pix(imcom_ctx *ctx, const double *wcs, const void *tab, int tab_f64, int tab_n2, double tab_lo, double tab_hi, const double *world, long n, int origin,
+                        double *pix, long *nbad, int memspace)
+{
+    return wcs_list(ctx, "wcs_world2pix", 1, wcs, tab, tab_f64, tab_n2, tab_lo, tab_hi, world, n, origin, pix, nbad, memspace);
+}
+
+int imcom_wcs_pix2pix(imcom_ctx *ctx, const double *from, const void *ftab, int ftab_f64, int ftab_n2, double ftab_lo, double ftab_hi, const double *to, const void *ttab,
+                      int ttab_f64, int ttab_n2, double ttab_lo, double ttab_hi, const double *points, const double *grid, long n, int origin, double nside, double pad,
+                      void *x, void *y, int out_f32, unsigned char *is_in_ref, long *counts, int memspace)
+{
+    const char *who = "wcs_pix2pix";
+    IMCOM_TRY(enter(ctx));
+    WcsDesc wf, wt;
+    IMCOM_TRY(wcs_descriptor(from, who, &wf));
+    IMCOM_TRY(wcs_descriptor(to, who, &wt));
+    IMCOM_REQUIRE((points != nullptr) != (grid != nullptr), "%s: either a point list or a grid", who);
+    IMCOM_REQUIRE(origin == 0 || origin == 1, "%s: origin %d", who, origin);
+    IMCOM_REQUIRE((x != nullptr) == (y != nullptr), "%s: x and y are given together", who);
+    if (grid) {
+        IMCOM_REQUIRE(grid[2] >= 0 && grid[5] >= 0 && grid[2] <= 0x7fffffff && grid[5] <= 0x7fffffff && grid[2] == std::floor(grid[2]) && grid[5] == std::floor(grid[5]),
+                      "%s: a grid of %g x %g points", who, grid[5], grid[2]);
+        n = (long)grid[2] * (long)grid[5];
+    }
+    IMCOM_REQUIRE(n >= 0 && n <= WCS_MAX_POINTS, "%s: %ld points (at most 2^40)", who, n);
+    IMCOM_REQUIRE(std::isfinite(nside) && std::isfinite(pad), "%s: nside = %g, pad = %g", who, nside, pad);
+    if (counts) counts[0] = counts[1] = 0;
+    if (n == 0) return IMCOM_OK;
+    const size_t el = out_f32 ? 4 : 8;
+    Stage st(ctx, memspace, who);
+    WsPlan plan;
+    plan.add(16);
+    st.plan(plan, {wcs_table_bytes(ftab, ftab_f64, ftab_n2), wcs_table_bytes(ttab, ttab_f64, ttab_n2), points ? (size_t)n * 16 : 0, x ? n * el : 0, y ? n * el : 0,
+                   is_in_ref ? (size_t)n : 0});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    unsigned long long *cnt;
+    IMCOM_TRY(ws_take(ctx, 2, &cnt, who));
+    WcsTab tf, tt;
+    IMCOM_TRY(wcs_table(st, ftab, ftab_f64, ftab_n2, ftab_lo, ftab_hi, who, &tf));
+    IMCOM_TRY(wcs_table(st, ttab, ttab_f64, ttab_n2, ttab_lo, ttab_hi, who, &tt));
+    const double *pts_d;
+    unsigned char *x_d, *y_d, *m_d;
+    IMCOM_TRY(st.in(points, points ? (size_t)n * 2 : 0, &pts_d));
+    IMCOM_TRY(st.out((unsigned char *)x, x ? n * el : 0, &x_d));
+    IMCOM_TRY(st.out((unsigned char *)y, y ? n * el : 0, &y_d));
+    IMCOM_TRY(st.out(is_in_ref, is_in_ref ? (size_t)n : 0, &m_d));
+    // M = R_to R_from^T: native vector of `to` = M (native vector of `from`)
+    double M[9];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            double s = 0.0;
+            for (int k = 0; k < 3; k++) s += wt.d[WCS_D_ROT + 3 * i + k] * wf.d[WCS_D_ROT + 3 * j + k];
+            M[3 * i + j] = s;
+        }
+    if (counts) IMCOM_HIP_CHECK(hipMemsetAsync(cnt, 0, 16, ctx->stream));
+    IMCOM_TRY(launch_wcs_pix2pix(ctx, wf, tf, wt, tt, M, pts_d, grid, n, origin, nside, pad, x_d, y_d, out_f32, m_d, counts ? cnt : nullptr));
+    if (x) IMCOM_TRY(st.back((unsigned char *)x, x_d, n * el));
+    if (y) IMCOM_TRY(st.back((unsigned char *)y, y_d, n * el));
+    if (is_in_ref) IMCOM_TRY(st.back(is_in_ref, m_d, (size_t)n));
+    if (counts) {
+        unsigned long long c[2];
+        IMCOM_HIP_CHECK(hipMemcpyAsync(c, cnt, 16, hipMemcpyDeviceToHost, ctx->stream));
+        IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        counts[0] = (long)c[0], counts[1] = (long)c[1];
+    }
+    return st.done();
+}
+
+int imcom_wcs_pix_area(imcom_ctx *ctx, const double *wcs, const void *tab, int tab_f64, int tab_n2, double tab_lo, double tab_hi, const double *xs, int W, const double *ys,
+                       int H, int op, double pad, double *area, int *rotated, int memspace)
+{
+    const char *who = "wcs_pix_area";
+    IMCOM_TRY(enter(ctx));
+    WcsDesc w;
+    IMCOM_TRY(wcs_descriptor(wcs, who, &w));
+    IMCOM_REQUIRE(xs && ys && area, "%s: null pointer", who);
+    IMCOM_REQUIRE(op >= 1 && pad > 0 && W > 2 * op && H > 2 * op && (long)W * H <= 0x7fffffffL, "%s: a frame of %d x %d points with a margin of %d", who, H, W, op);
+    const size_t nf = (size_t)W * H, na = (size_t)(W - 2 * op) * (H - 2 * op);
+    Stage st(ctx, memspace, who);
+    WsPlan plan;
+    plan.add(16);
+    plan.add(nf * 8);
+    plan.add(nf * 8);
+    st.plan(plan, {wcs_table_bytes(tab, tab_f64, tab_n2), (size_t)W * 8, (size_t)H * 8, na * 8});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    unsigned long long *ext;
+    double *ra, *dec, *area_d;
+    const double *xs_d, *ys_d;
+    IMCOM_TRY(ws_take(ctx, 2, &ext, who));
+    IMCOM_TRY(ws_take(ctx, nf, &ra, who));
+    IMCOM_TRY(ws_take(ctx, nf, &dec, who));
+    WcsTab t;
+    IMCOM_TRY(wcs_table(st, tab, tab_f64, tab_n2, tab_lo, tab_hi, who, &t));
+    IMCOM_TRY(st.in(xs, (size_t)W, &xs_d));
+    IMCOM_TRY(st.in(ys, (size_t)H, &ys_d));
+    IMCOM_TRY(st.out(area, na, &area_d));
+    const unsigned long long init[2] = {~0ull, 0ull};
+    IMCOM_TRY(upload(ctx, ext, init, 2));
+    IMCOM_TRY(launch_wcs_area_frame(ctx, w, t, xs_d, W, ys_d, H, ra, dec, ext));
+    unsigned long long e[2];
+    IMCOM_HIP_CHECK(hipMemcpyAsync(e, ext, 16, hipMemcpyDeviceToHost, ctx->stream));
+    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    // wcsutil.py:740: too close to the prime meridian (a frame without a finite ra keeps its NaN)
+    const int rotate = e[0] <= e[1] && wcs_key_value(e[1]) - wcs_key_value(e[0]) > 45.0;
+    if (rotated) *rotated = rotate;
+    IMCOM_TRY(launch_wcs_area_finish(ctx, ra, dec, W, H, op, pad, rotate, area_d));
+    IMCOM_TRY(st.back(area, area_d, na));
+    return st.done();
+}
+
+}  // extern "C"

@@ -109,6 +109,13 @@ NULL_CTX_ENTRIES = {
     "objmask.hip": "imcom_mask_dilate",
     "quantiles.hip": "imcom_codehist",
     "i24.hip": "imcom_i24_decompress",
+    "chol_solve.hip": "imcom_solve_chol_resident_end",
+    "gemm_f64.hip": "imcom_ctx_mfma_probe",
+    "interp.hip": "imcom_d5512_getw",
+    "build_a.hip": "imcom_build_A",
+    "la_kernels.hip": "imcom_trapezoid_f32",
+    "starmom.hip": "imcom_star_moments",
+    "wcs.hip": "imcom_wcs_pix2world",
 }
 
 
@@ -141,3 +148,27 @@ def test_every_context_source_is_covered():
         if f.endswith(".hip") and re.search(r'^(extern "C" )?int imcom_\w+\(imcom_ctx \*', open(os.path.join(csrc, f)).read(), re.M):
             have.add(f)
     assert have == set(NULL_CTX_ENTRIES), have ^ set(NULL_CTX_ENTRIES)
+
+
+def test_launchers_header_declares_only_cross_file_calls():
+    """launchers.h's first sentence as an assertion: every function it declares is defined in exactly one .hip and called from at
+    least one other source file of csrc/ (what only its own file calls is static there and has no line in the header)."""
+    csrc = os.path.join(ROOT, "pyimcom_amd", "csrc")
+
+    def code(f):  # the file without its comments
+        txt = open(os.path.join(csrc, f)).read()
+        return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+
+    not_functions = {"int", "sizeof", "static_assert"}  # std::function<int(int)> and the like
+    header = code("launchers.h")
+    names = sorted(set(re.findall(r"\b([A-Za-z_]\w*)\s*\(", header)) - not_functions)
+    assert len(names) >= 40, names
+    sources = {f: code(f) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")) and f != "launchers.h"}
+    for name in names:
+        # a definition: the name at the start of a declarator on a line that does not end the statement, followed by a body
+        definition = re.compile(r"^[A-Za-z_][\w \t\*&:<>]*?\b%s\s*\([^;{}]*\)\s*(const\s*)?\{" % re.escape(name), re.M)
+        defined = [f for f, txt in sources.items() if f.endswith(".hip") and definition.search(txt)]
+        assert len(defined) == 1, f"{name}: defined in {defined}"
+        assert not re.search(r"^static\b[^;{}]*\b%s\s*\(" % re.escape(name), sources[defined[0]], re.M), f"{name} is static in {defined[0]}"
+        callers = [f for f, txt in sources.items() if f != defined[0] and re.search(r"\b%s\s*\(" % re.escape(name), txt)]
+        assert callers, f"{name} (launchers.h) is called only from {defined[0]}: make it static there"

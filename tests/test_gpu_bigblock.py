@@ -11,7 +11,7 @@ table sets, the spectra arena running out of rows, and windowed cross tables -- 
   grid cells can reach, a spectra arena of a few batches -- must give the block maps BIT FOR BIT: a table read from a slot
   that was evicted, not yet rewritten, or outside its computed window would show as NaN or as a different number;
 * the block in small explicit batches agrees to rounding (not bit for bit: the factorisation deals the K loop of launches with
-  fewer than 256 tiles to several workgroups, csrc/api.hip splitk_parts, so the summation order of the last block rows
+  fewer than 256 tiles to several workgroups, csrc/chol_solve.hip splitk_parts, so the summation order of the last block rows
   depends on the batch size);
 * a sample of stamps against the oracle's CholKernel on the device's own A and -B/2 (the builders are compared with the oracle
   at this stamp size in test_gpu_fullsize.py).

@@ -1,4 +1,4 @@
-"""The Cholesky repair of the paper4 shape alone (api.hip lambda_min_subspace):  [IMCOM_LMIN_DEBUG=1] python tools/bench_repair.py [batch] [reps] [check]
+"""The Cholesky repair of the paper4 shape alone (chol_solve.hip lambda_min_subspace):  [IMCOM_LMIN_DEBUG=1] python tools/bench_repair.py [batch] [reps] [check]
 One JSON line: ms per stamp of a whole run() and of the eigen_repair family; with `check` the smallest eigenvalue the run used (info = 1 stamps:
 shift = kappa + |w0| + 1e-16 read back through T is not possible, so the check is LAPACK's w[0] of two stamps' A against IMCOM_LMIN=eigh's path
 -- run the script twice, once per setting, and compare `T_digest`)."""
