@@ -960,6 +960,42 @@ int imcom_wcs_pix2pix(imcom_ctx *ctx, const double *from, const void *ftab, int 
 int imcom_wcs_pix_area(imcom_ctx *ctx, const double *wcs, const void *tab, int tab_f64, int tab_n2, double tab_lo, double tab_hi, const double *xs, int W, const double *ys,
                        int H, int op, double pad, double *area, int *rotated, int memspace);
 
+/* ---- a block's input-stamp pool from two WCSs (seam 17): InImage.partition_pixels coadd.py:329-358, InImage.extract_layers 394-404 and
+ * InStamp.__init__ 688-707, between the device WCS above and imcom_select_pixels.  Arrays marked (device) are device pointers, those marked
+ * (host) host pointers; there is no memspace argument.  pyimcom_amd/inpool.py is the caller.
+ *
+ *   imcom_partition_wcs  coadd.py:329-358 with the positions formed where they are used.  `from` (the input image) and `to` (the block) with
+ *                        their optional error tables are the arguments of imcom_wcs_pix2pix (descriptors (host), tables (device)).
+ *                        sp_arr [sp_res + 1] u16 (host) is the sparse axis of line 201 -- np.linspace(..., dtype=np.uint16) truncates, so the
+ *                        cells are not of one size -- and relevant [sp_res][sp_res] u8 (host) the relevant_matrix of 211-233.  The visited
+ *                        pixels are those of the relevant cells row-major, row-major inside a cell; cell (j, i) spans the columns
+ *                        sp_arr[i] .. sp_arr[i + 1] and the rows sp_arr[j] .. sp_arr[j + 1] (335-337).  A visit index is decoded to its pixel
+ *                        on the device from a prefix sum over the relevant cells; the pixel's position is that of imcom_wcs_pix2pix for the
+ *                        integer pixel, origin 0, bit for bit (338).  mask [nside][nside] u8 (device; 0 = masked; NULL = none) is the FRAME
+ *                        mask of 345; use_instamps, nst, n2, pix_lower, pix_upper, npixmax and the five outputs (device, zeroed by the caller)
+ *                        are those of imcom_partition_pixels, and a pixel is kept or dropped exactly as there (343-351; a NaN position is
+ *                        dropped).  *nvisited (may be NULL): the visited pixels.  IMCOM_ERR_ARG if a stamp would receive more than npixmax.
+ *   imcom_extract_layers 394-404: data [n_inframe][nstamps][max_count] f32 with data[f][s][k] = indata[f][y_idx[s][k]][x_idx[s][k]] for
+ *                        k < pix_count[s] and zero beyond, from indata [n_inframe][nside][nside] f32 and the y_idx, x_idx [nstamps][npixmax]
+ *                        u16, pix_count [nstamps] u32 of the partition (all device); every element of data is written.
+ *   imcom_pool_assemble  688-707 for all stamps at once: image m of n_img (in list order) has its pixels in x_src[m], y_src[m] (f64) and
+ *                        data_src[m] (f32, n_inframe planes frame_stride[m] elements apart) -- pointer lists (host) of device arrays --, the
+ *                        count[m][s] pixels of stamp s from element s xy_pitch[m] (x, y) and s data_pitch[m] (a plane of data); a pitch of 0
+ *                        says that the image's list is compact, stamp after stamp.  xy_pitch, data_pitch, frame_stride [n_img] long, expo_of
+ *                        [n_img] int and count [n_img][nstamps] u32 are host arrays; the entry forms the prefix sums.  Written (device): the
+ *                        pool of imcom_select_pixels -- x, y [npool] f64, data [n_inframe][npool] f32, expo [npool] i32 (= expo_of[m]; NULL:
+ *                        not wanted) -- with the stamps row-major, inside a stamp the images in list order and an image's pixels in its own
+ *                        order (698-707), and inst_off [nstamps + 1] i64.  npool must be the sum of count.  A segmented copy; no sort. */
+int imcom_partition_wcs(imcom_ctx *ctx, const double *from, const void *ftab, int ftab_f64, int ftab_n2, double ftab_lo, double ftab_hi, const double *to,
+                        const void *ttab, int ttab_f64, int ttab_n2, double ttab_lo, double ttab_hi, const unsigned short *sp_arr, const unsigned char *relevant,
+                        int sp_res, int nside, const unsigned char *mask, const unsigned char *use_instamps, int nst, int n2, double pix_lower, double pix_upper,
+                        int npixmax, unsigned short *y_idx, unsigned short *x_idx, double *y_val, double *x_val, unsigned int *pix_count, long *nvisited);
+int imcom_extract_layers(imcom_ctx *ctx, const float *indata, int n_inframe, int nside, const unsigned short *y_idx, const unsigned short *x_idx,
+                         const unsigned int *pix_count, int nstamps, int npixmax, int max_count, float *data);
+int imcom_pool_assemble(imcom_ctx *ctx, int n_img, int nstamps, int n_inframe, const void *const *x_src, const void *const *y_src, const void *const *data_src,
+                        const long *xy_pitch, const long *data_pitch, const long *frame_stride, const int *expo_of, const unsigned int *count, long npool, double *x,
+                        double *y, float *data, int *expo, long *inst_off);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,6 +200,10 @@ SIGNATURES = {
     "imcom_wcs_world2pix": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _l, _i, _vp, C.POINTER(_l), _i],
     "imcom_wcs_pix2pix": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _l, _i, _d, _d, _vp, _vp, _i, _vp, _vp, _i],
     "imcom_wcs_pix_area": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _i, _vp, _i, _i, _d, _vp, _ip, _i],
+    "imcom_partition_wcs": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp,
+                            C.POINTER(_l)],
+    "imcom_extract_layers": [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "imcom_pool_assemble": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

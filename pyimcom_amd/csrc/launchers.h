@@ -146,4 +146,11 @@ constexpr int PCG64_JUMPS = 128;
 constexpr long PCG64_MAX_COUNT = 1L << 36;  // most draws of one call
 int pcg64_jumps(imcom_ctx *ctx, uint64_t inc_lo, uint64_t inc_hi, const unsigned long long **jumps_d, const char *who);
 
+// wcs.hip: what every entry that takes packed descriptors does with them -- the refusals of a descriptor and of an error table's geometry, and
+// the rotation product M = R_to R_from^T (row-major, nine doubles) that wcs_pix2pix (wcs_core.h) takes
+struct WcsDesc;
+int wcs_descriptor(const double *d, const char *who, WcsDesc *out);
+int wcs_table_check(const void *tab, int f64, int n2, double lo, double hi, const char *who);
+void wcs_rotation_product(const WcsDesc &from, const WcsDesc &to, double *M);
+
 }  // namespace imcom

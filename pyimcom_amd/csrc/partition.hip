@@ -6,8 +6,14 @@
 // (j_st, i_st) = floor((pos - pix_lower) / n2).  The order inside every stamp is the visiting order, so this is a
 // STABLE partition by stamp: a stable least-significant-digit radix sort of (stamp key, visit index) pairs (own kernels
 // below: 6-bit digits, two passes for up to 4095 stamps), segment starts from the sorted keys, then a gather.  The WCS
-// evaluation that produces the positions stays on the host.
-#include "common.h"
+// evaluation that produces the positions stays on the host for imcom_partition_pixels; imcom_partition_wcs (the end of the file) forms the
+// positions from two WCS descriptors where they are used, and imcom_extract_layers / imcom_pool_assemble carry the result into the pool that
+// the Block seam reads.
+#include <vector>
+
+#include "launchers.h"
+#include "partition_core.h"
+#include "wcs_core.h"
 
 namespace imcom {
 
@@ -132,19 +138,26 @@ __device__ inline double py_floordiv(double a, double b)
     return fl;
 }
 
+// The stamp key of a pixel at (x, y) of the block (coadd.py:343-351): nst * nst (dropped: sorts behind every stamp) outside (lo, hi) -- NaN
+// fails the strict comparisons --, masked, or in a stamp the block does not use.
+__device__ inline unsigned int partition_key(double x, double y, bool unmasked, const unsigned char *__restrict__ use, int nst, double n2, double lo,
+                                             double hi)
+{
+    unsigned int key = (unsigned int)(nst * nst);
+    if (lo < x && x < hi && lo < y && y < hi && unmasked) {
+        const int ist = (int)py_floordiv(x - lo, n2), jst = (int)py_floordiv(y - lo, n2);
+        if (ist >= 0 && ist < nst && jst >= 0 && jst < nst && use[jst * nst + ist]) key = (unsigned int)(jst * nst + ist);
+    }
+    return key;
+}
+
 __global__ void partition_key_kernel(const double *__restrict__ ox, const double *__restrict__ oy,
                                      const unsigned char *__restrict__ mask, const unsigned char *__restrict__ use, int nst,
                                      double n2, double lo, double hi, long npix, unsigned int *__restrict__ keys)
 {
     const long p = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (p >= npix) return;
-    unsigned int key = (unsigned int)(nst * nst);  // dropped pixels sort behind every stamp
-    const double x = ox[p], y = oy[p];
-    if (lo < x && x < hi && lo < y && y < hi && (!mask || mask[p])) {
-        const int ist = (int)py_floordiv(x - lo, n2), jst = (int)py_floordiv(y - lo, n2);
-        if (ist >= 0 && ist < nst && jst >= 0 && jst < nst && use[jst * nst + ist]) key = (unsigned int)(jst * nst + ist);
-    }
-    keys[p] = key;
+    keys[p] = partition_key(ox[p], oy[p], !mask || mask[p], use, nst, n2, lo, hi);
 }
 
 // start[k] = first sorted position of key k (npix where absent); one thread per sorted position
@@ -190,6 +203,114 @@ __global__ void partition_gather_kernel(const unsigned int *__restrict__ keys, c
     x_idx[o] = ix[v];
     y_val[o] = oy[v];
     x_val[o] = ox[v];
+}
+
+
+// ---- the same partition with the positions formed from two WCSs (imcom_partition_wcs) -------------------------------------------------------
+// A visit index is decoded to its pixel by partition_core.h and the pixel's position in the block is wcs_core.h's wcs_pix2pix, origin 0, with
+// the NaN rule of wcs_pix2pix_kernel (wcs.hip): the same arithmetic on the same integer pixel, so the same bits as imcom_wcs_pix2pix returns.
+// The position is formed twice -- for the key of every visited pixel, and again for the pixels that are kept, where it is stored -- instead of
+// being parked in 16 bytes a visited pixel in between.
+struct PartWcs {
+    WcsDesc from, to;
+    WcsTab tf, tt;
+    double M[9];
+};
+
+struct PartVisit {
+    const unsigned int *start, *cell;  // partition_cells' lists
+    const unsigned short *sp_arr;
+    int ncell, sp_res;
+};
+
+__device__ __forceinline__ void partition_wcs_position(const PartWcs &w, int x, int y, double *xo, double *yo)
+{
+    double xf, yf;
+    if (!wcs_pix2pix(w.from, w.tf, w.to, w.tt, w.M, (double)x, (double)y, 0, &xf, &yf) || !(xf - xf == 0.0 && yf - yf == 0.0)) xf = NAN, yf = NAN;
+    *xo = xf, *yo = yf;
+}
+
+// mask: the frame mask [nside][nside] (null: none)
+__global__ __launch_bounds__(256) void partition_wcs_key_kernel(const PartWcs w, const PartVisit v, const unsigned char *__restrict__ mask, int nside,
+                                                                const unsigned char *__restrict__ use, int nst, double n2, double lo, double hi, long npix,
+                                                                unsigned int *__restrict__ keys)
+{
+    const long p = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    int x, y;
+    partition_decode(v.start, v.cell, v.ncell, v.sp_arr, v.sp_res, (unsigned int)p, &y, &x);
+    double xf, yf;
+    partition_wcs_position(w, x, y, &xf, &yf);
+    keys[p] = partition_key(xf, yf, !mask || mask[(long)y * nside + x], use, nst, n2, lo, hi);
+}
+
+__global__ __launch_bounds__(256) void partition_wcs_gather_kernel(const PartWcs w, const PartVisit vis, const unsigned int *__restrict__ keys,
+                                                                   const unsigned int *__restrict__ vals, const unsigned int *__restrict__ start, long npix,
+                                                                   int nkeys, int npixmax, unsigned short *__restrict__ y_idx, unsigned short *__restrict__ x_idx,
+                                                                   double *__restrict__ y_val, double *__restrict__ x_val)
+{
+    const long p = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const unsigned int k = keys[p];
+    if (k >= (unsigned int)nkeys) return;
+    const long slot = p - start[k];
+    if (slot >= npixmax) return;
+    int x, y;
+    partition_decode(vis.start, vis.cell, vis.ncell, vis.sp_arr, vis.sp_res, vals[p], &y, &x);
+    double xf, yf;
+    partition_wcs_position(w, x, y, &xf, &yf);
+    const long o = (long)k * npixmax + slot;
+    y_idx[o] = (unsigned short)y;
+    x_idx[o] = (unsigned short)x;
+    y_val[o] = yf;
+    x_val[o] = xf;
+}
+
+// InImage.extract_layers (coadd.py:394-404): data[f][s][k] = indata[f][y_idx[s][k]][x_idx[s][k]] for k < pix_count[s], zero beyond; one thread
+// per element of data [n_inframe][nstamps][max_count].
+__global__ __launch_bounds__(256) void extract_layers_kernel(const float *__restrict__ indata, int n_inframe, int nside, const unsigned short *__restrict__ y_idx,
+                                                             const unsigned short *__restrict__ x_idx, const unsigned int *__restrict__ count, int nstamps,
+                                                             int npixmax, int max_count, float *__restrict__ data)
+{
+    const long per = (long)nstamps * max_count, q = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (q >= per) return;
+    const int s = (int)(q / max_count), k = (int)(q - (long)s * max_count);
+    const bool on = k < npixmax && (unsigned int)k < count[s];
+    long at = 0;
+    if (on) {
+        const int y = y_idx[(long)s * npixmax + k], x = x_idx[(long)s * npixmax + k];
+        at = y < nside && x < nside ? (long)y * nside + x : -1;
+    }
+    for (int f = 0; f < n_inframe; f++) data[f * per + q] = on && at >= 0 ? indata[(long)f * nside * nside + at] : 0.0f;
+}
+
+// InStamp.__init__ (coadd.py:688-707) for every stamp of a block: workgroup (s, m) copies the count[m][s] pixels of image m in stamp s from
+// the image's lists (at src_xy / src_d elements from their starts) to dst[m][s] of the pool.  One owner per pool element; no sort.
+struct PoolTables {
+    const unsigned long long *xp, *yp, *dp;  // [n_img] device addresses: x, y float64, data float32 [n_inframe] frame_stride apart
+    const long *frame_stride;                // [n_img]
+    const unsigned int *count;               // [n_img][nstamps]
+    const long *src_xy, *src_d, *dst;        // [n_img][nstamps]
+    const int *expo_of;                      // [n_img]
+};
+
+__global__ __launch_bounds__(128) void pool_assemble_kernel(const PoolTables t, int nstamps, int n_inframe, long npool, double *__restrict__ x,
+                                                            double *__restrict__ y, float *__restrict__ data, int *__restrict__ expo)
+{
+    const int s = blockIdx.x, m = blockIdx.y;
+    const long e = (long)m * nstamps + s;
+    const unsigned int n = t.count[e];
+    if (n == 0) return;
+    const double *sx = (const double *)t.xp[m] + t.src_xy[e], *sy = (const double *)t.yp[m] + t.src_xy[e];
+    const float *sd = (const float *)t.dp[m] + t.src_d[e];
+    const long fs = t.frame_stride[m], d0 = t.dst[e];
+    const int ex = t.expo_of[m];
+    for (unsigned int k = threadIdx.x; k < n; k += blockDim.x) {
+        x[d0 + k] = sx[k];
+        y[d0 + k] = sy[k];
+        if (expo) expo[d0 + k] = ex;
+        for (int f = 0; f < n_inframe; f++) data[f * npool + d0 + k] = sd[f * fs + k];
+    }
 }
 
 }  // namespace imcom
@@ -240,4 +361,166 @@ extern "C" int imcom_partition_pixels(imcom_ctx *ctx, long npix, const double *o
     IMCOM_HIP_CHECK(hipStreamSynchronize(st));
     IMCOM_REQUIRE(sth == 0, "a stamp receives %d pixels of this image, more than npixmax=%d (coadd.py:270-279)", sth, npixmax);
     return IMCOM_OK;
+}
+
+extern "C" int imcom_partition_wcs(imcom_ctx *ctx, const double *from, const void *ftab, int ftab_f64, int ftab_n2, double ftab_lo, double ftab_hi, const double *to,
+                                   const void *ttab, int ttab_f64, int ttab_n2, double ttab_lo, double ttab_hi, const unsigned short *sp_arr,
+                                   const unsigned char *relevant, int sp_res, int nside, const unsigned char *mask, const unsigned char *use_instamps, int nst, int n2,
+                                   double pix_lower, double pix_upper, int npixmax, unsigned short *y_idx, unsigned short *x_idx, double *y_val, double *x_val,
+                                   unsigned int *pix_count, long *nvisited)
+{
+    const char *who = "partition_wcs";
+    IMCOM_TRY(enter(ctx));
+    PartWcs w;
+    IMCOM_TRY(wcs_descriptor(from, who, &w.from));
+    IMCOM_TRY(wcs_descriptor(to, who, &w.to));
+    IMCOM_TRY(wcs_table_check(ftab, ftab_f64, ftab_n2, ftab_lo, ftab_hi, who));
+    IMCOM_TRY(wcs_table_check(ttab, ttab_f64, ttab_n2, ttab_lo, ttab_hi, who));
+    w.tf = ftab ? WcsTab{ftab, ftab_f64 ? 1 : 0, ftab_n2, ftab_lo, ftab_hi} : WcsTab{nullptr, 0, 0, 0.0, 0.0};
+    w.tt = ttab ? WcsTab{ttab, ttab_f64 ? 1 : 0, ttab_n2, ttab_lo, ttab_hi} : WcsTab{nullptr, 0, 0, 0.0, 0.0};
+    wcs_rotation_product(w.from, w.to, w.M);
+    IMCOM_REQUIRE(sp_res >= 1 && sp_res <= 4096 && nside >= 1 && nside <= 65535 && nst >= 1 && nst <= 2048 && n2 >= 1 && npixmax >= 1, "%s: bad sizes", who);
+    IMCOM_REQUIRE(sp_arr && relevant && use_instamps && y_idx && x_idx && y_val && x_val && pix_count, "%s: null pointer", who);
+    for (int k = 0; k < sp_res; k++) IMCOM_REQUIRE(sp_arr[k] <= sp_arr[k + 1], "%s: sp_arr decreases at node %d", who, k + 1);
+    IMCOM_REQUIRE(sp_arr[sp_res] <= nside, "%s: sp_arr ends at %d, beyond the frame of %d pixels a side", who, (int)sp_arr[sp_res], nside);
+    std::vector<unsigned int> cstart((size_t)sp_res * sp_res + 1), cell((size_t)sp_res * sp_res);
+    const int ncell = partition_cells(sp_arr, relevant, sp_res, cstart.data(), cell.data());
+    const long npix = (long)cstart[ncell];
+    if (nvisited) *nvisited = npix;
+    const int nkeys = nst * nst;
+    hipStream_t st = ctx->stream;
+    int bits = 1;
+    while ((1L << bits) <= nkeys) bits++;  // keys 0 .. nkeys (nkeys = dropped)
+    const long nblk = (npix + RS_TILE - 1) / RS_TILE;
+    WsPlan plan;
+    for (int k = 0; k < 4; k++) plan.add((size_t)npix * 4 + 4);
+    plan.add((size_t)nblk * RS_BINS * 4 + 16);
+    plan.add((size_t)(nkeys + 1) * 4);
+    plan.add(4);
+    plan.add((size_t)(ncell + 1) * 4);
+    plan.add((size_t)(ncell + 1) * 4);
+    plan.add((size_t)(sp_res + 1) * 2);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    unsigned int *k0, *k1, *v0, *v1, *hist, *start, *cstart_d, *cell_d;
+    int *status;
+    unsigned short *sp_d;
+    IMCOM_TRY(ws_take(ctx, (size_t)npix + 1, &k0, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)npix + 1, &k1, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)npix + 1, &v0, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)npix + 1, &v1, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)nblk * RS_BINS + 4, &hist, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)nkeys + 1, &start, who));
+    IMCOM_TRY(ws_take(ctx, 1, &status, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)ncell + 1, &cstart_d, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)ncell + 1, &cell_d, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)sp_res + 1, &sp_d, who));
+    IMCOM_TRY(upload(ctx, cstart_d, cstart.data(), (size_t)ncell + 1));
+    IMCOM_TRY(upload(ctx, cell_d, cell.data(), (size_t)ncell));
+    IMCOM_TRY(upload(ctx, sp_d, sp_arr, (size_t)sp_res + 1));
+    const PartVisit vis = {cstart_d, cell_d, sp_d, ncell, sp_res};
+    unsigned int *ks = k0, *vs = v0;  // the sorted pairs
+    IMCOM_HIP_CHECK(hipMemsetAsync(start, 0xff, (size_t)(nkeys + 1) * 4, st));
+    IMCOM_HIP_CHECK(hipMemsetAsync(status, 0, 4, st));
+    const unsigned nb = (unsigned)((npix + 255) / 256);
+    if (npix > 0) {
+        hipLaunchKernelGGL(partition_wcs_key_kernel, dim3(nb), dim3(256), 0, st, w, vis, mask, nside, use_instamps, nst, (double)n2, pix_lower, pix_upper, npix, k0);
+        IMCOM_TRY(check_launch("partition_wcs_key_kernel"));
+        IMCOM_TRY(radix_sort_pairs(ctx, k0, k1, v0, v1, npix, bits, hist, &ks, &vs));
+        hipLaunchKernelGGL(partition_bounds_kernel, dim3(nb), dim3(256), 0, st, ks, npix, nkeys, start);
+    }
+    hipLaunchKernelGGL(partition_count_kernel, dim3((nkeys + 255) / 256), dim3(256), 0, st, start, nkeys, npix, pix_count, npixmax, status);
+    if (npix > 0)
+        hipLaunchKernelGGL(partition_wcs_gather_kernel, dim3(nb), dim3(256), 0, st, w, vis, ks, vs, start, npix, nkeys, npixmax, y_idx, x_idx, y_val, x_val);
+    IMCOM_TRY(check_launch("partition_wcs kernels"));
+    int sth = 0;
+    IMCOM_HIP_CHECK(hipMemcpyAsync(&sth, status, 4, hipMemcpyDeviceToHost, st));
+    IMCOM_HIP_CHECK(hipStreamSynchronize(st));
+    IMCOM_REQUIRE(sth == 0, "a stamp receives %d pixels of this image, more than npixmax=%d (coadd.py:270-279)", sth, npixmax);
+    return IMCOM_OK;
+}
+
+extern "C" int imcom_extract_layers(imcom_ctx *ctx, const float *indata, int n_inframe, int nside, const unsigned short *y_idx, const unsigned short *x_idx,
+                                    const unsigned int *pix_count, int nstamps, int npixmax, int max_count, float *data)
+{
+    const char *who = "extract_layers";
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(n_inframe >= 1 && nside >= 1 && nside <= 65535 && nstamps >= 1 && npixmax >= 1 && max_count >= 0, "%s: bad sizes", who);
+    const long per = (long)nstamps * max_count;
+    if (per == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(indata && y_idx && x_idx && pix_count && data, "%s: null pointer", who);
+    hipLaunchKernelGGL(extract_layers_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, ctx->stream, indata, n_inframe, nside, y_idx, x_idx, pix_count, nstamps,
+                       npixmax, max_count, data);
+    return check_launch("extract_layers_kernel");
+}
+
+extern "C" int imcom_pool_assemble(imcom_ctx *ctx, int n_img, int nstamps, int n_inframe, const void *const *x_src, const void *const *y_src,
+                                   const void *const *data_src, const long *xy_pitch, const long *data_pitch, const long *frame_stride, const int *expo_of,
+                                   const unsigned int *count, long npool, double *x, double *y, float *data, int *expo, long *inst_off)
+{
+    const char *who = "pool_assemble";
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(n_img >= 0 && n_img <= 65535 && nstamps >= 1 && n_inframe >= 1 && npool >= 0, "%s: bad sizes", who);
+    IMCOM_REQUIRE(inst_off && (n_img == 0 || (x_src && y_src && data_src && xy_pitch && data_pitch && frame_stride && expo_of && count)), "%s: null pointer", who);
+    const size_t ne = (size_t)n_img * nstamps;
+    // the prefix sums: a stamp's pixels are the images' in list order (coadd.py:698-707), the stamps row-major
+    std::vector<long> off((size_t)nstamps + 1, 0), dst(ne), sxy(ne), sd(ne);
+    for (int s = 0; s < nstamps; s++) {
+        long run = off[s];
+        for (int m = 0; m < n_img; m++) {
+            dst[(size_t)m * nstamps + s] = run;
+            run += count[(size_t)m * nstamps + s];
+        }
+        off[s + 1] = run;
+    }
+    IMCOM_REQUIRE(off[nstamps] == npool, "%s: the counts sum to %ld pixels, the pool holds %ld", who, off[nstamps], npool);
+    std::vector<unsigned long long> ptrs((size_t)3 * n_img);
+    for (int m = 0; m < n_img; m++) {
+        IMCOM_REQUIRE(xy_pitch[m] >= 0 && data_pitch[m] >= 0 && frame_stride[m] >= 0, "%s: image %d has a negative pitch", who, m);
+        long run = 0;  // pitch 0: the image's lists are compact, stamp after stamp
+        bool any = false;
+        for (int s = 0; s < nstamps; s++) {
+            const size_t e = (size_t)m * nstamps + s;
+            IMCOM_REQUIRE((xy_pitch[m] == 0 || count[e] <= (unsigned long)xy_pitch[m]) && (data_pitch[m] == 0 || count[e] <= (unsigned long)data_pitch[m]),
+                          "%s: image %d has %u pixels in stamp %d, more than its pitch", who, m, count[e], s);
+            sxy[e] = xy_pitch[m] ? s * xy_pitch[m] : run;
+            sd[e] = data_pitch[m] ? s * data_pitch[m] : run;
+            run += count[e];
+            any = any || count[e];
+        }
+        IMCOM_REQUIRE(!any || (x_src[m] && y_src[m] && data_src[m]), "%s: image %d has pixels and a null list", who, m);
+        ptrs[m] = (unsigned long long)(uintptr_t)x_src[m];
+        ptrs[(size_t)n_img + m] = (unsigned long long)(uintptr_t)y_src[m];
+        ptrs[(size_t)2 * n_img + m] = (unsigned long long)(uintptr_t)data_src[m];
+    }
+    IMCOM_TRY(upload(ctx, inst_off, off.data(), (size_t)nstamps + 1));
+    if (npool == 0 || n_img == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(x && y && data, "%s: null pointer", who);  // (expo may be null: an image's own lists carry none)
+    WsPlan plan;
+    plan.add((size_t)3 * n_img * 8);
+    plan.add((size_t)n_img * 8);
+    plan.add((size_t)n_img * 4);
+    plan.add(ne * 4);
+    for (int k = 0; k < 3; k++) plan.add(ne * 8);
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    unsigned long long *ptrs_d;
+    long *fs_d, *sxy_d, *sd_d, *dst_d;
+    int *ex_d;
+    unsigned int *cnt_d;
+    IMCOM_TRY(ws_take(ctx, (size_t)3 * n_img, &ptrs_d, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)n_img, &fs_d, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)n_img, &ex_d, who));
+    IMCOM_TRY(ws_take(ctx, ne, &cnt_d, who));
+    IMCOM_TRY(ws_take(ctx, ne, &sxy_d, who));
+    IMCOM_TRY(ws_take(ctx, ne, &sd_d, who));
+    IMCOM_TRY(ws_take(ctx, ne, &dst_d, who));
+    IMCOM_TRY(upload(ctx, ptrs_d, ptrs.data(), (size_t)3 * n_img));
+    IMCOM_TRY(upload(ctx, fs_d, frame_stride, (size_t)n_img));
+    IMCOM_TRY(upload(ctx, ex_d, expo_of, (size_t)n_img));
+    IMCOM_TRY(upload(ctx, cnt_d, count, ne));
+    IMCOM_TRY(upload(ctx, sxy_d, sxy.data(), ne));
+    IMCOM_TRY(upload(ctx, sd_d, sd.data(), ne));
+    IMCOM_TRY(upload(ctx, dst_d, dst.data(), ne));
+    const PoolTables t = {ptrs_d, ptrs_d + n_img, ptrs_d + 2 * (size_t)n_img, fs_d, cnt_d, sxy_d, sd_d, dst_d, ex_d};
+    hipLaunchKernelGGL(pool_assemble_kernel, dim3((unsigned)nstamps, (unsigned)n_img), dim3(128), 0, ctx->stream, t, nstamps, n_inframe, npool, x, y, data, expo);
+    return check_launch("pool_assemble_kernel");
 }

@@ -239,15 +239,6 @@ static double wcs_key_value(unsigned long long k)
     return v;
 }
 
-}  // namespace imcom
-
-using namespace imcom;
-
-// ---------------------------------------------------------------------------------------------
-// C entries -- the positions that set_pair's full storage holds are formed by them
-
-namespace {
-
 // The refusals of a packed descriptor, and the descriptor as the kernels take it.
 int wcs_descriptor(const double *d, const char *who, WcsDesc *out)
 {
@@ -270,14 +261,42 @@ int wcs_descriptor(const double *d, const char *who, WcsDesc *out)
     return IMCOM_OK;
 }
 
+// The refusals of an error table's geometry (tab == nullptr: no table, nothing to refuse).
+int wcs_table_check(const void *tab, int f64, int n2, double lo, double hi, const char *who)
+{
+    if (!tab) return IMCOM_OK;
+    IMCOM_REQUIRE(n2 >= 4 && n2 <= 32768 && lo < 0.0 && hi > (double)(n2 - 3) && std::isfinite(lo) && std::isfinite(hi) && ((uintptr_t)tab & (f64 ? 7 : 3)) == 0,
+                  "%s: an error table of %d nodes an axis with end nodes %g, %g (needed: 4 .. 32768 nodes, first node < 0, last node > %d)", who, n2, lo, hi, n2 - 3);
+    return IMCOM_OK;
+}
+
+// M = R_to R_from^T, row-major: native vector of `to` = M (native vector of `from`).  Every caller of wcs_pix2pix forms its M here.
+void wcs_rotation_product(const WcsDesc &from, const WcsDesc &to, double *M)
+{
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            double s = 0.0;
+            for (int k = 0; k < 3; k++) s += to.d[WCS_D_ROT + 3 * i + k] * from.d[WCS_D_ROT + 3 * j + k];
+            M[3 * i + j] = s;
+        }
+}
+
+}  // namespace imcom
+
+using namespace imcom;
+
+// ---------------------------------------------------------------------------------------------
+// C entries -- the positions that set_pair's full storage holds are formed by them
+
+namespace {
+
 size_t wcs_table_bytes(const void *tab, int f64, int n2) { return tab ? (size_t)2 * n2 * n2 * (f64 ? 8 : 4) : 0; }
 
 int wcs_table(Stage &st, const void *tab, int f64, int n2, double lo, double hi, const char *who, WcsTab *out)
 {
     *out = WcsTab{nullptr, 0, 0, 0.0, 0.0};
     if (!tab) return IMCOM_OK;
-    IMCOM_REQUIRE(n2 >= 4 && n2 <= 32768 && lo < 0.0 && hi > (double)(n2 - 3) && std::isfinite(lo) && std::isfinite(hi) && ((uintptr_t)tab & (f64 ? 7 : 3)) == 0,
-                  "%s: an error table of %d nodes an axis with end nodes %g, %g (needed: 4 .. 32768 nodes, first node < 0, last node > %d)", who, n2, lo, hi, n2 - 3);
+    IMCOM_TRY(wcs_table_check(tab, f64, n2, lo, hi, who));
     const unsigned char *dev;
     IMCOM_TRY(st.in((const unsigned char *)tab, wcs_table_bytes(tab, f64, n2), &dev));
     *out = WcsTab{dev, f64 ? 1 : 0, n2, lo, hi};
@@ -388,14 +407,8 @@ int imcom_wcs_pix2pix(imcom_ctx *ctx, const double *from, const void *ftab, int 
     IMCOM_TRY(st.out((unsigned char *)x, x ? n * el : 0, &x_d));
     IMCOM_TRY(st.out((unsigned char *)y, y ? n * el : 0, &y_d));
     IMCOM_TRY(st.out(is_in_ref, is_in_ref ? (size_t)n : 0, &m_d));
-    // M = R_to R_from^T: native vector of `to` = M (native vector of `from`)
     double M[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            double s = 0.0;
-            for (int k = 0; k < 3; k++) s += wt.d[WCS_D_ROT + 3 * i + k] * wf.d[WCS_D_ROT + 3 * j + k];
-            M[3 * i + j] = s;
-        }
+    wcs_rotation_product(wf, wt, M);
     if (counts) IMCOM_HIP_CHECK(hipMemsetAsync(cnt, 0, 16, ctx->stream));
     IMCOM_TRY(launch_wcs_pix2pix(ctx, wf, tf, wt, tt, M, pts_d, grid, n, origin, nside, pad, x_d, y_d, out_f32, m_d, counts ? cnt : nullptr));
     if (x) IMCOM_TRY(st.back((unsigned char *)x, x_d, n * el));

@@ -10,6 +10,8 @@ images and partitioned their pixels (coadd.py:1560-1937); what is read from it:
                        uctarget, sigmamax, psf_circ, psf_norm, amp_penalty, outpsf, sigmatarget, use_filter,
                        outpsf_extra / sigmatarget_extra, postage_pad, iter_rtol / iter_max (Iterative), psfsplit, psf_interp
     blk.instamps[j][i] x_val, y_val, data, pix_count, pix_cumsum; psf_compute_point_pix on the even-even ones (coadd.py:682-714)
+    blk.instamp_pool   (optional) a select.InStampPool of the block that is on the device already (pyimcom_amd.inpool.PoolBuilder.attach);
+                       the instamps then need no x_val, y_val and data
     blk.inimages[e]    get_psf_pos(world, use_shortrange=True), outpix2world2inpix(xy)   (coadd.py:531-640)
     blk.outwcs         all_pix2world(xy, 0);   blk.n_inimage;   blk.pad_sides
     PSFGrp             the reference's class after PSFGrp.setup(): nsamp, oversamp, dscale, nfft, npixpsf (psfutil.py:568-613);
@@ -283,7 +285,11 @@ def coadd_output_stamps(blk, psfgrp, flat_penalty=None, batch=None, device="cuda
     for k in ("iter_rtol", "iter_max"):
         if hasattr(cfg, k):
             setattr(scfg, k, getattr(cfg, k))
-    pool = InStampPool([(st.x_val, st.y_val, st.data, st.pix_cumsum) for row in blk.instamps for st in row], scfg.n_inframe, device=device)
+    pool = getattr(blk, "instamp_pool", None)  # pyimcom_amd.inpool.PoolBuilder: the pool is on the device already (seam 17)
+    if pool is None:
+        pool = InStampPool([(st.x_val, st.y_val, st.data, st.pix_cumsum) for row in blk.instamps for st in row], scfg.n_inframe, device=device)
+    elif pool.n_inst != (int(cfg.n1P) + 2) ** 2 or pool.n_inframe != scfg.n_inframe:
+        raise ValueError(f"blk.instamp_pool holds {pool.n_inst} InStamps of {pool.n_inframe} layers; the block has {(int(cfg.n1P) + 2) ** 2} of {scfg.n_inframe}")
     count, expo, provider, ahead = input_psf_groups(blk, psfgrp, device, ctx, host_threads, positions, psfsplit)
     target = target_psfs(cfg, psfgrp, device, ctx)
     amp = getattr(cfg, "amp_penalty", None)

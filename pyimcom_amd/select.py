@@ -39,6 +39,28 @@ class InStampPool:
         self.data, self.expo = h2d(data, dev), h2d(expo, dev)
         self.inst_off_dev = h2d(self.inst_off, dev)
 
+    @classmethod
+    def from_device(cls, x, y, data, expo, inst_off, n_inframe):
+        """A pool that adopts tensors already on the device (pyimcom_amd.inpool.PoolBuilder): ``x``, ``y`` float64 [npool], ``data`` float32
+        [n_inframe, npool], ``expo`` int32 [npool], ``inst_off`` int64 [n_inst + 1].  Nothing is copied but the offsets, to the host."""
+        import torch
+
+        pool = cls.__new__(cls)
+        pool.n_inframe = int(n_inframe)
+        pool.npool = int(x.numel())
+        pool.device = x.device
+        if not (x.dtype == y.dtype == torch.float64 and data.dtype == torch.float32 and expo.dtype == torch.int32 and inst_off.dtype == torch.int64):
+            raise TypeError("InStampPool.from_device: x, y float64, data float32, expo int32, inst_off int64")
+        if not (tuple(y.shape) == tuple(expo.shape) == (pool.npool,) and tuple(data.shape) == (pool.n_inframe, pool.npool) and inst_off.dim() == 1):
+            raise ValueError("InStampPool.from_device: shapes do not describe one pool")
+        pool.x, pool.y, pool.data, pool.expo = x.contiguous(), y.contiguous(), data.contiguous(), expo.contiguous()
+        pool.inst_off_dev = inst_off.contiguous()
+        pool.inst_off = inst_off.cpu().numpy()
+        pool.n_inst = len(pool.inst_off) - 1
+        if pool.inst_off[0] != 0 or pool.inst_off[-1] != pool.npool:
+            raise ValueError("InStampPool.from_device: the offsets do not span the pool")
+        return pool
+
 
 def select_pixels(pool, inst_id, pivot_x, pivot_y, radius, ldn, ctx=None):
     """Selections of a batch of output stamps.  ``inst_id`` int [B,9] (-1 = absent), ``pivot_x/pivot_y`` float [B,9]
