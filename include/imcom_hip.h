@@ -996,6 +996,36 @@ int imcom_pool_assemble(imcom_ctx *ctx, int n_img, int nstamps, int n_inframe, c
                         const long *xy_pitch, const long *data_pitch, const long *frame_stride, const int *expo_of, const unsigned int *count, long npool, double *x,
                         double *y, float *data, int *expo, long *inst_off);
 
+/* ---- HEALPix star grids (seam 18): the pixels of the RING scheme (Gorski et al. 2005, ApJ 622, 759; nside = 2^res, res 0 .. 29, int64
+ * indices) inside a circle on the sky, their centres, and those centres through a WCS.  healpy is not needed; the arithmetic is that of the
+ * paper (section 4.1, eqs. 2-9, and the inverse) in float64 and has not been compared with healpy.  NEST order is not served.
+ *
+ *   imcom_healpix_pix2ang  healpy.pix2ang(2**res, ipix, nest=False, lonlat=lonlat) (analysis.py:964, truthcats.py:203, starcube_nonoise.py,
+ *                          dynrange.py): ipix [n] -> a, b [n] = (theta, phi) in radians, or with lonlat (lon, lat) = (degrees(phi),
+ *                          90 - degrees(theta)).  A pixel outside 0 .. 12 * 4^res - 1 is IMCOM_ERR_ARG (its outputs are NaN).
+ *   imcom_healpix_ang2pix  healpy.ang2pix(2**res, a, b, nest=False, lonlat=lonlat) (layer.py:724-725): the pixel that holds each point; phi is
+ *                          reduced into [0, 2 pi).  An angle that is not finite, or a colatitude outside [0, pi], is IMCOM_ERR_ARG (its pixel
+ *                          is -1).
+ *   imcom_healpix_cap      GridInject.make_sph_grid and generate_star_grid (layer.py:690-789), and healpy.ang2vec + query_disc + pix2ang +
+ *                          all_world2pix + the box selection of analysis.py:957-978, starcube_nonoise.py:145-175, dynrange.py:167-191 and
+ *                          truthcats.py:190-241.  Centre (ra, dec) and radius in radians.  mode 0: the reference's contiguous pixel range
+ *                          pmin .. pmax of layer.py:721-725 (a cap that holds a pole loses the pixels of the polar ring beyond it); mode 1:
+ *                          the full disc, what query_disc(inclusive=False) returns.  A pixel belongs when mu = sin(dec_p) sin(dec) +
+ *                          cos(dec_p) cos(dec) cos(ra - phi_p) >= cos(radius) in float64 (layer.py:732-733).  Outputs, each [capacity] and
+ *                          each NULL or not, ascending in the pixel: ipix; ra_pix, dec_pix in radians (phi and pi / 2 - theta); ra_deg,
+ *                          dec_deg in degrees -- lonlat 0: rad / (pi / 180) as layer.py:787-789 forms them, lonlat 1: healpy's lonlat values;
+ *                          with a WCS (`wcs` .. `origin`: the arguments of imcom_wcs_world2pix, NULL: none) x, y of (ra_deg, dec_deg), the bits
+ *                          imcom_wcs_world2pix gives; pa, the position angle of truthcats.py:229-241 in degrees in [0, 360).  box_n > 0 keeps
+ *                          only the pixels with box_bdpad <= rint(x) < box_n - box_bdpad and the same in y (analysis.py:967-973; a rint that
+ *                          does not fit int16 is outside).  *count (HOST, may be NULL): the pixels selected.  With every output NULL only
+ *                          the count is formed; otherwise capacity must equal the count (IMCOM_ERR_ARG if not): count, allocate, fill.
+ *                          At most 2^22 rings a call.  No atomics: the same bits for every run. */
+int imcom_healpix_pix2ang(imcom_ctx *ctx, int res, const long *ipix, long n, int lonlat, double *a, double *b, int memspace);
+int imcom_healpix_ang2pix(imcom_ctx *ctx, int res, const double *a, const double *b, long n, int lonlat, long *ipix, int memspace);
+int imcom_healpix_cap(imcom_ctx *ctx, int res, double ra, double dec, double radius, int mode, int lonlat, const double *wcs, const void *tab, int tab_f64, int tab_n2,
+                      double tab_lo, double tab_hi, int origin, int box_n, int box_bdpad, long capacity, long *ipix, double *ra_pix, double *dec_pix, double *ra_deg,
+                      double *dec_deg, double *x, double *y, double *pa, long *count, int memspace);
+
 #ifdef __cplusplus
 }
 #endif

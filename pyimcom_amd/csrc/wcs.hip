@@ -7,11 +7,13 @@
 // kernel arguments, so every coefficient is wave-uniform; the only gathers are the eight taps of an error-table look-up (four in each of its two
 // planes).
 // Counts are summed as integers inside a workgroup and added once a workgroup; there is no float atomic and no float sum across threads, so
-// the results are the same bits for every run and every chunking.  The C entries imcom_wcs_* end the file.
+// the results are the same bits for every run and every chunking.  The C entries imcom_wcs_* follow the kernels; the HEALPix star grids
+// (seam 18), which end in wcs_world2pix, and their entries imcom_healpix_* end the file.
 #include <algorithm>
 
 #include "launchers.h"
 #include "wcs_core.h"
+#include "healpix_core.h"
 
 namespace imcom {
 
@@ -462,6 +464,324 @@ int imcom_wcs_pix_area(imcom_ctx *ctx, const double *wcs, const void *tab, int t
     if (rotated) *rotated = rotate;
     IMCOM_TRY(launch_wcs_area_finish(ctx, ra, dec, W, H, op, pad, rotate, area_d));
     IMCOM_TRY(st.back(area, area_d, na));
+    return st.done();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// HEALPix star grids (seam 18): the pixels of the RING scheme inside a circle on the sky, their centres, and those centres through a WCS --
+// GridInject.make_sph_grid / generate_star_grid (src/pyimcom/layer.py:690-789), and healpy's query_disc + pix2ang + all_world2pix of
+// StarsAnal.__call__ (analysis.py:957-978), gen_starcube_nonoise (starcube_nonoise.py:145-175), gen_dynrange_data (dynrange.py:167-191) and
+// gen_truthcats (truthcats.py:190-241).  The per-pixel arithmetic is healpix_core.h's.
+//
+// The cap: one workgroup owns one ring of the range and strides that ring's phi window.  A first pass counts the ring's hits (a ballot and a
+// population count a wave, one LDS slot a wave), one workgroup scans the ring counts, and a second pass with the same traversal writes every
+// hit at (ring offset + rank in ring).  The output ascends in the pixel index; there is no atomic, so the bits do not depend on the run.
+
+namespace imcom {
+
+namespace {
+
+constexpr int HP_THREADS = 256;
+constexpr long HP_MAX_RINGS = 1L << 22;  // most rings of one cap (a workgroup a ring; the scan is one workgroup's)
+
+struct HpCapArgs {
+    int res, lonlat, origin, has_wcs, box_n, box_bdpad;
+    long ring0, plo, phi, capacity;  // the first ring; the pixel range, both ends included; the room of the outputs
+    double ra, ra_window, sd, cd, cosr, radius, theta0, s0;
+};
+
+struct HpCapOut {
+    long *ipix;
+    double *ra, *dec, *ra_deg, *dec_deg, *x, *y, *pa;
+};
+
+struct HpHit {
+    long p;
+    double phi, lon, lat, x, y;
+};
+
+// Whether index j of ring g belongs to the selection; h: the pixel, its centre in degrees and (with a WCS, when the box or the output needs
+// it) its position.
+template <bool FILL>
+__device__ __forceinline__ bool hp_cap_test(const HpCapArgs &a, const WcsDesc &w, const WcsTab &t, const HpRing &g, double theta, long j, HpHit *h)
+{
+    const long p = g.start + j;
+    if (p < a.plo || p > a.phi) return false;
+    const double phi = hp_ring_phi(g, j);
+    if (!(hp_cap_mu(a.sd, a.cd, a.ra, theta, phi) >= a.cosr)) return false;
+    h->p = p, h->phi = phi;
+    if (!FILL && a.box_n <= 0) return true;
+    hp_degrees(theta, phi, a.lonlat, &h->lon, &h->lat);
+    if (!a.has_wcs) return true;
+    wcs_world2pix(w, t, h->lon, h->lat, a.origin, &h->x, &h->y);
+    return a.box_n <= 0 || (hp_in_box(h->x, a.box_n, a.box_bdpad) && hp_in_box(h->y, a.box_n, a.box_bdpad));
+}
+
+// FILL false: counts[ring] = the ring's hits.  FILL true: the hits at offsets[ring] + rank in ring.
+template <bool FILL>
+__global__ __launch_bounds__(HP_THREADS) void hp_cap_kernel(const HpCapArgs a, const WcsDesc w, const WcsTab t, unsigned *__restrict__ counts,
+                                                           const long *__restrict__ offsets, const HpCapOut o)
+{
+    __shared__ unsigned wcnt[HP_THREADS / 64];
+    HpRing g;
+    hp_ring_info(a.res, a.ring0 + (long)blockIdx.x, &g);
+    double z, sth;
+    const double theta = hp_ring_theta(a.res, g.ring, &z, &sth);
+    int64_t first, count;
+    hp_ring_window(theta, sth, a.theta0, a.s0, a.radius, a.ra_window, g, &first, &count);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long base = FILL ? offsets[blockIdx.x] : 0;
+    unsigned total = 0;
+#pragma unroll 1
+    for (long k0 = 0; k0 < count; k0 += HP_THREADS) {  // (count is the workgroup's: every thread makes every trip)
+        const long k = k0 + threadIdx.x;
+        HpHit h;
+        const bool hit = k < count && hp_cap_test<FILL>(a, w, t, g, theta, hp_window_index(g, first, count, k), &h);
+        const unsigned long long mask = __ballot(hit);
+        if (lane == 0) wcnt[wave] = (unsigned)__popcll(mask);
+        __syncthreads();
+        unsigned before = 0, all = 0;
+        for (int q = 0; q < HP_THREADS / 64; q++) {
+            before += q < wave ? wcnt[q] : 0u;
+            all += wcnt[q];
+        }
+        if (FILL && hit) {
+            const long at = base + total + before + __popcll(mask & ((1ull << lane) - 1ull));
+            if (at < a.capacity) {
+                if (o.ipix) o.ipix[at] = h.p;
+                if (o.ra) o.ra[at] = h.phi;
+                if (o.dec) o.dec[at] = HP_HALFPI - theta;
+                if (o.ra_deg) o.ra_deg[at] = h.lon;
+                if (o.dec_deg) o.dec_deg[at] = h.lat;
+                if (o.x) o.x[at] = h.x, o.y[at] = h.y;
+                if (o.pa) {  // truthcats.py:229-241: the direction of north at +- 1 arcsec
+                    double xpp, ypp, xmm, ymm;
+                    wcs_world2pix(w, t, h.lon, h.lat + 1.0 / 3600.0, a.origin, &xpp, &ypp);
+                    wcs_world2pix(w, t, h.lon, h.lat - 1.0 / 3600.0, a.origin, &xmm, &ymm);
+                    o.pa[at] = hp_position_angle(xpp, ypp, xmm, ymm);
+                }
+            }
+        }
+        total += all;
+        __syncthreads();
+    }
+    if (!FILL && threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+// offsets [n + 1] = the exclusive prefix sums of counts [n] and their total: one workgroup, every thread a contiguous share.
+__global__ __launch_bounds__(HP_THREADS) void hp_ring_scan_kernel(const unsigned *__restrict__ counts, long n, long *__restrict__ offsets)
+{
+    __shared__ long part[HP_THREADS];
+    const long share = (n + HP_THREADS - 1) / HP_THREADS, lo = (long)threadIdx.x * share, hi = lo + share < n ? lo + share : n;
+    long s = 0;
+    for (long k = lo; k < hi; k++) s += counts[k];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long run = 0;
+        for (int q = 0; q < HP_THREADS; q++) {
+            const long c = part[q];
+            part[q] = run;
+            run += c;
+        }
+        offsets[n] = run;
+    }
+    __syncthreads();
+    s = part[threadIdx.x];
+    for (long k = lo; k < hi; k++) {
+        offsets[k] = s;
+        s += counts[k];
+    }
+}
+
+// ipix [n] -> (theta, phi) in radians or (lonlat) (lon, lat) in degrees; a pixel outside 0 .. npix - 1 gives NaN and is counted in bad[1].
+__global__ __launch_bounds__(WCS_THREADS) void hp_pix2ang_kernel(int res, const long *__restrict__ ipix, long n, int lonlat, double *__restrict__ a, double *__restrict__ b,
+                                                                unsigned long long *bad)
+{
+    unsigned nbad = 0;
+    const long p0 = (long)blockIdx.x * WCS_TILE + threadIdx.x, npix = hp_npix(res);
+#pragma unroll 1
+    for (int i = 0; i < WCS_ITEMS; i++) {
+        const long k = p0 + (long)i * WCS_THREADS;
+        if (k >= n) break;
+        const long p = ipix[k];
+        double theta = NAN, phi = NAN;
+        if (p >= 0 && p < npix) {
+            hp_pix2ang(res, p, &theta, &phi);
+            if (lonlat) hp_degrees(theta, phi, 1, &phi, &theta);  // (lon, lat) take the places of (phi, theta)
+        } else {
+            nbad++;
+        }
+        a[k] = lonlat ? phi : theta;
+        b[k] = lonlat ? theta : phi;
+    }
+    wcs_block_counts(0u, nbad, bad);
+}
+
+// (theta, phi) in radians, or (lonlat) (lon, lat) in degrees as healpy turns them (theta = pi / 2 - radians(lat), phi = radians(lon)), ->
+// ipix [n]; an angle that is not finite or a colatitude outside [0, pi] gives -1 and is counted in bad[1].
+__global__ __launch_bounds__(WCS_THREADS) void hp_ang2pix_kernel(int res, const double *__restrict__ a, const double *__restrict__ b, long n, int lonlat,
+                                                                long *__restrict__ ipix, unsigned long long *bad)
+{
+    unsigned nbad = 0;
+    const long p0 = (long)blockIdx.x * WCS_TILE + threadIdx.x;
+#pragma unroll 1
+    for (int i = 0; i < WCS_ITEMS; i++) {
+        const long k = p0 + (long)i * WCS_THREADS;
+        if (k >= n) break;
+        double theta = a[k], phi = b[k];
+        if (lonlat) {
+            HP_SEPARATE_ROUNDINGS
+            const double lat = b[k] * HP_DEG;
+            phi = a[k] * HP_DEG, theta = HP_HALFPI - lat;
+        }
+        long p = -1;
+        if (theta - theta == 0.0 && phi - phi == 0.0 && theta >= 0.0 && theta <= HP_PI) p = hp_ang2pix(res, theta, phi);
+        else nbad++;
+        ipix[k] = p;
+    }
+    wcs_block_counts(0u, nbad, bad);
+}
+
+}  // namespace
+
+}  // namespace imcom
+
+namespace {
+
+int healpix_list(imcom_ctx *ctx, const char *who, int inverse, int res, const void *in_a, const void *in_b, long n, int lonlat, void *out_a, void *out_b, int memspace)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(res >= 0 && res <= HP_MAX_RES && n >= 0 && n <= WCS_MAX_POINTS && (lonlat == 0 || lonlat == 1), "%s: res %d (0 .. %d), %ld points, lonlat %d", who, res,
+                  HP_MAX_RES, n, lonlat);
+    if (n == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(in_a && out_a && (inverse ? in_b != nullptr : out_b != nullptr), "%s: null pointer", who);
+    Stage st(ctx, memspace, who);
+    WsPlan plan;
+    plan.add(16);
+    st.plan(plan, {(size_t)n * 8, inverse ? (size_t)n * 8 : 0, (size_t)n * 8, inverse ? 0 : (size_t)n * 8});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    unsigned long long *counts;
+    IMCOM_TRY(ws_take(ctx, 2, &counts, who));
+    const double *ia, *ib;
+    double *oa, *ob;
+    IMCOM_TRY(st.in((const double *)in_a, (size_t)n, &ia));  // (eight bytes an element either way)
+    IMCOM_TRY(st.in((const double *)in_b, inverse ? (size_t)n : 0, &ib));
+    IMCOM_TRY(st.out((double *)out_a, (size_t)n, &oa));
+    IMCOM_TRY(st.out((double *)out_b, inverse ? 0 : (size_t)n, &ob));
+    IMCOM_HIP_CHECK(hipMemsetAsync(counts, 0, 16, ctx->stream));
+    {
+        ProfScope ps(ctx, "healpix");
+        if (inverse) hipLaunchKernelGGL(hp_ang2pix_kernel, dim3(wcs_blocks(n)), dim3(WCS_THREADS), 0, ctx->stream, res, ia, ib, n, lonlat, (long *)oa, counts);
+        else hipLaunchKernelGGL(hp_pix2ang_kernel, dim3(wcs_blocks(n)), dim3(WCS_THREADS), 0, ctx->stream, res, (const long *)ia, n, lonlat, oa, ob, counts);
+        IMCOM_TRY(check_launch(inverse ? "hp_ang2pix_kernel" : "hp_pix2ang_kernel"));
+    }
+    IMCOM_TRY(st.back((double *)out_a, oa, (size_t)n));
+    IMCOM_TRY(st.back((double *)out_b, ob, inverse ? 0 : (size_t)n));
+    unsigned long long c[2];
+    IMCOM_HIP_CHECK(hipMemcpyAsync(c, counts, 16, hipMemcpyDeviceToHost, ctx->stream));
+    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    IMCOM_REQUIRE(c[1] == 0, inverse ? "%s: %llu angles that are not finite or whose colatitude is outside [0, pi]" : "%s: %llu pixels outside 0 .. 12 * 4^res - 1", who, c[1]);
+    return IMCOM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int imcom_healpix_pix2ang(imcom_ctx *ctx, int res, const long *ipix, long n, int lonlat, double *a, double *b, int memspace)
+{
+    return healpix_list(ctx, "healpix_pix2ang", 0, res, ipix, nullptr, n, lonlat, a, b, memspace);
+}
+
+int imcom_healpix_ang2pix(imcom_ctx *ctx, int res, const double *a, const double *b, long n, int lonlat, long *ipix, int memspace)
+{
+    return healpix_list(ctx, "healpix_ang2pix", 1, res, a, b, n, lonlat, ipix, nullptr, memspace);
+}
+
+int imcom_healpix_cap(imcom_ctx *ctx, int res, double ra, double dec, double radius, int mode, int lonlat, const double *wcs, const void *tab, int tab_f64, int tab_n2,
+                      double tab_lo, double tab_hi, int origin, int box_n, int box_bdpad, long capacity, long *ipix, double *ra_pix, double *dec_pix, double *ra_deg,
+                      double *dec_deg, double *x, double *y, double *pa, long *count, int memspace)
+{
+    const char *who = "healpix_cap";
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(res >= 0 && res <= HP_MAX_RES && (mode == 0 || mode == 1) && (lonlat == 0 || lonlat == 1), "%s: res %d (0 .. %d), mode %d, lonlat %d", who, res,
+                  HP_MAX_RES, mode, lonlat);
+    IMCOM_REQUIRE(std::isfinite(ra) && std::fabs(dec) <= HP_HALFPI && radius >= 0.0 && radius <= HP_PI, "%s: centre (%g, %g) rad, radius %g rad", who, ra, dec, radius);
+    IMCOM_REQUIRE((x != nullptr) == (y != nullptr), "%s: x and y are given together", who);
+    IMCOM_REQUIRE(wcs || (!x && !pa && box_n <= 0), "%s: positions, the box and the position angle need a WCS", who);
+    IMCOM_REQUIRE(origin == 0 || origin == 1, "%s: origin %d", who, origin);
+    IMCOM_REQUIRE(box_n <= 0 || (box_bdpad >= 0 && 2L * box_bdpad < box_n), "%s: a box of %d pixels with a border of %d", who, box_n, box_bdpad);
+    const bool fill = ipix || ra_pix || dec_pix || ra_deg || dec_deg || x || pa;
+    IMCOM_REQUIRE(fill || count, "%s: nothing to return", who);
+    IMCOM_REQUIRE(!fill || capacity >= 0, "%s: room for %ld pixels", who, capacity);
+    HpCapArgs a = {};
+    WcsDesc w = {};
+    if (wcs) IMCOM_TRY(wcs_descriptor(wcs, who, &w));
+    a.res = res, a.lonlat = lonlat, a.origin = origin, a.has_wcs = wcs ? 1 : 0, a.box_n = box_n > 0 ? box_n : 0, a.box_bdpad = box_bdpad;
+    a.ra = ra, a.ra_window = hp_fmodulo(ra, HP_TWOPI), a.sd = std::sin(dec), a.cd = std::cos(dec), a.cosr = std::cos(radius), a.radius = radius;
+    a.theta0 = HP_HALFPI - dec, a.s0 = a.cd > 0.0 ? a.cd : 0.0, a.capacity = fill ? capacity : 0;
+    int64_t pmin, pmax;
+    hp_cap_range(res, ra, dec, radius, &pmin, &pmax);
+    HpRing g0, g1;
+    hp_ring_info(res, hp_pix2ring(res, pmin), &g0);
+    hp_ring_info(res, hp_pix2ring(res, pmax), &g1);
+    const long nrings = (long)(g1.ring - g0.ring + 1);
+    IMCOM_REQUIRE(nrings >= 1 && nrings <= HP_MAX_RINGS, "%s: the cap spans %ld rings (at most %ld)", who, nrings, HP_MAX_RINGS);
+    a.ring0 = g0.ring;
+    a.plo = mode ? g0.start : pmin, a.phi = mode ? g1.start + g1.len - 1 : pmax;  // the full disc takes whole rings
+    const size_t cap = fill ? (size_t)capacity : 0;
+    Stage st(ctx, memspace, who);
+    WsPlan plan;
+    plan.add((size_t)nrings * 4);
+    plan.add((size_t)(nrings + 1) * 8);
+    st.plan(plan, {wcs_table_bytes(wcs ? tab : nullptr, tab_f64, tab_n2), ipix ? cap * 8 : 0, ra_pix ? cap * 8 : 0, dec_pix ? cap * 8 : 0, ra_deg ? cap * 8 : 0,
+                   dec_deg ? cap * 8 : 0, x ? cap * 8 : 0, y ? cap * 8 : 0, pa ? cap * 8 : 0});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    unsigned *counts;
+    long *offsets;
+    IMCOM_TRY(ws_take(ctx, (size_t)nrings, &counts, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)nrings + 1, &offsets, who));
+    WcsTab t;
+    IMCOM_TRY(wcs_table(st, wcs ? tab : nullptr, tab_f64, tab_n2, tab_lo, tab_hi, who, &t));
+    HpCapOut o = {};
+    IMCOM_TRY(st.out(ipix, ipix ? cap : 0, &o.ipix));
+    IMCOM_TRY(st.out(ra_pix, ra_pix ? cap : 0, &o.ra));
+    IMCOM_TRY(st.out(dec_pix, dec_pix ? cap : 0, &o.dec));
+    IMCOM_TRY(st.out(ra_deg, ra_deg ? cap : 0, &o.ra_deg));
+    IMCOM_TRY(st.out(dec_deg, dec_deg ? cap : 0, &o.dec_deg));
+    IMCOM_TRY(st.out(x, x ? cap : 0, &o.x));
+    IMCOM_TRY(st.out(y, y ? cap : 0, &o.y));
+    IMCOM_TRY(st.out(pa, pa ? cap : 0, &o.pa));
+    long total = 0;
+    {
+        ProfScope ps(ctx, "healpix", 2);
+        hipLaunchKernelGGL(hp_cap_kernel<false>, dim3((unsigned)nrings), dim3(HP_THREADS), 0, ctx->stream, a, w, t, counts, (const long *)nullptr, HpCapOut{});
+        IMCOM_TRY(check_launch("hp_cap_kernel (count)"));
+        hipLaunchKernelGGL(hp_ring_scan_kernel, dim3(1), dim3(HP_THREADS), 0, ctx->stream, (const unsigned *)counts, nrings, offsets);
+        IMCOM_TRY(check_launch("hp_ring_scan_kernel"));
+    }
+    IMCOM_HIP_CHECK(hipMemcpyAsync(&total, offsets + nrings, 8, hipMemcpyDeviceToHost, ctx->stream));
+    IMCOM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (count) *count = total;
+    if (!fill) return IMCOM_OK;
+    IMCOM_REQUIRE(total == capacity, "%s: the selection holds %ld pixels and the outputs have room for %ld", who, total, capacity);
+    if (total == 0) return IMCOM_OK;
+    {
+        ProfScope ps(ctx, "healpix");
+        hipLaunchKernelGGL(hp_cap_kernel<true>, dim3((unsigned)nrings), dim3(HP_THREADS), 0, ctx->stream, a, w, t, (unsigned *)nullptr, (const long *)offsets, o);
+        IMCOM_TRY(check_launch("hp_cap_kernel (fill)"));
+    }
+    IMCOM_TRY(st.back(ipix, o.ipix, ipix ? cap : 0));
+    IMCOM_TRY(st.back(ra_pix, o.ra, ra_pix ? cap : 0));
+    IMCOM_TRY(st.back(dec_pix, o.dec, dec_pix ? cap : 0));
+    IMCOM_TRY(st.back(ra_deg, o.ra_deg, ra_deg ? cap : 0));
+    IMCOM_TRY(st.back(dec_deg, o.dec_deg, dec_deg ? cap : 0));
+    IMCOM_TRY(st.back(x, o.x, x ? cap : 0));
+    IMCOM_TRY(st.back(y, o.y, y ? cap : 0));
+    IMCOM_TRY(st.back(pa, o.pa, pa ? cap : 0));
     return st.done();
 }
 

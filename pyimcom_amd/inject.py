@@ -208,7 +208,8 @@ def star_image(xsca, ysca, nside, oversamp, cube=None, lpoly=None, psf=None, psf
 def make_image_from_grid(res, inpsf, idsca, obsdata, mywcs, nside_sca, inpsf_oversamp, star_grid=None):
     """``GridInject.make_image_from_grid`` (layer.py:792-854) with the reference's signature: the SCA image [nside_sca, nside_sca]
     (float64, host) of the unit-flux star grid at HEALPix resolution ``res``.  ``star_grid(res, mywcs)`` -> (ipix, xsca, ysca, ra, dec)
-    defaults to the reference's ``GridInject.generate_star_grid`` (HEALPix and the WCS stay on the host).  ``inpsf`` is
+    defaults to the reference's ``GridInject.generate_star_grid`` (HEALPix and the WCS on the host; it needs healpy) --
+    ``star_grid=pyimcom_amd.healpix.generate_star_grid`` forms the grid and its positions on the device.  ``inpsf`` is
     ``InImage.get_psf_pos``: when its ``InImage`` holds a Legendre cube (``anlsim`` / ``L2_2506``) the PSFs are formed on the device
     from the cube, a ``dc2_imsim`` PSF is used for all stars, and anything else is called once per star that reaches the chip."""
     if star_grid is None:

@@ -25,7 +25,7 @@ model (``from_pyimcom`` of type ``"GWCS"``: TypeError -- it is arbitrary Python)
 The error map: each point takes its own correction, table axes (y, x), which is what ``LocWCS.err_interp`` documents.  The reference's
 ``pos[::-1, :]`` (wcsutil.py:516, 589) reverses the order of the points instead of the two columns; that is not reproduced.
 
-What stays on the host: FITS / ASDF, fitting the SIP and the error map of a gwcs, the cap algebra of ``getfootprint``, HEALPix.  A numpy
+What stays on the host: FITS / ASDF, fitting the SIP and the error map of a gwcs, the cap algebra of ``getfootprint``.  (HEALPix: pyimcom_amd.healpix.)  A numpy
 input gives numpy results; a tensor on a device gives tensors on that device, with no host round trip."""
 
 import ctypes as C
