@@ -1026,6 +1026,35 @@ int imcom_healpix_cap(imcom_ctx *ctx, int res, double ra, double dec, double rad
                       double tab_lo, double tab_hi, int origin, int box_n, int box_bdpad, long capacity, long *ipix, double *ra_pix, double *dec_pix, double *ra_deg,
                       double *dec_deg, double *x, double *y, double *pa, long *count, int memspace);
 
+/* ---- the metadetection mosaic (seam 19): what MetaMosaic (src/pyimcom/meta/distortimage.py) does to its arrays before and between the
+ * calls of imcom_ginterp_resample.  Every pointer is DEVICE memory; there is no memspace argument and nothing waits for the device.  The
+ * mosaic is in_image [nlayer][ns][ns] (float32 or float64), in_fidelity and in_noise [ns][ns] float32 (dB) and in_mask [ns][ns] u8; ns <=
+ * 32768; in_image, in_fidelity and in_noise 16-byte aligned, the masks 4-byte aligned.  pyimcom_amd/metamosaic.py is the caller.
+ *
+ *   imcom_mosaic_paste     distortimage.py:191-207 for one block file, one launch: the window rows symin .. symax - 1, columns sxmin ..
+ *                          sxmax - 1 of the file's planes (by x bx pixels) go to the rows cy + symin .., columns cx + sxmin .. of the mosaic
+ *                          (146-170 give the six numbers; a window that leaves the file or the mosaic is IMCOM_ERR_ARG).  primary: nlayer
+ *                          planes layer_stride elements apart, rows row_stride elements apart, float32 or (prim_f64) float64, copied bit for
+ *                          bit.  fid, sig: the coded FIDELITY and SIGMA planes, rows fid_stride / sig_stride elements apart, of type 0 = uint8,
+ *                          1 = uint16, 2 = int16.  in_fidelity = float(code) * (float)fid_bels / (float)(-0.1) and in_noise = float(code) *
+ *                          (float)sig_bels / (float)0.1, each two correctly rounded float32 operations as numpy's 197-207 are (bels: what
+ *                          HDU_to_bels gave; NaN allowed).  in_mask = (in_fidelity == 0) on the window (210).  16-byte accesses along a row
+ *                          where source and destination agree in their offset within 16 bytes, element by element elsewhere.
+ *   imcom_mosaic_mask_cut  223-280 and 499-503: mask [n] |= map [n] < cut (mode 1), |= map > cut (mode 2), nothing (mode 0; map may be NULL),
+ *                          and |= extra [n] != 0 (extra NULL: none).  The float32 map value and cut are compared as doubles; NaN is false.
+ *   imcom_mosaic_caps      340-352: n circles at the pixel positions (x, y) with the radii r (float64 [n], pixels).  Circle j sets the pixels
+ *                          (ix, iy) of its box xmin = max(floor(x - r), 0) .. xmax = min(ceil(x + r) + 1, ns) (341-344; float64, clamped to
+ *                          [0, ns] before the conversion to an integer; the same in y) with hypot(ix - x, iy - y) < r.  A position or radius
+ *                          that is not finite sets nothing.  Three launches: boxes, their prefix sum, and the pixels of all boxes as one
+ *                          flat index space in chunks of 4096 strided over the grid -- one large circle is spread over the whole device and
+ *                          small ones share a wave.  The only writes are byte stores of 1: the result depends neither on the order of the
+ *                          objects nor on the launch.  Workspace: 24 bytes an object. */
+int imcom_mosaic_paste(imcom_ctx *ctx, const void *primary, int prim_f64, long layer_stride, long row_stride, int nlayer, int by, int bx, const void *fid,
+                       int fid_type, long fid_stride, double fid_bels, const void *sig, int sig_type, long sig_stride, double sig_bels, int symin, int symax,
+                       int sxmin, int sxmax, int cy, int cx, int ns, void *in_image, float *in_fidelity, float *in_noise, unsigned char *in_mask);
+int imcom_mosaic_mask_cut(imcom_ctx *ctx, unsigned char *mask, const float *map, long n, double cut, int mode, const unsigned char *extra);
+int imcom_mosaic_caps(imcom_ctx *ctx, const double *x, const double *y, const double *r, long n, int ns, unsigned char *mask);
+
 #ifdef __cplusplus
 }
 #endif

@@ -207,6 +207,9 @@ SIGNATURES = {
     "imcom_healpix_pix2ang": [_vp, _i, _vp, _l, _i, _vp, _vp, _i],
     "imcom_healpix_ang2pix": [_vp, _i, _vp, _vp, _l, _i, _vp, _i],
     "imcom_healpix_cap": [_vp, _i, _d, _d, _d, _i, _i, _vp, _vp, _i, _i, _d, _d, _i, _i, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_l), _i],
+    "imcom_mosaic_paste": [_vp, _vp, _i, _l, _l, _i, _i, _i, _vp, _i, _l, _d, _vp, _i, _l, _d, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "imcom_mosaic_mask_cut": [_vp, _vp, _vp, _l, _d, _i, _vp],
+    "imcom_mosaic_caps": [_vp, _vp, _vp, _vp, _l, _i, _vp],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

@@ -14,10 +14,14 @@
 // sweeps run on them in place (a column per lane, four rows per wave: the L entries a wave needs are uniform, scalar loads), and the
 // epilogue blends the corners into T [NN][16] (in the same LDS), forms U and Sigma on the stest points and, for the resampler, the
 // mask and the gather of every layer.  T never exists beyond its tile.
+//
+// The input side of the resampler -- the mosaic of MetaMosaic (reference src/pyimcom/meta/distortimage.py): the paste of the block files,
+// the mask cuts and the circles of mask_caps (seam 19) -- follows the resampler's entries and ends the file.
 #include <cmath>
 #include <vector>
 
 #include "launchers.h"
+#include "mosaic_core.h"
 
 namespace imcom {
 
@@ -615,4 +619,265 @@ extern "C" int imcom_ginterp_resample(imcom_ctx *ctx, int nlayer, int ny_in, int
     // UmaxSmax: a copy in either memory space (the kernel's maxima are bit patterns in the workspace)
     IMCOM_HIP_CHECK(hipMemcpyAsync(UmaxSmax, um, 16, st.host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
     return st.done();
+}
+
+// ------------------------------------------------------------------------------------------------
+// The mosaic that the resampler reads (seam 19; reference src/pyimcom/meta/distortimage.py): the input side of this file.  MetaMosaic's
+// constructor pastes the windows of up to nine block files into one square (146-207), its mask methods cut on the dB maps (223-280) and
+// rasterise circles (340-352).  The entries imcom_mosaic_paste, imcom_mosaic_mask_cut and imcom_mosaic_caps end the file; the index
+// maps, the dB arithmetic, the boxes and the predicate are mosaic_core.h's.  Every pointer of these entries is device memory.
+
+namespace {
+
+struct MoPaste {
+    MoWindow W;
+    int ns, nlayer, es;  // side of the mosaic; layers; bytes of a layer element (4 or 8)
+    const unsigned char *primary;
+    long layer_stride, row_stride;  // elements
+    const void *fid, *sig;          // the coded maps, [by][..] with the row strides below
+    int fid_type, sig_type;
+    long fid_stride, sig_stride;
+    float fid_bels, sig_bels;
+    unsigned char *image;
+    float *fidelity, *noise;
+    unsigned char *mask;
+};
+
+template <typename T>
+__device__ __forceinline__ void mo_copy_row(const unsigned char *src, unsigned char *dst, int w, int lane)
+{
+    int lead, nvec;
+    mo_row_split((uint64_t)dst, (uint64_t)src, w, (int)sizeof(T), &lead, &nvec);
+    constexpr int per = 16 / (int)sizeof(T);
+    const T *s = (const T *)src;
+    T *d = (T *)dst;
+    const uint4 *sv = (const uint4 *)(s + lead);
+    uint4 *dv = (uint4 *)(d + lead);
+    for (int k = lane; k < nvec; k += 64) dv[k] = sv[k];
+    const int tail = lead + nvec * per;  // the scalar edges: [0, lead) and [tail, w)
+    for (int k = lane; k < lead + (w - tail); k += 64) {
+        const int c = k < lead ? k : tail + (k - lead);
+        d[c] = s[c];
+    }
+}
+
+// One wave a row of the window, four rows a workgroup, the rows strided over gridDim.x; blockIdx.y: a layer, or (= nlayer) the two dB
+// maps and the mask.  Layers are moved as integers: bit for bit, NaN payloads included.
+__global__ __launch_bounds__(256) void mosaic_paste_kernel(MoPaste P)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, plane = blockIdx.y;
+    const int h = mo_rows(P.W), w = mo_cols(P.W);
+    for (int r = blockIdx.x * 4 + wave; r < h; r += gridDim.x * 4) {
+        const long d0 = mo_dst_offset(P.W, r, P.ns);
+        if (plane < P.nlayer) {
+            const unsigned char *src = P.primary + ((long)plane * P.layer_stride + mo_src_offset(P.W, r, P.row_stride)) * P.es;
+            unsigned char *dst = P.image + ((long)plane * P.ns * P.ns + d0) * P.es;
+            if (P.es == 4) mo_copy_row<uint32_t>(src, dst, w, lane);
+            else mo_copy_row<uint64_t>(src, dst, w, lane);
+            continue;
+        }
+        const long f0 = mo_src_offset(P.W, r, P.fid_stride), s0 = mo_src_offset(P.W, r, P.sig_stride);
+        float *fd = P.fidelity + d0, *nd = P.noise + d0;
+        unsigned char *md = P.mask + d0;
+        // the float32 rows of both maps share their offset within 16 bytes (the entry checks the bases), and there the mask's four bytes are aligned
+        int lead, nvec;
+        mo_row_split((uint64_t)fd, (uint64_t)fd, w, 4, &lead, &nvec);
+        for (int k = lane; k < nvec; k += 64) {
+            const int c = lead + 4 * k;
+            float f[4], n[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                f[j] = mo_db(mo_code_value(P.fid, P.fid_type, f0 + c + j), P.fid_bels, MO_FIDELITY_DIV);
+                n[j] = mo_db(mo_code_value(P.sig, P.sig_type, s0 + c + j), P.sig_bels, MO_NOISE_DIV);
+            }
+            *(float4 *)(fd + c) = make_float4(f[0], f[1], f[2], f[3]);
+            *(float4 *)(nd + c) = make_float4(n[0], n[1], n[2], n[3]);
+            *(uchar4 *)(md + c) = make_uchar4(f[0] == 0.0f, f[1] == 0.0f, f[2] == 0.0f, f[3] == 0.0f);
+        }
+        const int tail = lead + nvec * 4;
+        for (int k = lane; k < lead + (w - tail); k += 64) {
+            const int c = k < lead ? k : tail + (k - lead);
+            const float f = mo_db(mo_code_value(P.fid, P.fid_type, f0 + c), P.fid_bels, MO_FIDELITY_DIV);
+            fd[c] = f;
+            nd[c] = mo_db(mo_code_value(P.sig, P.sig_type, s0 + c), P.sig_bels, MO_NOISE_DIV);
+            md[c] = f == 0.0f;
+        }
+    }
+}
+
+// mask |= map < cut (mode 1) or map > cut (mode 2), and |= extra != 0.  The map's float32 value and the cut are compared as doubles: exact,
+// and a NaN compares false.  Four pixels a thread where n allows (the bases are 16-byte aligned), the last n % 4 one by one.
+__global__ __launch_bounds__(256) void mosaic_mask_cut_kernel(unsigned char *__restrict__ mask, const float *__restrict__ map, long n, double cut, int mode,
+                                                              const unsigned char *__restrict__ extra)
+{
+    const long n4 = n / 4, stride = (long)gridDim.x * 256;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < n4 + (n - 4 * n4); q += stride) {
+        if (q < n4) {
+            uchar4 m = ((const uchar4 *)mask)[q];
+            if (mode) {
+                const float4 v = ((const float4 *)map)[q];
+                if (mode == 1) m.x |= (double)v.x < cut, m.y |= (double)v.y < cut, m.z |= (double)v.z < cut, m.w |= (double)v.w < cut;
+                else m.x |= (double)v.x > cut, m.y |= (double)v.y > cut, m.z |= (double)v.z > cut, m.w |= (double)v.w > cut;
+            }
+            if (extra) {
+                const uchar4 e = ((const uchar4 *)extra)[q];
+                m.x |= e.x != 0, m.y |= e.y != 0, m.z |= e.z != 0, m.w |= e.w != 0;
+            }
+            ((uchar4 *)mask)[q] = m;
+        } else {
+            const long i = 4 * n4 + (q - n4);
+            unsigned char m = mask[i];
+            if (mode == 1) m |= (double)map[i] < cut;
+            if (mode == 2) m |= (double)map[i] > cut;
+            if (extra) m |= extra[i] != 0;
+            mask[i] = m;
+        }
+    }
+}
+
+// Circles.  The launch shape: the pixels of all boxes, box after box and row-major inside a box, are ONE flat index space; start [n + 1]
+// (int64) is its prefix sum.  A workgroup takes MO_CAPS_CHUNK consecutive flat indices at a time (the chunks strided over the grid) and a
+// thread every 256th of them, so a box as large as the mosaic is spread over thousands of workgroups, and boxes of a few pixels fill the
+// lanes of a wave one behind the other.  The only writes are byte stores of 1: no atomics, the same result for every order of the objects
+// and every grid.
+constexpr int MO_CAPS_CHUNK = 4096;
+
+__global__ __launch_bounds__(256) void mosaic_caps_box_kernel(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ r, long n, int ns,
+                                                              MoBox *__restrict__ box, long *__restrict__ start)
+{
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const MoBox b = mo_cap_box(x[i], y[i], r[i], ns);
+        box[i] = b;
+        start[i + 1] = mo_box_pixels(b);  // (the scan below turns the counts into offsets)
+    }
+}
+
+// One workgroup: start[i + 1] = sum of the counts up to and including object i, start[0] = 0.
+__global__ __launch_bounds__(256) void mosaic_caps_scan_kernel(long n, long *__restrict__ start)
+{
+    __shared__ long part[256];
+    __shared__ long carry;
+    const int t = threadIdx.x;
+    if (t == 0) carry = 0, start[0] = 0;
+    __syncthreads();
+    for (long base = 0; base < n; base += 256) {
+        const long i = base + t, v = i < n ? start[i + 1] : 0;
+        part[t] = v;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {
+            const long a = t >= d ? part[t - d] : 0;
+            __syncthreads();
+            part[t] += a;
+            __syncthreads();
+        }
+        if (i < n) start[i + 1] = carry + part[t];
+        __syncthreads();
+        if (t == 255) carry += part[255];
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void mosaic_caps_kernel(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ r, long n, int ns,
+                                                          const MoBox *__restrict__ box, const long *__restrict__ start, unsigned char *__restrict__ mask)
+{
+    const long total = start[n];
+    for (long c0 = (long)blockIdx.x * MO_CAPS_CHUNK; c0 < total; c0 += (long)gridDim.x * MO_CAPS_CHUNK) {
+        long p = c0 + threadIdx.x;
+        if (p >= total) continue;
+        // the object that holds p: the last i with start[i] <= p (objects with empty boxes are stepped over)
+        long lo = 0, hi = n;  // start[lo] <= p < start[hi]
+        while (hi - lo > 1) {
+            const long mid = (lo + hi) >> 1;
+            if (start[mid] <= p) lo = mid;
+            else hi = mid;
+        }
+        long obj = lo, end = start[obj + 1], first = start[obj];
+        MoBox b = box[obj];
+        double ox = x[obj], oy = y[obj], orad = r[obj];
+        const long stop = c0 + MO_CAPS_CHUNK < total ? c0 + MO_CAPS_CHUNK : total;
+        for (; p < stop; p += 256) {
+            if (p >= end) {
+                do {
+                    obj++;
+                    end = start[obj + 1];
+                } while (p >= end);  // (p < total = start[n]: obj stays below n)
+                first = start[obj];
+                b = box[obj];
+                ox = x[obj], oy = y[obj], orad = r[obj];
+            }
+            int ix, iy;
+            mo_box_pixel(b, p - first, &ix, &iy);
+            if (mo_cap_hit(ix, iy, ox, oy, orad)) mask[(long)iy * ns + ix] = 1;
+        }
+    }
+}
+
+constexpr int MO_MAX_SIDE = 32768;  // (a box holds fewer than 2^31 pixels)
+
+int mo_code_bytes(int type) { return type == 0 ? 1 : 2; }
+
+}  // namespace
+
+extern "C" int imcom_mosaic_paste(imcom_ctx *ctx, const void *primary, int prim_f64, long layer_stride, long row_stride, int nlayer, int by, int bx,
+                                  const void *fid, int fid_type, long fid_stride, double fid_bels, const void *sig, int sig_type, long sig_stride,
+                                  double sig_bels, int symin, int symax, int sxmin, int sxmax, int cy, int cx, int ns, void *in_image, float *in_fidelity,
+                                  float *in_noise, unsigned char *in_mask)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(primary && fid && sig && in_image && in_fidelity && in_noise && in_mask && (prim_f64 == 0 || prim_f64 == 1), "mosaic_paste: bad arguments");
+    IMCOM_REQUIRE(nlayer >= 1 && nlayer <= 1024 && by >= 1 && bx >= 1 && ns >= 1 && ns <= MO_MAX_SIDE && by <= MO_MAX_SIDE && bx <= MO_MAX_SIDE,
+                  "mosaic_paste: %d layers, a block file of %d x %d, a mosaic of side %d", nlayer, by, bx, ns);
+    IMCOM_REQUIRE(fid_type >= 0 && fid_type <= 2 && sig_type >= 0 && sig_type <= 2, "mosaic_paste: code types %d, %d (0 uint8, 1 uint16, 2 int16)", fid_type, sig_type);
+    IMCOM_REQUIRE(row_stride >= bx && layer_stride >= 0 && fid_stride >= bx && sig_stride >= bx, "mosaic_paste: a row stride below the %d columns of the block file", bx);
+    MoPaste P;
+    P.W = MoWindow{symin, symax, sxmin, sxmax, cy, cx};
+    IMCOM_REQUIRE(mo_window_ok(P.W, by, bx, ns), "mosaic_paste: the window [%d:%d, %d:%d] + (%d, %d) leaves the block file (%d x %d) or the mosaic (%d)", symin, symax,
+                  sxmin, sxmax, cy, cx, by, bx, ns);
+    const int es = prim_f64 ? 8 : 4;
+    IMCOM_REQUIRE((uintptr_t)primary % es == 0 && (uintptr_t)in_image % 16 == 0 && (uintptr_t)in_fidelity % 16 == 0 && (uintptr_t)in_noise % 16 == 0 &&
+                      (uintptr_t)in_mask % 4 == 0 && (uintptr_t)fid % mo_code_bytes(fid_type) == 0 && (uintptr_t)sig % mo_code_bytes(sig_type) == 0,
+                  "mosaic_paste: a misaligned array");
+    const int h = mo_rows(P.W), w = mo_cols(P.W);
+    if (h == 0 || w == 0) return IMCOM_OK;
+    P.ns = ns; P.nlayer = nlayer; P.es = es;
+    P.primary = (const unsigned char *)primary; P.layer_stride = layer_stride; P.row_stride = row_stride;
+    P.fid = fid; P.sig = sig; P.fid_type = fid_type; P.sig_type = sig_type; P.fid_stride = fid_stride; P.sig_stride = sig_stride;
+    P.fid_bels = (float)fid_bels; P.sig_bels = (float)sig_bels;
+    P.image = (unsigned char *)in_image; P.fidelity = in_fidelity; P.noise = in_noise; P.mask = in_mask;
+    ProfScope ps(ctx, "mosaic");
+    hipLaunchKernelGGL(mosaic_paste_kernel, dim3(std::min((h + 3) / 4, 2048), nlayer + 1), dim3(256), 0, ctx->stream, P);
+    return check_launch("mosaic_paste_kernel");
+}
+
+extern "C" int imcom_mosaic_mask_cut(imcom_ctx *ctx, unsigned char *mask, const float *map, long n, double cut, int mode, const unsigned char *extra)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(mask && n >= 0 && mode >= 0 && mode <= 2 && (mode == 0 || map) && (mode != 0 || extra), "mosaic_mask_cut: bad arguments");
+    IMCOM_REQUIRE((uintptr_t)mask % 4 == 0 && (uintptr_t)map % 16 == 0 && (uintptr_t)extra % 4 == 0, "mosaic_mask_cut: a misaligned array");
+    if (n == 0) return IMCOM_OK;
+    ProfScope ps(ctx, "mosaic");
+    hipLaunchKernelGGL(mosaic_mask_cut_kernel, dim3((unsigned)std::min((n / 4 + 3 + 255) / 256, 4096L)), dim3(256), 0, ctx->stream, mask, map, n, cut, mode, extra);
+    return check_launch("mosaic_mask_cut_kernel");
+}
+
+extern "C" int imcom_mosaic_caps(imcom_ctx *ctx, const double *x, const double *y, const double *r, long n, int ns, unsigned char *mask)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(n >= 0 && n < (1L << 31) && ns >= 1 && ns <= MO_MAX_SIDE && mask && (n == 0 || (x && y && r)), "mosaic_caps: bad arguments");
+    if (n == 0) return IMCOM_OK;
+    WsPlan plan;
+    plan.add((size_t)n * sizeof(MoBox));
+    plan.add((size_t)(n + 1) * sizeof(long));
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    MoBox *box;
+    long *start;
+    IMCOM_TRY(ws_take(ctx, (size_t)n, &box, __func__));
+    IMCOM_TRY(ws_take(ctx, (size_t)n + 1, &start, __func__));
+    ProfScope ps(ctx, "mosaic", 3);
+    hipLaunchKernelGGL(mosaic_caps_box_kernel, dim3((unsigned)std::min((n + 255) / 256, 2048L)), dim3(256), 0, ctx->stream, x, y, r, n, ns, box, start);
+    IMCOM_TRY(check_launch("mosaic_caps_box_kernel"));
+    hipLaunchKernelGGL(mosaic_caps_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, n, start);
+    IMCOM_TRY(check_launch("mosaic_caps_scan_kernel"));
+    hipLaunchKernelGGL(mosaic_caps_kernel, dim3(ctx->cu_count * 8), dim3(256), 0, ctx->stream, x, y, r, n, ns, box, start, mask);
+    return check_launch("mosaic_caps_kernel");
 }
