@@ -1055,6 +1055,50 @@ int imcom_mosaic_paste(imcom_ctx *ctx, const void *primary, int prim_f64, long l
 int imcom_mosaic_mask_cut(imcom_ctx *ctx, unsigned char *mask, const float *map, long n, double cut, int mode, const unsigned char *extra);
 int imcom_mosaic_caps(imcom_ctx *ctx, const double *x, const double *y, const double *r, long n, int ns, unsigned char *mask);
 
+/* Padding stamps shared between neighbouring blocks (reference src/pyimcom/analysis.py:394-537, OutImage._update_hdu_data; the loop of
+ * Mosaic.share_padding_stamps, 1429-1467, is the caller's): with pad_sides = "auto" a block coadds no padding stamps towards a neighbour,
+ * and "my" strip on that side is filled from the neighbour's interior afterwards.  direction: 0 left, 1 right (a range of columns),
+ * 2 bottom, 3 top (a range of rows).  With width = postage_pad * n2 and fk = fade_kernel my strip is 0 .. width + fk - 1 (left, bottom) or
+ * NsideP - width - fk .. NsideP - 1 (right, top), and the neighbour's is NsideP - 2 width .. NsideP - width + fk - 1 or width - fk ..
+ * 2 width - 1 (435-446).  Every entry refuses direction outside 0 .. 3, width < fk and 2 width > NsideP (IMCOM_ERR_ARG), reads the
+ * neighbour, writes only my strip, and refuses mine == theirs: the two blocks are distinct allocations.  All pointers are device memory
+ * except the two small tables, which are host memory and go through the pinned ring.
+ *
+ *   imcom_padshare_layers   435-450, PRIMARY: mine[strip] = mine[strip] * add_mode + theirs[strip] on nplanes (= n_out * nlayer) float32
+ *                           planes, rows `row` and planes `plane` elements apart on either side (a view of BlockMaps.out_map cropped by
+ *                           fk is updated in place).  The product by the bool is formed in float32 as numpy forms it: in replace mode
+ *                           (add_mode = 0) -0.0 of mine gives +0.0 and a value of mine that is not finite gives NaN.  One launch.
+ *   imcom_padshare_weights  453-488, INWEIGHT [n_out][n_mine | n_theirs][n1P][n1P] float32: for each of the npairs rows (my_idx, ur_idx) of
+ *                           pairs_host -- the first occurrences of an (obsid, sca) that both INDATA tables hold, 468-470 -- the strip of
+ *                           `pad` stamps is copied (never added; the strips are those above with n1P, pad, 0 for NsideP, width, fk).  A
+ *                           my_idx may appear once.  One launch; npairs = 0 is a no-op.
+ *   imcom_padshare_maps     498-537, the quality maps, all nmaps of them in one launch.  Both codes of a strip pixel are decoded as
+ *                           get_output_map decodes them (377-387): float32(pow(10.0, code / decode_coef)) with decode_coef the double
+ *                           1.0 / HDU_to_bels(hdu), and 0 for the code floor_code (IMCOM_PADSHARE_NO_FLOOR: for none -- whether line 387
+ *                           zeroes the floor depends on the numpy beside the reference, and the caller decides).  In add mode both are
+ *                           tapered as OutStamp.trapezoid tapers them (coadd.py:1269-1282, pad widths of 504-526; one product in
+ *                           double, rounded to float32).  mine * add_mode + theirs in float32 goes to sums ([n_out][strip], the strip
+ *                           row-major as numpy slices it; NULL in production) and, encoded as Block.compress_map encodes
+ *                           (coadd.py:2123-2130, see imcom_compress_map_f32) with the integer encode_coef, into my strip.
+ *                           Codes: [n_out][NsideP][NsideP] int16 or (is_unsigned) uint16. */
+#define IMCOM_PADSHARE_NO_FLOOR (1 << 20)
+typedef struct imcom_padshare_map {
+    void *mine;          /* my codes, updated in place */
+    const void *theirs;  /* the neighbour's codes */
+    double decode_coef;  /* 1.0 / HDU_to_bels */
+    float *sums;         /* NULL, or where the float32 sums before the encode go */
+    int floor_code;      /* the code that decodes to 0, or IMCOM_PADSHARE_NO_FLOOR */
+    int encode_coef;     /* int(comment.partition("*")[0]), analysis.py:530 */
+    int is_unsigned;
+    int reserved;
+} imcom_padshare_map;
+int imcom_padshare_layers(imcom_ctx *ctx, int direction, int add_mode, int nside_p, int width, int fk, long nplanes, float *mine, long mine_row,
+                          long mine_plane, const float *theirs, long theirs_row, long theirs_plane);
+int imcom_padshare_weights(imcom_ctx *ctx, int direction, int n_out, int n1P, int pad, int npairs, const int *pairs_host, float *mine, int n_mine,
+                           const float *theirs, int n_theirs);
+int imcom_padshare_maps(imcom_ctx *ctx, int direction, int add_mode, int nside_p, int width, int fk, int n_out, int nmaps,
+                        const imcom_padshare_map *maps_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,14 @@ class ImcomError(RuntimeError):
         self.status = status
 
 
+class PadshareMap(C.Structure):  # imcom_padshare_map
+    _fields_ = [("mine", C.c_void_p), ("theirs", C.c_void_p), ("decode_coef", C.c_double), ("sums", C.c_void_p), ("floor_code", C.c_int), ("encode_coef", C.c_int),
+                ("is_unsigned", C.c_int), ("reserved", C.c_int)]
+
+
+PADSHARE_NO_FLOOR = 1 << 20  # IMCOM_PADSHARE_NO_FLOOR
+
+
 class TableGeom(C.Structure):
     _fields_ = [("nsamp", C.c_int), ("nc", C.c_double), ("dscale", C.c_double), ("flat_penalty", C.c_double)]
 
@@ -210,6 +218,9 @@ SIGNATURES = {
     "imcom_mosaic_paste": [_vp, _vp, _i, _l, _l, _i, _i, _i, _vp, _i, _l, _d, _vp, _i, _l, _d, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "imcom_mosaic_mask_cut": [_vp, _vp, _vp, _l, _d, _i, _vp],
     "imcom_mosaic_caps": [_vp, _vp, _vp, _vp, _l, _i, _vp],
+    "imcom_padshare_layers": [_vp, _i, _i, _i, _i, _i, _l, _vp, _l, _l, _vp, _l, _l],
+    "imcom_padshare_weights": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i],
+    "imcom_padshare_maps": [_vp, _i, _i, _i, _i, _i, _i, _i, _vp],
 }
 _cdll = lib
 for _name, _args in SIGNATURES.items():

@@ -223,3 +223,160 @@ extern "C" int imcom_compress_map_f32(imcom_ctx *ctx, const float *map, long cou
                        is_unsigned ? 0.0f : -32768.0f, is_unsigned ? 65535.0f : 32767.0f, (short *)out);
     return check_launch("compress_map_kernel");
 }
+
+// ---- seam 20: padding stamps shared between neighbouring blocks (reference src/pyimcom/analysis.py:394-537) ----------------------------
+// OutImage._update_hdu_data for device-resident blocks: "my" strip towards the neighbour is updated from the neighbour's interior strip.
+// padshare_core.h holds the index ranges and the arithmetic; the kernels below only walk the strips.  Each reads the neighbour, reads
+// and writes my strip, and touches nothing else.
+#include "padshare_core.h"
+
+namespace imcom {
+
+static_assert(PS_NO_FLOOR == IMCOM_PADSHARE_NO_FLOOR, "the floor code that zeroes nothing");
+
+// Strip pixel t of a plane of side n: the position p along the strip axis, and the element offsets in my plane and the neighbour's.
+// (A strip has fewer than 2^31 pixels -- the entries check it -- so the one division a pixel is a 32-bit one.)
+__device__ __forceinline__ void padshare_pixel(int direction, const PsStrip &s, int n, unsigned t, long my_row, long ur_row, int *p, long *mo, long *uo)
+{
+    if (ps_along_x(direction)) {
+        const unsigned y = t / (unsigned)s.len;
+        *p = (int)(t - y * (unsigned)s.len);
+        *mo = y * my_row + s.my0 + *p;
+        *uo = y * ur_row + s.ur0 + *p;
+    } else {
+        *p = (int)(t / (unsigned)n);
+        const unsigned x = t - (unsigned)*p * (unsigned)n;
+        *mo = (s.my0 + *p) * my_row + x;
+        *uo = (s.ur0 + *p) * ur_row + x;
+    }
+}
+
+// 435-450: PRIMARY, plane blockIdx.y
+__global__ void padshare_layers_kernel(int direction, int add_mode, int n, int w, int fk, float *__restrict__ mine, long my_row, long my_plane,
+                                       const float *__restrict__ theirs, long ur_row, long ur_plane)
+{
+    const PsStrip s = ps_strip(direction, n, w, fk);
+    const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (unsigned)s.len * (unsigned)n) return;
+    int p;
+    long mo, uo;
+    padshare_pixel(direction, s, n, t, my_row, ur_row, &p, &mo, &uo);
+    float *m = mine + blockIdx.y * my_plane + mo;
+    *m = ps_combine(*m, theirs[blockIdx.y * ur_plane + uo], add_mode);
+}
+
+// 468-486: INWEIGHT [n_out][n_expo][n1P][n1P], pair blockIdx.y of (my_idx, ur_idx); a plain copy
+__global__ void padshare_weights_kernel(int direction, int n_out, int n1P, int pad, const int *__restrict__ pairs, float *__restrict__ mine, int n_mine,
+                                        const float *__restrict__ theirs, int n_theirs)
+{
+    const PsStrip s = ps_strip(direction, n1P, pad, 0);
+    const unsigned per = (unsigned)s.len * (unsigned)n1P;
+    const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= per * (unsigned)n_out) return;
+    const unsigned o = t / per;
+    int p;
+    long mo, uo;
+    padshare_pixel(direction, s, n1P, t - o * per, n1P, n1P, &p, &mo, &uo);
+    const long plane = (long)n1P * n1P;
+    const int my_idx = pairs[2 * blockIdx.y], ur_idx = pairs[2 * blockIdx.y + 1];
+    mine[((long)o * n_mine + my_idx) * plane + mo] = theirs[((long)o * n_theirs + ur_idx) * plane + uo];
+}
+
+// 498-537: the quality maps, map blockIdx.y / n_out, plane blockIdx.y % n_out: decode both codes, taper both sides in add mode, combine,
+// encode, store into my strip
+__global__ void padshare_maps_kernel(int direction, int add_mode, int n, int w, int fk, int n_out, const imcom_padshare_map *__restrict__ maps)
+{
+    const PsStrip s = ps_strip(direction, n, w, fk);
+    const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned per = (unsigned)s.len * (unsigned)n;
+    if (t >= per) return;
+    const imcom_padshare_map d = maps[blockIdx.y / (unsigned)n_out];
+    const unsigned o = blockIdx.y % (unsigned)n_out;
+    int p;
+    long mo, uo;
+    padshare_pixel(direction, s, n, t, n, n, &p, &mo, &uo);
+    uint16_t *m = (uint16_t *)d.mine + (long)o * n * n + mo;
+    float mv = ps_decode(ps_code(*m, d.is_unsigned), d.decode_coef, d.floor_code);
+    float uv = ps_decode(ps_code(((const uint16_t *)d.theirs)[(long)o * n * n + uo], d.is_unsigned), d.decode_coef, d.floor_code);
+    if (add_mode) {
+        mv = ps_taper(mv, ps_taper_mine(direction, p, w, fk), fk);
+        uv = ps_taper(uv, ps_taper_theirs(direction, p, w, fk), fk);
+    }
+    const float sum = ps_combine(mv, uv, add_mode);
+    if (d.sums) d.sums[(long)o * per + t] = sum;
+    *m = ps_encode(sum, (float)d.encode_coef, d.is_unsigned);
+}
+
+}  // namespace imcom
+
+extern "C" int imcom_padshare_layers(imcom_ctx *ctx, int direction, int add_mode, int nside_p, int width, int fk, long nplanes, float *mine,
+                                     long mine_row, long mine_plane, const float *theirs, long theirs_row, long theirs_plane)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(ps_shape_ok(direction, nside_p, width, fk), "direction %d, NsideP %d, width %d, fade kernel %d: not a padding strip (0 <= direction <= 3, "
+                  "fk <= width, 2 width <= NsideP)", direction, nside_p, width, fk);
+    IMCOM_REQUIRE(mine && theirs && nplanes >= 0 && nplanes <= 65535 && mine_row >= nside_p && theirs_row >= nside_p &&
+                  mine_plane >= (nside_p - 1) * mine_row + nside_p && theirs_plane >= (nside_p - 1) * theirs_row + nside_p, "bad arguments");
+    IMCOM_REQUIRE(mine != theirs, "a block does not share padding stamps with itself");
+    const long tot = (long)(width + fk) * nside_p;
+    IMCOM_REQUIRE(tot < (1L << 31), "a strip of %ld pixels", tot);
+    if (tot == 0 || nplanes == 0) return IMCOM_OK;
+    ProfScope ps(ctx, "padshare");
+    hipLaunchKernelGGL(padshare_layers_kernel, dim3((unsigned)((tot + 255) / 256), (unsigned)nplanes), dim3(256), 0, ctx->stream, direction, add_mode ? 1 : 0,
+                       nside_p, width, fk, mine, mine_row, mine_plane, theirs, theirs_row, theirs_plane);
+    return check_launch("padshare_layers_kernel");
+}
+
+extern "C" int imcom_padshare_weights(imcom_ctx *ctx, int direction, int n_out, int n1P, int pad, int npairs, const int *pairs_host, float *mine,
+                                      int n_mine, const float *theirs, int n_theirs)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(ps_shape_ok(direction, n1P, pad, 0), "direction %d, n1P %d, postage_pad %d: not a padding strip (0 <= direction <= 3, 2 pad <= n1P)",
+                  direction, n1P, pad);
+    IMCOM_REQUIRE(npairs >= 0 && npairs <= 65535 && n_out >= 0 && n_mine >= 0 && n_theirs >= 0, "bad arguments");
+    if (npairs == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(pairs_host && mine && theirs, "bad arguments");
+    IMCOM_REQUIRE(mine != theirs, "a block does not share padding stamps with itself");
+    for (int k = 0; k < npairs; k++) {
+        IMCOM_REQUIRE(pairs_host[2 * k] >= 0 && pairs_host[2 * k] < n_mine && pairs_host[2 * k + 1] >= 0 && pairs_host[2 * k + 1] < n_theirs,
+                      "pair %d (%d, %d) outside the %d and %d exposures", k, pairs_host[2 * k], pairs_host[2 * k + 1], n_mine, n_theirs);
+        for (int j = 0; j < k; j++) IMCOM_REQUIRE(pairs_host[2 * j] != pairs_host[2 * k], "exposure %d of mine is written twice", pairs_host[2 * k]);
+    }
+    const long tot = (long)pad * n1P * n_out;
+    IMCOM_REQUIRE(tot < (1L << 31), "strips of %ld pixels", tot);
+    if (tot == 0) return IMCOM_OK;
+    IMCOM_TRY(ws_reserve(ctx, (size_t)npairs * 8 + 1024));
+    int *pd;
+    IMCOM_TRY(ws_take(ctx, (size_t)npairs * 2, &pd, "imcom_padshare_weights"));
+    IMCOM_TRY(upload(ctx, pd, pairs_host, (size_t)npairs * 2));
+    ProfScope ps(ctx, "padshare");
+    hipLaunchKernelGGL(padshare_weights_kernel, dim3((unsigned)((tot + 255) / 256), (unsigned)npairs), dim3(256), 0, ctx->stream, direction, n_out, n1P, pad,
+                       pd, mine, n_mine, theirs, n_theirs);
+    return check_launch("padshare_weights_kernel");
+}
+
+extern "C" int imcom_padshare_maps(imcom_ctx *ctx, int direction, int add_mode, int nside_p, int width, int fk, int n_out, int nmaps,
+                                   const imcom_padshare_map *maps_host)
+{
+    IMCOM_TRY(enter(ctx));
+    IMCOM_REQUIRE(ps_shape_ok(direction, nside_p, width, fk), "direction %d, NsideP %d, width %d, fade kernel %d: not a padding strip (0 <= direction <= 3, "
+                  "fk <= width, 2 width <= NsideP)", direction, nside_p, width, fk);
+    IMCOM_REQUIRE(nmaps >= 0 && n_out >= 0 && (long)nmaps * n_out <= 65535, "bad arguments");
+    const long tot = (long)(width + fk) * nside_p;
+    IMCOM_REQUIRE(tot < (1L << 31), "a strip of %ld pixels", tot);
+    if (nmaps == 0 || n_out == 0 || tot == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(maps_host, "bad arguments");
+    for (int k = 0; k < nmaps; k++) {
+        const imcom_padshare_map &d = maps_host[k];
+        IMCOM_REQUIRE(d.mine && d.theirs && d.decode_coef != 0.0 && d.decode_coef == d.decode_coef && d.encode_coef != 0, "map %d: bad descriptor", k);
+        IMCOM_REQUIRE(d.mine != d.theirs, "a block does not share padding stamps with itself");
+    }
+    IMCOM_TRY(ws_reserve(ctx, (size_t)nmaps * sizeof(imcom_padshare_map) + 1024));
+    imcom_padshare_map *md;
+    IMCOM_TRY(ws_take(ctx, (size_t)nmaps, &md, "imcom_padshare_maps"));
+    IMCOM_TRY(upload(ctx, md, maps_host, (size_t)nmaps));
+    ProfScope ps(ctx, "padshare");
+    hipLaunchKernelGGL(padshare_maps_kernel, dim3((unsigned)((tot + 255) / 256), (unsigned)(nmaps * n_out)), dim3(256), 0, ctx->stream, direction,
+                       add_mode ? 1 : 0, nside_p, width, fk, n_out, md);
+    return check_launch("padshare_maps_kernel");
+}
