@@ -612,6 +612,16 @@ int imcom_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npo
  * lattice over a's pixel range (row node, column node) with W [nside][L] the Lagrange weights of the nodes at every pixel index: the
  * kernels contract the row axis once per image row and spend L multiply-adds per pixel and coordinate, as imcom_lattice_positions does.
  * The cell is floor; a target pixel whose cell is not wholly inside the source contributes nothing.
+ * Seam 21: with pair_x[i], pair_y[i] and pair_lat[i] all NULL the positions of pair i are FORMED in the kernels from the WCSs of its two
+ * SCAs and nothing of the grid's size is kept: wcs_desc (DEVICE, float64 [n_sca][130], the packed descriptor of every SCA in the layout
+ * stated at imcom_wcs_*; the rows of SCAs no formed pair names are not read), the error tables as five HOST arrays indexed by SCA (tab[s] a
+ * DEVICE pointer or NULL, tab_f64, tab_n2, tab_lo, tab_hi as imcom_wcs_* take them; all five NULL: no SCA has one) and pair_M (DEVICE, float64
+ * [npairs][9]: row i = R_b R_a^T of imcom_destripe_pair_rotation; read for formed pairs only).  The position of pixel (row r, column c) is
+ * imcom_wcs_pix2pix's of the point (c, r), origin 0, with its NaN rule -- the same arithmetic in the same order, so the same bits as the
+ * arrays that entry would have stored.  A mosaic may mix the three sources pair by pair.  All seven NULL: no pair is formed.
+ *   imcom_destripe_wcs_sizes out[4] = {bytes kept for one formed pair (its row of pair_M), bytes of wcs_desc for n_sca SCAs, doubles of a
+ *                            descriptor, workspace bytes of imcom_wcs_effective_gain for an SCA of this side}.
+ *   imcom_destripe_pair_rotation   M [9] (HOST) = R_ref R_target^T of two packed descriptors (HOST) after their refusals.
  *   imcom_destripe_sizes     out[8] = {nbins, column blocks, resident bytes per SCA (image, mask, g_eff, N_eff, psi), bytes of a pair's
  *                            position arrays, bytes of a pair's lattice, workspace bytes of imcom_destripe_cost, of imcom_destripe_residual,
  *                            bytes of W}.  IMCOM_ERR_UNSUPPORTED: ds_rows != nside (the "linear" model's 2 ds_rows parameters cannot be
@@ -639,15 +649,21 @@ int imcom_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npo
 #define IMCOM_DESTRIPE_HUBER 2
 int imcom_destripe_sizes(int n_sca, int nside, int ds_rows, int amp_cols, int L, int max_np, int npairs, long *out);
 int imcom_destripe_neff(imcom_ctx *ctx, int n_sca, int nside, int L, const unsigned char *mask, int npairs, const int *pair_a, const int *pair_b,
-                        const void *const *pair_x, const void *const *pair_y, const void *const *pair_lat, const double *W, double *neff);
+                        const void *const *pair_x, const void *const *pair_y, const void *const *pair_lat, const double *W, double *neff,
+                        const double *wcs_desc, const void *const *tab, const int *tab_f64, const int *tab_n2, const double *tab_lo, const double *tab_hi,
+                        const double *pair_M);
 int imcom_destripe_cost(imcom_ctx *ctx, int n_sca, int nside, int ds_rows, int amp_cols, int L, const float *image, const unsigned char *mask,
                         const float *geff, const double *neff, const double *params, int npairs, const int *pair_a, const int *pair_b,
                         const void *const *pair_x, const void *const *pair_y, const void *const *pair_lat, const double *W, int model, double thresh,
-                        double neff_min, double col_boundary_const, float *psi, double *eps);
+                        double neff_min, double col_boundary_const, float *psi, double *eps, const double *wcs_desc, const void *const *tab, const int *tab_f64,
+                        const int *tab_n2, const double *tab_lo, const double *tab_hi, const double *pair_M);
 int imcom_destripe_residual(imcom_ctx *ctx, int n_sca, int nside, int ds_rows, int amp_cols, int L, const float *psi, const float *geff, const double *neff,
                             int npairs, const int *pair_a, const int *pair_b, const void *const *pair_x, const void *const *pair_y,
                             const void *const *pair_lat, const double *W, int model, double thresh, double geff_max, double *resids, double *resids1,
-                            double *resids2);
+                            double *resids2, const double *wcs_desc, const void *const *tab, const int *tab_f64, const int *tab_n2, const double *tab_lo,
+                            const double *tab_hi, const double *pair_M);
+int imcom_destripe_wcs_sizes(int n_sca, int nside, long *out);
+int imcom_destripe_pair_rotation(const double *target, const double *ref, double *M);
 int imcom_destripe_interp(imcom_ctx *ctx, const double *src, const double *gsrc, int rows, int cols, const double *x, const double *y, long npix, double *out);
 int imcom_destripe_interp_transpose(imcom_ctx *ctx, const double *image, const double *x, const double *y, long npix, int rows, int cols, double *out);
 
@@ -948,7 +964,12 @@ int imcom_star_cuts(imcom_ctx *ctx, const void *frame, int is_f64, long rows, lo
  *                        only the counts are formed (get_overlap_matrix, 161-167).
  *   imcom_wcs_pix_area   wcsutil.py:729-786 in two launches: ra, dec of the frame (xs [W], ys [H]: the two linspaces of 718-726) with the
  *                        exact extrema of ra; the host decides the turn of 740-749 (*rotated, may be NULL); then the centred differences
- *                        over op = ovsamp pad points, / 2 / pad, the determinant and cos(dec): area [H - 2 op][W - 2 op], square degrees. */
+ *                        over op = ovsamp pad points, / 2 / pad, the determinant and cos(dec): area [H - 2 op][W - 2 op], square degrees.
+ *   imcom_wcs_effective_gain   Sca_img's effective gain (imdestripe.py:281-297 with get_coordinates(pad=2.0), 451-474): ra, dec in degrees of
+ *                        the pixels -1 .. nside on both axes, the four centred differences / 2, their determinant and 1 / (|det| cos(dec)),
+ *                        with no turn away from the prime meridian (the reference has none here).  gain [nside][nside], float64 or (out_f32)
+ *                        float32.  Kept from 292-293: the determinants come back transposed, so gain[i][j] has the determinant of pixel
+ *                        (row j, column i) and the cosine of pixel (row i, column j). */
 int imcom_wcs_sizes(long n, int W, int H, long *out);
 int imcom_wcs_pix2world(imcom_ctx *ctx, const double *wcs, const void *tab, int tab_f64, int tab_n2, double tab_lo, double tab_hi, const double *pix, long n, int origin,
                         double *world, long *nbad, int memspace);
@@ -959,6 +980,8 @@ int imcom_wcs_pix2pix(imcom_ctx *ctx, const double *from, const void *ftab, int 
                       void *x, void *y, int out_f32, unsigned char *is_in_ref, long *counts, int memspace);
 int imcom_wcs_pix_area(imcom_ctx *ctx, const double *wcs, const void *tab, int tab_f64, int tab_n2, double tab_lo, double tab_hi, const double *xs, int W, const double *ys,
                        int H, int op, double pad, double *area, int *rotated, int memspace);
+int imcom_wcs_effective_gain(imcom_ctx *ctx, const double *wcs, const void *tab, int tab_f64, int tab_n2, double tab_lo, double tab_hi, int nside, void *gain,
+                             int out_f32, int memspace);
 
 /* ---- a block's input-stamp pool from two WCSs (seam 17): InImage.partition_pixels coadd.py:329-358, InImage.extract_layers 394-404 and
  * InStamp.__init__ 688-707, between the device WCS above and imcom_select_pixels.  Arrays marked (device) are device pointers, those marked

@@ -160,11 +160,14 @@ SIGNATURES = {
     "imcom_splitpsf_split": [_vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _i],
     "imcom_splitpsf_points": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _i],
     "imcom_destripe_sizes": [_i, _i, _i, _i, _i, _i, _i, _vp],
-    "imcom_destripe_neff": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "imcom_destripe_cost": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _d, _vp, _vp],
-    "imcom_destripe_residual": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _vp],
+    "imcom_destripe_neff": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "imcom_destripe_cost": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "imcom_destripe_residual": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp],
     "imcom_destripe_interp": [_vp, _vp, _vp, _i, _i, _vp, _vp, _l, _vp],
     "imcom_destripe_interp_transpose": [_vp, _vp, _vp, _vp, _l, _i, _i, _vp],
+    "imcom_destripe_wcs_sizes": [_i, _i, _vp],
+    "imcom_destripe_pair_rotation": [_vp, _vp, _vp],
     "imcom_noiseps_route": [_i],
     "imcom_noiseps_sizes": [_i, _i, _i, _i, _vp],
     "imcom_noiseps_2d": [_vp, _vp, _i, _i, _i, _l, _l, _vp, _l, _vp, _i, _i, _vp, _i],
@@ -208,6 +211,7 @@ SIGNATURES = {
     "imcom_wcs_world2pix": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _l, _i, _vp, C.POINTER(_l), _i],
     "imcom_wcs_pix2pix": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _l, _i, _d, _d, _vp, _vp, _i, _vp, _vp, _i],
     "imcom_wcs_pix_area": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _i, _vp, _i, _i, _d, _vp, _ip, _i],
+    "imcom_wcs_effective_gain": [_vp, _vp, _vp, _i, _i, _d, _d, _i, _vp, _i, _i],
     "imcom_partition_wcs": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp,
                             C.POINTER(_l)],
     "imcom_extract_layers": [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp],

@@ -8,16 +8,27 @@
 // (x, y) = (column, row) in the source, the cell is floor, a target pixel whose cell is not wholly inside the source contributes
 // nothing.  Sums that many threads feed (the parameter bins, the transposed image) are exact: every contribution is rounded once to
 // a fixed-point integer of a scale common to the call and added as an integer, so the order of arrival cannot change a bit.
+//
+// Where a pair's positions come from: two stored arrays, a lattice, or (seam 21) the two WCSs themselves -- wcs_core.h's wcs_pix2pix on
+// the integer pixel, the arithmetic of wcs_pix2pix_kernel (wcs.hip) in its order, so the position a kernel forms is the one that kernel
+// would have stored, bit for bit.  The descriptors sit in a device table indexed by SCA; a workgroup's pair is one, so every coefficient
+// read is wave-uniform.
 #include <algorithm>
 
 #include "launchers.h"
+#include "wcs_core.h"
 
 namespace imcom {
 
 struct DsPair {            // one ordered pair: neighbour b gathered onto / scattered from target a
     const double *x, *y;   // positions of a's pixels in b [nside][nside] (column, row), or both null:
-    const double *lat;     // their values on the lattice [2][L][L] (x plane, y plane; row node, column node)
+    const double *lat;     // their values on the lattice [2][L][L] (x plane, y plane; row node, column node), or null as well:
+    const double *M;       // R_b R_a^T (nine doubles): the positions are formed from the descriptors and error tables of a and b
     int a, b;
+};
+struct DsWcs {             // the WCSs of the mosaic, indexed by SCA (null: no pair is formed)
+    const WcsDesc *desc;
+    const WcsTab *tab;
 };
 struct DsGeom {
     int n_sca, nside, ds_rows, amp_cols, ncb, nbins;  // ncb column blocks (0: rows only), nbins = ds_rows + ncb
@@ -42,14 +53,29 @@ __device__ inline double block_sum(double v, double *red)  // fixed-order tree o
     return red[0];
 }
 
-// The position of target pixel (r, c) in the source of a pair: the stored arrays, or the tensor product over the lattice with the
-// row axis already contracted (T [2][L] in LDS: T[k][j] = sum_i W[r][i] lat[k][i][j]).
-__device__ inline void pair_position(const DsPair &p, const double *T, const double *__restrict__ W, int L, int nside, int r, int c, double *x, double *y)
+// The position of target pixel (r, c) in the source of a pair: the stored arrays, the tensor product over the lattice with the
+// row axis already contracted (T [2][L] in LDS: T[k][j] = sum_i W[r][i] lat[k][i][j]), or wcs_pix2pix of the pixel with the NaN rule
+// of wcs_pix2pix_kernel (a point that has no image, or one that is not finite, is NaN: outside every cell).
+__device__ inline void pair_position(const DsPair &p, const DsWcs &ws, const double *T, const double *__restrict__ W, int L, int nside, int r, int c, double *x,
+                                     double *y)
 {
     if (p.x) {
         const long o = (long)r * nside + c;
         *x = p.x[o];
         *y = p.y[o];
+        return;
+    }
+    if (!p.lat) {
+        const WcsDesc &from = ws.desc[p.a], &to = ws.desc[p.b];
+        double xf = NAN, yf = NAN;
+        // (imcom_destripe_pair_rotation refuses a bad descriptor on the host when the pair is registered; the table in device memory is
+        // bounded here once more, by a few wave-uniform compares, since the orders are loop bounds over the coefficient blocks)
+        const bool sane = from.d[WCS_D_AORDER] <= WCS_MAX_ORDER && from.d[WCS_D_BORDER] <= WCS_MAX_ORDER && to.d[WCS_D_AORDER] <= WCS_MAX_ORDER &&
+                          to.d[WCS_D_BORDER] <= WCS_MAX_ORDER && to.d[WCS_D_NITER] <= WCS_MAX_NITER;
+        if (!sane || !wcs_pix2pix(from, ws.tab[p.a], to, ws.tab[p.b], p.M, (double)c, (double)r, 0, &xf, &yf) || !(xf - xf == 0.0 && yf - yf == 0.0))
+            xf = NAN, yf = NAN;
+        *x = xf;
+        *y = yf;
         return;
     }
     const double *w = W + (long)c * L;
@@ -67,7 +93,7 @@ __device__ inline void contract_rows(const DsPair *pairs, int np, const double *
     for (int idx = threadIdx.x; idx < np * 2 * L; idx += DS_T) {
         const int q = idx / (2 * L), kj = idx - q * 2 * L;
         double s = 0.0;
-        if (!pairs[q].x) {
+        if (!pairs[q].x && pairs[q].lat) {
             const double *lat = pairs[q].lat + kj / L * L * L + kj % L;
             for (int i = 0; i < L; i++) s = fma(W[(long)r * L + i], lat[(long)i * L], s);
         }
@@ -120,7 +146,7 @@ __device__ inline double cost_fprime(double x, int model, double d)
 template <int MODE>
 __global__ __launch_bounds__(DS_T) void destripe_forward_kernel(DsGeom g, const float *__restrict__ img, const unsigned char *__restrict__ mask,
                                                                 const float *__restrict__ geff, const double *__restrict__ params,
-                                                                const DsPair *__restrict__ pairs, const int *__restrict__ start,
+                                                                const DsPair *__restrict__ pairs, const int *__restrict__ start, const DsWcs ws,
                                                                 const double *__restrict__ W, double *__restrict__ neff, float *__restrict__ psi,
                                                                 double *__restrict__ eps_rows)
 {
@@ -136,7 +162,7 @@ __global__ __launch_bounds__(DS_T) void destripe_forward_kernel(DsGeom g, const 
         for (int q = 0; q < np; q++) {
             const DsPair &p = pairs[p0 + q];
             double x, y;
-            pair_position(p, Tl + (size_t)q * 2 * g.L, W, g.L, n, r, c, &x, &y);
+            pair_position(p, ws, Tl + (size_t)q * 2 * g.L, W, g.L, n, r, c, &x, &y);
             int x1, y1;
             double w[4];
             if (!bilinear_cell(x, y, n, n, &x1, &y1, w)) continue;
@@ -295,7 +321,7 @@ __device__ inline void hist_add(unsigned long long *hist, int key, long long v)
 // term_2 (1392-1403) for one ordered pair per blockIdx.y and DS_ROWS target rows per workgroup: every target pixel is read once
 // and its four weighted values, times g_B at the corners, go straight into the row and column-block bins of B.
 __global__ __launch_bounds__(DS_T) void destripe_scatter_kernel(DsGeom g, const float *__restrict__ psi, const float *__restrict__ geff,
-                                                                const double *__restrict__ neff, const DsPair *__restrict__ pairs,
+                                                                const double *__restrict__ neff, const DsPair *__restrict__ pairs, const DsWcs ws,
                                                                 const double *__restrict__ W, const double *__restrict__ scale,
                                                                 unsigned long long *__restrict__ bins)
 {
@@ -319,8 +345,8 @@ __global__ __launch_bounds__(DS_T) void destripe_scatter_kernel(DsGeom g, const 
             if (c < n) {
                 const long o = (long)a * plane + (long)r * n + c;
                 const double gv = grad_scaled(g, psi[o], geff[o], neff[o]);
-                double x, y;
-                pair_position(p, T, W, g.L, n, r, c, &x, &y);
+                double x = NAN, y = NAN;
+                if (gv != 0.0) pair_position(p, ws, T, W, g.L, n, r, c, &x, &y);  // (a pixel without a gradient needs no position)
                 int x1, y1;
                 double w[4];
                 if (gv != 0.0 && bilinear_cell(x, y, n, n, &x1, &y1, w)) {
@@ -415,17 +441,17 @@ static size_t destripe_prep_lds(const DsGeom &g) { return ((size_t)g.nside + DS_
 static size_t destripe_scatter_lds(const DsGeom &g) { return ((size_t)2 * g.L + g.nbins) * sizeof(double); }
 
 static int launch_destripe_forward(imcom_ctx *ctx, const DsGeom &g, bool make_neff, const float *img, const unsigned char *mask, const float *geff, const double *params,
-                            const DsPair *pairs, const int *start, const double *W, double *neff, float *psi, double *eps_rows)
+                            const DsPair *pairs, const int *start, const DsWcs &ws, const double *W, double *neff, float *psi, double *eps_rows)
 {
     ProfScope ps(ctx, make_neff ? "destripe_neff" : "destripe_forward");
     const size_t lds = destripe_forward_lds(g);
     const dim3 grid((unsigned)g.nside, (unsigned)g.n_sca);
     if (make_neff) {
         IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)destripe_forward_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(destripe_forward_kernel<0>, grid, dim3(DS_T), lds, ctx->stream, g, img, mask, geff, params, pairs, start, W, neff, psi, eps_rows);
+        hipLaunchKernelGGL(destripe_forward_kernel<0>, grid, dim3(DS_T), lds, ctx->stream, g, img, mask, geff, params, pairs, start, ws, W, neff, psi, eps_rows);
     } else {
         IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)destripe_forward_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(destripe_forward_kernel<1>, grid, dim3(DS_T), lds, ctx->stream, g, img, mask, geff, params, pairs, start, W, neff, psi, eps_rows);
+        hipLaunchKernelGGL(destripe_forward_kernel<1>, grid, dim3(DS_T), lds, ctx->stream, g, img, mask, geff, params, pairs, start, ws, W, neff, psi, eps_rows);
     }
     return check_launch("destripe_forward_kernel");
 }
@@ -446,7 +472,7 @@ static int launch_destripe_eps(imcom_ctx *ctx, const DsGeom &g, const float *img
 }
 
 static int launch_destripe_gradient(imcom_ctx *ctx, const DsGeom &g, const float *psi, const float *geff, const double *neff, const DsPair *pairs, int npairs,
-                             const double *W, double gmax_all, double *term1, double *rowcb, unsigned long long *gmax_bits, double *scale,
+                             const DsWcs &ws, const double *W, double gmax_all, double *term1, double *rowcb, unsigned long long *gmax_bits, double *scale,
                              unsigned long long *bins, double *resids, double *r1, double *r2)
 {
     ProfScope ps(ctx, "destripe_gradient", 5);
@@ -469,7 +495,7 @@ static int launch_destripe_gradient(imcom_ctx *ctx, const DsGeom &g, const float
         lds = destripe_scatter_lds(g);
         IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)destripe_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(destripe_scatter_kernel, dim3((unsigned)((g.nside + DS_ROWS - 1) / DS_ROWS), (unsigned)npairs), dim3(DS_T), lds, ctx->stream, g, psi,
-                           geff, neff, pairs, W, (const double *)scale, bins);
+                           geff, neff, pairs, ws, W, (const double *)scale, bins);
         IMCOM_TRY(check_launch("destripe_scatter_kernel"));
     }
     hipLaunchKernelGGL(destripe_resids_kernel, dim3((unsigned)((total + DS_T - 1) / DS_T)), dim3(DS_T), 0, ctx->stream, total, (const double *)term1,
@@ -548,35 +574,64 @@ int destripe_model(int model, double thresh, DsGeom *g)
 
 // the pair table: sorted by (a, b), no pair twice, a != b; *max_np = the most neighbours of one target
 int destripe_check_pairs(int n_sca, int L, int npairs, const int *pa, const int *pb, const void *const *px, const void *const *py, const void *const *pl,
-                         int *max_np)
+                         bool wcs, int *max_np, int *nformed)
 {
     IMCOM_REQUIRE(npairs >= 0 && (npairs == 0 || (pa && pb && px && py && pl)), "destripe: null pair table");
     int run = 0;
-    *max_np = 0;
+    *max_np = 0, *nformed = 0;
     for (int i = 0; i < npairs; i++) {
         IMCOM_REQUIRE(pa[i] >= 0 && pa[i] < n_sca && pb[i] >= 0 && pb[i] < n_sca && pa[i] != pb[i], "destripe: pair %d is (%d, %d) of %d SCAs", i, pa[i], pb[i], n_sca);
         IMCOM_REQUIRE(i == 0 || pa[i] > pa[i - 1] || (pa[i] == pa[i - 1] && pb[i] > pb[i - 1]), "destripe: the pair table is not sorted by (a, b) at %d", i);
-        IMCOM_REQUIRE((px[i] && py[i]) || (!px[i] && !py[i] && pl[i] && L >= 2), "destripe: pair %d has neither position arrays nor a lattice", i);
+        IMCOM_REQUIRE((px[i] && py[i]) || (!px[i] && !py[i] && ((pl[i] && L >= 2) || (!pl[i] && wcs))),
+                      "destripe: pair %d has neither position arrays nor a lattice, and there is no WCS table to form its positions from", i);
+        if (!px[i] && !pl[i]) ++*nformed;
         run = (i > 0 && pa[i] == pa[i - 1]) ? run + 1 : 1;
         if (run > *max_np) *max_np = run;
     }
     return IMCOM_OK;
 }
 
+// The WCS arguments of the three entries: wcs_desc [n_sca][WCS_DESC_LEN] and pair_M [npairs][9] in device memory (the row of a pair that is
+// not formed is not read), and the error tables as host arrays indexed by SCA (tab[s] a device pointer or null; all five null: no tables).
+struct DsWcsArgs {
+    const double *desc, *M;
+    const void *const *tab;
+    const int *f64, *n2;
+    const double *lo, *hi;
+};
+
 int destripe_upload_pairs(imcom_ctx *ctx, int n_sca, int npairs, const int *pa, const int *pb, const void *const *px, const void *const *py,
-                          const void *const *pl, DsPair **pairs_d, int **start_d, const char *who)
+                          const void *const *pl, const DsWcsArgs &wa, int nformed, DsPair **pairs_d, int **start_d, DsWcs *ws, const char *who)
 {
     std::vector<DsPair> tab((size_t)std::max(npairs, 1));
     std::vector<int> start((size_t)n_sca + 1, 0);
     for (int i = 0; i < npairs; i++) {
         tab[i].x = (const double *)px[i], tab[i].y = (const double *)py[i], tab[i].lat = (const double *)pl[i], tab[i].a = pa[i], tab[i].b = pb[i];
+        tab[i].M = (!px[i] && !pl[i]) ? wa.M + (size_t)9 * i : nullptr;
         start[pa[i] + 1]++;
     }
     for (int a = 0; a < n_sca; a++) start[a + 1] += start[a];
     IMCOM_TRY(ws_take(ctx, tab.size(), pairs_d, who));
     IMCOM_TRY(ws_take(ctx, start.size(), start_d, who));
     IMCOM_TRY(upload(ctx, *pairs_d, tab.data(), tab.size()));
-    return upload(ctx, *start_d, start.data(), start.size());
+    IMCOM_TRY(upload(ctx, *start_d, start.data(), start.size()));
+    *ws = DsWcs{nullptr, nullptr};
+    if (nformed == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(wa.desc && wa.M && ((uintptr_t)wa.desc & 7) == 0 && ((uintptr_t)wa.M & 7) == 0, "%s: formed pairs need the descriptor table and the rotation products", who);
+    const bool tables = wa.tab != nullptr;
+    IMCOM_REQUIRE(tables == (wa.f64 != nullptr) && tables == (wa.n2 != nullptr) && tables == (wa.lo != nullptr) && tables == (wa.hi != nullptr),
+                  "%s: the five arrays of the error tables are given together", who);
+    std::vector<WcsTab> wt((size_t)n_sca, WcsTab{nullptr, 0, 0, 0.0, 0.0});
+    for (int s = 0; tables && s < n_sca; s++) {
+        if (!wa.tab[s]) continue;
+        IMCOM_TRY(wcs_table_check(wa.tab[s], wa.f64[s], wa.n2[s], wa.lo[s], wa.hi[s], who));
+        wt[s] = WcsTab{wa.tab[s], wa.f64[s] ? 1 : 0, wa.n2[s], wa.lo[s], wa.hi[s]};
+    }
+    WcsTab *wt_d;
+    IMCOM_TRY(ws_take(ctx, wt.size(), &wt_d, who));
+    IMCOM_TRY(upload(ctx, wt_d, wt.data(), wt.size()));
+    *ws = DsWcs{(const WcsDesc *)wa.desc, wt_d};
+    return IMCOM_OK;
 }
 
 size_t destripe_cost_ws(const DsGeom &g, int npairs, bool forward)
@@ -584,6 +639,7 @@ size_t destripe_cost_ws(const DsGeom &g, int npairs, bool forward)
     WsPlan plan;
     plan.add((size_t)std::max(npairs, 1) * sizeof(DsPair));
     plan.add(((size_t)g.n_sca + 1) * sizeof(int));
+    plan.add((size_t)g.n_sca * sizeof(WcsTab));
     if (forward) {
         plan.add((size_t)g.n_sca * g.nside * 8);
         plan.add((size_t)g.n_sca * std::max(g.ncb - 1, 1) * ((g.nside + 399) / 400) * 8);
@@ -596,6 +652,7 @@ size_t destripe_resid_ws(const DsGeom &g, int npairs)
     WsPlan plan;
     plan.add((size_t)std::max(npairs, 1) * sizeof(DsPair));
     plan.add(((size_t)g.n_sca + 1) * sizeof(int));
+    plan.add((size_t)g.n_sca * sizeof(WcsTab));
     plan.add((size_t)g.n_sca * g.nbins * 8);
     plan.add((size_t)g.n_sca * g.nside * std::max(g.ncb, 1) * 8);
     plan.add(8);
@@ -625,30 +682,36 @@ int imcom_destripe_sizes(int n_sca, int nside, int ds_rows, int amp_cols, int L,
 }
 
 int imcom_destripe_neff(imcom_ctx *ctx, int n_sca, int nside, int L, const unsigned char *mask, int npairs, const int *pair_a, const int *pair_b,
-                        const void *const *pair_x, const void *const *pair_y, const void *const *pair_lat, const double *W, double *neff)
+                        const void *const *pair_x, const void *const *pair_y, const void *const *pair_lat, const double *W, double *neff,
+                        const double *wcs_desc, const void *const *tab, const int *tab_f64, const int *tab_n2, const double *tab_lo, const double *tab_hi,
+                        const double *pair_M)
 {
     IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(mask && neff && (L == 0 || W), "null pointer");
-    int max_np;
-    IMCOM_TRY(destripe_check_pairs(n_sca, L, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &max_np));
+    int max_np, nformed;
+    const DsWcsArgs wa = {wcs_desc, pair_M, tab, tab_f64, tab_n2, tab_lo, tab_hi};
+    IMCOM_TRY(destripe_check_pairs(n_sca, L, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, wcs_desc && pair_M, &max_np, &nformed));
     DsGeom g;
     IMCOM_TRY(destripe_geom(n_sca, nside, nside, 0, L, max_np, &g));
     IMCOM_TRY(ws_reserve(ctx, destripe_cost_ws(g, npairs, false)));
     DsPair *pairs_d;
     int *start_d;
-    IMCOM_TRY(destripe_upload_pairs(ctx, n_sca, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &pairs_d, &start_d, __func__));
-    return launch_destripe_forward(ctx, g, true, nullptr, mask, nullptr, nullptr, pairs_d, start_d, W, neff, nullptr, nullptr);
+    DsWcs ws;
+    IMCOM_TRY(destripe_upload_pairs(ctx, n_sca, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, wa, nformed, &pairs_d, &start_d, &ws, __func__));
+    return launch_destripe_forward(ctx, g, true, nullptr, mask, nullptr, nullptr, pairs_d, start_d, ws, W, neff, nullptr, nullptr);
 }
 
 int imcom_destripe_cost(imcom_ctx *ctx, int n_sca, int nside, int ds_rows, int amp_cols, int L, const float *image, const unsigned char *mask,
                         const float *geff, const double *neff, const double *params, int npairs, const int *pair_a, const int *pair_b,
                         const void *const *pair_x, const void *const *pair_y, const void *const *pair_lat, const double *W, int model, double thresh,
-                        double neff_min, double col_boundary_const, float *psi, double *eps)
+                        double neff_min, double col_boundary_const, float *psi, double *eps, const double *wcs_desc, const void *const *tab, const int *tab_f64,
+                        const int *tab_n2, const double *tab_lo, const double *tab_hi, const double *pair_M)
 {
     IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(image && mask && geff && neff && params && psi && eps && (L == 0 || W), "null pointer");
-    int max_np;
-    IMCOM_TRY(destripe_check_pairs(n_sca, L, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &max_np));
+    int max_np, nformed;
+    const DsWcsArgs wa = {wcs_desc, pair_M, tab, tab_f64, tab_n2, tab_lo, tab_hi};
+    IMCOM_TRY(destripe_check_pairs(n_sca, L, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, wcs_desc && pair_M, &max_np, &nformed));
     DsGeom g;
     IMCOM_TRY(destripe_geom(n_sca, nside, ds_rows, amp_cols, L, max_np, &g));
     IMCOM_TRY(destripe_model(model, thresh, &g));
@@ -660,40 +723,44 @@ int imcom_destripe_cost(imcom_ctx *ctx, int n_sca, int nside, int ds_rows, int a
     IMCOM_TRY(ws_reserve(ctx, destripe_cost_ws(g, npairs, true)));
     DsPair *pairs_d;
     int *start_d;
+    DsWcs ws;
     double *eps_rows, *pen;
     const int nchunk = (nside + 399) / 400;
-    IMCOM_TRY(destripe_upload_pairs(ctx, n_sca, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &pairs_d, &start_d, __func__));
+    IMCOM_TRY(destripe_upload_pairs(ctx, n_sca, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, wa, nformed, &pairs_d, &start_d, &ws, __func__));
     IMCOM_TRY(ws_take(ctx, (size_t)n_sca * nside, &eps_rows, __func__));
     IMCOM_TRY(ws_take(ctx, (size_t)n_sca * std::max(g.ncb - 1, 1) * nchunk, &pen, __func__));
-    IMCOM_TRY(launch_destripe_forward(ctx, g, false, image, mask, geff, params, pairs_d, start_d, W, (double *)neff, psi, eps_rows));
+    IMCOM_TRY(launch_destripe_forward(ctx, g, false, image, mask, geff, params, pairs_d, start_d, ws, W, (double *)neff, psi, eps_rows));
     return launch_destripe_eps(ctx, g, image, mask, params, eps_rows, pen, nchunk, eps);
 }
 
 int imcom_destripe_residual(imcom_ctx *ctx, int n_sca, int nside, int ds_rows, int amp_cols, int L, const float *psi, const float *geff, const double *neff,
                             int npairs, const int *pair_a, const int *pair_b, const void *const *pair_x, const void *const *pair_y,
                             const void *const *pair_lat, const double *W, int model, double thresh, double geff_max, double *resids, double *resids1,
-                            double *resids2)
+                            double *resids2, const double *wcs_desc, const void *const *tab, const int *tab_f64, const int *tab_n2, const double *tab_lo,
+                            const double *tab_hi, const double *pair_M)
 {
     IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(psi && geff && neff && resids && (L == 0 || W), "null pointer");
     IMCOM_REQUIRE(geff_max >= 0.0 && geff_max < 1e300, "destripe: geff_max = %g", geff_max);
-    int max_np;
-    IMCOM_TRY(destripe_check_pairs(n_sca, L, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &max_np));
+    int max_np, nformed;
+    const DsWcsArgs wa = {wcs_desc, pair_M, tab, tab_f64, tab_n2, tab_lo, tab_hi};
+    IMCOM_TRY(destripe_check_pairs(n_sca, L, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, wcs_desc && pair_M, &max_np, &nformed));
     DsGeom g;
     IMCOM_TRY(destripe_geom(n_sca, nside, ds_rows, amp_cols, L, max_np, &g));
     IMCOM_TRY(destripe_model(model, thresh, &g));
     IMCOM_TRY(ws_reserve(ctx, destripe_resid_ws(g, npairs)));
     DsPair *pairs_d;
     int *start_d;
+    DsWcs ws;
     double *term1, *rowcb, *scale;
     unsigned long long *bits, *bins;
-    IMCOM_TRY(destripe_upload_pairs(ctx, n_sca, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, &pairs_d, &start_d, __func__));
+    IMCOM_TRY(destripe_upload_pairs(ctx, n_sca, npairs, pair_a, pair_b, pair_x, pair_y, pair_lat, wa, nformed, &pairs_d, &start_d, &ws, __func__));
     IMCOM_TRY(ws_take(ctx, (size_t)n_sca * g.nbins, &term1, __func__));
     IMCOM_TRY(ws_take(ctx, (size_t)n_sca * nside * std::max(g.ncb, 1), &rowcb, __func__));
     IMCOM_TRY(ws_take(ctx, 1, &bits, __func__));
     IMCOM_TRY(ws_take(ctx, 2, &scale, __func__));
     IMCOM_TRY(ws_take(ctx, (size_t)n_sca * g.nbins, &bins, __func__));
-    return launch_destripe_gradient(ctx, g, psi, geff, neff, pairs_d, npairs, W, geff_max, term1, rowcb, bits, scale, bins, resids, resids1, resids2);
+    return launch_destripe_gradient(ctx, g, psi, geff, neff, pairs_d, npairs, ws, W, geff_max, term1, rowcb, bits, scale, bins, resids, resids1, resids2);
 }
 
 int imcom_destripe_interp(imcom_ctx *ctx, const double *src, const double *gsrc, int rows, int cols, const double *x, const double *y, long npix, double *out)
@@ -720,6 +787,31 @@ int imcom_destripe_interp_transpose(imcom_ctx *ctx, const double *image, const d
     IMCOM_TRY(ws_take(ctx, 1, &bits, __func__));
     IMCOM_TRY(ws_take(ctx, 2, &scale, __func__));
     return launch_destripe_transpose(ctx, image, x, y, npix, rows, cols, acc, bits, scale, out);
+}
+
+// Seam 21: what a mosaic whose pairs are formed from its WCSs keeps on the device, exactly.  out[0]: bytes of one formed pair (its rotation
+// product); out[1]: bytes of the descriptor table of n_sca SCAs; out[2]: doubles of one descriptor; out[3]: the workspace that making the
+// gain of one SCA of this side takes (imcom_wcs_effective_gain; a peak during set-up).  The error tables are the caller's.
+int imcom_destripe_wcs_sizes(int n_sca, int nside, long *out)
+{
+    IMCOM_REQUIRE(out && n_sca >= 0 && nside >= 1 && nside <= 32768, "destripe_wcs_sizes: %d SCAs of side %d", n_sca, nside);
+    out[0] = 9 * sizeof(double);
+    out[1] = (long)n_sca * (long)sizeof(WcsDesc);
+    out[2] = WCS_DESC_LEN;
+    out[3] = (long)wcs_gain_ws_bytes(nside);
+    return IMCOM_OK;
+}
+
+// M [9] = R_ref R_target^T of two packed descriptors (host memory), after their refusals: the rotation product wcs_pix2pix takes, formed
+// where imcom_wcs_pix2pix forms it, so that a formed pair and a stored one start from the same nine numbers.
+int imcom_destripe_pair_rotation(const double *target, const double *ref, double *M)
+{
+    IMCOM_REQUIRE(M, "destripe_pair_rotation: null output");
+    WcsDesc wt, wr;
+    IMCOM_TRY(wcs_descriptor(target, "destripe_pair_rotation", &wt));
+    IMCOM_TRY(wcs_descriptor(ref, "destripe_pair_rotation", &wr));
+    wcs_rotation_product(wt, wr, M);
+    return IMCOM_OK;
 }
 
 }  // extern "C"

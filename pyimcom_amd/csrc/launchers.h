@@ -152,5 +152,6 @@ struct WcsDesc;
 int wcs_descriptor(const double *d, const char *who, WcsDesc *out);
 int wcs_table_check(const void *tab, int f64, int n2, double lo, double hi, const char *who);
 void wcs_rotation_product(const WcsDesc &from, const WcsDesc &to, double *M);
+size_t wcs_gain_ws_bytes(int nside);  // the workspace of imcom_wcs_effective_gain (a destripe mosaic plans for it)
 
 }  // namespace imcom

@@ -193,6 +193,28 @@ __global__ __launch_bounds__(WCS_THREADS) void wcs_area_finish_kernel(const doub
     }
 }
 
+// Sca_img's effective gain (imdestripe.py:281-297) from the frame of wcs_area_frame_kernel, ra and dec [n + 2][n + 2] in degrees of the pixels
+// -1 .. n (get_coordinates(pad=2.0), 451-474): the centred differences, their determinant, 1 / (|det| cos(dec)).  No turn away from the prime
+// meridian: the reference has none here.  The reference transposes its stack of derivatives before it takes the determinants (292-293), so
+// gain[i][j] has the determinant of pixel (row j, column i) and the cosine of pixel (row i, column j); that is kept.
+__global__ __launch_bounds__(WCS_THREADS) void wcs_gain_finish_kernel(const double *__restrict__ ra, const double *__restrict__ dec, int n, void *__restrict__ gain, int f32)
+{
+    const long W = n + 2, total = (long)n * n, p0 = (long)blockIdx.x * WCS_TILE + threadIdx.x;
+#pragma unroll 1
+    for (int k = 0; k < WCS_ITEMS; k++) {
+        const long p = p0 + (long)k * WCS_THREADS;
+        if (p >= total) break;
+        const long i = p / n, j = p - i * n;
+        const long c = (j + 1) * W + (i + 1);  // frame index of pixel (row j, column i)
+        const double rx = (ra[c + 1] - ra[c - 1]) / 2.0, ry = (ra[c + W] - ra[c - W]) / 2.0;
+        const double dx = (dec[c + 1] - dec[c - 1]) / 2.0, dy = (dec[c + W] - dec[c - W]) / 2.0;
+        const double det = rx * dy - ry * dx;
+        const double g = 1.0 / (fabs(det) * cos(dec[(i + 1) * W + (j + 1)] * WCS_DEG));
+        if (f32) ((float *)gain)[p] = (float)g;
+        else ((double *)gain)[p] = g;
+    }
+}
+
 unsigned wcs_blocks(long n) { return (unsigned)std::max(1L, (n + WCS_TILE - 1) / WCS_TILE); }
 
 }  // namespace
@@ -231,6 +253,13 @@ static int launch_wcs_area_finish(imcom_ctx *ctx, const double *ra, const double
     hipLaunchKernelGGL(wcs_area_finish_kernel, dim3(wcs_blocks((long)(W - 2 * op) * (H - 2 * op))), dim3(WCS_THREADS), 0, ctx->stream, ra, dec, W, H, op, pad, rotate,
                        area);
     return check_launch("wcs_area_finish_kernel");
+}
+
+static int launch_wcs_gain_finish(imcom_ctx *ctx, const double *ra, const double *dec, int n, void *gain, int f32)
+{
+    ProfScope ps(ctx, "wcs");
+    hipLaunchKernelGGL(wcs_gain_finish_kernel, dim3(wcs_blocks((long)n * n)), dim3(WCS_THREADS), 0, ctx->stream, ra, dec, n, gain, f32);
+    return check_launch("wcs_gain_finish_kernel");
 }
 
 static double wcs_key_value(unsigned long long k)
@@ -281,6 +310,18 @@ void wcs_rotation_product(const WcsDesc &from, const WcsDesc &to, double *M)
             for (int k = 0; k < 3; k++) s += to.d[WCS_D_ROT + 3 * i + k] * from.d[WCS_D_ROT + 3 * j + k];
             M[3 * i + j] = s;
         }
+}
+
+// The workspace of imcom_wcs_effective_gain with device arrays: the extremes, the ra and dec frames of (nside + 2)^2 points, the axis.
+size_t wcs_gain_ws_bytes(int nside)
+{
+    const size_t W = (size_t)nside + 2;
+    WsPlan plan;
+    plan.add(16);
+    plan.add(W * W * 8);
+    plan.add(W * W * 8);
+    plan.add(W * 8);
+    return plan.total;
 }
 
 }  // namespace imcom
@@ -782,6 +823,44 @@ int imcom_healpix_cap(imcom_ctx *ctx, int res, double ra, double dec, double rad
     IMCOM_TRY(st.back(x, o.x, x ? cap : 0));
     IMCOM_TRY(st.back(y, o.y, y ? cap : 0));
     IMCOM_TRY(st.back(pa, o.pa, pa ? cap : 0));
+    return st.done();
+}
+
+// Seam 21: the effective gain of an SCA of nside x nside pixels from its WCS (imdestripe.py:281-297), float32 (out_f32) or float64
+// [nside][nside].
+int imcom_wcs_effective_gain(imcom_ctx *ctx, const double *wcs, const void *tab, int tab_f64, int tab_n2, double tab_lo, double tab_hi, int nside, void *gain,
+                             int out_f32, int memspace)
+{
+    const char *who = "wcs_effective_gain";
+    IMCOM_TRY(enter(ctx));
+    WcsDesc w;
+    IMCOM_TRY(wcs_descriptor(wcs, who, &w));
+    IMCOM_REQUIRE(nside >= 1 && nside <= 32768 && gain, "%s: an SCA of %d pixels a side, or a null output", who, nside);
+    const int W = nside + 2;
+    const size_t nf = (size_t)W * W, ng = (size_t)nside * nside, el = out_f32 ? 4 : 8;
+    WsPlan plan;
+    plan.add(wcs_gain_ws_bytes(nside));
+    Stage st(ctx, memspace, who);
+    st.plan(plan, {wcs_table_bytes(tab, tab_f64, tab_n2), ng * el});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    unsigned long long *ext;
+    double *ra, *dec, *axis;
+    IMCOM_TRY(ws_take(ctx, 2, &ext, who));
+    IMCOM_TRY(ws_take(ctx, nf, &ra, who));
+    IMCOM_TRY(ws_take(ctx, nf, &dec, who));
+    IMCOM_TRY(ws_take(ctx, (size_t)W, &axis, who));
+    WcsTab t;
+    IMCOM_TRY(wcs_table(st, tab, tab_f64, tab_n2, tab_lo, tab_hi, who, &t));
+    unsigned char *gain_d;
+    IMCOM_TRY(st.out((unsigned char *)gain, ng * el, &gain_d));
+    std::vector<double> pix((size_t)W);
+    for (int k = 0; k < W; k++) pix[k] = (double)k - 1.0;  // 468-470: arange(nside + 2) - 2 / 2
+    IMCOM_TRY(upload(ctx, axis, pix.data(), pix.size()));
+    const unsigned long long init[2] = {~0ull, 0ull};
+    IMCOM_TRY(upload(ctx, ext, init, 2));
+    IMCOM_TRY(launch_wcs_area_frame(ctx, w, t, axis, W, axis, W, ra, dec, ext));
+    IMCOM_TRY(launch_wcs_gain_finish(ctx, ra, dec, nside, gain_d, out_f32 ? 1 : 0));
+    IMCOM_TRY(st.back((unsigned char *)gain, gain_d, ng * el));
     return st.done();
 }
 

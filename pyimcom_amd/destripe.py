@@ -10,16 +10,23 @@
     eng.bind(imdestripe)                                 # imdestripe.cost_function / residual_function now run here
     imdestripe.conjugate_gradient(...)                   # unchanged
 
-The host keeps the files, the masks' construction, the WCS chain, ``get_neighbors`` and the optimiser.  csrc/destripe.hip has the kernels;
+or, from the WCSs alone (seam 21: the gain, the neighbour table and every pair's positions are made on the device, and a pair keeps nothing
+of the grid's size):
+
+    for sca in all_scas:
+        eng.add_sca(image, mask, wcs=sca.w)              # g_eff = effective_gain(sca.w), made into the engine's own plane
+    ov_mat, neighbors = eng.set_pairs_from_wcs(overlap_thresh=0.1, subsamp=8)   # get_overlap_matrix + get_neighbors + set_pair
+
+The host keeps the files, the masks' construction and the optimiser.  csrc/destripe.hip has the kernels;
 INTEGRATION.md, seam 8, the binding lines and the quirks that are kept."""
 
 import ctypes as C
 
 import numpy as np
 
-from ._lib import ImcomError, check, default_context, lib, ptr
+from ._lib import MEM_DEVICE, ImcomError, check, default_context, lib, ptr
 
-__all__ = ["DestripeEngine", "MODELS", "lattice_nodes", "interpolate_bilinear", "transpose_bilinear", "memory_plan"]
+__all__ = ["DestripeEngine", "MODELS", "lattice_nodes", "interpolate_bilinear", "transpose_bilinear", "memory_plan", "effective_gain", "formed_pair_bytes"]
 
 IMCOM_ERR_NOMEM = -3
 IMCOM_ERR_UNSUPPORTED = -4
@@ -57,17 +64,34 @@ def model_name(f):
     return name
 
 
-def memory_plan(n_sca, nside, ds_rows, amp_cols, n_full, n_lattice, L, max_np, objmask_setup=0):
-    """Exact device bytes of a mosaic: n_sca SCAs, ``n_full`` ordered pairs with position arrays, ``n_lattice`` with lattices.  Two psi
+def _wcs_sizes(n_sca, nside):
+    sz = np.zeros(4, dtype=np.int64)
+    check(lib.imcom_destripe_wcs_sizes(int(n_sca), int(nside), ptr(sz)))
+    return sz
+
+
+def formed_pair_bytes(nside=4088):
+    """What a pair registered with ``keep_positions=False`` keeps on the device: its rotation product, whatever the side."""
+    return int(_wcs_sizes(0, nside)[0])
+
+
+def memory_plan(n_sca, nside, ds_rows, amp_cols, n_full, n_lattice, L, max_np, objmask_setup=0, n_wcs=0, wcs_tables=0, gain_setup=False):
+    """Exact device bytes of a mosaic: n_sca SCAs, ``n_full`` ordered pairs with position arrays, ``n_lattice`` with lattices, ``n_wcs``
+    whose positions the kernels form from the WCSs (``pairs_wcs``; with any, ``wcs`` counts the descriptor table of the n_sca SCAs and
+    ``wcs_tables``, the bytes of the registered WCSs' error tables, each once).  Two psi
     stacks are counted: the one ``cost`` makes (in ``per_sca``) and one uploaded by ``residual`` when psi comes from the host; the bound
     ``cost_function`` lets go of its previous psi before it makes the next.  ``objmask_setup``: the temporaries of the object mask of ONE
-    SCA (``objmask.setup_bytes``), a peak during set-up that is not there per SCA; 0 when no SCA asks for one."""
+    SCA (``objmask.setup_bytes``), a peak during set-up that is not there per SCA; 0 when no SCA asks for one.  ``gain_setup``: some SCA's
+    gain is made from its WCS, whose two coordinate frames pass through the workspace."""
     sz = np.zeros(8, dtype=np.int64)
     check(lib.imcom_destripe_sizes(int(n_sca), int(nside), int(ds_rows), int(amp_cols or 0), int(L if n_lattice else 0), int(max_np),
-                                   int(n_full + n_lattice), ptr(sz)))
+                                   int(n_full + n_lattice + n_wcs), ptr(sz)))
+    wz = _wcs_sizes(n_sca, nside)
     nbins = int(sz[0])
     plan = {"nbins": nbins, "per_sca": int(sz[2]), "scas": int(sz[2]) * n_sca, "pairs_full": int(sz[3]) * n_full, "pairs_lattice": int(sz[4]) * n_lattice,
-            "weights": int(sz[7]) if n_lattice else 0, "params_and_resids": 8 * n_sca * nbins * 4 + 8 * n_sca, "workspace": int(max(sz[5], sz[6])),
+            "pairs_wcs": int(wz[0]) * n_wcs, "wcs": (int(wz[1]) if n_wcs else 0) + int(wcs_tables),
+            "weights": int(sz[7]) if n_lattice else 0, "params_and_resids": 8 * n_sca * nbins * 4 + 8 * n_sca,
+            "workspace": int(max(sz[5], sz[6], wz[3] if gain_setup else 0)),
             "psi_upload": 4 * n_sca * int(nside) ** 2}  # a psi handed to residual() from the host sits beside the one cost() made
     if objmask_setup:
         plan["objmask_setup"] = int(objmask_setup)
@@ -92,6 +116,7 @@ class DestripeEngine:
         self.nbins, self.n_col_blocks = int(sz[0]), int(sz[1])
         self._ctx, self._device = context, device
         self._scas, self._pairs, self.L = [], {}, 0
+        self._wcs = []  # per SCA: the DeviceWCS given to add_sca(wcs=) or first named by a formed pair, or None
         self._frozen = self._tables = None
         self._last = None  # (host psi, device psi) of the last cost_function call
 
@@ -100,13 +125,24 @@ class DestripeEngine:
     def n_sca(self):
         return len(self._scas)
 
-    def add_sca(self, image, mask, g_eff, object_mask=None):
+    def add_sca(self, image, mask, g_eff=None, object_mask=None, wcs=None):
         """``object_mask=(threshold_m, threshold_c, type)``: what ``Sca_img.__init__`` does after its masks (imdestripe.py:324-332) happens
         on the device when the mosaic is uploaded -- ``apply_object_mask`` of the image in its own type (float32 or float64), its
-        complement and-ed into ``mask``.  The image itself is not zeroed: the reference discards ``image_out`` there."""
+        complement and-ed into ``mask``.  The image itself is not zeroed: the reference discards ``image_out`` there.
+
+        ``wcs``: the SCA's WCS (anything ``pyimcom_amd.wcs.as_device_wcs`` takes), the one ``set_pairs_from_wcs`` and formed pairs refer
+        to.  With ``g_eff=None`` the gain is ``effective_gain(wcs)``, made at upload into the engine's own plane (no host array)."""
         if self._frozen is not None:
             raise RuntimeError("destripe: the mosaic is already on the device")
-        for arr in (image, mask, g_eff):
+        if wcs is not None:
+            from .wcs import as_device_wcs
+
+            wcs = as_device_wcs(wcs)
+            if wcs.array_shape[-1] != self.nside:
+                raise ValueError(f"destripe: the WCS describes an SCA of {wcs.array_shape[-1]} pixels a side, the engine's has {self.nside}")
+        if g_eff is None and wcs is None:
+            raise ValueError("destripe: an SCA has g_eff=, or wcs= to make it from")
+        for arr in (image, mask) + ((g_eff,) if g_eff is not None else ()):
             if tuple(arr.shape) != (self.nside, self.nside):
                 raise ValueError(f"destripe: an array of shape {tuple(arr.shape)}, the SCA is {self.nside} x {self.nside}")
         if object_mask is not None:
@@ -115,24 +151,41 @@ class DestripeEngine:
                 raise TypeError(f"destripe: the object mask is made of a float32 or float64 image, not {image.dtype}")
             object_mask = (threshold_m, threshold_c, str(kind))
         self._scas.append((image, mask, g_eff, object_mask))
+        self._wcs.append(wcs)
         return len(self._scas) - 1
 
-    def set_pair(self, a, b, x=None, y=None, lattice=None, L=None, wcs=None):
+    def set_pair(self, a, b, x=None, y=None, lattice=None, L=None, wcs=None, keep_positions=True):
         """The positions of SCA a's pixels in SCA b: ``x=`` and ``y=`` (the arrays of ``map_sca2sca``), ``lattice=``, or
         ``wcs=(target, ref)`` -- the two WCSs of ``map_sca2sca(all_wcs[a], all_wcs[b])``, anything ``pyimcom_amd.wcs.as_device_wcs`` takes: the
-        two float64 arrays are then formed on the device (pyimcom_amd.wcs.map_sca2sca) and kept as the full storage.  Exactly one way."""
+        two float64 arrays are then formed on the device (pyimcom_amd.wcs.map_sca2sca) and kept as the full storage.  Exactly one way.
+
+        ``keep_positions=False`` (with ``wcs=`` only): nothing of the grid's size is kept; the kernels form every position from the two
+        descriptors where they use it, the same bits as the stored arrays.  The descriptors are the SCAs': an SCA has one WCS in all its
+        formed pairs (and in ``add_sca(wcs=)``)."""
         a, b = int(a), int(b)
         if a == b or min(a, b) < 0 or max(a, b) >= self.n_sca:
             raise ValueError(f"destripe: pair ({a}, {b}) of {self.n_sca} SCAs")
         if (x is None) != (y is None) or (x is not None) + (lattice is not None) + (wcs is not None) != 1:
             raise ValueError("destripe: a pair has x= and y=, or lattice=, or wcs=")
+        if not keep_positions and wcs is None:
+            raise ValueError("destripe: keep_positions=False goes with wcs=: stored arrays and lattices are what is kept")
         if wcs is not None:
             from .wcs import as_device_wcs
 
             target, ref = (as_device_wcs(w) for w in wcs)
             if target.array_shape[-1] != self.nside:
                 raise ValueError(f"destripe: the target WCS describes an SCA of {target.array_shape[-1]} pixels a side, the engine's has {self.nside}")
-            self._pairs[(a, b)] = ("wcs", target, ref)
+            if keep_positions:
+                self._pairs[(a, b)] = ("wcs", target, ref)
+            else:
+                for s, w in ((a, target), (b, ref)):
+                    have = self._wcs[s]
+                    if have is not None and have is not w and not (np.array_equal(have.descriptor, w.descriptor) and have.table is w.table):
+                        raise ValueError(f"destripe: SCA {s} already has another WCS; the formed pairs of an SCA share its one descriptor")
+                for s, w in ((a, target), (b, ref)):
+                    if self._wcs[s] is None:
+                        self._wcs[s] = w
+                self._pairs[(a, b)] = ("formed",)
             self._tables = None
             return
         if lattice is not None:
@@ -159,11 +212,40 @@ class DestripeEngine:
             nb[a].append(b)
         return nb
 
+    def set_pairs_from_wcs(self, overlap_thresh=0.1, subsamp=8, pad=0, keep_positions=False):
+        """The neighbour table from the WCSs given to ``add_sca(wcs=)``: ``compareutils.get_overlap_matrix`` (pyimcom_amd.wcs), then the
+        rule of ``get_neighbors`` (imdestripe.py:1225-1228: ``ov_mat[k, j] >= overlap_thresh and j != k``), and ``set_pair`` for every
+        ordered pair found.  Returns ``(ov_mat, neighbors)`` in the reference's types: float32 [n, n] and the dict of lists that
+        ``conjugate_gradient(..., neighbors=...)`` takes."""
+        from .wcs import get_overlap_matrix
+
+        if self.n_sca == 0 or any(w is None for w in self._wcs):
+            raise ValueError("destripe: set_pairs_from_wcs needs every SCA registered with add_sca(wcs=)")
+        ov_mat = get_overlap_matrix(self._wcs, pad=pad, subsamp=subsamp, device=self._device, ctx=self._ctx)
+        n = self.n_sca
+        neighbors = {k: [j for j in range(n) if ov_mat[k, j] >= overlap_thresh and j != k] for k in range(n)}
+        for k, nb in neighbors.items():
+            for j in nb:
+                self.set_pair(k, j, wcs=(self._wcs[k], self._wcs[j]), keep_positions=keep_positions)
+        return ov_mat, neighbors
+
+    def _formed_wcs(self):
+        """The SCAs that a formed pair names."""
+        return sorted({s for k, p in self._pairs.items() if p[0] == "formed" for s in k})
+
     def plan(self):
         n_lat = sum(1 for p in self._pairs.values() if p[0] == "lattice")
+        n_wcs = sum(1 for p in self._pairs.values() if p[0] == "formed")
         nb = self.neighbors()
-        return memory_plan(max(self.n_sca, 1), self.nside, self.ds_rows, self.amp_cols, len(self._pairs) - n_lat, n_lat, self.L,
-                           max([len(v) for v in nb.values()] or [0]), objmask_setup=self._objmask_setup)
+        tables, seen = 0, set()
+        for w in self._wcs:  # each registered WCS's error table once (add_sca(wcs=) and the formed pairs' WCSs: their tables stay on the device)
+            t = w.table if w is not None else None
+            if t is not None and id(t[0]) not in seen:
+                seen.add(id(t[0]))
+                tables += 2 * int(t[0].shape[1]) ** 2 * (4 if "float32" in str(t[0].dtype) else 8)
+        return memory_plan(max(self.n_sca, 1), self.nside, self.ds_rows, self.amp_cols, len(self._pairs) - n_lat - n_wcs, n_lat, self.L,
+                           max([len(v) for v in nb.values()] or [0]), objmask_setup=self._objmask_setup, n_wcs=n_wcs, wcs_tables=tables,
+                           gain_setup=any(s is not None and s[2] is None for s in self._scas))
 
     @property
     def _objmask_setup(self):
@@ -212,7 +294,10 @@ class DestripeEngine:
                     objmask._apply(ctx, msk[i], omask, msk[i])
                     img[i].copy_(own.to(torch.float32))
                     del own, omask
-                gef[i].copy_(torch.as_tensor(ge if _is_torch(ge) else np.ascontiguousarray(ge, dtype=np.float32)).to(torch.float32))
+                if ge is None:  # imdestripe.py:281-297 from the WCS, straight into the plane
+                    effective_gain(self._wcs[i], self.nside, device=self.dev, ctx=ctx, out=gef[i])
+                else:
+                    gef[i].copy_(torch.as_tensor(ge if _is_torch(ge) else np.ascontiguousarray(ge, dtype=np.float32)).to(torch.float32))
             self._frozen = {"image": img, "mask": msk, "geff": gef, "neff": torch.zeros((n, ns, ns), dtype=torch.float64, device=self.dev),
                             "gmax": float(gef.abs().max().item())}  # set-up, once: the bound the fixed-point scale of the gradient needs
             self._scas = [None] * n
@@ -220,13 +305,18 @@ class DestripeEngine:
             from .stamps import free_device_bytes
 
             new = sum(16 * self.nside ** 2 if p[0] == "wcs" else sum(v.nbytes if not _is_torch(v) else 0 for v in p[1:])
-                      for p in self._pairs.values())  # pairs not yet on the device
+                      for p in self._pairs.values())  # pairs not yet on the device (a formed pair brings nothing of that size)
             if new > FILL * free_device_bytes(self.dev):
                 raise ImcomError(IMCOM_ERR_NOMEM, f"destripe: the pairs registered since the last evaluation need {new} more bytes on the device")
             keys = sorted(self._pairs)  # the order of the sums: (a, b) ascending, whatever the order of registration
             keep, px, py, pl = [], [], [], []
-            for k in keys:
+            rot = np.zeros((max(len(keys), 1), 9), dtype=np.float64)  # R_b R_a^T of the formed pairs, in the table's order
+            for i, k in enumerate(keys):
                 p = self._pairs[k]
+                if p[0] == "formed":
+                    check(lib.imcom_destripe_pair_rotation(ptr(self._wcs[k[0]].descriptor), ptr(self._wcs[k[1]].descriptor), ptr(rot[i])))
+                    px.append(0), py.append(0), pl.append(0)
+                    continue
                 if p[0] == "wcs":  # the positions of the whole target grid, formed where they are used
                     from .wcs import map_sca2sca
 
@@ -245,11 +335,31 @@ class DestripeEngine:
                     px.append(0), py.append(0), pl.append(la.data_ptr())
             W = torch.as_tensor(lattice_nodes(self.nside, self.L)[1], device=self.dev) if self.L else None
             arr = lambda v: np.asarray(v, dtype=np.uint64)  # noqa: E731
+            wcs = [None] * 7  # the WCS arguments of the three entries (include/imcom_hip.h): none when no pair is formed
+            formed = self._formed_wcs()
+            if formed:
+                from .wcs import DESC_LEN
+
+                desc = np.zeros((self.n_sca, DESC_LEN), dtype=np.float64)
+                tab = [(0, 0, 0, 0.0, 0.0)] * self.n_sca
+                for s in formed:
+                    desc[s] = self._wcs[s].descriptor
+                    ta = self._wcs[s]._table_args(self.dev)  # (the DeviceWCS keeps its table's tensor: one a WCS, whatever its pairs)
+                    tab[s] = (ta[0].value if ta[0] is not None else 0,) + tuple(ta[1:])
+                desc_d, rot_d = torch.as_tensor(desc).to(self.dev), torch.as_tensor(rot).to(self.dev)
+                keep += [desc_d, rot_d]
+                wcs = [desc_d]
+                if any(t[0] for t in tab):
+                    wcs += [arr([t[0] for t in tab]), np.asarray([t[1] for t in tab], dtype=np.int32), np.asarray([t[2] for t in tab], dtype=np.int32),
+                            np.asarray([t[3] for t in tab], dtype=np.float64), np.asarray([t[4] for t in tab], dtype=np.float64)]
+                else:
+                    wcs += [None] * 5
+                wcs.append(rot_d)
             self._tables = {"n": len(keys), "a": np.asarray([k[0] for k in keys], dtype=np.int32), "b": np.asarray([k[1] for k in keys], dtype=np.int32),
-                            "x": arr(px), "y": arr(py), "lat": arr(pl), "W": W, "keep": keep}
+                            "x": arr(px), "y": arr(py), "lat": arr(pl), "W": W, "keep": keep, "wcs": [ptr(v) for v in wcs], "wcs_keep": wcs}
             t, f = self._tables, self._frozen
             check(lib.imcom_destripe_neff(ctx.handle, self.n_sca, self.nside, self.L, ptr(f["mask"]), t["n"], ptr(t["a"]), ptr(t["b"]), ptr(t["x"]),
-                                          ptr(t["y"]), ptr(t["lat"]), ptr(W), ptr(f["neff"])))
+                                          ptr(t["y"]), ptr(t["lat"]), ptr(W), ptr(f["neff"]), *t["wcs"]))
         return self._frozen, self._tables
 
     @property
@@ -275,7 +385,7 @@ class DestripeEngine:
         eps = torch.empty(self.n_sca, dtype=torch.float64, device=self.dev)
         check(lib.imcom_destripe_cost(self._ctx.handle, self.n_sca, self.nside, self.ds_rows, self.amp_cols, self.L, ptr(f["image"]), ptr(f["mask"]),
                                       ptr(f["geff"]), ptr(f["neff"]), ptr(params), t["n"], ptr(t["a"]), ptr(t["b"]), ptr(t["x"]), ptr(t["y"]), ptr(t["lat"]),
-                                      ptr(t["W"]), m, th, self.N_eff_min, self.col_boundary_const, ptr(psi), ptr(eps)))
+                                      ptr(t["W"]), m, th, self.N_eff_min, self.col_boundary_const, ptr(psi), ptr(eps), *t["wcs"]))
         epsilon = 0.0
         for e in eps.cpu().numpy():  # (the copy waits for the stream: `params` may go)
             epsilon += float(e)
@@ -293,7 +403,7 @@ class DestripeEngine:
         out = torch.empty((3 if extrareturn else 1, self.n_sca, self.nbins), dtype=torch.float64, device=self.dev)
         check(lib.imcom_destripe_residual(self._ctx.handle, self.n_sca, self.nside, self.ds_rows, self.amp_cols, self.L, ptr(psi), ptr(f["geff"]),
                                           ptr(f["neff"]), t["n"], ptr(t["a"]), ptr(t["b"]), ptr(t["x"]), ptr(t["y"]), ptr(t["lat"]), ptr(t["W"]), m, th,
-                                          f["gmax"], ptr(out[0]), ptr(out[1]) if extrareturn else None, ptr(out[2]) if extrareturn else None))
+                                          f["gmax"], ptr(out[0]), ptr(out[1]) if extrareturn else None, ptr(out[2]) if extrareturn else None, *t["wcs"]))
         res = out.cpu().numpy()
         return (res[0], res[1], res[2]) if extrareturn else res[0]
 
@@ -324,6 +434,33 @@ class DestripeEngine:
         module.cost_function = self.cost_function
         module.residual_function = self.residual_function
         return module
+
+
+def effective_gain(wcs, nside=4088, dtype=np.float32, device_out=False, device="cuda:0", ctx=None, out=None):
+    """``Sca_img``'s effective gain from its WCS (imdestripe.py:281-297 with ``get_coordinates(pad=2.0)``, 451-474) on the device: (ra, dec)
+    in degrees of the ``(nside + 2)^2`` frame, the four centred differences, their determinant, ``1 / (|det| cos(dec))``.  ``wcs``: anything
+    ``pyimcom_amd.wcs.as_device_wcs`` takes.  dtype float32 (the reference's ``use_output_float``) or float64.  Kept from 292-293: the
+    determinants come back transposed against ``dec`` (seam 8).  ``out``: a contiguous device tensor [nside, nside] of
+    that dtype to write into."""
+    import torch
+
+    from .wcs import as_device_wcs
+
+    w, nside = as_device_wcs(wcs), int(nside)
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError(f"destripe: a gain as {dtype}; served are float32 and float64")
+    tdt = torch.float32 if dtype == np.float32 else torch.float64
+    dev = torch.device(device if out is None else out.device)
+    ctx = ctx or default_context(dev.index or 0)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    if out is None:
+        out = torch.empty((nside, nside), dtype=tdt, device=dev)
+    elif tuple(out.shape) != (nside, nside) or out.dtype != tdt or not out.is_contiguous():
+        raise ValueError(f"destripe: out of shape {tuple(out.shape)} and type {out.dtype}, expected a contiguous ({nside}, {nside}) of {tdt}")
+    tab = w._table_args(dev)
+    check(lib.imcom_wcs_effective_gain(ctx.handle, ptr(w.descriptor), tab[0], tab[1], tab[2], tab[3], tab[4], nside, ptr(out), int(dtype == np.float32), MEM_DEVICE))
+    return out if device_out else out.cpu().numpy()
 
 
 def _f64(a, dev):

@@ -8,6 +8,7 @@ it: ``compareutils.map_sca2sca`` and ``get_overlap_matrix`` (src/pyimcom/utils/c
     ov = pyimcom_amd.wcs.get_overlap_matrix(list_of_wcs, pad=0, subsamp=8)
     area = pyimcom_amd.wcs.pix_area(inwcs, [0, 4088, 0, 4088], pad=1, ovsamp=1)
     eng.set_pair(a, b, wcs=(all_wcs[a], all_wcs[b]))           # pyimcom_amd.destripe: the positions are formed on the device
+                                                               # (keep_positions=False: inside the destripe kernels, nothing stored)
 
 csrc/wcs.hip gives every point one owner thread; the descriptors travel as kernel arguments (csrc/wcs_core.h holds the arithmetic).
 
