@@ -353,10 +353,10 @@ __global__ __launch_bounds__(256, 1) void iter_block_cg_kernel(const double *__r
 // q_I += T P_K and q_K += T^T P_I (the transposed operand is the same 2 KB read again, through L1, with the lanes' roles swapped).
 // The first product lands where its vector lives (wave I mod 4 owns tile row I).  The second belongs to another wave's tile row K:
 // the tiles are visited column panel by column panel (K outer), a wave keeps ONE accumulator for its share of panel K's transposed
-// products, leaves it in an LDS ring when the panel is done, and after a barrier per `ring` panels the owner of tile row K adds the four
-// waves' pieces in wave order -- a fixed order of sums: results are reproducible.  LDS: P [ups][16], the ring 2 x ring x 4 x 2 KB.
+// products, leaves it in an LDS ring when the panel is done, and after a barrier per `ring` panels the owner of tile row K adds the BCG_NW
+// waves' pieces in wave order -- a fixed order of sums: results are reproducible.  LDS: P [ups][16], the ring 2 x ring x BCG_NW x 2 KB.
 // MEASURED (128 default-configuration stamps): 134 ms against the full-storage kernel's 142, the gather 8.6 against 16.5 -- the default for
-// unions up to 768 rows since round 6 (IMCOM_ITER_SYM=0 turns it off).
+// unions up to 864 rows (768 with the four waves of round 6; IMCOM_ITER_SYM=0 turns it off).
 // RG (the seven-row variant): the residual r lives in workspace beside x (with r among the accumulators and the fetch slots the
 // compiler spilled): read twice per step, updated by atomic adds without return.
 template <class F, int... Q>
@@ -464,7 +464,7 @@ __global__ __launch_bounds__(64 * BCG_NW, 1) void iter_block_cg_sym_kernel(const
         // the wave's other rows.  The panels are grouped in PHASES by the first row that still has a tile in them (qmin: it moves up one row
         // every BCG_NW panels), so that inside a phase the rows above qmin run as straight-line code -- no test per tile, the scheduler
         // overlaps one row's LDS round trips with another's MFMAs; only row qmin (whose last tile of the phase is the diagonal one) tests.
-        // Rows beyond the patch (the last row of three of the four waves) multiply an all-zero tile.
+        // Rows beyond the patch (the last rows of the waves past its last tile row) multiply an all-zero tile.
         f64x4 accv[TPW];
 #pragma unroll
         for (int q = 0; q < TPW; q++) accv[q] = f64x4{0.0, 0.0, 0.0, 0.0};
@@ -483,7 +483,7 @@ __global__ __launch_bounds__(64 * BCG_NW, 1) void iter_block_cg_sym_kernel(const
         long cs1 = ntile;  // first tile index of panel K + 1
         auto panel_end = [&](int K) __attribute__((always_inline)) {
             // panel K is complete for this wave: its transposed sums go to the ring; after every `ring` panels (and after the last) the
-            // owners of those tile rows add the four waves' pieces, in wave order
+            // owners of those tile rows add the eight waves' pieces, in wave order
             const int slot = ((K / ring) & 1) * ring + K % ring;
             double *dst = Rg + ((long)slot * BCG_NW + wave) * 256 + lane;
 #pragma unroll
@@ -552,9 +552,11 @@ __global__ __launch_bounds__(64 * BCG_NW, 1) void iter_block_cg_sym_kernel(const
             }
         };
         bcg_for_each(phase, std::make_integer_sequence<int, TPW>{});
-        // panels beyond this wave's last row (ntile > wave + 4 TPW - 3): nothing to multiply, but every wave ends EVERY panel -- its (zero)
-        // piece of the ring and the barriers (the first build lacked this: right at ntile = 45 = 4 x 12 - 3, wrong from 46 and for the
-        // eight-row variant from 30; tests/test_gpu_iter_default.py::test_point_source_known_answer_on_a_block caught it)
+        // panels beyond this wave's last row (K > wave + BCG_NW (TPW - 1): they exist from ntile = 26 with four rows per wave, 42 with six and
+        // 50 with seven): nothing to multiply, but every wave ends EVERY panel -- its (zero) piece of the ring and the barriers (the first,
+        // four-wave build lacked this: right at ntile = 45 = 4 x 12 - 3, wrong from 46 and for its eight-row variant from 30;
+        // tests/test_gpu_iter_default.py::test_point_source_known_answer_on_a_block caught it, tests/test_gpu_iter_edges.py brackets the three
+        // thresholds of the eight waves)
         for (int K = wave + BCG_NW * (TPW - 1) + 1; K < ntile; K++) panel_end(K);
         double pq = 0.0;
 #pragma unroll
@@ -616,8 +618,8 @@ size_t iter_block_patch_bytes(int ups) { return (size_t)ups * ups * 8 + 2 * (siz
 
 // One kappa node for the whole batch.  *max_union = the largest union selection: above iter_block_umax() nothing was solved and
 // the caller takes the per-pixel kernel.  T must have been zeroed.  `ws` holds iter_block_select_bytes() + `budget` bytes: the
-// patches go through the solver in groups whose sub-matrices fit the budget.  stats (device, 4 x u64) and steps (device,
-// [batch][m]) are optional.
+// patches go through the solver in groups whose sub-matrices fit the budget.  stats (device, 5 x u64: the fifth, the bytes streamed, only
+// from the half-storage kernel) and steps (device, [batch][m]) are optional.
 int launch_iter_block(imcom_ctx *ctx, const double *A, long lda, long strideA, const double *diag, long ldd, const double *B, long ldb,
                       const double *oyx, const double *iy, const double *ix, long ldxy, const int *n, int m, int W, int batch,
                       double rho, double rtol, int maxiter, float *T, long ldt, void *ws, size_t budget, int *max_union, int *steps,

@@ -448,7 +448,10 @@ extern "C" int imcom_solve_iter(imcom_ctx *ctx, int batch, const int *n, int ldn
     if (exact) total += big * (1 + nv) + (size_t)batch * np * np * 8;
     // The blocked solver keeps one dense sub-matrix per 4 x 4 patch (4 MB at the reference's default configuration, 64 patches per
     // stamp): the patches of a call go through it in groups that fit a fixed share of workspace instead of batch x 0.3 GB.
-    const size_t blk_budget = per_pixel ? 0 : std::min<size_t>((size_t)8 << 30, (size_t)batch * nblocks * iter_block_patch_bytes(iter_block_umax()));
+    // IMCOM_ITER_BUDGET_MB (positive): that share in MB instead of 8 GB, never below one patch -- small groups for tests/test_gpu_iter_edges.py.
+    const int budget_mb = env_int("IMCOM_ITER_BUDGET_MB", 0);
+    const size_t blk_cap = budget_mb > 0 ? std::max<size_t>((size_t)budget_mb << 20, iter_block_patch_bytes(iter_block_umax())) : (size_t)8 << 30;
+    const size_t blk_budget = per_pixel ? 0 : std::min<size_t>(blk_cap, (size_t)batch * nblocks * iter_block_patch_bytes(iter_block_umax()));
     if (!per_pixel) total += iter_block_select_bytes(batch, nblocks) + blk_budget + 8192;
     total += szM * 4 + 64;  // per-pixel step counts, statistics
     WsPlan plan;

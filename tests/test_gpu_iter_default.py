@@ -123,7 +123,7 @@ def test_iterative_against_cholesky_image_on_a_block():
 
 def test_full_storage_kernel_agrees_with_the_half_storage_default():
     """The blocked CG on the tiles on and below the diagonal only (csrc/iter_block.hip iter_block_cg_sym_kernel: every tile used for
-    q_I += T P_K and q_K += T^T P_I; half the bytes, a fixed order of sums) is the default for unions up to 768 rows; IMCOM_ITER_SYM=0 selects
+    q_I += T P_K and q_K += T^T P_I; half the bytes, a fixed order of sums) is the default for unions up to 864 rows; IMCOM_ITER_SYM=0 selects
     the full-storage kernel (which also serves the larger unions).  In a subprocess, one default-configuration stamp through the
     full-storage kernel against the default of this process: the same steps for nearly every pixel, T where they agree within 2e-3 of
     its largest entry."""
@@ -170,8 +170,8 @@ def test_deeper_stacks_take_the_wide_kernel_or_the_per_pixel_one(n_expo, blocked
     """The default configuration at other exposure depths.  Eight exposures: ~750 input pixels per acceptance disc, a 4 x 4 patch's union
     ~950 rows -- the full-storage solver's widest variant (up to 1024 rows).  Seven: 828 rows, the half-storage kernel's largest.  Ten: the unions pass 1024 (1190) and the call falls back to the
     per-pixel kernel (one workgroup per output pixel, lakernel.py:545-586 as written).  Six exposures with INPAD 0.61": unions of 740 rows
-    = 47 tiles -- the half-storage kernel where a wave's last tile row ends before the last column panel (4 x 12 - 3 = 45 < 47: the
-    panels beyond it are still ended by every wave).  All against the oracle on one stamp with the parity statement of
+    = 47 tiles -- the half-storage kernel where a wave's last tile row ends before the last column panel (eight waves of six rows: wave 0's
+    last row is tile row 40, so panels 41 .. 46 lie beyond it; they are still ended by every wave).  All against the oracle on one stamp with the parity statement of
     tests/parity.py iter_parity."""
     import dataclasses
 
