@@ -5,6 +5,7 @@ boundary recovery of Block.build_output_file (coadd.py:2163-2181)."""
 import numpy as np
 import torch
 
+from ._dev import bound_context
 from ._lib import check, default_context, lib, ptr
 
 
@@ -57,7 +58,7 @@ class BlockMaps:
     def add(self, res, jst, ist):
         """Add a finished batch: a StampBatchResult, or the list of n_out of them (StampBatch.results());
         jst/ist = 1-based OutStamp indices of its stamps (coadd.py:1963)."""
-        self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        bound_context(ctx=self.ctx)
         jst = np.ascontiguousarray(jst, dtype=np.int32)
         ist = np.ascontiguousarray(ist, dtype=np.int32)
         b = len(jst)
@@ -92,7 +93,7 @@ class BlockMaps:
         """Maps <- the layers' sums in the reference's stamp order (a no-op with fade == 0 or when nothing was added since)."""
         if not self._dirty:
             return
-        self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        bound_context(ctx=self.ctx)
         for name, lay in self.layers.items():
             for o in range(self.n_out):
                 dst = self._out_map[o] if name == "out_map" else self._maps[name][o]
@@ -138,7 +139,7 @@ class BlockMaps:
         coef, uns = self.COMPRESS[name]
         m = self.maps[name][:, fk : self.nside - fk, fk : self.nside - fk].contiguous()
         out = torch.empty(m.shape, dtype=torch.uint16 if uns else torch.int16, device=m.device)
-        self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        bound_context(ctx=self.ctx)
         check(lib.imcom_compress_map_f32(self.ctx.handle, ptr(m), m.numel(), coef, 1 if uns else 0, ptr(out)))
         return out
 
@@ -148,7 +149,7 @@ class BlockMaps:
         self.combine()
         assert not self._recovered, "the block boundary has been recovered already"
         self._recovered = True
-        self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        bound_context(ctx=self.ctx)
         h = self.ctx.handle
         check(lib.imcom_trapezoid_recover_f32(h, ptr(self.out_map), self.n_out * self.n_inframe, self.nside, self.nside, self.fade, 0, 0, 0, 0))
         w = postage_pad * self.n2

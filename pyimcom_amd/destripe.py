@@ -24,7 +24,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import MEM_DEVICE, ImcomError, check, default_context, lib, ptr
+from ._dev import bound_context, is_torch, np_dtype, staged
+from ._lib import MEM_DEVICE, ImcomError, check, lib, ptr
 
 __all__ = ["DestripeEngine", "MODELS", "lattice_nodes", "interpolate_bilinear", "transpose_bilinear", "memory_plan", "effective_gain", "formed_pair_bytes"]
 
@@ -34,10 +35,6 @@ MODELS = {"quadratic": 0, "absolute": 1, "huber_loss": 2}
 PRIMES = {"quad_prime": "quadratic", "abs_prime": "absolute", "huber_prime": "huber_loss"}
 FILL = 0.9  # share of the free device memory a mosaic may take
 MAX_L = 33
-
-
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
 
 
 def _unsupported(msg):
@@ -252,23 +249,15 @@ class DestripeEngine:
         """Bytes of the largest object-mask set-up among the registered SCAs (0: none asks for one; nothing once they are uploaded)."""
         from . import objmask
 
-        return max([objmask.setup_bytes(s[0].shape, str(s[0].dtype).replace("torch.", ""), s[3][2]) for s in self._scas if s is not None and s[3] is not None]
+        return max([objmask.setup_bytes(s[0].shape, np_dtype(s[0]).name, s[3][2]) for s in self._scas if s is not None and s[3] is not None]
                    or [0])
 
     # ---- device ----
-    def _bind_stream(self):
-        import torch
-
-        self.dev = torch.device(self._device)
-        if self._ctx is None:
-            self._ctx = default_context(self.dev.index or 0)
-        self._ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
-        return self._ctx
-
     def _freeze(self):
         import torch
 
-        ctx = self._bind_stream()
+        self.dev = torch.device(self._device)
+        ctx = self._ctx = bound_context(self.dev, self._ctx)
         if self._frozen is None:
             if not self._scas:
                 raise ValueError("destripe: no SCA registered")
@@ -283,13 +272,13 @@ class DestripeEngine:
             msk = torch.empty((n, ns, ns), dtype=torch.uint8, device=self.dev)
             gef = torch.empty((n, ns, ns), dtype=torch.float32, device=self.dev)
             for i, (im, ma, ge, om) in enumerate(self._scas):
-                msk[i].copy_(torch.as_tensor(ma if _is_torch(ma) else np.ascontiguousarray(ma).astype(bool)).to(torch.bool))
+                msk[i].copy_(staged(ma, self.dev, astype=np.bool_))
                 if om is None:
-                    img[i].copy_(torch.as_tensor(im if _is_torch(im) else np.ascontiguousarray(im, dtype=np.float32)).to(torch.float32))
+                    img[i].copy_(staged(im, self.dev, astype=np.float32))
                 else:  # imdestripe.py:324-332: self.mask *= ~object_mask, the image in its own type, image_out discarded
                     from . import objmask
 
-                    own = (im if _is_torch(im) else torch.as_tensor(np.ascontiguousarray(im))).to(self.dev).contiguous()
+                    own = staged(im, self.dev)
                     omask = objmask.object_mask(own, om[0], om[1], om[2])
                     objmask._apply(ctx, msk[i], omask, msk[i])
                     img[i].copy_(own.to(torch.float32))
@@ -297,14 +286,14 @@ class DestripeEngine:
                 if ge is None:  # imdestripe.py:281-297 from the WCS, straight into the plane
                     effective_gain(self._wcs[i], self.nside, device=self.dev, ctx=ctx, out=gef[i])
                 else:
-                    gef[i].copy_(torch.as_tensor(ge if _is_torch(ge) else np.ascontiguousarray(ge, dtype=np.float32)).to(torch.float32))
+                    gef[i].copy_(staged(ge, self.dev, astype=np.float32))
             self._frozen = {"image": img, "mask": msk, "geff": gef, "neff": torch.zeros((n, ns, ns), dtype=torch.float64, device=self.dev),
                             "gmax": float(gef.abs().max().item())}  # set-up, once: the bound the fixed-point scale of the gradient needs
             self._scas = [None] * n
         if self._tables is None:
             from .stamps import free_device_bytes
 
-            new = sum(16 * self.nside ** 2 if p[0] == "wcs" else sum(v.nbytes if not _is_torch(v) else 0 for v in p[1:])
+            new = sum(16 * self.nside ** 2 if p[0] == "wcs" else sum(v.nbytes if not is_torch(v) else 0 for v in p[1:])
                       for p in self._pairs.values())  # pairs not yet on the device (a formed pair brings nothing of that size)
             if new > FILL * free_device_bytes(self.dev):
                 raise ImcomError(IMCOM_ERR_NOMEM, f"destripe: the pairs registered since the last evaluation need {new} more bytes on the device")
@@ -323,13 +312,12 @@ class DestripeEngine:
                     xw, yw, _ = map_sca2sca(p[1], p[2], pad=0, device_out=True, device=self.dev, ctx=ctx)
                     p = ("full", xw.reshape(-1), yw.reshape(-1))
                 if p[0] == "full":
-                    xs = [torch.as_tensor(v if _is_torch(v) else np.ascontiguousarray(v, dtype=np.float64)).to(self.dev, torch.float64).contiguous()
-                          for v in p[1:]]
+                    xs = [staged(v, self.dev, astype=np.float64) for v in p[1:]]
                     self._pairs[k] = ("full", xs[0], xs[1])
                     keep += xs
                     px.append(xs[0].data_ptr()), py.append(xs[1].data_ptr()), pl.append(0)
                 else:
-                    la = torch.as_tensor(p[1] if _is_torch(p[1]) else np.ascontiguousarray(p[1], dtype=np.float64)).to(self.dev, torch.float64).contiguous()
+                    la = staged(p[1], self.dev, astype=np.float64)
                     self._pairs[k] = ("lattice", la)
                     keep.append(la)
                     px.append(0), py.append(0), pl.append(la.data_ptr())
@@ -378,7 +366,7 @@ class DestripeEngine:
 
         m, th = self._model(model, thresh)
         f, t = self._freeze()
-        params = torch.as_tensor(params if _is_torch(params) else np.ascontiguousarray(params, dtype=np.float64)).to(self.dev, torch.float64).contiguous()
+        params = staged(params, self.dev, astype=np.float64)
         if tuple(params.shape) != (self.n_sca, self.nbins):
             raise ValueError(f"destripe: params of shape {tuple(params.shape)}, expected {(self.n_sca, self.nbins)}")
         psi = torch.empty((self.n_sca, self.nside, self.nside), dtype=torch.float32, device=self.dev)
@@ -397,7 +385,7 @@ class DestripeEngine:
 
         m, th = self._model(model, thresh)
         f, t = self._freeze()
-        psi = torch.as_tensor(psi if _is_torch(psi) else np.ascontiguousarray(psi, dtype=np.float32)).to(self.dev, torch.float32).contiguous()
+        psi = staged(psi, self.dev, astype=np.float32)
         if tuple(psi.shape) != (self.n_sca, self.nside, self.nside):
             raise ValueError(f"destripe: psi of shape {tuple(psi.shape)}")
         out = torch.empty((3 if extrareturn else 1, self.n_sca, self.nbins), dtype=torch.float64, device=self.dev)
@@ -452,8 +440,7 @@ def effective_gain(wcs, nside=4088, dtype=np.float32, device_out=False, device="
         raise TypeError(f"destripe: a gain as {dtype}; served are float32 and float64")
     tdt = torch.float32 if dtype == np.float32 else torch.float64
     dev = torch.device(device if out is None else out.device)
-    ctx = ctx or default_context(dev.index or 0)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ctx = bound_context(dev, ctx)
     if out is None:
         out = torch.empty((nside, nside), dtype=tdt, device=dev)
     elif tuple(out.shape) != (nside, nside) or out.dtype != tdt or not out.is_contiguous():
@@ -464,9 +451,7 @@ def effective_gain(wcs, nside=4088, dtype=np.float32, device_out=False, device="
 
 
 def _f64(a, dev):
-    import torch
-
-    return torch.as_tensor(a if _is_torch(a) else np.ascontiguousarray(a, dtype=np.float64)).to(dev, torch.float64).contiguous()
+    return staged(a, dev, astype=np.float64)
 
 
 def interpolate_bilinear(image, g_eff, x, y, out=None, device="cuda:0", ctx=None):
@@ -475,8 +460,7 @@ def interpolate_bilinear(image, g_eff, x, y, out=None, device="cuda:0", ctx=None
     import torch
 
     dev = torch.device(device)
-    ctx = ctx or default_context(dev.index or 0)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ctx = bound_context(dev, ctx)
     src, gs, xs, ys = (_f64(v, dev) for v in (image, g_eff, x, y))
     res = torch.zeros(xs.shape, dtype=torch.float64, device=dev) if out is None else _f64(out, dev).clone()
     check(lib.imcom_destripe_interp(ctx.handle, ptr(src), ptr(gs), int(src.shape[0]), int(src.shape[1]), ptr(xs), ptr(ys), C.c_long(xs.numel()), ptr(res)))
@@ -489,8 +473,7 @@ def transpose_bilinear(image, x, y, shape, device="cuda:0", ctx=None):
     import torch
 
     dev = torch.device(device)
-    ctx = ctx or default_context(dev.index or 0)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ctx = bound_context(dev, ctx)
     img, xs, ys = (_f64(v, dev) for v in (image, x, y))
     res = torch.zeros(tuple(shape), dtype=torch.float64, device=dev)
     check(lib.imcom_destripe_interp_transpose(ctx.handle, ptr(img), ptr(xs), ptr(ys), C.c_long(img.numel()), int(shape[0]), int(shape[1]), ptr(res)))

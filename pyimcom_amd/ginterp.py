@@ -9,13 +9,10 @@ import ctypes as C
 
 import numpy as np
 
+from ._dev import bound_context, is_torch
 from ._lib import MEM_DEVICE, MEM_HOST, check, default_context, lib, ptr
 
 __all__ = ["InterpMatrix", "MultiInterp", "geometry", "stest_points"]
-
-
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
 
 
 def geometry(Rsearch):
@@ -45,7 +42,7 @@ def InterpMatrix(Rsearch, samp, x_out, y_out, Cov, epsilon=1.0e-7, stest=1):
     nn = posx.size
     cov = np.ascontiguousarray(np.asarray(Cov, dtype=np.float64).ravel()[:3])
     stest = int(stest)
-    if _is_torch(x_out):
+    if is_torch(x_out):
         import torch
 
         dev = x_out.device
@@ -56,7 +53,7 @@ def InterpMatrix(Rsearch, samp, x_out, y_out, Cov, epsilon=1.0e-7, stest=1):
         T = torch.empty((n, nn), dtype=torch.float64, device=dev)
         U = torch.empty(nu, dtype=torch.float64, device=dev)
         S = torch.empty(nu, dtype=torch.float64, device=dev)
-        ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        bound_context(ctx=ctx)
         mem = MEM_DEVICE
     else:
         x = np.ascontiguousarray(np.asarray(x_out, dtype=np.float64).ravel())
@@ -77,7 +74,7 @@ def InterpMatrix(Rsearch, samp, x_out, y_out, Cov, epsilon=1.0e-7, stest=1):
 def MultiInterp(in_array, in_mask, out_size, out_origin, out_transform, Rsearch, samp, Cov, epsilon=1.0e-7, stest=1, blocksize=393216):
     """``ginterp.MultiInterp`` (ginterp.py:189-340): returns (out_array [nlayer,] ny, nx in the input's dtype, out_mask bool [ny, nx],
     Umax, Smax).  2-D in -> 2-D out, 3-D in -> 3-D out; float32 and float64 inputs (others: TypeError)."""
-    tor = _is_torch(in_array)
+    tor = is_torch(in_array)
     ndim = in_array.ndim
     if ndim not in (2, 3):
         raise ValueError("in_array must be 2-D or 3-D")
@@ -116,7 +113,7 @@ def MultiInterp(in_array, in_mask, out_size, out_origin, out_transform, Rsearch,
         raise ValueError(f"in_mask shape {tuple(m.shape)} != {(ny_in, nx_in)}")
     ctx = default_context()
     if tor:
-        ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        bound_context(ctx=ctx)
     check(lib.imcom_ginterp_resample(ctx.handle, int(nlayer), int(ny_in), int(nx_in), ptr(a3), f64, ptr(m), ny, nx, ptr(origin), ptr(transform),
                                      float(Rsearch), float(samp), ptr(cov), float(epsilon), int(stest), int(blocksize), ptr(out), ptr(omask),
                                      ptr(us), mem))

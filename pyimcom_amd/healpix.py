@@ -29,8 +29,9 @@ import ctypes as C
 
 import numpy as np
 
+from ._dev import DEVICE, bound_context, device_of, is_torch, staged
 from ._lib import MEM_DEVICE, ImcomError, check, lib, ptr
-from .wcs import DEVICE, _ctx, _is_torch, as_device_wcs
+from .wcs import as_device_wcs
 
 __all__ = ["pix2ang", "ang2pix", "ang2vec", "vec2ang", "query_disc", "make_sph_grid", "generate_star_grid", "block_star_grid", "cap", "MAX_RES"]
 
@@ -59,11 +60,9 @@ def _to_device(a, dtype, device):
     """(contiguous 1-D tensor of ``a`` on the device, its shape, whether ``a`` was a tensor)."""
     import torch
 
-    was = _is_torch(a)
-    t = a if was else torch.as_tensor(np.ascontiguousarray(a, dtype=np.int64 if dtype is torch.int64 else np.float64))
+    was = is_torch(a)
     shape = tuple(a.shape) if was else np.shape(a)
-    dev = t.device if was and t.is_cuda else torch.device(device)
-    return t.to(dev, dtype).reshape(-1).contiguous(), shape, was
+    return staged(a, device_of(a, device=device), astype=np.int64 if dtype is torch.int64 else np.float64).reshape(-1), shape, was
 
 
 def _home(t, shape, stay):
@@ -81,7 +80,7 @@ def pix2ang(nside, ipix, nest=False, lonlat=False, device_out=False, device=DEVI
     _ring_only(nest)
     res = _res(nside)
     p, shape, was = _to_device(ipix, torch.int64, device)
-    ctx = _ctx(p.device, ctx)
+    ctx = bound_context(p.device, ctx)
     a, b = torch.empty(p.shape, dtype=torch.float64, device=p.device), torch.empty(p.shape, dtype=torch.float64, device=p.device)
     check(lib.imcom_healpix_pix2ang(ctx.handle, res, ptr(p), p.numel(), int(bool(lonlat)), ptr(a), ptr(b), MEM_DEVICE))
     stay = was or device_out
@@ -94,13 +93,13 @@ def ang2pix(nside, theta, phi, nest=False, lonlat=False, device_out=False, devic
 
     _ring_only(nest)
     res = _res(nside)
-    if not _is_torch(theta) and not _is_torch(phi):
+    if not is_torch(theta) and not is_torch(phi):
         theta, phi = np.broadcast_arrays(np.asarray(theta, dtype=np.float64), np.asarray(phi, dtype=np.float64))
     a, shape, was = _to_device(theta, torch.float64, device)
     b = _to_device(phi, torch.float64, a.device)[0].to(a.device)
     if a.shape != b.shape:
         raise ValueError(f"healpix: {a.numel()} and {b.numel()} angles")
-    ctx = _ctx(a.device, ctx)
+    ctx = bound_context(a.device, ctx)
     p = torch.empty(a.shape, dtype=torch.int64, device=a.device)
     check(lib.imcom_healpix_ang2pix(ctx.handle, res, ptr(a), ptr(b), a.numel(), int(bool(lonlat)), ptr(p), MEM_DEVICE))
     return _home(p, shape, was or device_out)
@@ -142,7 +141,7 @@ def cap(res, ra, dec, radius, full_disc=False, lonlat=False, wcs=None, origin=0,
     if unknown:
         raise ValueError(f"healpix: unknown outputs {sorted(unknown)}")
     dev = torch.device(device)
-    ctx = _ctx(dev, ctx)
+    ctx = bound_context(dev, ctx)
     desc, tab = None, (None, 0, 0, 0.0, 0.0)
     if wcs is not None:
         desc, tab = wcs.descriptor, wcs._table_args(dev)

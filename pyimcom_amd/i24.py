@@ -26,16 +26,12 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import I24Pars, ImcomError, check, default_context, lib, ptr
+from ._dev import DEVICE, bound_context, is_torch, np_dtype, staged, to_host
+from ._lib import I24Pars, ImcomError, check, lib, ptr
 
 __all__ = ["i24compress", "i24decompress", "compress_layers", "decompress_layers", "OverflowTable", "parse_pars", "check_pars", "tile_constants", "RECOGNIZED_SCHEMES"]
 
 RECOGNIZED_SCHEMES = ["I24A", "I24B"]  # i24.py:36
-DEVICE = "cuda:0"
-
-
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
 
 
 def parse_pars(pars):
@@ -89,13 +85,7 @@ class OverflowTable:
 
     def columns(self):
         """The three host arrays, for ``fits.Column(name=..., format="J" | "J" | "E", array=...)``."""
-        return tuple(v.cpu().numpy() if _is_torch(v) else np.asarray(v) for v in (self.data["y"], self.data["x"], self.data["value"]))
-
-
-def _bind(ctx, dev):
-    import torch
-
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        return tuple(to_host(v) for v in (self.data["y"], self.data["x"], self.data["value"]))
 
 
 def _frames_view(frames, dev):
@@ -103,8 +93,8 @@ def _frames_view(frames, dev):
     import torch
 
     if isinstance(frames, (list, tuple)):
-        frames = torch.stack([f.to(dev) if _is_torch(f) else torch.as_tensor(np.ascontiguousarray(f)).to(dev) for f in frames])
-    t = frames.to(dev) if _is_torch(frames) else torch.as_tensor(np.ascontiguousarray(frames)).to(dev)
+        frames = torch.stack([staged(f, dev, layout="any") for f in frames])
+    t = staged(frames, dev, layout="any")
     if t.dtype != torch.float32 or t.dim() != 3:
         raise TypeError(f"compress_layers: float32 [L, ny, nx], not {t.dtype} {tuple(t.shape)}")
     if t.numel() and not (t.stride(2) == 1 and t.stride(1) >= t.shape[2] and t.stride(0) >= 0):
@@ -128,7 +118,6 @@ def compress_layers(frames, pars_list, scheme="I24B", ctx=None, device=None):
     if L != len(pars_list):
         raise ValueError(f"compress_layers: {L} layers and {len(pars_list)} parameter dicts")
     sz = _sizes(recs, ny, nx, scheme)
-    ctx = ctx or default_context(dev.index or 0)
     n = ny * nx
     if scheme == "I24A":
         out = torch.empty((L, ny, nx), dtype=torch.int32, device=dev)
@@ -136,7 +125,7 @@ def compress_layers(frames, pars_list, scheme="I24B", ctx=None, device=None):
         out = torch.empty((L, sz[3] // n, ny, nx), dtype=torch.uint8, device=dev)
     state = torch.empty(sz[0] // 4, dtype=torch.int32, device=dev)
     counts = (C.c_long * L)()
-    _bind(ctx, dev)
+    ctx = bound_context(dev, ctx)
     args = (ptr(t), t.stride(0) if L > 1 else 0, t.stride(1), L, ny, nx, recs)
     check(lib.imcom_i24_compress(ctx.handle, *args, RECOGNIZED_SCHEMES.index(scheme), ptr(out), sz[3], ptr(state), state.numel() * 4, counts))
     total = sum(counts)
@@ -158,11 +147,11 @@ def _column(d, name, dev, index):
     import torch
 
     v = d[name]
-    if _is_torch(v):
+    if is_torch(v):
         return (v.clamp(-1, 2**31 - 1).to(torch.int32) if index else v.to(torch.float32)).to(dev).contiguous()
     a = np.asarray(v)
     a = np.clip(a.astype(np.int64), -1, 2**31 - 1).astype(np.int32) if index else a.astype(np.float32)
-    return torch.as_tensor(np.ascontiguousarray(a)).to(dev)
+    return staged(a, dev)
 
 
 def decompress_layers(cubes, pars_list, overflows=None, ctx=None, device=None):
@@ -175,11 +164,11 @@ def decompress_layers(cubes, pars_list, overflows=None, ctx=None, device=None):
     pars_list = list(pars_list)
     recs = _records(pars_list)
     L = len(pars_list)
-    whole = cubes if _is_torch(cubes) and cubes.is_cuda and cubes.is_contiguous() else None  # one stacked tensor: read in place
+    whole = cubes if is_torch(cubes) and cubes.is_cuda and cubes.is_contiguous() else None  # one stacked tensor: read in place
     cubes = list(cubes)
     if len(cubes) != L or L == 0:
         raise ValueError(f"decompress_layers: {len(cubes)} cubes and {L} parameter dicts")
-    kinds = [(str(c.dtype).replace("torch.", ""), len(c.shape)) for c in cubes]
+    kinds = [(np_dtype(c).name, len(c.shape)) for c in cubes]
     if all(k == ("uint8", 3) for k in kinds):
         scheme = "I24B"
     elif all(k == ("int32", 2) for k in kinds):
@@ -193,11 +182,10 @@ def decompress_layers(cubes, pars_list, overflows=None, ctx=None, device=None):
     for l, c in enumerate(cubes):
         if scheme == "I24B" and c.shape[0] != (recs[l].bitkeep + 7) // 8:
             raise ImcomError(-1, f"i24_decompress: a cube of {c.shape[0]} byte planes for layer {l}, BITKEEP = {recs[l].bitkeep} needs {(recs[l].bitkeep + 7) // 8}")
-    ts = [c.to(dev) if _is_torch(c) else torch.as_tensor(np.ascontiguousarray(c)).to(dev) for c in cubes]
+    ts = [staged(c, dev, layout="any") for c in cubes]
     overflows = list(overflows) if overflows is not None else [None] * L
     if len(overflows) != L:
         raise ValueError(f"decompress_layers: {len(overflows)} overflow tables and {L} layers")
-    ctx = ctx or default_context(dev.index or 0)
     out = torch.empty((L, ny, nx), dtype=torch.float32, device=dev)
     planes = [c.shape[0] if scheme == "I24B" else 0 for c in ts]
     for g in sorted(set(planes)):  # one call for the layers of one cube depth (in practice: one)
@@ -220,7 +208,7 @@ def decompress_layers(cubes, pars_list, overflows=None, ctx=None, device=None):
                 raise ValueError(f"decompress_layers: the overflow columns of layer {l} differ in length")
         tab = {name: (torch.cat([c.reshape(-1) for c in v]) if v else None) for name, v in cols.items()}
         dst = out if len(idx) == L else torch.empty((len(idx), ny, nx), dtype=torch.float32, device=dev)
-        _bind(ctx, dev)
+        ctx = bound_context(dev, ctx)
         check(lib.imcom_i24_decompress(ctx.handle, ptr(src), src[0].numel() * src.element_size(), int(g), RECOGNIZED_SCHEMES.index(scheme), len(idx), ny, nx, grecs,
                                        ptr(tab["y"]), ptr(tab["x"]), ptr(tab["value"]), counts if tab["y"] is not None else None, ptr(dst)))
         if dst is not out:
@@ -234,7 +222,7 @@ def i24compress(im, scheme, pars, ctx=None):
     unrecognised scheme hands the input back (469-470)."""
     if scheme not in RECOGNIZED_SCHEMES:
         return im, None
-    tin = _is_torch(im)
+    tin = is_torch(im)
     if not (len(im.shape) == 2 and (str(im.dtype) in ("float32", "torch.float32"))):
         raise TypeError("Can't initialize I24Cube: a 2D float32 image is what the device codec compresses.")
     cubes, ovs = compress_layers(im[None], [pars], scheme, ctx=ctx, device=im.device if tin and im.is_cuda else None)
@@ -250,8 +238,8 @@ def i24decompress(im, scheme, pars, overflow=None, ctx=None):
     numpy out, a torch tensor in a torch tensor on the device it came from.  An unrecognised scheme hands the input back (507-508)."""
     if scheme not in RECOGNIZED_SCHEMES:
         return im
-    tin = _is_torch(im)
-    name = str(im.dtype).replace("torch.", "")
+    tin = is_torch(im)
+    name = np_dtype(im).name
     if not ((len(im.shape) == 3 and name == "uint8") or (len(im.shape) == 2 and name == "int32")):
         raise TypeError("Can't initialize I24Cube: a 3D uint8 cube or a 2D int32 image is what the device codec decompresses.")
     out = decompress_layers([im], [pars], [overflow], ctx=ctx, device=im.device if tin and im.is_cuda else None)[0]

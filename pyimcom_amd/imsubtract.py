@@ -14,16 +14,13 @@ import math
 
 import numpy as np
 
+from ._dev import bound_context, device_of, is_torch, staged, to_host
 from ._lib import MEM_DEVICE, MEM_HOST, check, default_context, lib, ptr
 
 __all__ = ["geometry", "legendre_order", "phase_tables", "prepare_kernel", "plan_bands", "canvas_add", "subtract_long_range", "LongRangeSubtractor"]
 
 FILL = 0.8  # share of the free device memory a band plan may use
 TILE_ROWS = 32  # output rows of a workgroup (csrc/imsubtract.hip: IMS_TY); bands are cut at multiples of it
-
-
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
 
 
 def geometry(axis_num, oversamp, nside):
@@ -119,14 +116,14 @@ def canvas_add(canvas, H, area, oversamp, bottom, left, ctx=None):
     ctx = ctx or default_context()
     s = int(oversamp)
     hh, hw = H.shape
-    if _is_torch(canvas):
+    if is_torch(canvas):
         import torch
 
         if not (canvas.dtype == torch.float32 and canvas.is_contiguous() and canvas.ndim == 2 and canvas.shape[0] == canvas.shape[1]):
             raise ValueError("canvas must be a contiguous square float32 tensor")
         H = torch.as_tensor(H, dtype=torch.float64, device=canvas.device).contiguous()
         area = torch.as_tensor(area, dtype=torch.float32, device=canvas.device).contiguous()
-        ctx.set_stream(torch.cuda.current_stream(canvas.device).cuda_stream)
+        bound_context(ctx=ctx)
         mem = MEM_DEVICE
     else:
         if not (isinstance(canvas, np.ndarray) and canvas.dtype == np.float32 and canvas.flags.c_contiguous and canvas.ndim == 2
@@ -155,8 +152,8 @@ class LongRangeSubtractor:
         import torch
 
         self.dev = torch.device(device)
-        self.ctx = ctx or default_context(self.dev.index or 0)
-        K = K.detach().cpu().numpy() if _is_torch(K) else np.asarray(K)
+        self.ctx = bound_context(self.dev, ctx)
+        K = to_host(K)
         if K.ndim != 3 or K.shape[1] != K.shape[2]:
             raise ValueError("K is [ncoeff, axis_num, axis_num]")
         self.ncoeff, self.ax = int(K.shape[0]), int(K.shape[1])
@@ -169,15 +166,10 @@ class LongRangeSubtractor:
         sz = np.zeros(6, dtype=np.int64)
         check(lib.imcom_imsub_sizes(self.ax, self.s, self.nside, self.Nl, ptr(sz)))
         self.kf = torch.empty(int(sz[5]), dtype=torch.float64, device=self.dev)
-        planes = torch.as_tensor(np.ascontiguousarray(K[:self.Nl * self.Nl], dtype=np.float32), device=self.dev)
-        self._bind()
+        planes = staged(K[:self.Nl * self.Nl], self.dev, astype=np.float32)
+        bound_context(ctx=self.ctx)
         check(lib.imcom_imsub_prepare_kernel_f32(self.ctx.handle, ptr(planes), self.Nl * self.Nl, self.ax, self.Nl, self.s, ptr(self.kf), MEM_DEVICE))
         torch.cuda.current_stream(self.dev).synchronize()  # `planes` is dropped on return
-
-    def _bind(self):
-        import torch
-
-        self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
 
     def plan(self, canvas_on_device, free_bytes=None):
         if free_bytes is None:
@@ -196,23 +188,23 @@ class LongRangeSubtractor:
             raise ValueError(f"image is {tuple(image.shape)}, the SCA {nside} x {nside}")
         if tuple(canvas.shape) != (A, A):
             raise ValueError(f"canvas is {tuple(canvas.shape)}, oversamp * (nside + 2 * I_pad) = {A}")
-        host_image = not _is_torch(image)
+        host_image = not is_torch(image)
         if host_image:
             if not (isinstance(image, np.ndarray) and image.dtype == np.float32):
                 raise ValueError("image must be a float32 array")
-            img_d = torch.as_tensor(np.ascontiguousarray(image), device=self.dev)
+            img_d = staged(image, self.dev)
         else:
             if not (image.dtype == torch.float32 and image.is_contiguous() and image.device == self.dev):
                 raise ValueError("image must be a contiguous float32 tensor on the subtractor's device")
             img_d = image
         kh = torch.zeros((nside, nside), dtype=torch.float64, device=self.dev) if return_kh else None
         if self.kf is not None:
-            on_dev = _is_torch(canvas)
+            on_dev = is_torch(canvas)
             if on_dev and not (canvas.dtype == torch.float32 and canvas.is_contiguous() and canvas.device == self.dev):
                 raise ValueError("canvas must be a contiguous float32 tensor on the subtractor's device")
             if not on_dev and canvas.dtype != np.float32:
                 raise ValueError("canvas must be float32")
-            self._bind()
+            bound_context(ctx=self.ctx)
             for y0, ny in (bands if bands is not None else self.plan(on_dev)):
                 lo, hi = band_rows(y0, ny, ax, s, self.first)
                 band = canvas if on_dev else torch.from_numpy(np.array(canvas[lo:hi], dtype=np.float32, order="C", subok=False)).to(self.dev)
@@ -237,5 +229,5 @@ def subtract_long_range(image, canvas, K, *, oversamp, nside, porder=-1, bands=N
     """One layer of imsubtract.py:689-707: ``image -= KH[first_index::oversamp, first_index::oversamp]`` for the canvas ``canvas`` and the
     kernel cube ``K`` [Ncoeff, axis_num, axis_num] (``prepare_kernel`` first for ``bin2x2``); ``porder`` is PORDER_IMSUBTRACT.  For
     several layers of one SCA keep a ``LongRangeSubtractor``."""
-    dev = image.device if _is_torch(image) else (canvas.device if _is_torch(canvas) else "cuda:0")
+    dev = device_of(image, canvas)
     return LongRangeSubtractor(K, oversamp, nside, porder, device=dev, ctx=ctx).subtract(image, canvas, bands=bands, return_kh=return_kh)

@@ -11,16 +11,13 @@ Arrays may be numpy (host in, host out) or torch CUDA tensors (device in, device
 
 import numpy as np
 
+from ._dev import bound_context, is_torch
 from ._lib import MEM_DEVICE, MEM_HOST, check, default_context, lib, ptr
 
 __all__ = ["lpoly_arr", "psf_from_cube", "draw_stars", "on_chip", "star_image", "make_image_from_grid"]
 
 NB = 128  # tile of the library's GEMM (csrc/common.h): smooth_and_pad works on images padded to it
 FILL = 0.8  # share of the free device memory a chunk is planned into
-
-
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
 
 
 def lpoly_arr(porder, u, v):
@@ -57,13 +54,13 @@ def psf_from_cube(cube, lpoly, tophatwidth, gaussiansigma=0.0, scale=1.0, ctx=No
         raise ValueError(f"lpoly shape {tuple(lpoly.shape)} does not match a cube of {na} planes")
     npad = pad_width(tophatwidth, gaussiansigma)
     shape = (S, ny + 2 * npad, nx + 2 * npad)
-    if _is_torch(cube):
+    if is_torch(cube):
         import torch
 
         cube = cube.to(torch.float64).contiguous()
         lpoly = torch.as_tensor(lpoly, dtype=torch.float64, device=cube.device).contiguous()
         out = torch.empty(shape, dtype=torch.float64, device=cube.device)
-        ctx.set_stream(torch.cuda.current_stream(cube.device).cuda_stream)
+        bound_context(ctx=ctx)
         mem = MEM_DEVICE
     else:
         cube = np.ascontiguousarray(cube, dtype=np.float64)
@@ -82,7 +79,7 @@ def draw_stars(psfs, xsca, ysca, nside, oversamp, d=64, out=None, ctx=None):
     ctx = ctx or default_context()
     S, py, px = psfs.shape
     nside = int(nside)
-    if _is_torch(psfs):
+    if is_torch(psfs):
         import torch
 
         dev = psfs.device
@@ -91,9 +88,9 @@ def draw_stars(psfs, xsca, ysca, nside, oversamp, d=64, out=None, ctx=None):
         ysca = torch.as_tensor(ysca, dtype=torch.float64, device=dev).contiguous()
         if out is None:
             out = torch.zeros((nside, nside), dtype=torch.float64, device=dev)
-        elif not (_is_torch(out) and out.dtype == torch.float64 and out.is_contiguous() and out.device == dev):
+        elif not (is_torch(out) and out.dtype == torch.float64 and out.is_contiguous() and out.device == dev):
             raise ValueError("out must be a contiguous float64 tensor on the PSFs' device")
-        ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        bound_context(ctx=ctx)
         mem = MEM_DEVICE
     else:
         psfs = np.ascontiguousarray(psfs, dtype=np.float64)

@@ -24,12 +24,12 @@ import ctypes as C
 import numpy as np
 
 from . import wcs as _wcs
+from ._dev import DEVICE, bound_context
 from ._lib import check, lib, ptr
 from .select import InStampPool
 
 __all__ = ["relevant_cells", "npixmax_of", "partition_image", "Partition", "PoolBuilder"]
 
-DEVICE = "cuda:0"
 _ARCSEC = 4.84813681109536e-06  # Settings.arcsec (config.py:87)
 
 
@@ -112,7 +112,7 @@ class Partition:
             raise ValueError(f"inpool: input layers of shape {tuple(indata.shape)}, expected (n_inframe, {self.nside}, {self.nside})")
         nst = self.pix_count.shape[0]
         data = torch.empty((indata.shape[0], nst, nst, self.max_count), dtype=torch.float32, device=dev)
-        ctx = _wcs._ctx(dev, self._ctx)
+        ctx = bound_context(dev, self._ctx)
         check(lib.imcom_extract_layers(ctx.handle, ptr(indata), indata.shape[0], self.nside, ptr(self.y_idx), ptr(self.x_idx), ptr(self.pix_count), nst * nst,
                                        self.y_idx.shape[2], self.max_count, ptr(data)))
         return data
@@ -160,7 +160,7 @@ def partition_image(inwcs, outwcs, use_instamps, n2, n1P, npixmax, mask=None, ns
     part.x_val = torch.zeros_like(part.y_val)
     part.pix_count = torch.zeros((nst, nst), dtype=torch.uint32, device=dev)
     pix_lower, pix_upper = _limits(n2, n1P)
-    ctx = _wcs._ctx(dev, ctx)
+    ctx = bound_context(dev, ctx)
     ta, tb = a._table_args(dev), b._table_args(dev)
     rel = np.ascontiguousarray(matrix.view(np.uint8))
     nvis = C.c_long(0)
@@ -235,7 +235,7 @@ class PoolBuilder:
             raise ValueError(f"inpool: {data.shape[0]} input layers, the pool holds {self.n_inframe}")
         nst = self.n1P + 2
         counts = part.pix_count_host.reshape(1, nst * nst)
-        ctx = _wcs._ctx(data.device, self.ctx)
+        ctx = bound_context(data.device, self.ctx)
         x, y, d, _, _ = _assemble(ctx, [(part.x_val, part.y_val, data)], counts, [self.npixmax], [part.max_count], [nst * nst * part.max_count], self.n_inframe,
                                   data.device, False)
         self.lists.append((x, y, d))
@@ -249,7 +249,7 @@ class PoolBuilder:
         nst = self.n1P + 2
         dev = torch.device(self.device)
         counts = np.array(self.counts, dtype=np.uint32).reshape(len(self.lists), nst * nst)
-        ctx = _wcs._ctx(dev, self.ctx)
+        ctx = bound_context(dev, self.ctx)
         x, y, data, expo, inst_off = _assemble(ctx, self.lists, counts, [0] * len(self.lists), [0] * len(self.lists), [t[0].numel() for t in self.lists],
                                                self.n_inframe, dev, True)
         pix_cumsum = np.zeros((nst * nst, len(self.lists) + 1), dtype=np.uint32)

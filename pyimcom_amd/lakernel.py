@@ -20,6 +20,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._dev import torch_dtype
 from ._lib import MEM_HOST, check, default_context, lib, ptr
 
 
@@ -33,7 +34,7 @@ def _host_out(shape, dtype=np.float32, zero=False):
     import torch
 
     make = torch.zeros if zero else torch.empty
-    return make(tuple(int(v) for v in shape), dtype=getattr(torch, np.dtype(dtype).name), pin_memory=True).numpy()
+    return make(tuple(int(v) for v in shape), dtype=torch_dtype(dtype), pin_memory=True).numpy()
 
 
 class _repair_memory:

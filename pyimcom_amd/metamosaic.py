@@ -28,8 +28,9 @@ reference's; ``to_host()`` gives the arrays ``to_file`` writes."""
 import numpy as np
 
 from . import ginterp
+from ._dev import DEVICE, bound_context, np_dtype, staged
 from ._lib import check, lib, ptr
-from .wcs import DEVICE, DeviceWCS, _ctx, _is_torch
+from .wcs import DeviceWCS
 
 __all__ = ["DeviceMetaMosaic", "block_windows", "mosaic_header", "shear_geometry", "orig_geometry", "PIXSCALE_NATIVE", "CODE_TYPES"]
 
@@ -249,31 +250,13 @@ class DeviceMetaMosaic:
         self.wcs = DeviceWCS.from_header(self.header, array_shape=(ns, ns))
 
     def _context(self):
-        return _ctx(self.device, self._ctx)
+        return bound_context(self.device, self._ctx)
 
     # ---- blocks ----
     def _on_device(self, a, what, dtypes):
         """A tensor of ``a`` on the mosaic's device with unit stride along its rows, read in place when it already is one."""
-        import torch
-
-        if not _is_torch(a):
-            a = np.asarray(a)
-        name = str(a.dtype).replace("torch.", "") if _is_torch(a) else a.dtype.name
-        if name not in dtypes:
-            raise TypeError(f"DeviceMetaMosaic: {what} of dtype {name} (supported: {', '.join(dtypes)})")
-        if _is_torch(a):
-            t = a.to(self.device)
-        else:
-            if not a.dtype.isnative:  # (a FITS array is big-endian)
-                a = a.astype(a.dtype.newbyteorder("="))
-            a = np.ascontiguousarray(a)
-            if a.dtype == np.uint16:  # (torch moves uint16 as bytes of the same layout)
-                t = torch.as_tensor(a.view(np.int16)).to(self.device).view(torch.uint16)
-            else:
-                t = torch.as_tensor(a).to(self.device)
-        if t.numel() and t.stride(-1) != 1:
-            t = t.contiguous()
-        return t, name
+        t = staged(a, self.device, dtypes, f"DeviceMetaMosaic: {what} of dtype {{name}} (supported: {', '.join(dtypes)})", layout="rows")
+        return t, np_dtype(t).name
 
     def paste(self, window, primary, fidelity, sigma, fid_bels, sig_bels):
         """The launch of ``add_block`` with an explicit ``window`` = (symin, symax, sxmin, sxmax, cx, cy)."""
@@ -326,10 +309,7 @@ class DeviceMetaMosaic:
 
     def maskpix(self, extramask):
         """223-240: pixels that are True in ``extramask`` (numpy or tensor, [Nside, Nside]) are masked."""
-        import torch
-
-        e = extramask if _is_torch(extramask) else torch.as_tensor(np.ascontiguousarray(np.asarray(extramask) != 0))
-        e = (e != 0).to(self.device).contiguous()
+        e = staged(extramask, self.device) != 0
         if tuple(e.shape) != (self.Nside, self.Nside):
             raise ValueError(f"maskpix: a mask of shape {tuple(e.shape)} for a mosaic of side {self.Nside}")
         self._cut(self.in_mask, 0, None, None, e)
@@ -348,8 +328,7 @@ class DeviceMetaMosaic:
 
         cols = []
         for v in (x, y, r):
-            t = v if _is_torch(v) else torch.as_tensor(np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()))
-            cols.append(t.to(self.device, torch.float64).reshape(-1).contiguous())
+            cols.append(staged(v, self.device, astype=np.float64).reshape(-1))
         n = cols[0].numel()
         if cols[1].numel() != n or cols[2].numel() != n:
             raise ValueError(f"mask_caps_pixels: {[c.numel() for c in cols]} positions and radii")

@@ -31,8 +31,9 @@ import math
 
 import numpy as np
 
-from ._lib import MEM_DEVICE, check, default_context, lib, ptr
-from .simmask import _halves, _out
+from ._dev import bound_context, out_array
+from ._lib import MEM_DEVICE, check, lib, ptr
+from .simmask import halves
 
 __all__ = ["standard_normal", "normal", "white_noise_frame", "noise_1f", "noise_1f_amp", "noise_1f_frame", "last_info"]
 
@@ -80,13 +81,13 @@ def standard_normal(bitgen_or_seed, shape, offset=0, device=None, return_info=Fa
     if offset < 0 or offset >= 1 << 128 or any(s < 0 for s in shape):
         raise ValueError("standard_normal: offset in 0 .. 2^128 - 1 and a shape without negative sides")
     count = int(np.prod(shape, dtype=object)) if shape else 1
-    out, mem, ctx = _out(shape, np.float64, device)
+    out, mem, ctx = out_array(shape, np.float64, device)
     cap = C.c_long(0)
     check(lib.imcom_pcg64_normal_sizes(count, C.byref(cap)))
-    tail_idx, _, _ = _out((cap.value,), np.int64, device)
-    tail_raw, _, _ = _out((cap.value, 2), np.uint64 if device is None else np.int64, device)
+    tail_idx, _, _ = out_array((cap.value,), np.int64, device)
+    tail_raw, _, _ = out_array((cap.value, 2), np.uint64 if device is None else np.int64, device)
     info = np.zeros(4, dtype=np.uint64)
-    check(lib.imcom_pcg64_normal_ex(ctx.handle, *_halves(state), *_halves(inc), *_halves(offset), count, ptr(out) if count else None,
+    check(lib.imcom_pcg64_normal_ex(ctx.handle, *halves(state), *halves(inc), *halves(offset), count, ptr(out) if count else None,
                                     ptr(tail_idx) if count else None, ptr(tail_raw) if count else None, ptr(info), mem, _tile, _chunk_tiles, _guard))
     consumed, slow, tails, undecided = (int(v) for v in info)
     if undecided:  # the whole request from numpy; the state it leaves is the one to keep
@@ -168,8 +169,7 @@ def noise_1f(normals, amp, nch, w, border=4, return_block=False):
     if amp.shape != (length,):
         raise ValueError("noise_1f: amp has one entry per draw of a channel")
     dev = normals.device
-    ctx = default_context(dev.index or 0)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ctx = bound_context(dev)
     shape = (max(length // 2 // max(w, 1) - 2 * border, 0), max(nch * w - 2 * border, 0))
     frame = torch.empty(shape, dtype=torch.float32, device=dev)
     block = torch.empty((nch, length // 2), dtype=torch.float64, device=dev) if return_block else None

@@ -11,7 +11,8 @@ A numpy input gives numpy results; a torch tensor on the device gives torch resu
 
 import numpy as np
 
-from ._lib import MEM_DEVICE, check, default_context, lib, ptr
+from ._dev import bound_context, is_torch, staged, to_host
+from ._lib import MEM_DEVICE, check, lib, ptr
 
 __all__ = ["power_spectrum_2d", "windowed_norm", "radial_labels", "azimuthal_average", "wavenumbers", "NoiseSpectra", "noise_anal_call", "get_norm",
            "route", "ROUTE_LINES", "ROUTE_DENSE", "ROUTE_TWOLEVEL"]
@@ -19,10 +20,6 @@ __all__ = ["power_spectrum_2d", "windowed_norm", "radial_labels", "azimuthal_ave
 FILL = 0.8  # share of the free device memory a chunk plan may use
 ROUTE_LINES, ROUTE_DENSE, ROUTE_TWOLEVEL = 1, 2, 3  # csrc/noisespec.hip: wave-per-line butterflies, dense DFT on the MFMA engine, N1 x N2 lines in LDS
 MAXN = 4096
-
-
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
 
 
 def route(L):
@@ -60,7 +57,7 @@ def _plan_frames(L, nframe, bin8, route_, free_bytes):
 
 def windowed_norm(norm, w):
     """noise_diagnostics.py:432: the norm of a windowed frame, ``norm * mean(w^2)``."""
-    w = w.detach().cpu().numpy() if _is_torch(w) else np.asarray(w)
+    w = to_host(w)
     return norm * np.average(w.astype(np.float64) ** 2)
 
 
@@ -74,7 +71,7 @@ def power_spectrum_2d(frames, norm=1.0, window=None, bin8=True, ctx=None, route=
 
     from .stamps import free_device_bytes
 
-    torch_in = _is_torch(frames)
+    torch_in = is_torch(frames)
     shape = tuple(frames.shape)
     if len(shape) not in (2, 3) or shape[-1] != shape[-2]:
         raise ValueError("frames is [L, L] or [n, L, L]")
@@ -92,20 +89,18 @@ def power_spectrum_2d(frames, norm=1.0, window=None, bin8=True, ctx=None, route=
     else:
         dev = torch.device(device)
         a = np.asarray(frames)
-        a = np.ascontiguousarray(a, dtype=a.dtype if a.dtype in (np.float32, np.float64) else np.float64)
-        t = torch.as_tensor(a[None] if single else a, device=dev)
+        t = staged(a[None] if single else a, dev, astype=None if a.dtype in (np.float32, np.float64) else np.float64)
     nframe = int(t.shape[0])
     if nframe < 1:
         raise ValueError("no frames")
     norms = np.ascontiguousarray(np.broadcast_to(np.asarray(norm, dtype=np.float64), (nframe,)))
     w = None
     if window is not None:
-        w = (window.to(device=dev, dtype=torch.float64) if _is_torch(window) else torch.as_tensor(np.asarray(window, dtype=np.float64), device=dev)).contiguous()
-    ctx = ctx or default_context(dev.index or 0)
+        w = staged(window, dev, astype=np.float64)
+    ctx = bound_context(dev, ctx)
     n = L // 8 if bin8 else L
     out = torch.empty((nframe, n, n), dtype=torch.float64, device=dev)
     step = int(frames_per_call) if frames_per_call else _plan_frames(L, nframe, bin8, route, free_device_bytes(dev))
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     fstride = int(t.stride(0)) if nframe > 1 else L * int(t.stride(1))
     for f0 in range(0, nframe, step):
         k = min(step, nframe - f0)
@@ -131,7 +126,7 @@ def azimuthal_average(image, nradbins, rbin=None, ridx=None, ctx=None, device="c
     ``arange(1, rbin.max() + 1)`` is refused."""
     import torch
 
-    torch_in = _is_torch(image)
+    torch_in = is_torch(image)
     shape = tuple(image.shape)
     if len(shape) not in (2, 3) or shape[-1] != shape[-2]:
         raise ValueError("image is [n, n] or [f, n, n]")
@@ -142,7 +137,7 @@ def azimuthal_average(image, nradbins, rbin=None, ridx=None, ctx=None, device="c
         raise ValueError(f"labels of shape {tuple(rbin.shape)} for an image of side {n}")
     nidx = int(rbin.max())
     if ridx is not None:
-        r = ridx.detach().cpu().numpy() if _is_torch(ridx) else np.asarray(ridx)
+        r = to_host(ridx)
         if r.shape != (nidx,) or not np.array_equal(r, np.arange(1, nidx + 1)):
             raise ValueError("ridx must be arange(1, rbin.max() + 1)")
     if nidx < 1:
@@ -154,13 +149,12 @@ def azimuthal_average(image, nradbins, rbin=None, ridx=None, ctx=None, device="c
         img = image.contiguous()
     else:
         dev = torch.device(device)
-        img = torch.as_tensor(np.ascontiguousarray(image, dtype=np.float64), device=dev)
-    lab = (rbin.to(device=dev, dtype=torch.int32) if _is_torch(rbin) else torch.as_tensor(np.ascontiguousarray(rbin, dtype=np.int32), device=dev)).contiguous()
+        img = staged(image, dev, astype=np.float64)
+    lab = staged(rbin, dev, astype=np.int32)
     nframe = 1 if single else int(shape[0])
-    ctx = ctx or default_context(dev.index or 0)
+    ctx = bound_context(dev, ctx)
     mean = torch.empty((nframe, nidx), dtype=torch.float64, device=dev)
     err = torch.empty_like(mean)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     check(lib.imcom_noiseps_radial(ctx.handle, ptr(img), nframe, n, ptr(lab), nidx, ptr(mean), ptr(err), MEM_DEVICE))
     torch.cuda.current_stream(dev).synchronize()
     if single:
@@ -200,12 +194,12 @@ class NoiseSpectra:
         _check_side(L, bin8)
         self.L, self.nlayers, self.bins, self.bin8 = int(L), int(nlayers), int(bins), bool(bin8)
         self.dev = torch.device(device)
-        self.ctx = ctx or default_context(self.dev.index or 0)
+        self.ctx = bound_context(self.dev, ctx)
         self.n = self.L // 8 if bin8 else self.L
         self.nradbins = self.L // 16  # 1257-1259
         self.rbin = radial_labels(self.n, self.nradbins)  # 1260-1262
         self.ridx = np.arange(1, self.rbin.max() + 1)
-        self._rbin_dev = torch.as_tensor(np.ascontiguousarray(self.rbin, dtype=np.int32), device=self.dev)
+        self._rbin_dev = staged(self.rbin, self.dev, astype=np.int32)
         self.window = None if window is None else torch.as_tensor(np.asarray(window, dtype=np.float64), device=self.dev)
         self.norm = np.broadcast_to(np.asarray(norm if window is None else windowed_norm(norm, window), dtype=np.float64), (self.nlayers,)).copy()
         self.wavenumbers = wavenumbers(self.L, self.nradbins)  # 1266 (the caller divides by s_out, 1268)
@@ -222,12 +216,12 @@ class NoiseSpectra:
             raise ValueError(f"frames of shape {tuple(frames.shape)}, not {(self.nlayers, self.L, self.L)}")
         if not 0 <= int(coverage_bin) < self.bins:
             raise ValueError(f"coverage bin {coverage_bin} of {self.bins}")
-        if not _is_torch(frames):
+        if not is_torch(frames):
             a = np.asarray(frames)
-            frames = torch.as_tensor(np.ascontiguousarray(a, dtype=a.dtype if a.dtype in (np.float32, np.float64) else np.float64), device=self.dev)
+            frames = staged(a, self.dev, astype=None if a.dtype in (np.float32, np.float64) else np.float64)
         ps2d = power_spectrum_2d(frames, self.norm, self.window, self.bin8, ctx=self.ctx)
         mean, err = azimuthal_average(ps2d, self.nradbins, self._rbin_dev, ctx=self.ctx)
-        self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+        bound_context(ctx=self.ctx)
         check(lib.imcom_noiseps_accumulate(self.ctx.handle, ptr(ps2d), ptr(mean), ptr(err), self.nlayers, self.n, len(self.ridx), self.bins, int(coverage_bin),
                                            ptr(self.ps2d_all), ptr(self.ps1d_all)))
         torch.cuda.current_stream(self.dev).synchronize()  # ps2d, mean, err go back to the allocator
@@ -272,7 +266,7 @@ def noise_anal_call(self, padding=False, bin_=True, rbin=None, ridx=None):
     self.ps2d = power_spectrum_2d(indata[:Lcut, :Lcut], norm, None, True)
     nradbins = Lcut // 16
     mean, err = azimuthal_average(self.ps2d, nradbins, rbin, ridx)
-    if _is_torch(mean):
+    if is_torch(mean):
         import torch
 
         self.ps1d = torch.stack((mean, err), dim=1)

@@ -23,7 +23,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import MEM_DEVICE, ImcomError, check, default_context, lib, ptr
+from ._dev import DEVICE, bound_context, compare_value, device_of, is_torch, np_dtype, staged  # noqa: F401 (DEVICE: a public name here)
+from ._lib import MEM_DEVICE, ImcomError, check, lib, ptr
 
 __all__ = ["apply_object_mask", "object_mask", "median", "order_statistics", "propagate", "dilate", "jwst_valid", "setup_bytes", "DILATE_TILE",
            "PROPAGATE_TILE", "DILATE_MAX_R"]
@@ -31,70 +32,27 @@ __all__ = ["apply_object_mask", "object_mask", "median", "order_statistics", "pr
 DILATE_TILE = (32, 48)  # rows, columns of output pixels of a dilation workgroup (csrc/objmask.hip)
 PROPAGATE_TILE = 62  # side of a propagation tile
 DILATE_MAX_R = 8
-DEVICE = "cuda:0"  # where a numpy image is worked on
 IMCOM_ERR_UNSUPPORTED = -4
 _WORKSPACE = 64 << 10  # the selection's state and histograms, rounded up
 
 
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
-
-
-def _bind(dev):
-    import torch
-
-    ctx = default_context(dev.index or 0)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    return ctx
-
-
-def _device_of(*arrays, device=None):
-    import torch
-
-    for a in arrays:
-        if _is_torch(a) and a.is_cuda:
-            return a.device
-    return torch.device(device or DEVICE)
-
-
 def _image(a, dev):
     """A contiguous float32 / float64 tensor on ``dev`` with the values of ``a``."""
-    import torch
-
-    if _is_torch(a):
-        if a.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"objmask: a float32 or float64 image, not {a.dtype}")
-        return a.to(dev).contiguous()
-    a = np.asarray(a)
-    if a.dtype not in (np.float32, np.float64):
-        raise TypeError(f"objmask: a float32 or float64 image, not {a.dtype}")
-    return torch.as_tensor(np.ascontiguousarray(a)).to(dev)
+    return staged(a, dev, (np.float32, np.float64), "objmask: a float32 or float64 image, not {dtype}")
 
 
 def _flags(a, dev, shape=None):
     """A contiguous uint8 tensor on ``dev``: a bool / uint8 tensor as it is, anything else as ``!= 0``."""
     import torch
 
-    if _is_torch(a):
-        t = a.to(dev)
-        t = t.view(torch.uint8) if t.dtype == torch.bool else t if t.dtype == torch.uint8 else (t != 0).view(torch.uint8)
-    else:
+    if not is_torch(a):
         a = np.asarray(a)
-        t = torch.as_tensor(np.ascontiguousarray(a if a.dtype == np.bool_ else a != 0).view(np.uint8)).to(dev)
+        a = a if a.dtype == np.bool_ else a != 0
+    t = staged(a, dev, layout="any")
+    t = t.view(torch.uint8) if t.dtype == torch.bool else t if t.dtype == torch.uint8 else (t != 0).view(torch.uint8)
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise ValueError(f"objmask: flags of shape {tuple(t.shape)} for an array of shape {tuple(shape)}")
     return t.contiguous()
-
-
-def _np_dtype(t):
-    return np.dtype(str(t.dtype).replace("torch.", ""))
-
-
-def compare_value(threshold, dtype):
-    """The float64 value of ``threshold`` after the rounding numpy applies to it in ``array_of_dtype >= threshold``: a Python float and a
-    scalar of the array's type take the array's type, a wider numpy scalar promotes the comparison (and float32 -> float64 is exact)."""
-    with np.errstate(over="ignore", invalid="ignore"):
-        return float(np.asarray(threshold).astype(np.result_type(dtype, threshold)))
 
 
 # ---- the kernels' callers: tensors on one device in, tensors out ----
@@ -124,7 +82,7 @@ def _threshold(ctx, t, bkg, t_seed, t_grow=None, finite_only=True):
 
     seed = torch.empty(t.shape, dtype=torch.uint8, device=t.device)
     grow = torch.empty_like(seed) if t_grow is not None else None
-    dt = _np_dtype(t)
+    dt = np_dtype(t)
     check(lib.imcom_mask_threshold(ctx.handle, ptr(t), int(t.dtype == torch.float64), t.numel(), float(bkg), compare_value(t_seed, dt),
                                    compare_value(t_grow, dt) if t_grow is not None else 0.0, int(finite_only), ptr(seed), ptr(grow), MEM_DEVICE))
     return seed, grow
@@ -136,7 +94,7 @@ def _clip(ctx, t, keep_in=None, bkg=0.0, limit=0.0):
 
     keep = torch.empty(t.shape, dtype=torch.uint8, device=t.device)
     count = torch.empty(1, dtype=torch.int64, device=t.device)
-    check(lib.imcom_mask_clip(ctx.handle, ptr(t), int(t.dtype == torch.float64), t.numel(), ptr(keep_in), float(bkg), compare_value(limit, _np_dtype(t)),
+    check(lib.imcom_mask_clip(ctx.handle, ptr(t), int(t.dtype == torch.float64), t.numel(), ptr(keep_in), float(bkg), compare_value(limit, np_dtype(t)),
                               ptr(keep), ptr(count), MEM_DEVICE))
     return keep, int(count.item())
 
@@ -170,7 +128,7 @@ def _apply(ctx, src, mask, dst):
 def _result(t, like, as_bool=True):
     import torch
 
-    if _is_torch(like):
+    if is_torch(like):
         return t.view(torch.bool) if as_bool and t.dtype == torch.uint8 else t
     a = t.cpu().numpy()
     return a.view(np.bool_) if as_bool and a.dtype == np.uint8 else a
@@ -179,12 +137,12 @@ def _result(t, like, as_bool=True):
 def order_statistics(a, k, where=None, device=None):
     """(k-th smallest, (k + 1)-th smallest or the largest) of ``a`` (of its elements where ``where``), as ``np.partition`` places them;
     NaNs sort last.  numpy scalars of the array's type."""
-    dev = _device_of(a, where, device=device)
+    dev = device_of(a, where, device=device)
     t = _image(a, dev)
     f = None if where is None else _flags(where, dev, t.shape)
     if not 0 <= int(k) < t.numel():  # (the entry reads a negative rank as "the middle" and refuses one past the array)
         raise ValueError(f"objmask: rank {k} of {t.numel()} values")
-    lo, hi, m, _ = _select(_bind(dev), t, f, int(k))
+    lo, hi, m, _ = _select(bound_context(dev), t, f, int(k))
     if int(k) >= m:  # fewer flagged than the rank asks for
         raise ValueError(f"objmask: rank {k} of {m} values")
     return lo, hi
@@ -194,23 +152,23 @@ def median(a, where=None, center=None, device=None):
     """``np.median(a)`` or ``np.median(a[where])`` for a float32 / float64 array or tensor of any shape: exact, a numpy scalar of the
     array's type.  Any NaN among the values gives NaN, as numpy does; so does an empty selection.  With ``center`` the median of
     ``np.abs(a - center)``, the differences formed in the array's type on the fly."""
-    dev = _device_of(a, where, device=device)
+    dev = device_of(a, where, device=device)
     t = _image(a, dev)
     f = None if where is None else _flags(where, dev, t.shape)
     if t.numel() == 0:
-        return _np_dtype(t).type(np.nan)
-    return _median(_bind(dev), t, f, None if center is None else _np_dtype(t).type(center))
+        return np_dtype(t).type(np.nan)
+    return _median(bound_context(dev), t, f, None if center is None else np_dtype(t).type(center))
 
 
 def propagate(seed, grow, device=None, return_sweeps=False):
     """``scipy.ndimage.binary_propagation(seed, mask=grow)`` for 2-D images, default structure (4-connectivity), border 0.  With
     ``return_sweeps`` also the number of sweeps over the tiles that it took."""
-    dev = _device_of(seed, grow, device=device)
+    dev = device_of(seed, grow, device=device)
     s = _flags(seed, dev)
     g = _flags(grow, dev, s.shape)
     if s.dim() != 2 or s.numel() == 0:
         raise ValueError(f"objmask: a 2-D image, not shape {tuple(s.shape)}")
-    out, sweeps = _propagate(_bind(dev), s, g)
+    out, sweeps = _propagate(bound_context(dev), s, g)
     return (_result(out, seed), sweeps) if return_sweeps else _result(out, seed)
 
 
@@ -218,17 +176,17 @@ def dilate(mask, r, device=None):
     """``scipy.ndimage.binary_dilation(mask, structure=np.ones((2 r + 1, 2 r + 1)))`` for a 2-D image, border 0; 1 <= r <= 8."""
     if not 1 <= int(r) <= DILATE_MAX_R:
         raise ImcomError(IMCOM_ERR_UNSUPPORTED, f"objmask: dilation radius {r}, served are 1 .. {DILATE_MAX_R}")
-    dev = _device_of(mask, device=device)
+    dev = device_of(mask, device=device)
     m = _flags(mask, dev)
     if m.dim() != 2 or m.numel() == 0:
         raise ValueError(f"objmask: a 2-D image, not shape {tuple(m.shape)}")
-    return _result(_dilate(_bind(dev), m, r), mask)
+    return _result(_dilate(bound_context(dev), m, r), mask)
 
 
 def jwst_valid(image, mask=None):
     """``Sca_img.apply_jwst_mask`` (imdestripe.py:412-419): (the image with its NaNs set to 0, ``mask & ~isnan(image)``, or the valid
     pixels alone without a mask).  Two torch expressions for a tensor, the reference's numpy lines for an array."""
-    if _is_torch(image):
+    if is_torch(image):
         import torch
 
         valid = ~torch.isnan(image)
@@ -252,7 +210,7 @@ def object_mask(image, threshold_m=0, threshold_c=0.3, type="fits", details=None
     if image.dim() != 2 or image.numel() == 0:
         raise ValueError(f"objmask: a 2-D image, not shape {tuple(image.shape)}")
     t = _image(image, image.device)
-    ctx = _bind(t.device)
+    ctx = bound_context(t.device)
     d = details if details is not None else {}
     if type == "jwst":
         keep, count = _clip(ctx, t)  # valid = isfinite(image)
@@ -304,13 +262,13 @@ def apply_object_mask(image, mask=None, threshold_m=0, threshold_c=0.3, inplace=
     tensor image) is applied as it is, as in the reference.  ``type``: "jwst" takes the clipped-background, seed-and-grow route, anything
     else ("fits", "asdf") the plain threshold.  An image without a finite pixel gives an empty mask with "jwst".  The standard deviation
     the "jwst" route falls back to when the MAD is 0 is numpy's, on the downloaded kept pixels (module docstring)."""
-    on_device = _is_torch(image)
+    on_device = is_torch(image)
     if not on_device:
         if mask is not None and isinstance(mask, np.ndarray):  # 814-815: nothing to compute
             neighbor_mask = mask
         else:
             image = np.asarray(image) if not isinstance(image, np.ndarray) else image
-            t = _image(image, _device_of(device=device))
+            t = _image(image, device_of(device=device))
             neighbor_mask = object_mask(t, threshold_m, threshold_c, type, details).cpu().numpy().view(np.bool_)
         if inplace:
             image[neighbor_mask] = 0
@@ -318,12 +276,12 @@ def apply_object_mask(image, mask=None, threshold_m=0, threshold_c=0.3, inplace=
         return np.where(neighbor_mask, 0, image), neighbor_mask
     import torch
 
-    t = _image(image, image.device if image.is_cuda else _device_of(device=device))
-    if mask is not None and (_is_torch(mask) or isinstance(mask, np.ndarray)):
+    t = _image(image, device_of(image, device=device))
+    if mask is not None and (is_torch(mask) or isinstance(mask, np.ndarray)):
         m = _flags(mask, t.device, t.shape)
     else:
         m = object_mask(t, threshold_m, threshold_c, type, details)
-    ctx = _bind(t.device)
+    ctx = bound_context(t.device)
     if inplace:
         _apply(ctx, t, m, t)
         if t.data_ptr() != image.data_ptr():  # a view that was not contiguous, or an image that lived elsewhere

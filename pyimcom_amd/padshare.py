@@ -12,7 +12,8 @@ import re
 import numpy as np
 import torch
 
-from ._lib import PADSHARE_NO_FLOOR, PadshareMap, check, default_context, lib, ptr
+from ._dev import bound_context
+from ._lib import PADSHARE_NO_FLOOR, PadshareMap, check, lib, ptr
 
 DIRECTIONS = ("left", "right", "bottom", "top")
 # coadd.py:2247-2305, in the order of hdu_names[5:]: HDU name -> (outmaps letter, BlockMaps name, UNIT value, UNIT comment)
@@ -143,8 +144,7 @@ def update(mine, theirs, direction, add_mode=True, zero_floor=None, ctx=None, su
     n2, postage_pad, fk = mine.n2, mine.postage_pad, mine.fk
     if (theirs.n2, theirs.postage_pad, theirs.fk) != (n2, postage_pad, fk):
         raise ValueError("the blocks differ in n2, postage_pad or fade_kernel")
-    ctx = ctx or default_context()
-    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    ctx = bound_context(ctx=ctx)
     h, d, add, width = ctx.handle, DIRECTIONS.index(direction), 1 if add_mode else 0, postage_pad * n2
     pm, pu = mine.primary, theirs.primary
     check(lib.imcom_padshare_layers(h, d, add, NsideP, width, fk, n_out * nlayer, ptr(pm), pm.stride(2), pm.stride(1), ptr(pu), pu.stride(2), pu.stride(1)))

@@ -5,14 +5,11 @@ Arrays may be numpy (host in, host out) or torch CUDA tensors (device in, device
 
 import numpy as np
 
+from ._dev import bound_context, is_torch
 from ._lib import MEM_DEVICE, MEM_HOST, check, default_context, lib, ptr
 
 QFILTER_NATIVE = [1.155, 1.456, 1.250, 1.021, 0.834, 0.689, 0.491, 1.009, 0.000, 1.159, 1.685]  # config.py:85-98
 OBSC = 0.31
-
-
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
 
 
 def _out(shape, like, device):
@@ -23,20 +20,12 @@ def _out(shape, like, device):
     return np.empty(shape, dtype=np.float64)
 
 
-def _bind(ctx, device):
-    """Device-mode calls enqueue on the context's stream and return without a sync: that stream must be torch's current
-    one, or torch could consume the output tensor before the kernel has written it."""
-    if device is not None:
-        import torch
-
-        ctx.set_stream(torch.cuda.current_stream(torch.device(device)).cuda_stream)
-
-
 def psf_gaussian(n, sigmax, sigmay, device=None, ctx=None):
     """``OutPSF.psf_gaussian`` (psfutil.py:117-146); ``device`` given -> torch tensor on that device."""
     ctx = ctx or default_context()
     out = _out((n, n), "torch" if device else "numpy", device)
-    _bind(ctx, device)
+    if device is not None:  # (a device-mode call returns without a sync: it must be on torch's current stream)
+        bound_context(ctx=ctx)
     check(lib.imcom_psf_gaussian(ctx.handle, int(n), float(sigmax), float(sigmay), ptr(out), MEM_DEVICE if device else MEM_HOST))
     return out
 
@@ -45,7 +34,8 @@ def psf_simple_airy(n, ldp, obsc=0.0, tophat_conv=0.0, sigma=0.0, device=None, c
     """``OutPSF.psf_simple_airy`` (psfutil.py:148-223)."""
     ctx = ctx or default_context()
     out = _out((n, n), "torch" if device else "numpy", device)
-    _bind(ctx, device)
+    if device is not None:  # (a device-mode call returns without a sync: it must be on torch's current stream)
+        bound_context(ctx=ctx)
     check(lib.imcom_psf_simple_airy(ctx.handle, int(n), float(ldp), float(obsc), float(tophat_conv), float(sigma), ptr(out),
                                     MEM_DEVICE if device else MEM_HOST))
     return out
@@ -59,12 +49,12 @@ def smooth_and_pad(inArray, tophatwidth=0.0, gaussiansigma=0.0, ctx=None):
     a = inArray[None] if single else inArray
     n, ny, nx = a.shape
     npad = int(lib.imcom_smooth_pad_width(float(tophatwidth), float(gaussiansigma)))
-    if _is_torch(a):
+    if is_torch(a):
         import torch
 
         a = a.to(torch.float64).contiguous()
         out = torch.empty((n, ny + 2 * npad, nx + 2 * npad), dtype=torch.float64, device=a.device)
-        ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        bound_context(ctx=ctx)
         mem = MEM_DEVICE
     else:
         a = np.ascontiguousarray(a, dtype=np.float64)
@@ -90,13 +80,11 @@ def sample_psf(psf, nsamp, yxco=None, psf_circ=False, psf_norm=False, ctx=None):
     psf [n_psf, ny, nx]; yxco [n_psf, 2, nsamp, nsamp] (y, x offsets from the image centre) or None for the
     unrotated grid.  Returns psf_arr [n_psf, nsamp, nsamp]."""
     ctx = ctx or default_context()
-    tor = _is_torch(psf)
+    tor = is_torch(psf)
     if tor:
-        import torch
-
         psf = psf.contiguous()
         yxco = None if yxco is None else yxco.contiguous()
-        ctx.set_stream(torch.cuda.current_stream(psf.device).cuda_stream)
+        bound_context(ctx=ctx)
     else:
         psf = np.ascontiguousarray(psf, dtype=np.float64)
         yxco = None if yxco is None else np.ascontiguousarray(yxco, dtype=np.float64)
@@ -134,15 +122,13 @@ def lattice_positions(lattice, W, nsamp, ctx=None):
     nodes (imcom_lattice_positions): ``lattice`` [count, 2, L, L] (numpy -> numpy out, torch device tensor -> device out), ``W`` from
     ``lattice_nodes_and_weights``.  Replaces the nsamp^2 WCS evaluations per PSF group and exposure of psfutil.py:751-771."""
     ctx = ctx or default_context()
-    tor = _is_torch(lattice)
+    tor = is_torch(lattice)
     count, two, L, L2 = lattice.shape
     assert two == 2 and L == L2 and W.shape == (nsamp, L)
     W = np.ascontiguousarray(W, dtype=np.float64)
     if tor:
-        import torch
-
         lattice = lattice.contiguous()
-        ctx.set_stream(torch.cuda.current_stream(lattice.device).cuda_stream)
+        bound_context(ctx=ctx)
     else:
         lattice = np.ascontiguousarray(lattice, dtype=np.float64)
     out = _out((count, 2, nsamp, nsamp), "torch" if tor else "numpy", lattice.device if tor else None)
@@ -156,14 +142,12 @@ def affine_positions(cardinal, nsamp, ctx=None):
     along x and y, flipped to (y, x), halved, times dscale (``cardinal_points``) -- the map is taken as affine over the PSF window.
     numpy -> numpy out, torch device tensor -> device out."""
     ctx = ctx or default_context()
-    tor = _is_torch(cardinal)
+    tor = is_torch(cardinal)
     count, four, two = cardinal.shape
     assert four == 4 and two == 2
     if tor:
-        import torch
-
         cardinal = cardinal.contiguous()
-        ctx.set_stream(torch.cuda.current_stream(cardinal.device).cuda_stream)
+        bound_context(ctx=ctx)
     else:
         cardinal = np.ascontiguousarray(cardinal, dtype=np.float64)
     out = _out((count, 2, nsamp, nsamp), "torch" if tor else "numpy", cardinal.device if tor else None)

@@ -20,7 +20,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import MEM_DEVICE, check, default_context, lib, ptr
+from ._dev import DEVICE, bound_context, device_of, is_torch, np_dtype, staged, to_host
+from ._lib import MEM_DEVICE, check, lib, ptr
 
 __all__ = ["StreamingQuantiles", "layer_percentiles", "dynrange_tables", "percentile_ranks", "percentile_from_order_statistics", "code_bin_table",
            "coded_map_histogram", "LAYER_PCTILES", "RING_PCTILES", "MAX_SEGMENTS", "MAX_RANKS"]
@@ -28,11 +29,6 @@ __all__ = ["StreamingQuantiles", "layer_percentiles", "dynrange_tables", "percen
 MAX_SEGMENTS, MAX_RANKS = 64, 32
 LAYER_PCTILES = [0, 0.01, 0.1, 1, 5, 25, 50, 75, 95, 99, 99.9, 99.99, 100]  # layer_diagnostics.py:103
 RING_PCTILES = [1, 5, 25, 50, 75, 95, 99]  # dynrange.py:237
-DEVICE = "cuda:0"
-
-
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
 
 
 class StreamingQuantiles:
@@ -54,42 +50,26 @@ class StreamingQuantiles:
             raise TypeError(f"StreamingQuantiles: float32 or float64, not {self.dtype}")
         self.S, self.R = int(n_segments), int(n_ranks)
         self.device = torch.device(device or DEVICE)
-        self.ctx = ctx or default_context(self.device.index or 0)
-        self._tdtype = torch.float32 if self.dtype == np.float32 else torch.float64
+        self.ctx = bound_context(self.device, ctx)
         sz = (C.c_long * 4)()
         check(lib.imcom_quant_sizes(self.S, self.R, int(self.dtype == np.float64), sz))
         self.passes = int(sz[1])
         self._state = torch.empty(int(sz[0]) // 8, dtype=torch.int64, device=self.device)
         self._h = C.c_void_p()
-        self._bind()
         check(lib.imcom_quant_begin(self.ctx.handle, self.S, self.R, int(self.dtype == np.float64), ptr(self._state), self._state.numel() * 8, C.byref(self._h)))
         self._nranks = 0
 
-    def _bind(self):
-        import torch
-
-        self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _values(self, a):
-        import torch
-
-        if _is_torch(a):
-            if a.dtype != self._tdtype:
-                raise TypeError(f"StreamingQuantiles of {self.dtype}: a chunk of {a.dtype}")
-            return a.to(self.device)
-        a = np.asarray(a)
-        if a.dtype != self.dtype:
-            raise TypeError(f"StreamingQuantiles of {self.dtype}: a chunk of {a.dtype}")
-        return torch.as_tensor(np.ascontiguousarray(a)).to(self.device)
+        return staged(a, self.device, (self.dtype,), f"StreamingQuantiles of {self.dtype}: a chunk of {{dtype}}", layout="any")
 
     def add(self, values, segment=0, segment_ids=None):
         """A chunk: every element into ``segment``, or element i into ``segment_ids[i]`` (uint8 / int32, same shape)."""
         import torch
 
         t = self._values(values)
-        self._bind()
+        bound_context(ctx=self.ctx)
         if segment_ids is not None:
-            ids = segment_ids.to(self.device) if _is_torch(segment_ids) else torch.as_tensor(np.ascontiguousarray(segment_ids)).to(self.device)
+            ids = staged(segment_ids, self.device, layout="any")
             if ids.dtype not in (torch.uint8, torch.int32) or ids.shape != t.shape:
                 raise TypeError(f"segment ids: uint8 or int32 of shape {tuple(t.shape)}, not {ids.dtype} {tuple(ids.shape)}")
             t, ids = t.contiguous(), ids.contiguous()
@@ -106,27 +86,24 @@ class StreamingQuantiles:
 
     def add_constant(self, segment, value, count):
         """``count`` copies of ``value`` (rounded to the accumulator's type) without data."""
-        self._bind()
+        bound_context(ctx=self.ctx)
         check(lib.imcom_quant_add_constant(self.ctx.handle, self._h, int(segment), float(self.dtype.type(value)), int(count)))
 
     def add_star_rings(self, frame, x, y, rpix):
         """dynrange.py:216-228: the pixels around the stars at (``x``, ``y``) (float64) of the square ``frame``, ring j into segment j."""
-        import torch
-
         t = self._values(frame)
         if t.dim() != 2 or t.shape[0] != t.shape[1] or t.stride(1) != 1:
             raise ValueError(f"add_star_rings: a square frame with unit column stride, not {tuple(t.shape)}")
-        xs = torch.as_tensor(np.ascontiguousarray(np.asarray(x.cpu() if _is_torch(x) else x, dtype=np.float64))).to(self.device)
-        ys = torch.as_tensor(np.ascontiguousarray(np.asarray(y.cpu() if _is_torch(y) else y, dtype=np.float64))).to(self.device)
+        xs, ys = (staged(np.asarray(to_host(v), dtype=np.float64), self.device) for v in (x, y))
         if xs.shape != ys.shape or xs.dim() != 1:
             raise ValueError("add_star_rings: x and y are 1-D arrays of one length")
-        self._bind()
+        bound_context(ctx=self.ctx)
         check(lib.imcom_quant_add_rings(self.ctx.handle, self._h, ptr(t), t.shape[0], t.stride(0), ptr(xs), ptr(ys), xs.numel(), int(rpix), MEM_DEVICE))
 
     def end_pass(self):
         """Ends the pass that was fed; returns the number of passes still to feed."""
         left = C.c_int(0)
-        self._bind()
+        bound_context(ctx=self.ctx)
         check(lib.imcom_quant_end_pass(self.ctx.handle, self._h, C.byref(left)))
         return left.value
 
@@ -143,7 +120,7 @@ class StreamingQuantiles:
             raise ValueError(f"set_ranks: an array [{self.S}, <= {self.R}], not {r.shape}")
         full = np.full((self.S, self.R), -1, dtype=np.int64)
         full[:, :r.shape[1]] = r
-        self._bind()
+        bound_context(ctx=self.ctx)
         check(lib.imcom_quant_set_ranks(self.ctx.handle, self._h, ptr(full)))
         self._nranks = r.shape[1]
 
@@ -163,7 +140,7 @@ class StreamingQuantiles:
         return self.order_statistics()
 
     def reset(self):
-        self._bind()
+        bound_context(ctx=self.ctx)
         check(lib.imcom_quant_reset(self.ctx.handle, self._h))
         self._nranks = 0
 
@@ -216,7 +193,7 @@ def layer_percentiles(frames_by_block, ns, d, nblock, pctiles=LAYER_PCTILES):
         raise ValueError(f"layer_percentiles: {len(pctiles)} percentiles need {len(ranks)} order statistics, served are {MAX_RANKS}")
     pcarray = np.zeros((nlayers, len(pctiles)), dtype=np.float32)
     first = next(iter(have.values()))
-    device = first.device if _is_torch(first) and first.is_cuda else None
+    device = device_of(first)
     for l0 in range(0, nlayers, MAX_SEGMENTS):
         nl = min(MAX_SEGMENTS, nlayers - l0)
         sq = StreamingQuantiles(nl, np.float32, device=device, n_ranks=len(ranks))
@@ -304,27 +281,16 @@ def coded_map_histogram(codes, table, nbins, ctx=None):
     ``table`` (``code_bin_table``); the last entry counts "off scale high"."""
     import torch
 
-    if _is_torch(codes):
-        t = codes if codes.is_cuda else codes.to(DEVICE)
-    else:
-        a = np.ascontiguousarray(codes)
-        if a.dtype not in (np.int16, np.uint16):
-            raise TypeError(f"a coded map is int16 or uint16, not {a.dtype}")
-        t = torch.as_tensor(a.view(np.int16)).to(DEVICE)
+    t = staged(codes, device_of(codes), None if is_torch(codes) else (np.int16, np.uint16), "a coded map is int16 or uint16, not {dtype}", layout="any")
     if t.dtype not in (torch.int16, torch.uint16) or t.dim() != 2:
         raise TypeError(f"a coded map is a 2-D int16 or uint16 array, not {t.dtype} {tuple(t.shape)}")
     if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
         t = t.contiguous()
-    ctx = ctx or default_context(t.device.index or 0)
-    ctx.set_stream(torch.cuda.current_stream(t.device).cuda_stream)
-    tab = torch.as_tensor(np.ascontiguousarray(table, dtype=np.uint8)).to(t.device)
+    ctx = bound_context(t.device, ctx)
+    tab = staged(np.asarray(table, dtype=np.uint8), t.device)
     out = torch.zeros(nbins + 1, dtype=torch.int64, device=t.device)
     check(lib.imcom_codehist(ctx.handle, ptr(t), t.shape[0], t.shape[1], t.stride(0), ptr(tab), int(nbins), ptr(out), MEM_DEVICE))
     return out.cpu().numpy()
-
-
-def _np_int_dtype(codes):
-    return np.dtype(str(codes.dtype).replace("torch.", "")) if _is_torch(codes) else np.asarray(codes).dtype
 
 
 N_NOISE, D_NOISE, N_NEFF, D_NEFF = 100, 0.02, 100, 0.1  # dynrange.py:68-77
@@ -353,7 +319,7 @@ def dynrange_tables(blocks, rpix, bd, nscale=1):
             if b.get(key) is None:
                 continue
             codes, bels = b[key]
-            dt = _np_int_dtype(codes)
+            dt = np_dtype(codes)
             if (key, dt, bels) not in tables:
                 with np.errstate(all="ignore"):
                     vals = 10 ** (0.5 * bels * _all_codes(dt)) if key == "sigma" else 10 ** (bels * _all_codes(dt) * nscale)  # (142-144, 155-157)
@@ -365,7 +331,7 @@ def dynrange_tables(blocks, rpix, bd, nscale=1):
             else:
                 tneff, tneff_gt = tneff + (n - 2 * bd) ** 2, tneff_gt + h[nb]
     first = blocks[0]["starmap"]
-    sq = StreamingQuantiles(rpix, np.float32, device=first.device if _is_torch(first) and first.is_cuda else None, n_ranks=2 * len(RING_PCTILES))
+    sq = StreamingQuantiles(rpix, np.float32, device=device_of(first), n_ranks=2 * len(RING_PCTILES))
 
     def feed(sq):
         for b in blocks:

@@ -4,7 +4,8 @@ gathers its nine neighbours' pixels inside the acceptance region straight into t
 
 import numpy as np
 
-from ._lib import MEM_DEVICE, check, default_context, lib, ptr
+from ._dev import bound_context, staged
+from ._lib import MEM_DEVICE, check, lib, ptr
 
 
 class InStampPool:
@@ -68,7 +69,7 @@ def select_pixels(pool, inst_id, pivot_x, pivot_y, radius, ldn, ctx=None):
     expo [B,ldn] and the host array cumsum [B,10] (inpix_cumsum of each stamp)."""
     import torch
 
-    ctx = ctx if ctx is not None else default_context(pool.device.index or 0)
+    ctx = bound_context(pool.device, ctx)
     inst_id = np.ascontiguousarray(inst_id, dtype=np.int32)
     B = inst_id.shape[0]
     assert inst_id.shape == (B, 9)
@@ -81,7 +82,6 @@ def select_pixels(pool, inst_id, pivot_x, pivot_y, radius, ldn, ctx=None):
     indata = torch.empty((B, pool.n_inframe, ldn), dtype=torch.float32, device=dev)
     expo = torch.empty((B, ldn), dtype=torch.int32, device=dev)
     cumsum = torch.empty((B, 10), dtype=torch.int32, device=dev)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     check(lib.imcom_select_pixels(ctx.handle, B, ptr(pool.x), ptr(pool.y), ptr(pool.data), pool.npool, pool.n_inframe, ptr(pool.expo),
                                   ptr(pool.inst_off_dev), pool.n_inst, ptr(iid), ptr(pvx), ptr(pvy), float(radius), int(ldn), ptr(x), ptr(y),
                                   ptr(indata), ptr(expo), ptr(cumsum), MEM_DEVICE))
@@ -111,13 +111,12 @@ def partition_pixels(out_x, out_y, in_x, in_y, mask, use_instamps, n2, n1P, npix
     import torch
 
     dev = torch.device(device)
-    ctx = ctx if ctx is not None else default_context(dev.index or 0)
-    t = lambda a, dt: (a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a), device=dev)).to(dt).contiguous()  # noqa: E731
-    ox, oy = t(out_x, torch.float64), t(out_y, torch.float64)
-    ix, iy = t(in_x, torch.uint16), t(in_y, torch.uint16)
-    mk = None if mask is None else t(mask, torch.uint8)
+    ctx = bound_context(dev, ctx)
+    ox, oy = staged(out_x, dev, astype=np.float64), staged(out_y, dev, astype=np.float64)
+    ix, iy = staged(in_x, dev, astype=np.uint16), staged(in_y, dev, astype=np.uint16)
+    mk = None if mask is None else staged(mask, dev, astype=np.uint8)
     nst = n1P + 2
-    use = t(np.asarray(use_instamps).astype(np.uint8) if not torch.is_tensor(use_instamps) else use_instamps, torch.uint8)
+    use = staged(use_instamps, dev, astype=np.uint8)
     assert tuple(use.shape) == (nst, nst)
     npix = ox.numel()
     y_idx = torch.zeros((nst, nst, npixmax), dtype=torch.uint16, device=dev)
@@ -126,7 +125,6 @@ def partition_pixels(out_x, out_y, in_x, in_y, mask, use_instamps, n2, n1P, npix
     x_val = torch.zeros_like(y_val)
     count = torch.zeros((nst, nst), dtype=torch.uint32, device=dev)
     pix_lower, pix_upper = -n2 - 0.5, n1P * n2 + n2 - 0.5  # coadd.py:208-209 (NsideP = n1P * n2)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     check(lib.imcom_partition_pixels(ctx.handle, npix, ptr(ox), ptr(oy), ptr(ix), ptr(iy), ptr(mk), ptr(use), nst, int(n2), pix_lower, pix_upper,
                                      int(npixmax), ptr(y_idx), ptr(x_idx), ptr(y_val), ptr(x_val), ptr(count)))
     return y_idx, x_idx, y_val, x_val, count

@@ -17,7 +17,8 @@ Outputs are numpy arrays (host memspace) or torch CUDA tensors (device memspace,
 
 import numpy as np
 
-from ._lib import MEM_DEVICE, MEM_HOST, check, default_context, lib, ptr
+from ._dev import compare_value, is_torch, out_array
+from ._lib import check, lib, ptr
 
 __all__ = ["uniform", "uniform_at", "cr_mask", "randmask", "load_cr_mask", "subgen", "subgen_multirow"]
 
@@ -25,10 +26,6 @@ PAD = 10  # layer.py:956
 N_SLICES = 18  # layer.py:957: one slice per SCA
 SEED0 = 100000000  # layer.py:954
 _M64 = (1 << 64) - 1
-
-
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
 
 
 def _stream(bitgen_or_seed):
@@ -47,20 +44,8 @@ def _stream(bitgen_or_seed):
     return int(st["state"]), int(st["inc"])
 
 
-def _halves(v):
+def halves(v):
     return v & _M64, (v >> 64) & _M64
-
-
-def _out(shape, dtype, device):
-    """(array, memspace, context): a torch tensor on ``device``, or a numpy array when ``device`` is None."""
-    if device is None:
-        return np.empty(shape, dtype=dtype), MEM_HOST, default_context()
-    import torch
-
-    dev = torch.device(device)
-    ctx = default_context(dev.index or 0)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev), MEM_DEVICE, ctx
 
 
 def uniform(bitgen_or_seed, offset, shape, device=None):
@@ -72,8 +57,8 @@ def uniform(bitgen_or_seed, offset, shape, device=None):
     if offset < 0 or offset >= 1 << 128 or any(s < 0 for s in shape):
         raise ValueError("uniform: offset in 0 .. 2^128 - 1 and a shape without negative sides")
     count = int(np.prod(shape, dtype=object)) if shape else 1
-    out, mem, ctx = _out(shape, np.float64, device)
-    check(lib.imcom_pcg64_uniform(ctx.handle, *_halves(state), *_halves(inc), *_halves(offset), count, ptr(out) if count else None, mem))
+    out, mem, ctx = out_array(shape, np.float64, device)
+    check(lib.imcom_pcg64_uniform(ctx.handle, *halves(state), *halves(inc), *halves(offset), count, ptr(out) if count else None, mem))
     return out
 
 
@@ -81,7 +66,7 @@ def uniform_at(bitgen_or_seed, positions, device=None):
     """Draws ``positions`` (integers >= 0 of any shape, in any order) of the stream, float64 of the same shape.  ``positions`` may be a
     torch tensor on ``device``."""
     state, inc = _stream(bitgen_or_seed)
-    if _is_torch(positions):
+    if is_torch(positions):
         import torch
 
         if device is None:
@@ -102,17 +87,10 @@ def uniform_at(bitgen_or_seed, positions, device=None):
             pos = torch.as_tensor(pos, device=device)
     if neg:
         raise ValueError("uniform_at: positions are not negative")
-    out, mem, ctx = _out(tuple(pos.shape), np.float64, device)
+    out, mem, ctx = out_array(tuple(pos.shape), np.float64, device)
     count = int(np.prod(tuple(pos.shape), dtype=object))
-    check(lib.imcom_pcg64_uniform_at(ctx.handle, *_halves(state), *_halves(inc), ptr(pos) if count else None, count, ptr(out) if count else None, mem))
+    check(lib.imcom_pcg64_uniform_at(ctx.handle, *halves(state), *halves(inc), ptr(pos) if count else None, count, ptr(out) if count else None, mem))
     return out
-
-
-def _numpy_compare_value(threshold, dtype=np.float32):
-    """The float64 value of ``threshold`` after the rounding numpy applies to it in ``array_of_dtype < threshold`` (a Python float takes
-    the array's type; a numpy float64 scalar promotes the comparison to float64)."""
-    with np.errstate(over="ignore"):
-        return float(np.asarray(threshold).astype(np.result_type(dtype, threshold)))
 
 
 def cr_mask(bitgen_or_seed, nside, sca_slice, pcut, labnoise=None, threshold=0.0, pad=PAD, n_slices=N_SLICES, device=None):
@@ -123,7 +101,7 @@ def cr_mask(bitgen_or_seed, nside, sca_slice, pcut, labnoise=None, threshold=0.0
     if nside < 1:
         raise ValueError("cr_mask: nside >= 1")
     if labnoise is not None:
-        if _is_torch(labnoise):
+        if is_torch(labnoise):
             import torch
 
             if labnoise.dtype != torch.float32:
@@ -142,10 +120,10 @@ def cr_mask(bitgen_or_seed, nside, sca_slice, pcut, labnoise=None, threshold=0.0
                 labnoise = torch.as_tensor(labnoise, device=device)
         if tuple(labnoise.shape) != (nside, nside):
             raise ValueError(f"cr_mask: labnoise of shape {tuple(labnoise.shape)} for nside {nside}")
-        threshold = _numpy_compare_value(threshold)
-    mask, mem, ctx = _out((nside, nside), np.uint8, device)
-    ngood, _, _ = _out((1,), np.int64, device)
-    check(lib.imcom_cr_mask(ctx.handle, *_halves(state), *_halves(inc), nside, int(pad), int(sca_slice), int(n_slices), float(pcut), ptr(labnoise),
+        threshold = compare_value(threshold, np.float32)
+    mask, mem, ctx = out_array((nside, nside), np.uint8, device)
+    ngood, _, _ = out_array((1,), np.int64, device)
+    check(lib.imcom_cr_mask(ctx.handle, *halves(state), *halves(inc), nside, int(pad), int(sca_slice), int(n_slices), float(pcut), ptr(labnoise),
                             float(threshold), ptr(mask), ptr(ngood), mem))
     return mask, int(ngood[0])
 
@@ -188,13 +166,13 @@ def load_cr_mask(inimage):
         print("Cosmic ray mask: good pix --> ", ngood, "/", 4088**2)
         return mask.view(np.bool_)
     lab = inimage.indata[idx]
-    if not _is_torch(lab):
+    if not is_torch(lab):
         lab = np.asarray(lab)
         if lab.dtype != np.float32:  # (the reference's indata is float32, layer.py:1246-1252; anything else is compared as numpy would)
             raise TypeError(f"load_cr_mask: the labnoise layer is {lab.dtype}, float32 expected")
     nside = int(lab.shape[-1])
     mask, ngood = cr_mask(seed, nside, sl, config.cr_mask_rate, labnoise=lab, threshold=config.labnoisethreshold)
-    if _is_torch(mask):
+    if is_torch(mask):
         mask = mask.cpu().numpy()
     print("Lab noise threshold: good pix --> ", ngood, "/", 4088**2)
     return mask.view(np.bool_)

@@ -11,7 +11,8 @@ A numpy cube gives numpy attributes; a float64 torch tensor on the device gives 
 
 import numpy as np
 
-from ._lib import MEM_DEVICE, check, default_context, lib, ptr
+from ._dev import bound_context, is_torch, staged
+from ._lib import MEM_DEVICE, check, lib, ptr
 
 __all__ = ["SplitPSF", "split_cubes", "gauss_legendre_grid", "legendre_weights", "jacobian", "covariances", "routes", "ROUTE_LINES", "ROUTE_DENSE"]
 
@@ -19,10 +20,6 @@ FILL = 0.8  # share of the free device memory a chunk plan may use
 ROUTE_LINES, ROUTE_DENSE = 1, 2  # how a transform side is served (csrc/splitpsf.hip): wave-per-line butterflies, dense DFT on the MFMA engine
 DEFAULTS = {"ref_pixscale": 0.11, "oversamp": 8, "tophat_in": False, "nside": 4088, "r_in": 4.0, "r_out": 9.0, "sigmaGamma": 1.0, "eps": 0.02,
             "m_trunc": 0}  # splitpsf.py:190-200; smallstamp_size defaults to the side of the cube
-
-
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
 
 
 def gauss_legendre_grid(lorder):
@@ -131,7 +128,7 @@ class SplitPSF:
             raise ValueError("SplitPSF Legendre polynomial dimension error")
         if self.smallstamp_size > self.largestamp_size or self.smallstamp_size < 2:
             raise ValueError(f"smallstamp_size={self.smallstamp_size} for a cube of side {self.largestamp_size}")
-        self._torch_in = _is_torch(psfcube)
+        self._torch_in = is_torch(psfcube)
         if self._torch_in:
             if not (psfcube.dtype == torch.float64 and psfcube.is_cuda):
                 raise ValueError("a torch psfcube must be a float64 tensor on the device")
@@ -139,23 +136,17 @@ class SplitPSF:
             cube = psfcube.contiguous()
         else:
             self.dev = torch.device(device)
-            cube = torch.as_tensor(np.ascontiguousarray(psfcube, dtype=np.float64), device=self.dev)
-        self.ctx = ctx or default_context(self.dev.index or 0)
+            cube = staged(psfcube, self.dev, astype=np.float64)
+        self.ctx = bound_context(self.dev, ctx)
         self._cov_in = None if cov is None else np.ascontiguousarray(cov, dtype=np.float64).reshape(self.npoly, 2, 2)
         n = self.largestamp_size
         if self.tophat_in:
             self._cube = cube.clone() if self._torch_in else cube  # (np.copy of the reference)
         else:
             self._cube = torch.empty_like(cube)
-            self._bind()
             check(lib.imcom_splitpsf_tophat(self.ctx.handle, ptr(cube), self.npoly, n, float(self.oversamp), ptr(self._cube), MEM_DEVICE))
             torch.cuda.current_stream(self.dev).synchronize()  # `cube` may be dropped on return
         self.psfcube = self._cube if self._torch_in else self._cube.cpu().numpy()
-
-    def _bind(self):
-        import torch
-
-        self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
 
     def _out(self, t):
         return t if self._torch_in else t.cpu().numpy()
@@ -184,7 +175,7 @@ class SplitPSF:
         kreal = torch.empty((npoly, n, n), **f64) if "K_real" in keep else None
         zeta = torch.empty((npoly, n, n), **f64) if "zeta_real" in keep else None
         zmax = torch.zeros(1, **f64)
-        self._bind()
+        bound_context(ctx=self.ctx)
         h = self.ctx.handle
         check(lib.imcom_splitpsf_split(h, ptr(self._cube), npoly, n, ns, float(self.oversamp * self.r_in), float(self.oversamp * self.r_out),
                                        int(self.m_trunc), ptr(small), ptr(resid), MEM_DEVICE))
@@ -217,7 +208,7 @@ def split_cubes(cubes, wcs_list, pars, *, covs=None, device="cuda:0", ctx=None, 
 
     pars = dict(pars or {})
     P = {k: pars.get(k, v) for k, v in DEFAULTS.items()}
-    torch_in = _is_torch(cubes)
+    torch_in = is_torch(cubes)
     shape = tuple(cubes.shape)
     if len(shape) != 4 or shape[2] != shape[3]:
         raise ValueError("cubes is [nsca, npoly, n, n]")
@@ -240,7 +231,7 @@ def split_cubes(cubes, wcs_list, pars, *, covs=None, device="cuda:0", ctx=None, 
         dev = cubes.device
     else:
         dev = torch.device(device)
-    ctx = ctx or default_context(dev.index or 0)
+    ctx = bound_context(dev, ctx)
     s = P["oversamp"]
     xg, yg, wg = gauss_legendre_grid(lorder)
     lpw = legendre_weights(lorder, xg, yg)
@@ -264,11 +255,10 @@ def split_cubes(cubes, wcs_list, pars, *, covs=None, device="cuda:0", ctx=None, 
     if step < npoly:
         chunk = 1
     h = ctx.handle
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     for s0 in range(0, nsca, chunk):
         c = min(chunk, nsca - s0)
         part = cubes[s0:s0 + c]
-        cube = part.contiguous() if torch_in else torch.as_tensor(np.ascontiguousarray(part, dtype=np.float64), device=dev)
+        cube = part.contiguous() if torch_in else staged(part, dev, astype=np.float64)
         if P["tophat_in"]:
             filt = cube
         else:

@@ -13,6 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from ._dev import bound_context, staged
 from ._lib import PAIR_SWAP,  PAIR_FLIP, ImcomError, TableGeom, check, default_context, lib, ptr
 
 NB = 128
@@ -82,7 +83,7 @@ def psf_spectra(ctx, psf, nfft):
     if size == 0:
         return None
     spec = torch.empty((n, size), dtype=torch.float64, device=psf.device)
-    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    bound_context(ctx=ctx)
     check(lib.imcom_psf_spectra(ctx.handle, ptr(psf), n, ns, nfft, ptr(spec)))
     return spec
 
@@ -98,7 +99,7 @@ def overlap_tables(ctx, p1, s1, p2, s2, nsamp, nfft, pairs, amp, out, win=None, 
     assert tuple(out.shape[1:]) == ((int(ntab) if wide else int(nsamp)) + 12,) * 2
     pairs = np.ascontiguousarray(pairs, dtype=np.int32)
     ampp = None if amp is None else ptr(amp)
-    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    bound_context(ctx=ctx)
     if s1 is not None and s2 is not None:
         winp = None
         if win is not None:
@@ -146,7 +147,7 @@ class PSFGroupTables:
         nt = self.ntab = ns if ntab is None else int(ntab)  # side of the tables: what the builders' geometry and every buffer follow
         dev = torch.device(device)
         as_dev = lambda a: (a.to(dev).contiguous() if torch.is_tensor(a)  # noqa: E731
-                            else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev))
+                            else staged(a, dev, astype=np.float64))
         pin, pout = as_dev(psf_in), as_dev(psf_out)
         O = self.n_out = pout.shape[0]
         ng = nt + 12
@@ -176,16 +177,13 @@ class PSFGroupTables:
         from . import psfs
 
         dev = torch.device(device)
-        img = torch.as_tensor(np.ascontiguousarray(psf_images, dtype=np.float64), device=dev)
-        co = torch.as_tensor(np.ascontiguousarray(yxco, dtype=np.float64), device=dev)
+        img = staged(psf_images, dev, astype=np.float64)
+        co = staged(yxco, dev, astype=np.float64)
         psf_in = psfs.sample_psf(img, nsamp, co, psf_circ, psf_norm, ctx)
         targets = [target] if isinstance(target[0], str) else list(target)
         timg = torch.stack([psfs.get_outpsf(t[0], t[1], t[2], nsamp, oversamp, device=dev, ctx=ctx) for t in targets])
         psf_out = psfs.sample_psf(timg, nsamp, None, psf_circ, psf_norm, ctx)
         return cls(psf_in, psf_out, nfft, ctx=ctx, device=device, amp_penalty=amp_penalty, ntab=ntab)
-
-    def _set_stream(self):
-        self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
 
     def tri(self, i, j):
         """PSFOvl._idx_square2triangle (psfutil.py:1175)."""
@@ -278,8 +276,7 @@ class BlockTables:
         self.n_max = max(self._count_of.values())
         self.n_psf = self.n_max
         self.n_blk_expo = 1 + max(max(v) for v in self.expo.values())
-        self.pout = (psf_out.to(dev, torch.float64).contiguous() if torch.is_tensor(psf_out)
-                     else torch.as_tensor(np.ascontiguousarray(psf_out, dtype=np.float64), device=dev))
+        self.pout = staged(psf_out, dev, astype=np.float64)
         O = self.n_out = self.pout.shape[0]
         amp = None if amp_penalty is None or 0.0 in tuple(amp_penalty) else np.array(amp_penalty, dtype=np.float64)
         self._amp = amp
@@ -314,7 +311,7 @@ class BlockTables:
         self._spec_all = torch.empty((self._spec_cap, size), dtype=torch.float64, device=dev) if size else None
         self._dev_psf = {}  # device copies of the sampled PSFs, kept only when there are no spectra to keep instead
         if size:
-            self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            bound_context(ctx=self.ctx)
             check(lib.imcom_psf_spectra(self.ctx.handle, ptr(self.pout), O, self.nsamp, self.nfft, ptr(self._spec_all[:O])))
         cc = torch.empty((O, ng, ng), dtype=torch.float64, device=dev)
         self._compute([(None, None, [(o, o) for o in range(O)])], cc)
@@ -358,8 +355,7 @@ class BlockTables:
             if callable(p):
                 p = p()
                 assert tuple(p.shape) == (self._count_of[g], self.nsamp, self.nsamp), "group PSF provider returned the wrong shape"
-            got[g] = (p.to(self.dev, torch.float64).contiguous() if torch.is_tensor(p)
-                      else torch.as_tensor(np.ascontiguousarray(p, dtype=np.float64), device=self.dev))
+            got[g] = staged(p, self.dev, astype=np.float64)
         parts = [self._dev_psf[g] if g in self._dev_psf else got[g] for g in gs]
         return parts[0] if len(parts) == 1 else torch.cat(parts)
 
@@ -397,7 +393,7 @@ class BlockTables:
             part = miss[q0:q1]
             p = self._sampled(part)
             r0 = self._spec_next
-            self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            bound_context(ctx=self.ctx)
             check(lib.imcom_psf_spectra(self.ctx.handle, ptr(p), p.shape[0], self.nsamp, self.nfft, ptr(self._spec_all[r0 : r0 + p.shape[0]])))
             for g in part:
                 self._spec_row[g] = self._spec_next
@@ -750,7 +746,7 @@ class StampBatch:
             setattr(self, name, getattr(self, name + "_o")[0])
 
     def _stream(self):
-        self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        bound_context(ctx=self.ctx)
 
     def build(self):
         """A (psfutil.py:1401-1495, 1597-1732 + coadd.py:1027-1068) and B (1497-1595 + coadd.py:1075-1082)."""

@@ -26,13 +26,13 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import MEM_DEVICE, StarParams, check, default_context, lib, ptr
+from ._dev import DEVICE, bound_context, device_of, is_torch, np_dtype, staged, to_host, torch_dtype  # noqa: F401 (DEVICE: a public name here)
+from ._lib import MEM_DEVICE, StarParams, check, lib, ptr
 from . import reportstats
 
 __all__ = ["AdaptiveMomParams", "AdaptiveMoments", "adaptive_moments", "star_moments", "star_catalog", "starcube_rows", "star_cuts", "window_stats",
            "fidelity_table", "fidelity_histogram", "cumulative", "select_stars", "COLUMNS", "STATUS_MESSAGES", "MAX_SIDE", "NCOL"]
 
-DEVICE = "cuda:0"
 MAX_SIDE = 127
 # analysis.py:818-849 (ColDescr), in order
 COLUMNS = ["RA", "DEC", "X_POS", "Y_POS", "AMPLITUDE", "OFFSET_X", "OFFSET_Y", "WIDTH", "SHAPE_G1", "SHAPE_G2", "M42_REAL", "M42_IMAG", "FORCED_PLUS",
@@ -58,24 +58,12 @@ class AdaptiveMomParams:
                           self.max_mom2_iter, 0)
 
 
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
-
-
 def _frame(a, kinds):
     """(device tensor with unit column stride, was a tensor on a device)."""
-    import torch
-
-    stay = _is_torch(a) and a.is_cuda
-    if _is_torch(a):
-        t = a if a.is_cuda else a.to(DEVICE)
-    else:
-        a = np.ascontiguousarray(a)
-        if a.dtype == np.uint16:
-            a = a.view(np.int16)
-        t = torch.as_tensor(a).to(DEVICE)
-    if t.dtype not in kinds or t.dim() != 2:
-        raise TypeError(f"a 2-D array of {' / '.join(str(k).replace('torch.', '') for k in kinds)}, not {t.dtype} {tuple(t.shape)}")
+    stay = is_torch(a) and a.is_cuda
+    t = staged(a, device_of(a), layout="any")
+    if np_dtype(t).name not in kinds or t.dim() != 2:
+        raise TypeError(f"a 2-D array of {' / '.join(kinds)}, not {t.dtype} {tuple(t.shape)}")
     if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
         t = t.contiguous()
     return t, stay
@@ -84,18 +72,10 @@ def _frame(a, kinds):
 def _ints(a, device, what):
     import torch
 
-    a = np.ascontiguousarray(a.cpu().numpy() if _is_torch(a) else a)
+    a = np.ascontiguousarray(to_host(a))
     if a.ndim != 1 or a.dtype.kind not in "iu":
         raise TypeError(f"{what}: a 1-D integer array, not {a.dtype} {a.shape}")
     return torch.as_tensor(a.astype(np.int32)).to(device)
-
-
-def _ctx(t, ctx):
-    import torch
-
-    ctx = ctx or default_context(t.device.index or 0)
-    ctx.set_stream(torch.cuda.current_stream(t.device).cuda_stream)
-    return ctx
 
 
 def _moments(t, ox, oy, w, h, forced_scale, params, ctx=None):
@@ -104,7 +84,7 @@ def _moments(t, ox, oy, w, h, forced_scale, params, ctx=None):
 
     if w > MAX_SIDE or h > MAX_SIDE or w < 1 or h < 1:
         check(lib.imcom_star_sizes(0, int(w), int(h), 0, (C.c_long * 4)()))  # (raises IMCOM_ERR_UNSUPPORTED with the library's message)
-    ctx = _ctx(t, ctx)
+    ctx = bound_context(t.device, ctx)
     ox, oy = _ints(ox, t.device, "ox"), _ints(oy, t.device, "oy")
     if ox.shape != oy.shape:
         raise ValueError("the stars' x and y differ in length")
@@ -148,26 +128,25 @@ def adaptive_moments(images, params=None, ctx=None):
     the start centroid is ((1 + w) / 2, (1 + h) / 2))."""
     import torch
 
-    stay = _is_torch(images) and images.is_cuda
-    t = images if _is_torch(images) else torch.as_tensor(np.ascontiguousarray(images))
-    single = t.dim() == 2
-    if single:
-        t = t[None]
-    if t.dim() != 3 or t.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"adaptive_moments: float32 / float64 images [k, h, w] or [h, w], not {t.dtype} {tuple(t.shape)}")
-    k, h, w = t.shape
+    stay = is_torch(images) and images.is_cuda
+    a = images if is_torch(images) else np.asarray(images)
+    single = len(a.shape) == 2
+    shape = ((1,) if single else ()) + tuple(a.shape)
+    kind = a.dtype if is_torch(a) else torch_dtype(a.dtype)
+    if len(shape) != 3 or kind not in (torch.float32, torch.float64):
+        raise TypeError(f"adaptive_moments: float32 / float64 images [k, h, w] or [h, w], not {kind} {shape}")
+    k, h, w = shape
     if h < 1 or w < 1:
         raise ValueError(f"adaptive_moments: images of {h} x {w} pixels")
-    t = t if t.is_cuda else t.to(DEVICE)
-    t = t.contiguous().reshape(k * h, w) if k else torch.zeros((1, w), dtype=t.dtype, device=t.device)
+    t = staged(a, device_of(a))  # (after the checks: a refused input is not uploaded)
+    t = t.reshape(k * h, w) if k else torch.zeros((1, w), dtype=t.dtype, device=t.device)
     out = _moments(t, np.zeros(k, dtype=np.int32), np.arange(k, dtype=np.int32) * h, w, h, 0.0, params, ctx)
     return AdaptiveMoments(out, stay, single)
 
 
 def _positions(x, y):
     """analysis.py:982-983, 993-994: (x, y float64, xi, yi int16 as ints, dx, dy)."""
-    x = np.asarray(x.cpu().numpy() if _is_torch(x) else x, dtype=np.float64)
-    y = np.asarray(y.cpu().numpy() if _is_torch(y) else y, dtype=np.float64)
+    x, y = np.asarray(to_host(x), dtype=np.float64), np.asarray(to_host(y), dtype=np.float64)
     if x.ndim != 1 or x.shape != y.shape:
         raise ValueError("x and y are 1-D arrays of one length")
     xi = np.rint(x).astype(np.int16)
@@ -188,7 +167,7 @@ def star_moments(frame, x, y, bd=40, forced_scale=0.0, params=None, ctx=None):
     frame[yi + 1 - bd : yi + bd, xi + 1 - bd : xi + bd], zero outside the frame."""
     import torch
 
-    t, stay = _frame(frame, (torch.float32, torch.float64))
+    t, stay = _frame(frame, ("float32", "float64"))
     x, y, xi, yi, dx, dy = _positions(x, y)
     side = 2 * int(bd) - 1
     tab = _moments(t, xi.astype(np.int32) + 1 - int(bd), yi.astype(np.int32) + 1 - int(bd), side, side, forced_scale, params, ctx)
@@ -217,10 +196,10 @@ def window_stats(map_, xi, yi, bd2=8, table=None, ctx=None):
     import torch
 
     coded = table is not None
-    t, stay = _frame(map_, (torch.int16, torch.uint16) if coded else (torch.float32, torch.float64))
-    ctx = _ctx(t, ctx)
+    t, stay = _frame(map_, ("int16", "uint16") if coded else ("float32", "float64"))
+    ctx = bound_context(t.device, ctx)
     xi, yi = _ints(xi, t.device, "xi"), _ints(yi, t.device, "yi")
-    tab = torch.as_tensor(np.ascontiguousarray(table, dtype=np.int16)).to(t.device) if coded else None
+    tab = staged(np.asarray(table, dtype=np.int16), t.device) if coded else None
     if coded and tab.numel() != 65536:
         raise ValueError("window_stats: a table of 65536 int16 values")
     out = torch.zeros((xi.numel(), 2), dtype=torch.float64, device=t.device)
@@ -234,11 +213,11 @@ def star_cuts(frame, xi, yi, bd=40, ctx=None):
     """float32 [nstar, 2 bd - 1, 2 bd - 1]: the cuts, ``np.pad(frame, bd)[yi + 1 : yi + 2 bd, xi + 1 : xi + 2 bd]`` (starcube_nonoise.py:190-196)."""
     import torch
 
-    t, stay = _frame(frame, (torch.float32, torch.float64))
+    t, stay = _frame(frame, ("float32", "float64"))
     side = 2 * int(bd) - 1
     if side > MAX_SIDE or side < 1:
         check(lib.imcom_star_sizes(0, side, side, 0, (C.c_long * 4)()))
-    ctx = _ctx(t, ctx)
+    ctx = bound_context(t.device, ctx)
     ox, oy = _ints(np.asarray(xi).astype(np.int64) + 1 - int(bd), t.device, "xi"), _ints(np.asarray(yi).astype(np.int64) + 1 - int(bd), t.device, "yi")
     out = torch.zeros((ox.numel(), side, side), dtype=torch.float32, device=t.device)
     check(lib.imcom_star_cuts(ctx.handle, ptr(t), int(t.dtype == torch.float64), t.shape[0], t.shape[1], t.stride(0), ptr(ox), ptr(oy), ox.numel(), side, side, ptr(out),
@@ -246,17 +225,9 @@ def star_cuts(frame, xi, yi, bd=40, ctx=None):
     return out if stay else out.cpu().numpy()
 
 
-def _np_dtype(a):
-    return np.dtype(str(a.dtype).replace("torch.", "")) if _is_torch(a) else np.asarray(a).dtype
-
-
-def _host(a):
-    return a.cpu().numpy() if _is_torch(a) else np.asarray(a)
-
-
 def _coverage(inweight, n2, xi, yi):
     """analysis.py:937, 1049."""
-    wt = np.sum(np.where(_host(inweight) > 0.01, 1, 0), axis=0)
+    wt = np.sum(np.where(to_host(inweight) > 0.01, 1, 0), axis=0)
     return wt[yi // n2, xi // n2]
 
 
@@ -272,26 +243,26 @@ def star_catalog(frame, x, y, *, bd=40, bd2=8, forced_scale, fidelity, inweight=
     npix = len(x)
     cat = np.zeros((npix, len(COLUMNS)))
     col = {n: i for i, n in enumerate(COLUMNS)}
-    cat[:, col["RA"]] = 0.0 if ra is None else _host(ra)
-    cat[:, col["DEC"]] = 0.0 if dec is None else _host(dec)
+    cat[:, col["RA"]] = 0.0 if ra is None else to_host(ra)
+    cat[:, col["DEC"]] = 0.0 if dec is None else to_host(dec)
     cat[:, col["X_POS"]], cat[:, col["Y_POS"]] = x, y
     if npix == 0:
         return cat
     m = star_moments(frame, x, y, bd, forced_scale, params, ctx)
-    status = _host(m["status"])
+    status = to_host(m["status"])
     ok = status == 0
     for name in COLUMNS[4:14]:
-        cat[:, col[name]] = _host(m[name])
+        cat[:, col[name]] = to_host(m[name])
     codes, bels = fidelity
     rows = np.zeros((npix, 6))
-    rows[:, 0] = _host(window_stats(codes, xi, yi, bd2, table=fidelity_table(_np_dtype(codes), bels), ctx=ctx)[0])
+    rows[:, 0] = to_host(window_stats(codes, xi, yi, bd2, table=fidelity_table(np_dtype(codes), bels), ctx=ctx)[0])
     rows[:, 1] = _coverage(inweight, int(n2), xi, yi)
     for j, (mp, which) in enumerate(((uc, 0), (sigma, 0), (tsum, 1), (neff, 0))):
-        rows[:, 2 + j] = -1 if mp is None else _host(window_stats(mp, xi, yi, bd2, ctx=ctx)[which])
+        rows[:, 2 + j] = -1 if mp is None else to_host(window_stats(mp, xi, yi, bd2, ctx=ctx)[which])
     if empirical:
         rows[:, 4] = 0
     cat[ok, col["FIDELITY"]:] = rows[ok]
-    if _is_torch(frame) and frame.is_cuda:
+    if is_torch(frame) and frame.is_cuda:
         return torch.as_tensor(cat).to(frame.device)
     return cat
 
@@ -302,18 +273,18 @@ def starcube_rows(frame, x, y, ibx=0, iby=0, *, bd=40, bd2=8, force_scale, fidel
     x, y, xi, yi, dx, dy = _positions(x, y)
     npix = len(x)
     pos = np.zeros((npix, 22))
-    pos[:, 0], pos[:, 1] = 0.0 if ra is None else _host(ra), 0.0 if dec is None else _host(dec)
+    pos[:, 0], pos[:, 1] = 0.0 if ra is None else to_host(ra), 0.0 if dec is None else to_host(dec)
     pos[:, 2], pos[:, 3], pos[:, 4], pos[:, 5], pos[:, 6], pos[:, 7], pos[:, 8], pos[:, 9] = ibx, iby, x, y, xi, yi, dx, dy
-    cube = _host(star_cuts(frame, xi, yi, bd, ctx))
+    cube = to_host(star_cuts(frame, xi, yi, bd, ctx))
     if npix == 0:
         return pos, cube
     m = star_moments(frame, x, y, bd, force_scale, params, ctx)
-    ok = _host(m["status"]) == 0
+    ok = to_host(m["status"]) == 0
     for j, name in enumerate(COLUMNS[4:14]):
-        pos[:, 10 + j] = _host(m[name])
+        pos[:, 10 + j] = to_host(m[name])
     codes, bels = fidelity
     tail = np.zeros((npix, 2))
-    tail[:, 0] = _host(window_stats(codes, xi, yi, bd2, table=fidelity_table(_np_dtype(codes), bels), ctx=ctx)[0])
+    tail[:, 0] = to_host(window_stats(codes, xi, yi, bd2, table=fidelity_table(np_dtype(codes), bels), ctx=ctx)[0])
     tail[:, 1] = _coverage(inweight, int(n2), xi, yi)
     pos[ok, 20:] = tail[ok]
     return pos, cube
@@ -322,7 +293,7 @@ def starcube_rows(frame, x, y, ibx=0, iby=0, *, bd=40, bd2=8, force_scale, fidel
 def fidelity_histogram(codes, bels, bdpad, ctx=None):
     """uint32-valued int64 [81]: starcube_nonoise.py:142-143, the counts of floor(fidelity in dB) = 0 .. 80 inside the padding, through
     ``reportstats.coded_map_histogram`` (no kernel of its own)."""
-    fmap = fidelity_table(_np_dtype(codes), bels)
+    fmap = fidelity_table(np_dtype(codes), bels)
     table = np.where((fmap >= 0) & (fmap <= 80), fmap, 255).astype(np.uint8)
     bdpad = int(bdpad)
     n0, n1 = codes.shape

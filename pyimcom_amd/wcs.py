@@ -34,12 +34,12 @@ from collections.abc import Mapping
 
 import numpy as np
 
-from ._lib import MEM_DEVICE, ImcomError, check, default_context, lib, ptr
+from ._dev import DEVICE, bound_context, is_torch, staged
+from ._lib import MEM_DEVICE, ImcomError, check, lib, ptr
 
 __all__ = ["DeviceWCS", "as_device_wcs", "error_table", "map_sca2sca", "get_overlap_matrix", "footprint_cap", "caps_can_touch", "overlap_count", "pix_area", "rotation_matrix", "sip_index",
            "DESC_LEN", "MAX_ORDER", "TAN", "STG"]
 
-DEVICE = "cuda:0"
 IMCOM_ERR_UNSUPPORTED = -4
 TAN, STG = 0, 1
 MAX_ORDER = 9
@@ -52,10 +52,6 @@ SCA_NSIDE = 4088        # Settings.sca_nside, the default array_shape
 
 def _unsupported(msg):
     return ImcomError(IMCOM_ERR_UNSUPPORTED, "wcs: " + msg)
-
-
-def _is_torch(a):
-    return a is not None and type(a).__module__.startswith("torch")
 
 
 def sip_index(p, q):
@@ -164,7 +160,7 @@ class DeviceWCS:
         self._tab_dev = {}
         if table is not None:
             values, lo, hi = table
-            if not _is_torch(values):
+            if not is_torch(values):
                 values = np.ascontiguousarray(values)
                 if values.dtype not in (np.float32, np.float64):
                     values = values.astype(np.float64)
@@ -283,7 +279,7 @@ class DeviceWCS:
         values, lo, hi = self.table
         t = self._tab_dev.get(str(dev))
         if t is None:
-            t = (values if _is_torch(values) else torch.as_tensor(values)).to(dev).contiguous()
+            t = staged(values, dev)
             if t.dtype not in (torch.float32, torch.float64):
                 t = t.to(torch.float64)
             self._tab_dev[str(dev)] = t
@@ -296,13 +292,12 @@ class DeviceWCS:
         origin = int(origin)
         if origin not in (0, 1):
             raise ValueError(f"wcs: origin {origin}")
-        stay = _is_torch(pos) and pos.is_cuda
-        home = pos.device if _is_torch(pos) else None  # (a tensor in gives a tensor out, on the device it came from)
-        t = pos if _is_torch(pos) else torch.as_tensor(np.ascontiguousarray(pos, dtype=np.float64))
-        if t.dim() != 2 or t.shape[1] != 2:
-            raise ValueError(f"wcs: positions of shape {tuple(t.shape)}, expected (N, 2)")
-        t = t.to(pos.device if stay else DEVICE, torch.float64).contiguous()
-        ctx = _ctx(t.device, ctx)
+        stay = is_torch(pos) and pos.is_cuda
+        home = pos.device if is_torch(pos) else None  # (a tensor in gives a tensor out, on the device it came from)
+        if len(pos.shape) != 2 or pos.shape[1] != 2:
+            raise ValueError(f"wcs: positions of shape {tuple(pos.shape)}, expected (N, 2)")
+        t = staged(pos, pos.device if stay else DEVICE, astype=np.float64)
+        ctx = bound_context(t.device, ctx)
         out = torch.empty_like(t)
         nbad = C.c_long(0)
         tab = self._table_args(t.device)
@@ -316,11 +311,11 @@ class DeviceWCS:
         """The 2-argument and 3-argument forms of wcsutil.py:524-560 / 598-634."""
         if len(args) == 2:
             pos = args[0]
-            return self._list(inverse, pos if _is_torch(pos) else np.array(pos, dtype=np.float64).reshape(-1, 2), args[1])
+            return self._list(inverse, pos if is_torch(pos) else np.array(pos, dtype=np.float64).reshape(-1, 2), args[1])
         if len(args) != 3:
             raise TypeError("wcs: (pos, origin) or (pos, pos2, origin)")
         a, b, origin = args
-        if _is_torch(a):
+        if is_torch(a):
             import torch
 
             o = self._list(inverse, torch.stack((a.reshape(-1).to(torch.float64), b.reshape(-1).to(torch.float64).to(a.device)), dim=1), origin)
@@ -336,15 +331,6 @@ class DeviceWCS:
 
     def all_world2pix(self, *args):
         return self._call(1, args)
-
-
-def _ctx(dev, ctx):
-    import torch
-
-    dev = torch.device(dev)
-    ctx = ctx or default_context(dev.index or 0)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    return ctx
 
 
 def as_device_wcs(w):
@@ -373,13 +359,13 @@ def _pix2pix(target, ref, grid=None, points=None, nside=SCA_NSIDE, pad=0, origin
     import torch
 
     dev = torch.device(device)
-    ctx = _ctx(dev, ctx)
+    ctx = bound_context(dev, ctx)
     if grid is not None:
         g = np.asarray(grid, dtype=np.float64)
         n, shape = int(g[2]) * int(g[5]), (int(g[5]), int(g[2]))
         pts = None
     else:
-        pts = (points if _is_torch(points) else torch.as_tensor(np.ascontiguousarray(points, dtype=np.float64))).to(dev, torch.float64).contiguous()
+        pts = staged(points, dev, astype=np.float64)
         n, shape, g = pts.shape[0], (pts.shape[0],), None
     dt = torch.float32 if f32 else torch.float64
     x = torch.empty(shape, dtype=dt, device=dev) if "x" in want else None
@@ -484,7 +470,7 @@ def pix_area(wcs, region=(0, SCA_NSIDE, 0, SCA_NSIDE), pad=1, ovsamp=1, device_o
         raise ValueError(f"wcs: region {list(region)}, pad {pad}, ovsamp {ovsamp}")
     xs, ys = _area_axis(xmin, xmax, pad, ovsamp), _area_axis(ymin, ymax, pad, ovsamp)
     dev = torch.device(device)
-    ctx = _ctx(dev, ctx)
+    ctx = bound_context(dev, ctx)
     xs_d, ys_d = torch.as_tensor(xs).to(dev), torch.as_tensor(ys).to(dev)
     op = ovsamp * pad
     area = torch.empty((len(ys) - 2 * op, len(xs) - 2 * op), dtype=torch.float64, device=dev)

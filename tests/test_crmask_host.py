@@ -108,7 +108,7 @@ def test_python_layer_refusals_and_host_logic():
     import __graft_entry__ as g
 
     g.build()
-    from pyimcom_amd import simmask
+    from pyimcom_amd import _dev, simmask
 
     with pytest.raises(TypeError):
         simmask.uniform(np.random.MT19937(1), 0, 4)
@@ -117,7 +117,7 @@ def test_python_layer_refusals_and_host_logic():
     with pytest.raises(ValueError):
         simmask.uniform(1, -1, 4)
     assert simmask._stream(np.random.default_rng(5)) == R.stream(5)
-    assert simmask._numpy_compare_value(0.7) == float(np.float32(0.7)) and simmask._numpy_compare_value(np.float64(0.7)) == 0.7
+    assert _dev.compare_value(0.7, np.float32) == float(np.float32(0.7)) and _dev.compare_value(np.float64(0.7), np.float32) == 0.7
     bg = np.random.PCG64(3)
     assert simmask.subgen(bg, 2**31 + 7, np.zeros(0, dtype=np.int64)).shape == (0,)  # empty: nothing is drawn, the stream still moves
     want = np.random.PCG64(3)

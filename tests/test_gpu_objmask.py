@@ -185,6 +185,28 @@ def test_propagation():
     assert one.shape == (1, 1) and one.all()
 
 
+def test_outputs_are_ordered_on_a_side_stream():
+    """The seams launch on torch's current stream of the context's device: on a side stream, with no synchronise, a torch op of that
+    stream reads what the kernel wrote.  3 x 70 is wider than a 64-bit flood word and crosses a dilation tile's column boundary (48)."""
+    import torch
+
+    from pyimcom_amd import objmask, simmask
+
+    mask = np.zeros((3, 70), dtype=bool)
+    mask[1, 0] = mask[0, 47] = mask[2, 63] = mask[1, 69] = True
+    grow, seed = np.zeros((3, 70), dtype=bool), np.zeros((3, 70), dtype=bool)
+    grow[1, :] = seed[1, 0] = grow[0, 69] = grow[2, 30] = True
+    side = torch.cuda.Stream(DEV)
+    assert side != torch.cuda.default_stream(DEV)
+    with torch.cuda.stream(side):
+        u = (simmask.uniform(7, 0, (5,), device=DEV) + 0.0).cpu().numpy()
+        d = objmask.dilate(torch.as_tensor(mask, device=DEV), 1).logical_or(torch.zeros((), dtype=torch.bool, device=DEV)).cpu().numpy()
+        p = objmask.propagate(torch.as_tensor(seed, device=DEV), torch.as_tensor(grow, device=DEV)).clone().cpu().numpy()
+    assert u.dtype == np.float64 and np.array_equal(u, np.random.Generator(np.random.PCG64(7)).uniform(size=5))
+    assert d.dtype == np.bool_ and np.array_equal(d, R.dilate(mask, 1))
+    assert p.dtype == np.bool_ and np.array_equal(p, R.propagate(seed, grow)) and p[1].all() and p[0, 69] and p[2, 30]
+
+
 # ---- the whole function ----
 def _check_details(name, d):
     seen = 0
