@@ -1,4 +1,5 @@
-// fft_lines.h -- line FFTs, one wavefront per line (device side of the butterfly path of psf_overlap.hip).
+// fft_lines.h -- line FFTs, one wavefront per line: the device side of the engine.  Its plan is fft_plan_core.h, its host side (stage
+// tables, the opt-in to dynamic LDS, the dense-DFT fallback) fft.hip; psf_overlap.hip, splitpsf.hip, noisespec.hip and noise1f.hip run it.
 //
 // A line of n <= 1024 complex doubles is transformed by ONE wave: Stockham stages of radix 16 / 8 / 4 / 2 / 3 / 5 whose
 // butterflies sit in registers (a lane holds ceil(n / R / 64) butterflies of R values), with the line exchanged between
@@ -13,17 +14,10 @@
 //     256 B, i.e. one bank group) becomes conflict free, contiguous reads stay so;
 //   * twiddles per stage as tables tw[off_s + (t - 1) Ns + k] = exp(-2 pi i t k / (Ns R)), contiguous in k.
 #pragma once
+#include "fft_plan_core.h"
 #include "fft_radix.h"
 
 namespace imcom {
-
-constexpr int WF_MAXN = 1024;
-constexpr int WF_MAXST = 8;
-constexpr int WF_MAXWAVES = 12;  // waves per workgroup: three per SIMD leave a wave 168 registers (a radix-16 butterfly with its twiddles needs ~140)
-
-struct FftPlan {
-    int n, npad, nst, radix[WF_MAXST], twoff[WF_MAXST], twn, waves;  // npad: n rounded up to 16; waves per workgroup
-};
 
 // twiddle(k, n) = (cos, sin)(2 pi k / nfft) with k reduced mod nfft exactly
 __device__ __forceinline__ void twiddle(long k, int nfft, double *c, double *s)
@@ -112,6 +106,25 @@ __device__ __forceinline__ void wf_line(cplx *line, const cplx *twl, const FftPl
         Ns *= pl.radix[s];
     }
     wf_stage_r<INV>(pl.radix[last], pl.n, Ns, twl + pl.twoff[last], ld, storeN);
+}
+
+// The start of a line kernel.  The workgroup's dynamic LDS (`fbuf`) is `slices` line slices of pl.npad values with the stage tables behind
+// them (fft_line_lds_bytes).  wf_stage_tables copies the tables `tw` (global memory, fft_line_twiddles) there; wf_prologue, for a kernel
+// with one slice per wave, also runs the workgroup barrier and picks this wave's slice.  A wave without a line returns AFTER the prologue.
+__device__ __forceinline__ cplx *wf_stage_tables(cplx *fbuf, const FftPlan &pl, const cplx *__restrict__ tw, int slices)
+{
+    cplx *twl = fbuf + slices * pl.npad;
+    for (int e = threadIdx.x; e < pl.twn; e += blockDim.x) twl[e] = tw[e];
+    return twl;
+}
+struct WfWave { int wave; cplx *twl, *line; };  // the wave's index in its workgroup (uniform), the stage tables in LDS, the wave's slice
+__device__ __forceinline__ WfWave wf_prologue(const FftPlan &pl, const cplx *__restrict__ tw, int slices)
+{
+    extern __shared__ cplx fbuf[];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    cplx *twl = wf_stage_tables(fbuf, pl, tw, slices);
+    __syncthreads();
+    return {wave, twl, fbuf + wave * pl.npad};
 }
 
 // ---------------------------------------------------------------------------------------------------------

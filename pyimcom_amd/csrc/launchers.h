@@ -122,23 +122,22 @@ int smooth_pad_take(imcom_ctx *ctx, int n, int ny, int nx, double tophatwidth, d
 int smooth_pad_device(imcom_ctx *ctx, const SmoothPadWs &w, int n, const double *src, int ny, int nx, double tophatwidth, double gaussiansigma,
                       double *dst);
 
-// psf_overlap.hip: the plan of the wave-per-line transforms (fft_lines.h) and its stage tables (tw: pl.n complex values, device memory)
+// fft.hip: the host side of the line-transform engine.  For the wave-per-line butterflies (fft_lines.h; the plan is fft_plan_core.h): the
+// stage tables of a plan (tw: pl.n complex values, device memory), and the opt-in of a line kernel to more than 48 KiB of dynamic LDS
 struct FftPlan;
-bool fft_line_plan(int n, FftPlan *pl);
 int fft_line_twiddles(imcom_ctx *ctx, const FftPlan &pl, double2 *tw);
-
-// splitpsf.hip
-constexpr int SPLITPSF_MAXN = 4096;  // largest transform side (2 x the cube side)
-// the dense-DFT line engine (its route 2) for other callers: plan / take the DFT matrix (forward, and inverse if asked), the packed lines A and
-// the product C; after splitpsf_dense_product row l of d.C (stride d.Np doubles) holds the transform of line l of `in`, interleaved (re, im)
-struct SpDense {
+int fft_line_lds_opt_in(const void *kernel, size_t lds_bytes);
+// The dense-DFT line engine, for the sides the butterflies do not take: plan / take the DFT matrix (forward, and inverse if asked), the packed
+// lines A and the product C; after dft_dense_product row l of d.C (stride d.Np doubles) holds the transform of line l of `in`, interleaved (re, im)
+constexpr int DFT_DENSE_MAXN = 4096;  // largest line
+struct DftDense {
     int N = 0, Kp = 0, Np = 0;
     long Mp = 0;  // padded line count of the largest batch
     double *Mf = nullptr, *Mi = nullptr, *A = nullptr, *C = nullptr;
 };
-void splitpsf_dense_plan(SpDense &d, int N, long nlines, bool inverse, WsPlan &plan);
-int splitpsf_dense_take(imcom_ctx *ctx, SpDense &d, bool inverse, const char *who);
-int splitpsf_dense_product(imcom_ctx *ctx, const SpDense &d, const double2 *in, long nlines, bool inv);
+void dft_dense_plan(DftDense &d, int N, long nlines, bool inverse, WsPlan &plan);
+int dft_dense_take(imcom_ctx *ctx, DftDense &d, bool inverse, const char *who);
+int dft_dense_product(imcom_ctx *ctx, const DftDense &d, const double2 *in, long nlines, bool inv);
 
 // pcg64.hip: jumps [PCG64_JUMPS][2][2] (device memory), the (low, high) halves of A_j and C_j, the affine map of 2^j steps of numpy's
 // PCG64 stream with the increment (inc_lo, inc_hi); pcg64_jumps forms them on the host and puts them into the workspace

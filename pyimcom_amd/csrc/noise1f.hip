@@ -4,8 +4,8 @@
 // keeps the real part of outputs k < len / 2, divides by sqrt(2), subtracts the mean and lays the [len / 2 / w][w] block into columns
 // c w .. c w + w - 1 of a float32 frame, odd channels with their columns reversed; the frame is returned without a border of 4 pixels.
 //
-// The DFT is a four-step transform on the wave-per-line butterflies of fft_lines.h: len = N1 N2 (powers of two, 32 .. 1024 each; N1 >= N2),
-// n = n1 N2 + n2, k = k1 + N1 k2:
+// The DFT is a four-step transform on the wave-per-line butterflies of fft_lines.h (their plans: fft_plan_core.h, their stage tables: fft.hip):
+// len = N1 N2 (powers of two, 32 .. 1024 each; N1 >= N2), n = n1 N2 + n2, k = k1 + N1 k2:
 //   step 1  for every n2 the DFT over n1 of x[n1 N2 + n2] (amp applied in the loads), times exp(-2 pi i n2 k1 / len) in the stores (the
 //           twiddle from cospi / sinpi of the exactly reduced angle) -> S[c][n2][k1]
 //   step 2  for every k1 the DFT over n2 of S[c][.][k1]; only k2 < N2 / 2 is stored, and only its real part: blk[c][k1 + N1 k2] = Re / sqrt(2)
@@ -19,21 +19,13 @@
 
 namespace imcom {
 
-#define IMCOM_N1F_PROLOGUE                                                                       \
-    extern __shared__ cplx fbuf[];                                                               \
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                           \
-    cplx *twl = fbuf + pl.waves * pl.npad; /* the stage tables ride in LDS behind the lines */   \
-    for (int e = threadIdx.x; e < pl.twn; e += blockDim.x) twl[e] = tw[e];                       \
-    __syncthreads();                                                                             \
-    cplx *line = fbuf + wave * pl.npad;                                                          \
-    const long L = (long)blockIdx.x * pl.waves + wave;                                           \
-    if (L >= nlines) return /* (no workgroup barrier below) */
-
 // line L = (channel c of the group, n2): g, S and nlines are the group's
 __global__ __launch_bounds__(WF_MAXWAVES * 64) void n1f_step1_kernel(const double *__restrict__ g, const double *__restrict__ amp, int len, int N2, long nlines,
                                                                      FftPlan pl, const cplx *__restrict__ tw, cplx *__restrict__ S)
 {
-    IMCOM_N1F_PROLOGUE;
+    const WfWave w = wf_prologue(pl, tw, pl.waves);
+    const long L = (long)blockIdx.x * pl.waves + w.wave;
+    if (L >= nlines) return;  // (no workgroup barrier below)
     const long c = L / N2;
     const int n2 = (int)(L - c * N2);
     const double *re = g + 2 * c * len + n2, *im = re + len, *a = amp + n2;
@@ -48,14 +40,16 @@ __global__ __launch_bounds__(WF_MAXWAVES * 64) void n1f_step1_kernel(const doubl
         twiddle((long)n2 * k1, len, &cs, &sn);
         dst[k1] = cmulf(v, make_double2(cs, -sn));
     };
-    wf_line<false>(line, twl, pl, load0, storeN);
+    wf_line<false>(w.line, w.twl, pl, load0, storeN);
 }
 
 // line L = (channel c of the group, k1); pl.n = N2
 __global__ __launch_bounds__(WF_MAXWAVES * 64) void n1f_step2_kernel(const cplx *__restrict__ S, int N1, long nlines, FftPlan pl, const cplx *__restrict__ tw,
                                                                      double *__restrict__ blk)
 {
-    IMCOM_N1F_PROLOGUE;
+    const WfWave w = wf_prologue(pl, tw, pl.waves);
+    const long L = (long)blockIdx.x * pl.waves + w.wave;
+    if (L >= nlines) return;  // (no workgroup barrier below)
     const long c = L / N1;
     const int k1 = (int)(L - c * N1), N2 = pl.n;
     const cplx *src = S + c * N1 * N2 + k1;
@@ -64,7 +58,7 @@ __global__ __launch_bounds__(WF_MAXWAVES * 64) void n1f_step2_kernel(const cplx 
     auto storeN = [&](int k2, cplx v) {
         if (2 * k2 < N2) dst[(long)k2 * N1] = v.x / 1.4142135623730951;
     };
-    wf_line<false>(line, twl, pl, load0, storeN);
+    wf_line<false>(w.line, w.twl, pl, load0, storeN);
 }
 
 // sum[c] of blk[c][0 .. half): thread t adds elements t, t + 1024, ... in ascending order, then a tree over the 1024 threads
@@ -109,8 +103,6 @@ static bool noise1f_split(long len, int *N1, int *N2)
     return true;
 }
 
-static size_t n1f_lds(const FftPlan &pl) { return ((size_t)pl.waves * pl.npad + pl.twn) * 16; }
-
 // the stage tables of the two line plans: tw1 [N1], tw2 [N2] complex values
 static int noise1f_tables(imcom_ctx *ctx, long len, cplx *tw1, cplx *tw2)
 {
@@ -128,9 +120,9 @@ static int launch_noise1f_group(imcom_ctx *ctx, const double *g, const double *a
     int N1, N2;
     FftPlan p1, p2;
     IMCOM_REQUIRE(noise1f_split(len, &N1, &N2) && fft_line_plan(N1, &p1) && fft_line_plan(N2, &p2), "internal: noise_1f length %ld", len);
-    const size_t l1 = n1f_lds(p1), l2 = n1f_lds(p2);
-    if (l1 > 48 * 1024) IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)n1f_step1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1));
-    if (l2 > 48 * 1024) IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)n1f_step2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2));
+    const size_t l1 = fft_line_lds_bytes(p1), l2 = fft_line_lds_bytes(p2);
+    IMCOM_TRY(fft_line_lds_opt_in((const void *)n1f_step1_kernel, l1));
+    IMCOM_TRY(fft_line_lds_opt_in((const void *)n1f_step2_kernel, l2));
     const long lines1 = (long)nchg * N2, lines2 = (long)nchg * N1;
     ProfScope ps(ctx, "n1f_transform", 2);
     hipLaunchKernelGGL(n1f_step1_kernel, dim3((unsigned)((lines1 + p1.waves - 1) / p1.waves)), dim3(64 * p1.waves), l1, ctx->stream, g + 2L * ch0 * len, amp, (int)len,

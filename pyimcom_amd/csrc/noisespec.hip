@@ -17,9 +17,9 @@
 // X[k1 + N1 k2] = sum_n2 w_N2^(n2 k2) w_L^(n2 k1) Y_n2[k1].  A workgroup owns G lines:
 //   route "lines"      N2 = 1, L a side fft_line_plan takes, G = the plan's waves per workgroup;
 //   route "two-level"  2 <= N2 <= 16, the smallest N2 for which N1 = L / N2 is a side the butterflies take (a fft_line_plan side, or 4, 8, 16
-//                      as two stages), G = 1: 2560 = 640 x 4, 2688 = 384 x 7, 1040 = 80 x 13, 56 = 8 x 7.
+//                      as two stages: fft_short_plan; both in fft_plan_core.h), G = 1: 2560 = 640 x 4, 2688 = 384 x 7, 1040 = 80 x 13, 56 = 8 x 7.
 //                      LDS: L complex128 values + the stage tables (< N1 values): 50 KB at 2560, 48 KB at 2688, 68 KB at 4096 = 1024 x 4;
-//   route "dense"      every other side: the dense-DFT line engine of splitpsf.hip (fp64 MFMA tiles), with pack / unpack kernels around it.
+//   route "dense"      every other side: the dense-DFT line engine of fft.hip (fp64 MFMA tiles), with pack / unpack kernels around it.
 //
 // Determinism: every output element of every kernel has one owner thread and a fixed summation order; no atomics anywhere.
 #include <algorithm>
@@ -35,31 +35,20 @@ constexpr int NOISEPS_ROUTE_NONE = 0, NOISEPS_ROUTE_LINES = 1, NOISEPS_ROUTE_DEN
 constexpr int NS_MAXN2 = 16;
 constexpr int NS_MAXWAVES = 8;  // waves per workgroup: two per SIMD leave a wave 256 registers (a radix-16 butterfly with its twiddles needs ~140, the N2 column 64 more)
 
-// the plan of the length-N1 sub-transforms: what fft_line_plan takes, or 4, 8, 16 as two stages (fft_line_plan wants two stages and
-// factors these into one)
-static bool ns_sub_plan(int N1, FftPlan *pl)
-{
-    if (fft_line_plan(N1, pl)) return true;
-    if (N1 != 4 && N1 != 8 && N1 != 16) return false;
-    pl->n = N1, pl->npad = 16, pl->nst = 2, pl->waves = 1;
-    pl->radix[0] = N1 == 4 ? 2 : 4, pl->radix[1] = N1 / pl->radix[0];
-    pl->twoff[0] = pl->twoff[1] = 0, pl->twn = (pl->radix[1] - 1) * pl->radix[0];
-    return true;
-}
-
-// L = N1 N2 for the route; false: dense
+// L = N1 N2 for the route, pl the plan of the length-N1 sub-transforms: what fft_line_plan takes, or 4, 8, 16 as two stages
+// (fft_short_plan); false: dense
 static bool ns_factor(int L, FftPlan *pl, int *N2)
 {
     if (fft_line_plan(L, pl)) { *N2 = 1; return true; }
     for (int n2 = 2; n2 <= NS_MAXN2; n2++)
-        if (L % n2 == 0 && L / n2 <= WF_MAXN && ns_sub_plan(L / n2, pl)) { *N2 = n2; return true; }
+        if (L % n2 == 0 && (fft_line_plan(L / n2, pl) || fft_short_plan(L / n2, pl))) { *N2 = n2; return true; }
     return false;
 }
 
 // force_dense: IMCOM_NOISEPS_ROUTE=dense (the caller reads the environment)
 static int noiseps_route(int L, bool force_dense)
 {
-    if (L < 2 || L % 2 != 0 || L > SPLITPSF_MAXN) return NOISEPS_ROUTE_NONE;
+    if (L < 2 || L % 2 != 0 || L > DFT_DENSE_MAXN) return NOISEPS_ROUTE_NONE;
     FftPlan pl;
     int N2;
     if (force_dense || !ns_factor(L, &pl, &N2)) return NOISEPS_ROUTE_DENSE;
@@ -80,7 +69,7 @@ struct NsLines {
     cplx *out;
 };
 
-static size_t ns_lds_bytes(const NsLines &a) { return ((size_t)a.G * a.N2 * a.pl.npad + a.pl.twn + NS_MAXN2) * 16; }
+static size_t ns_lds_bytes(const NsLines &a) { return fft_line_lds_bytes(a.pl, a.G * a.N2) + NS_MAXN2 * 16; }  // G N2 slices, the tables, the N2 roots
 
 __global__ void ns_twiddle_kernel(int L, cplx *__restrict__ twL)
 {
@@ -101,8 +90,7 @@ __global__ __launch_bounds__(NS_MAXWAVES * 64) void ns_lines_kernel(NsLines a)
     const FftPlan &pl = a.pl;
     const int N1 = pl.n, npad = pl.npad, N2 = a.N2, G = a.G, L = a.L, half = L / 2;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), W = blockDim.x >> 6;
-    cplx *twl = fbuf + G * N2 * npad, *wn = twl + pl.twn;  // stage tables, then exp(-2 pi i m / N2)
-    for (int e = threadIdx.x; e < pl.twn; e += blockDim.x) twl[e] = a.tw[e];
+    cplx *twl = wf_stage_tables(fbuf, pl, a.tw, G * N2), *wn = twl + pl.twn;  // stage tables, then exp(-2 pi i m / N2)
     if ((int)threadIdx.x < N2) {
         double c, s;
         twiddle(threadIdx.x, N2, &c, &s);
@@ -196,7 +184,7 @@ __global__ __launch_bounds__(NS_MAXWAVES * 64) void ns_lines_kernel(NsLines a)
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// the dense route's kernels around splitpsf_dense_product
+// the dense route's kernels around dft_dense_product
 template <class T>
 __global__ void ns_dense_pack_kernel(const T *__restrict__ in, long fstride, long rstride, const double *__restrict__ win, int L, cplx *__restrict__ Z)
 {
@@ -324,7 +312,7 @@ __global__ void ns_accumulate_kernel(const double *__restrict__ ps2d, const doub
 struct NsPlan {
     int L = 0, nframe = 0, route = 0, N2 = 1;
     FftPlan pl;
-    SpDense d;
+    DftDense d;
     long nrow = 0, ncol = 0;  // lines of the two passes
 };
 
@@ -333,7 +321,7 @@ static size_t ns_plan(NsPlan &p, int L, int nframe, int route, WsPlan &plan)
     p.L = L, p.nframe = nframe, p.route = route;
     p.nrow = (long)nframe * (L / 2), p.ncol = (long)nframe * (L / 2 + 1);
     if (route == NOISEPS_ROUTE_DENSE) {
-        splitpsf_dense_plan(p.d, L, p.ncol, false, plan);
+        dft_dense_plan(p.d, L, p.ncol, false, plan);
     } else {
         ns_factor(L, &p.pl, &p.N2);
         plan.add((size_t)std::max(p.pl.twn, 1) * 16);
@@ -355,7 +343,7 @@ template <class T, bool ROWS, bool LOOP> static int ns_launch_lines_as(imcom_ctx
 {
     const size_t lds = ns_lds_bytes(a);
     IMCOM_REQUIRE(lds <= 160 * 1024, "internal: noise spectra line of %d needs %zu bytes of LDS", a.L, lds);
-    if (lds > 48 * 1024) IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)ns_lines_kernel<T, ROWS, LOOP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    IMCOM_TRY(fft_line_lds_opt_in((const void *)ns_lines_kernel<T, ROWS, LOOP>, lds));
     const int W = std::min(a.G * a.N2, NS_MAXWAVES);
     hipLaunchKernelGGL((ns_lines_kernel<T, ROWS, LOOP>), dim3((unsigned)((a.nlines + a.G - 1) / a.G)), dim3(64 * W), lds, ctx->stream, a);
     return check_launch("ns_lines_kernel");
@@ -376,7 +364,7 @@ static int launch_noiseps_2d(imcom_ctx *ctx, const void *frames, bool in_f64, in
     ns_plan(p, L, nframe, route, plan);
     cplx *tw = nullptr, *twL = nullptr, *H, *F;
     if (route == NOISEPS_ROUTE_DENSE) {
-        IMCOM_TRY(splitpsf_dense_take(ctx, p.d, false, __func__));
+        IMCOM_TRY(dft_dense_take(ctx, p.d, false, __func__));
     } else {
         IMCOM_TRY(ws_take(ctx, (size_t)std::max(p.pl.twn, 1), &tw, __func__));
         IMCOM_TRY(ws_take(ctx, (size_t)L, &twL, __func__));
@@ -391,10 +379,10 @@ static int launch_noiseps_2d(imcom_ctx *ctx, const void *frames, bool in_f64, in
             if (in_f64) hipLaunchKernelGGL(ns_dense_pack_kernel<double>, gp, dim3(256), 0, st, (const double *)frames, fstride, rstride, window, L, F);
             else hipLaunchKernelGGL(ns_dense_pack_kernel<float>, gp, dim3(256), 0, st, (const float *)frames, fstride, rstride, window, L, F);
             IMCOM_TRY(check_launch("ns_dense_pack_kernel"));
-            IMCOM_TRY(splitpsf_dense_product(ctx, p.d, F, p.nrow, false));
+            IMCOM_TRY(dft_dense_product(ctx, p.d, F, p.nrow, false));
             hipLaunchKernelGGL(ns_dense_separate_kernel, dim3((L / 2 + 255) / 256, L / 2 + 1, nframe), dim3(256), 0, st, (const double *)p.d.C, p.d.Np, L, H);
             IMCOM_TRY(check_launch("ns_dense_separate_kernel"));
-            IMCOM_TRY(splitpsf_dense_product(ctx, p.d, H, p.ncol, false));
+            IMCOM_TRY(dft_dense_product(ctx, p.d, H, p.ncol, false));
             hipLaunchKernelGGL(ns_dense_copy_kernel, dim3((L + 255) / 256, (unsigned)std::min<long>(p.ncol, 65535), (unsigned)((p.ncol + 65534) / 65535)), dim3(256), 0,
                                st, (const double *)p.d.C, p.d.Np, L, p.ncol, F);
             IMCOM_TRY(check_launch("ns_dense_copy_kernel"));
@@ -454,7 +442,7 @@ static int noiseps_check_side(int L, int bin8)
 {
     IMCOM_REQUIRE(L >= 2 && L % 2 == 0, "noise spectra: the side %d is not even", L);
     IMCOM_REQUIRE(!bin8 || L % 8 == 0, "noise spectra: the side %d is not a multiple of 8 (8 x 8 binning)", L);
-    IMCOM_REQUIRE(L <= SPLITPSF_MAXN, "noise spectra: a side of %d is beyond the %d this build transforms", L, SPLITPSF_MAXN);
+    IMCOM_REQUIRE(L <= DFT_DENSE_MAXN, "noise spectra: a side of %d is beyond the %d this build transforms", L, DFT_DENSE_MAXN);
     return IMCOM_OK;
 }
 
@@ -513,7 +501,7 @@ int imcom_noiseps_radial(imcom_ctx *ctx, const double *image, int nframe, int n,
 {
     IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(image && rbin && mean && err, "null pointer");
-    IMCOM_REQUIRE(nframe >= 1 && nframe <= 65535 && n >= 1 && n <= SPLITPSF_MAXN && nidx >= 1 && nidx <= 65535, "noise spectra: %d frames of side %d, %d annuli", nframe,
+    IMCOM_REQUIRE(nframe >= 1 && nframe <= 65535 && n >= 1 && n <= DFT_DENSE_MAXN && nidx >= 1 && nidx <= 65535, "noise spectra: %d frames of side %d, %d annuli", nframe,
                   n, nidx);
     Stage st(ctx, memspace, __func__);
     const size_t npix = (size_t)n * n, szI = (size_t)nframe * npix, szR = (size_t)nframe * nidx;
@@ -538,7 +526,7 @@ int imcom_noiseps_accumulate(imcom_ctx *ctx, const double *ps2d, const double *m
 {
     IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(ps2d && mean && err && ps2d_all && ps1d_all, "null pointer");
-    IMCOM_REQUIRE(nlayers >= 1 && nlayers <= 65535 && n >= 1 && n <= SPLITPSF_MAXN && nrad >= 1 && bins >= 1 && coverage_bin >= 0 && coverage_bin < bins,
+    IMCOM_REQUIRE(nlayers >= 1 && nlayers <= 65535 && n >= 1 && n <= DFT_DENSE_MAXN && nrad >= 1 && bins >= 1 && coverage_bin >= 0 && coverage_bin < bins,
                   "noise spectra: %d layers of side %d, %d annuli, coverage bin %d of %d", nlayers, n, nrad, coverage_bin, bins);
     return launch_noiseps_accumulate(ctx, ps2d, mean, err, nlayers, (long)n * n, nrad, bins, coverage_bin, ps2d_all, ps1d_all);
 }

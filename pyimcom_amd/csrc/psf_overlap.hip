@@ -10,7 +10,7 @@
 //
 // Two formulations.  (1) Butterfly path (default whenever nfft <= 1024 is a product of 16, 8, 4, 2, 3, 5): line FFTs with
 // one wavefront per line, butterflies in registers, the line exchanged through the wave's LDS slice without workgroup
-// barriers (fft_lines.h), see below.
+// barriers (fft_lines.h; the plan is fft_plan_core.h, the stage tables come from fft.hip), see below.
 // (2) Dense-DFT path (general fallback, IMCOM_PSF_OVERLAP=gemm): the zero-padded 2-D DFTs as dense real matrix
 // products with exact twiddle matrices (integer argument reduction mod nfft, then cos/sin of a multiple of
 // pi/nfft) on the fp64 MFMA tile engine of gemm_f64.hip; only the kept nsamp x nsamp window of the inverse is
@@ -108,43 +108,25 @@ __global__ void crop_table_kernel(const double *__restrict__ win, int Wp, int ns
 //             rolled by nc, cropped and scaled on store, inside the 6-sample zero border the same kernel writes.
 // Workgroups are ordered pair-fastest: the workgroups in flight work on the same few spectrum columns of different
 // pairs, so a spectrum column is fetched from HBM once per L2 instead of once per table that uses it.
-__global__ void fft_twiddle_kernel(FftPlan pl, cplx *__restrict__ tw)
-{
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= pl.twn) return;
-    int s = 1, Ns = pl.radix[0];
-    while (s + 1 < pl.nst && e >= pl.twoff[s + 1]) { Ns *= pl.radix[s]; s++; }
-    const int local = e - pl.twoff[s], t = local / Ns + 1, k = local - (t - 1) * Ns;
-    double c, sn;
-    twiddle((long)t * k * (pl.n / (Ns * pl.radix[s])), pl.n, &c, &sn);
-    tw[e] = make_double2(c, -sn);
-}
-
 // V, the intermediate between the two inverse transforms, is [pair][row pair l][kx][2]: rows 2l, 2l+1 of a column next to each
 // other (the row transform takes them as one complex line and reads its line as one contiguous run), columns padded to a
 // multiple of 4 so that four neighbouring columns of a row pair are exactly one aligned 128-byte line.
 __host__ __device__ constexpr int v_stride(int n) { return (n / 2 + 1 + 3) / 4 * 4; }
 
-#define IMCOM_WF_PROLOGUE                                                                        \
-    extern __shared__ cplx fbuf[];                                                               \
-    const int n = pl.n, nh = n / 2 + 1, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  \
-    cplx *twl = fbuf + pl.waves * pl.npad; /* the stage tables ride in LDS behind the lines */   \
-    for (int e = threadIdx.x; e < pl.twn; e += blockDim.x) twl[e] = tw[e];                       \
-    __syncthreads();                                                                             \
-    cplx *line = fbuf + wave * pl.npad
-
 // forward, along x: rows 2l, 2l+1 of PSF p as one complex line; Y1[p][kx][row], kx < nh
 __global__ __launch_bounds__(WF_MAXWAVES * 64) void fft_fwd_rows_kernel(const double *__restrict__ psf, int ns, FftPlan pl,
                                                             const cplx *__restrict__ tw, cplx *__restrict__ Y1)
 {
-    IMCOM_WF_PROLOGUE;
-    const int p = blockIdx.x, r0 = 2 * (blockIdx.y * pl.waves + wave), lane = threadIdx.x & 63;
+    const WfWave w = wf_prologue(pl, tw, pl.waves);
+    const int n = pl.n, nh = n / 2 + 1;
+    cplx *line = w.line;
+    const int p = blockIdx.x, r0 = 2 * (blockIdx.y * pl.waves + w.wave), lane = threadIdx.x & 63;
     if (r0 >= ns) return;
     const double *row0 = psf + ((long)p * ns + r0) * ns, *row1 = row0 + ns;
     const bool two = r0 + 1 < ns;
     auto load0 = [&](int x) { return x < ns ? make_double2(row0[x], two ? row1[x] : 0.0) : make_double2(0.0, 0.0); };
     auto keep = [line](int i, cplx v) { line[wf_swz(i)] = v; };
-    wf_line<false>(line, twl, pl, load0, keep);
+    wf_line<false>(line, w.twl, pl, load0, keep);
     // z = FFT(a + i b) of two real rows: A_k = (z_k + conj z_{n-k}) / 2, B_k = (z_k - conj z_{n-k}) / (2 i)
     for (int k = lane; k < nh; k += 64) {
         const cplx zk = line[wf_swz(k)], zm = line[wf_swz(k ? n - k : 0)];
@@ -158,14 +140,15 @@ __global__ __launch_bounds__(WF_MAXWAVES * 64) void fft_fwd_rows_kernel(const do
 __global__ __launch_bounds__(WF_MAXWAVES * 64) void fft_fwd_cols_kernel(const cplx *__restrict__ Y1, int ns, FftPlan pl,
                                                             const cplx *__restrict__ tw, cplx *__restrict__ R)
 {
-    IMCOM_WF_PROLOGUE;
-    const int p = blockIdx.x, kx = blockIdx.y * pl.waves + wave;
+    const WfWave w = wf_prologue(pl, tw, pl.waves);
+    const int n = pl.n, nh = n / 2 + 1;
+    const int p = blockIdx.x, kx = blockIdx.y * pl.waves + w.wave;
     if (kx >= nh) return;
     const cplx *src = Y1 + ((long)p * nh + kx) * ns;
     cplx *dst = R + ((long)p * nh + kx) * n;
     auto load0 = [&](int y) { return y < ns ? src[y] : make_double2(0.0, 0.0); };
     auto storeN = [&](int ky, cplx v) { dst[ky] = v; };
-    wf_line<false>(line, twl, pl, load0, storeN);
+    wf_line<false>(w.line, w.twl, pl, load0, storeN);
 }
 
 // inverse, along y: column kx of R1[p] conj(R2[q]) (x the squared Fourier-mode weight) -> V[t][y' / 2][kx][y' & 1] for the
@@ -176,8 +159,9 @@ __global__ __launch_bounds__(WF_MAXWAVES * 64) void fft_inv_cols_kernel(const cp
                                                             const cplx *__restrict__ tw, double amp0, double amps,
                                                             cplx *__restrict__ V)
 {
-    IMCOM_WF_PROLOGUE;
-    const int t = blockIdx.x, kx = blockIdx.y * pl.waves + wave, nc = ns / 2;
+    const WfWave w = wf_prologue(pl, tw, pl.waves);
+    const int n = pl.n, nh = n / 2 + 1;
+    const int t = blockIdx.x, kx = blockIdx.y * pl.waves + w.wave, nc = ns / 2;
     if (kx >= nh) return;
     const cplx *R1 = Ra + ((long)pairs[2 * t] * nh + kx) * n, *R2 = Rb + ((long)pairs[2 * t + 1] * nh + kx) * n;
     const int nhp = v_stride(n);
@@ -199,7 +183,7 @@ __global__ __launch_bounds__(WF_MAXWAVES * 64) void fft_inv_cols_kernel(const cp
         const int yp = i + nc - (i + nc >= n ? n : 0);
         if (yp < ns) dst[(yp >> 1) * (2 * nhp) + (yp & 1)] = v;
     };
-    wf_line<true>(line, twl, pl, load0, storeN);
+    wf_line<true>(w.line, w.twl, pl, load0, storeN);
 }
 
 // inverse, along x: window rows 2l, 2l+1 of pair t from their Hermitian halves as one complex line; the real and the
@@ -210,8 +194,9 @@ __global__ __launch_bounds__(WF_MAXWAVES * 64) void fft_inv_rows_kernel(const cp
                                                             const cplx *__restrict__ tw, const int *__restrict__ slot,
                                                             double *__restrict__ tables)
 {
-    IMCOM_WF_PROLOGUE;
-    const int t = blockIdx.x, r0 = 2 * (blockIdx.y * pl.waves + wave), nc = ns / 2, ng = ns + 12, lane = threadIdx.x & 63;
+    const WfWave w = wf_prologue(pl, tw, pl.waves);
+    const int n = pl.n, nh = n / 2 + 1;
+    const int t = blockIdx.x, r0 = 2 * (blockIdx.y * pl.waves + w.wave), nc = ns / 2, ng = ns + 12, lane = threadIdx.x & 63;
     if (r0 >= ns) return;
     const bool two = r0 + 1 < ns;
     const cplx *src = V + ((long)t * ((ns + 1) / 2) + r0 / 2) * v_stride(n) * 2;
@@ -234,7 +219,7 @@ __global__ __launch_bounds__(WF_MAXWAVES * 64) void fft_inv_rows_kernel(const cp
             if (two) o1[xp] = z.y * scale;
         }
     };
-    wf_line<true>(line, twl, pl, load0, storeN);
+    wf_line<true>(w.line, w.twl, pl, load0, storeN);
     // zero border
     if (lane < 12) {
         const int c = lane < 6 ? lane - 6 : ns + lane - 6;
@@ -249,51 +234,15 @@ __global__ __launch_bounds__(WF_MAXWAVES * 64) void fft_inv_rows_kernel(const cp
     }
 }
 
-// nfft = product of radices 16, 8, 4, 2, 3, 5 (at least two stages) with lines that fit the wave engine?
-static bool fft_plan(int n, FftPlan *pl)
-{
-    if (n > WF_MAXN || n < 6) return false;
-    pl->n = n;
-    pl->npad = (n + 15) / 16 * 16;
-    pl->nst = 0;
-    int r = n;
-    const int cand[6] = {16, 8, 4, 2, 3, 5};
-    for (int ci = 0; ci < 6; ci++)
-        while (r % cand[ci] == 0) {
-            if (pl->nst >= WF_MAXST) return false;
-            pl->radix[pl->nst++] = cand[ci];
-            r /= cand[ci];
-        }
-    if (r != 1 || pl->nst < 2) return false;
-    int Ns = pl->radix[0], off = 0;
-    pl->twoff[0] = 0;
-    for (int s = 1; s < pl->nst; s++) {
-        pl->twoff[s] = off;
-        off += (pl->radix[s] - 1) * Ns;
-        Ns *= pl->radix[s];
-    }
-    pl->twn = off;
-    // as many waves (= lines) per workgroup as LDS holds next to the tables, WF_MAXWAVES at most
-    const long line = (long)pl->npad * 16, lds = 160 * 1024;
-    pl->waves = (int)std::min<long>(WF_MAXWAVES, (lds - (long)pl->twn * 16) / line);
-    return pl->waves >= 1;
-}
-
 static bool fft_force_gemm()
 {
     return env_is("IMCOM_PSF_OVERLAP", "gemm");
 }
 
-static size_t fft_lds_bytes(const FftPlan &pl) { return ((size_t)pl.waves * pl.npad + pl.twn) * 16; }
-
 static int fft_set_lds(const FftPlan &pl)
 {
-    const size_t lds = fft_lds_bytes(pl);
-    if (lds <= 48 * 1024) return IMCOM_OK;
-    IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)fft_fwd_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)fft_fwd_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)fft_inv_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)fft_inv_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (const void *k : {(const void *)fft_fwd_rows_kernel, (const void *)fft_fwd_cols_kernel, (const void *)fft_inv_cols_kernel, (const void *)fft_inv_rows_kernel})
+        IMCOM_TRY(fft_line_lds_opt_in(k, fft_line_lds_bytes(pl)));
     return IMCOM_OK;
 }
 
@@ -527,20 +476,14 @@ static int wf16_inverse(imcom_ctx *ctx, const cplx *Ra, const cplx *Rb, const in
 static size_t fft_forward_ws(int n, int nsamp, int nfft) { return (size_t)nfft * 16 + (size_t)n * nsamp * (nfft / 2 + 1) * 16 + 1024; }
 static size_t fft_inverse_ws(int npairs, int nsamp, int nfft) { return (size_t)nfft * 16 + (size_t)npairs * (nsamp + 1) * v_stride(nfft) * 16 + (size_t)npairs * 28 + 4096; }
 
-static cplx *fft_twiddles(imcom_ctx *ctx, const FftPlan &pl)
-{
-    cplx *tw = (cplx *)ws_take(ctx, (size_t)pl.n * 16);  // twn < n
-    if (tw) hipLaunchKernelGGL(fft_twiddle_kernel, dim3((pl.twn + 255) / 256), dim3(256), 0, ctx->stream, pl, tw);
-    return tw;
-}
-
 // spectra R[n][nh][nfft] (complex) of n sampled PSFs; the caller has reserved fft_forward_ws() of workspace
 static int fft_forward(imcom_ctx *ctx, const FftPlan &pl, const double *psf, int n, int nsamp, cplx *R)
 {
     const int nfft = pl.n, nh = nfft / 2 + 1;
-    cplx *tw = fft_twiddles(ctx, pl);
+    cplx *tw = (cplx *)ws_take(ctx, (size_t)pl.n * 16);  // twn < n
     cplx *Y1 = (cplx *)ws_take(ctx, (size_t)n * nsamp * nh * 16);
     if (!tw || !Y1) return ws_short("psf_overlap forward");
+    IMCOM_TRY(fft_line_twiddles(ctx, pl, tw));
     switch (fft_static_r(pl)) {
     case 2: return wf16_forward<2>(ctx, psf, n, nsamp, tw, Y1, R);
     case 3: return wf16_forward<3>(ctx, psf, n, nsamp, tw, Y1, R);
@@ -549,7 +492,7 @@ static int fft_forward(imcom_ctx *ctx, const FftPlan &pl, const double *psf, int
     }
     IMCOM_TRY(fft_set_lds(pl));
     hipStream_t st = ctx->stream;
-    const size_t lds = fft_lds_bytes(pl);
+    const size_t lds = fft_line_lds_bytes(pl);
     const int W = pl.waves, row_blocks = ((nsamp + 1) / 2 + W - 1) / W, col_blocks = (nh + W - 1) / W;
     hipLaunchKernelGGL(fft_fwd_rows_kernel, dim3(n, row_blocks), dim3(64 * W), lds, st, psf, nsamp, pl, tw, Y1);
     hipLaunchKernelGGL(fft_fwd_cols_kernel, dim3(n, col_blocks), dim3(64 * W), lds, st, Y1, nsamp, pl, tw, R);
@@ -562,12 +505,13 @@ static int fft_inverse(imcom_ctx *ctx, const FftPlan &pl, const cplx *Ra, const 
                        int nsamp, const double *amp_penalty, double *tables, const int *win_host = nullptr, const int *slots_host = nullptr)
 {
     const int nfft = pl.n, nh = nfft / 2 + 1;
-    cplx *tw = fft_twiddles(ctx, pl);
+    cplx *tw = (cplx *)ws_take(ctx, (size_t)pl.n * 16);  // twn < n
     cplx *V = (cplx *)ws_take(ctx, (size_t)npairs * (nsamp + 1) * v_stride(nfft) * 16);  // [pair][row pair][kx, stride nhp][2]
     int *pairs_dev = (int *)ws_take(ctx, (size_t)npairs * 8);
     int *win_dev = win_host ? (int *)ws_take(ctx, (size_t)npairs * 16) : nullptr;  // the static kernels honour it; the general ones fill whole tables
     int *slot_dev = slots_host ? (int *)ws_take(ctx, (size_t)npairs * 4) : nullptr;
     if (!tw || !V || !pairs_dev || (win_host && !win_dev) || (slots_host && !slot_dev)) return ws_short("psf_overlap inverse");
+    IMCOM_TRY(fft_line_twiddles(ctx, pl, tw));
     IMCOM_TRY(fft_set_lds(pl));
     hipStream_t st = ctx->stream;
     IMCOM_TRY(upload(ctx, pairs_dev, pairs_host, 2 * (size_t)npairs));  // through the pinned ring: no stream drain
@@ -580,21 +524,11 @@ static int fft_inverse(imcom_ctx *ctx, const FftPlan &pl, const cplx *Ra, const 
     case 4: return wf16_inverse<4>(ctx, Ra, Rb, pairs_dev, npairs, nsamp, tw, a0, a1, win_dev, slot_dev, V, tables);
     default: break;
     }
-    const size_t lds = fft_lds_bytes(pl);
+    const size_t lds = fft_line_lds_bytes(pl);
     const int W = pl.waves, row_blocks = ((nsamp + 1) / 2 + W - 1) / W, col_blocks = (nh + W - 1) / W;
     hipLaunchKernelGGL(fft_inv_cols_kernel, dim3(npairs, col_blocks), dim3(64 * W), lds, st, Ra, Rb, pairs_dev, nsamp, pl, tw, a0, a1, V);
     hipLaunchKernelGGL(fft_inv_rows_kernel, dim3(npairs, row_blocks), dim3(64 * W), lds, st, V, nsamp, pl, tw, slot_dev, tables);
     return check_launch("psf_overlap (butterfly path)");
-}
-
-static int up(int v, int a) { return (v + a - 1) / a * a; }
-
-// the line engine's plan and stage tables for its other users (splitpsf.hip); tw: pl.n complex values
-bool fft_line_plan(int n, FftPlan *pl) { return fft_plan(n, pl); }
-int fft_line_twiddles(imcom_ctx *ctx, const FftPlan &pl, cplx *tw)
-{
-    hipLaunchKernelGGL(fft_twiddle_kernel, dim3((pl.twn + 255) / 256), dim3(256), 0, ctx->stream, pl, tw);
-    return check_launch("fft_twiddle_kernel");
 }
 
 }  // namespace imcom
@@ -607,7 +541,7 @@ static int overlap_from_psfs(imcom_ctx *ctx, const double *psf1, int n1, const d
                              const int *pairs_host, int npairs, const double *amp_penalty, double *tables, const char *who)
 {
     FftPlan pl;
-    if (!fft_force_gemm() && fft_plan(nfft, &pl)) {
+    if (!fft_force_gemm() && fft_line_plan(nfft, &pl)) {
         const int nh_ = nfft / 2 + 1;
         const bool same_ = (psf1 == psf2 && n1 == n2);
         const int npsf_ = same_ ? n1 : n1 + n2;
@@ -620,10 +554,10 @@ static int overlap_from_psfs(imcom_ctx *ctx, const double *psf1, int n1, const d
         return fft_inverse(ctx, pl, R, same_ ? R : R + (long)n1 * nfft * nh_, pairs_host, npairs, ntab, amp_penalty, tables);
     }
     const int nh = nfft / 2 + 1, nc = ntab / 2;
-    const int Sp = up(nsamp, NB);  // padded nsamp (as an M/N extent and as a K extent)
-    const int Tp = up(ntab, NB);   // padded table side (the kept rows / columns of the inverse)
-    const int Hp = up(nh, NB);     // padded half-spectrum width
-    const int Fp = up(nfft, NB);   // padded nfft
+    const int Sp = (int)align_up(nsamp, NB);  // padded nsamp (as an M/N extent and as a K extent)
+    const int Tp = (int)align_up(ntab, NB);   // padded table side (the kept rows / columns of the inverse)
+    const int Hp = (int)align_up(nh, NB);     // padded half-spectrum width
+    const int Fp = (int)align_up(nfft, NB);   // padded nfft
     const bool same = (psf1 == psf2 && n1 == n2);
     const long plane = (long)Fp * Hp;
     auto B8 = [](long n) { return (size_t)n * 8; };
@@ -736,7 +670,7 @@ extern "C" int imcom_psf_overlap_wide(imcom_ctx *ctx, const double *psf1, int n1
 extern "C" long imcom_psf_spectra_size(int nsamp, int nfft)
 {
     FftPlan pl;
-    if (nsamp < 1 || nfft < 2 * nsamp || nfft % 2 || fft_force_gemm() || !fft_plan(nfft, &pl)) return 0;
+    if (nsamp < 1 || nfft < 2 * nsamp || nfft % 2 || fft_force_gemm() || !fft_line_plan(nfft, &pl)) return 0;
     return 2L * (nfft / 2 + 1) * nfft;
 }
 
@@ -746,7 +680,7 @@ extern "C" int imcom_psf_spectra(imcom_ctx *ctx, const double *psf, int n, int n
     IMCOM_REQUIRE(psf && spectra && n >= 1, "null pointer / empty set");
     IMCOM_REQUIRE(imcom_psf_spectra_size(nsamp, nfft) > 0, "no butterfly plan for nfft=%d (use imcom_psf_overlap)", nfft);
     FftPlan pl;
-    fft_plan(nfft, &pl);
+    fft_line_plan(nfft, &pl);
     IMCOM_TRY(ws_reserve(ctx, fft_forward_ws(n, nsamp, nfft) + 8192));
     ProfScope ps(ctx, "psf_spectra");
     return fft_forward(ctx, pl, psf, n, nsamp, (cplx *)spectra);
@@ -767,7 +701,7 @@ static int overlap_from_spectra(imcom_ctx *ctx, const double *spec1, int n1, con
     if (slots_host)
         for (int t = 0; t < npairs; t++) IMCOM_REQUIRE(slots_host[t] >= 0 && slots_host[t] < nslots, "slot %d of pair %d outside the arena of %d tables", slots_host[t], t, nslots);
     FftPlan pl;
-    fft_plan(nfft, &pl);
+    fft_line_plan(nfft, &pl);
     // in chunks of pairs, so that the intermediate (ntab x nh complex per pair) stays within ~4 GB however many
     // tables a caller asks for at once; the chunks run back to back on the stream and reuse the workspace in order
     const size_t per_pair = (size_t)(ntab + 1) * v_stride(nfft) * 16;

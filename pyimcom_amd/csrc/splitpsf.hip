@@ -6,9 +6,9 @@
 //
 // Every transform is a cyclic 2-D DFT of complex planes [plane][N][N], done as two passes of ONE primitive: "transform the contiguous
 // lines of every plane and store the result transposed" -- after two passes the spectrum is in natural order again.  The primitive has
-// two routes: (1) the wave-per-line butterflies of fft_lines.h when N <= 1024 is a product of 2, 3, 5; (2) for every other N the dense
-// DFT as ONE real product on the fp64 MFMA tile engine (gemm_f64.hip): a complex line [N] is a real row [2N], the DFT a real
-// [2N x 2N] matrix of 2 x 2 rotation blocks, then a transposing copy.  Both routes compute the same formula.
+// two routes: (1) the wave-per-line butterflies of fft_lines.h when N is a side fft_line_plan (fft_plan_core.h) takes: N <= 1024, a
+// product of 2, 3, 5; (2) for every other N the dense-DFT line engine of fft.hip (ONE real product on the fp64 MFMA tile engine), then
+// a transposing copy.  Both routes compute the same formula.
 //
 // Determinism: a plane's transforms involve that plane only (a real plane rides as a complex one with a zero imaginary part; in the
 // zeta step K_real and its own Gaussian stamp ride together), every output element has one owner thread, and K_Legendre adds its
@@ -24,13 +24,11 @@
 
 namespace imcom {
 
-static int up(int v, int a) { return (v + a - 1) / a * a; }
-
 constexpr int SPLITPSF_ROUTE_NONE = 0, SPLITPSF_ROUTE_LINES = 1, SPLITPSF_ROUTE_DENSE = 2;
 
 static int splitpsf_route(int nfft)
 {
-    if (nfft < 2 || nfft > SPLITPSF_MAXN) return SPLITPSF_ROUTE_NONE;
+    if (nfft < 2 || nfft > DFT_DENSE_MAXN) return SPLITPSF_ROUTE_NONE;
     FftPlan pl;
     return fft_line_plan(nfft, &pl) ? SPLITPSF_ROUTE_LINES : SPLITPSF_ROUTE_DENSE;
 }
@@ -41,13 +39,9 @@ template <bool INV>
 __global__ __launch_bounds__(WF_MAXWAVES * 64) void sp_lines_kernel(const cplx *__restrict__ in, cplx *__restrict__ out, long nlines, FftPlan pl,
                                                                     const cplx *__restrict__ tw)
 {
-    extern __shared__ cplx fbuf[];
-    const int n = pl.n, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    cplx *twl = fbuf + pl.waves * pl.npad;  // the stage tables ride in LDS behind the lines
-    for (int e = threadIdx.x; e < pl.twn; e += blockDim.x) twl[e] = tw[e];
-    __syncthreads();
-    cplx *line = fbuf + wave * pl.npad;
-    const long L = (long)blockIdx.x * pl.waves + wave;
+    const WfWave w = wf_prologue(pl, tw, pl.waves);
+    const int n = pl.n;
+    const long L = (long)blockIdx.x * pl.waves + w.wave;
     if (L >= nlines) return;  // (no workgroup barrier below)
     const long b = L / n;
     const int y = (int)(L - b * n);
@@ -55,35 +49,10 @@ __global__ __launch_bounds__(WF_MAXWAVES * 64) void sp_lines_kernel(const cplx *
     cplx *dst = out + b * n * n + y;
     auto load0 = [&](int x) { return src[x]; };
     auto storeN = [&](int k, cplx v) { dst[(long)k * n] = v; };
-    wf_line<INV>(line, twl, pl, load0, storeN);
+    wf_line<INV>(w.line, w.twl, pl, load0, storeN);
 }
 
-// route 2: the [Kp x Np] real matrix of the DFT of interleaved complex rows: element x (re, im) to element k (re, im) by the rotation
-// (a + i b)(c -+ i s) = (a c +- b s) + i (b c -+ a s), c + i s = exp(2 pi i x k / N); zero outside 2N x 2N
-__global__ void sp_dft_matrix_kernel(int N, int Kp, int Np, int inv, double *__restrict__ M)
-{
-    const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
-    if (j >= Np || i >= Kp) return;
-    double v = 0.0;
-    if (i < 2 * N && j < 2 * N) {
-        double c, s;
-        twiddle((long)(i >> 1) * (j >> 1), N, &c, &s);
-        if (inv) s = -s;
-        v = ((i & 1) == (j & 1)) ? c : ((i & 1) ? s : -s);
-    }
-    M[(long)i * Np + j] = v;
-}
-
-// rows of interleaved complex lines [nlines][2N] -> [Mp][Kp], zero padded
-__global__ void sp_dense_pack_kernel(const double *__restrict__ in, long nlines, long Mp, int N2, int Kp, double *__restrict__ A)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    const long r = blockIdx.y + (long)blockIdx.z * 65535;
-    if (c >= Kp || r >= Mp) return;
-    A[r * Kp + c] = (r < nlines && c < N2) ? in[r * N2 + c] : 0.0;
-}
-
-// C [Mp][Np] (row b N + y holds the transformed line) -> out[b][k][y]
+// route 2: the dense-DFT line engine (fft.hip) leaves the transformed line (b, y) in row b N + y of C [Mp][Np] -> out[b][k][y]
 __global__ void sp_dense_transpose_kernel(const double *__restrict__ C, int N, int Np, cplx *__restrict__ out)
 {
     __shared__ cplx tile[16][17];
@@ -97,45 +66,10 @@ __global__ void sp_dense_transpose_kernel(const double *__restrict__ C, int N, i
     if (k0 + ty < N && y0 + tx < N) out[(b * N + k0 + ty) * N + y0 + tx] = tile[tx][ty];
 }
 
-// route 2 on its own (launchers.h: noisespec.hip runs its lines through it too): the tables and buffers of the dense DFT of lines of
-// length N, and the product -- row l of d.C (stride d.Np doubles) = the transform of line l, interleaved (re, im)
-void splitpsf_dense_plan(SpDense &d, int N, long nlines, bool inverse, WsPlan &plan)
-{
-    d.N = N;
-    d.Kp = up(2 * N, 16);
-    d.Np = up(2 * N, NB);
-    d.Mp = (nlines + NB - 1) / NB * NB;
-    plan.add((size_t)d.Kp * d.Np * 8);
-    if (inverse) plan.add((size_t)d.Kp * d.Np * 8);
-    plan.add((size_t)d.Mp * d.Kp * 8);
-    plan.add((size_t)d.Mp * d.Np * 8);
-}
-
-int splitpsf_dense_take(imcom_ctx *ctx, SpDense &d, bool inverse, const char *who)
-{
-    IMCOM_TRY(ws_take(ctx, (size_t)d.Kp * d.Np, &d.Mf, who));
-    if (inverse) IMCOM_TRY(ws_take(ctx, (size_t)d.Kp * d.Np, &d.Mi, who));
-    IMCOM_TRY(ws_take(ctx, (size_t)d.Mp * d.Kp, &d.A, who));
-    IMCOM_TRY(ws_take(ctx, (size_t)d.Mp * d.Np, &d.C, who));
-    hipLaunchKernelGGL(sp_dft_matrix_kernel, dim3((d.Np + 255) / 256, d.Kp), dim3(256), 0, ctx->stream, d.N, d.Kp, d.Np, 0, d.Mf);
-    if (inverse) hipLaunchKernelGGL(sp_dft_matrix_kernel, dim3((d.Np + 255) / 256, d.Kp), dim3(256), 0, ctx->stream, d.N, d.Kp, d.Np, 1, d.Mi);
-    return check_launch("sp_dft_matrix_kernel");
-}
-
-int splitpsf_dense_product(imcom_ctx *ctx, const SpDense &d, const cplx *in, long nlines, bool inv)
-{
-    const long Mp = (nlines + NB - 1) / NB * NB;
-    IMCOM_REQUIRE(Mp <= d.Mp && Mp <= 0x7fffffffL && (!inv || d.Mi), "internal: splitpsf dense batch of %ld lines", nlines);
-    hipLaunchKernelGGL(sp_dense_pack_kernel, dim3((d.Kp + 255) / 256, (unsigned)std::min<long>(Mp, 65535), (unsigned)((Mp + 65534) / 65535)), dim3(256), 0,
-                       ctx->stream, (const double *)in, nlines, Mp, 2 * d.N, d.Kp, d.A);
-    IMCOM_TRY(check_launch("sp_dense_pack_kernel"));
-    return launch_gemm(ctx, false, true, (int)Mp, d.Np, d.Kp, 1, d.A, d.Kp, 0, inv ? d.Mi : d.Mf, d.Np, 0, d.C, d.Np, 0, 1.0, 0.0);
-}
-
 // what one 2-D transform engine needs out of the workspace, and the engine itself
 struct SpFft {
     int N = 0, route = 0;
-    SpDense d;
+    DftDense d;
     FftPlan pl;
     cplx *tw = nullptr;
 };
@@ -148,7 +82,7 @@ static void sp_fft_plan(SpFft &f, int N, long planes, WsPlan &plan)
         fft_line_plan(N, &f.pl);
         plan.add((size_t)N * 16);
     } else {
-        splitpsf_dense_plan(f.d, N, planes * N, true, plan);
+        dft_dense_plan(f.d, N, planes * N, true, plan);
     }
 }
 
@@ -157,14 +91,10 @@ static int sp_fft_take(imcom_ctx *ctx, SpFft &f, const char *who)
     if (f.route == SPLITPSF_ROUTE_LINES) {
         IMCOM_TRY(ws_take(ctx, (size_t)f.N, &f.tw, who));
         IMCOM_TRY(fft_line_twiddles(ctx, f.pl, f.tw));
-        const size_t lds = ((size_t)f.pl.waves * f.pl.npad + f.pl.twn) * 16;
-        if (lds > 48 * 1024) {
-            IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)sp_lines_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            IMCOM_HIP_CHECK(hipFuncSetAttribute((const void *)sp_lines_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        return IMCOM_OK;
+        IMCOM_TRY(fft_line_lds_opt_in((const void *)sp_lines_kernel<false>, fft_line_lds_bytes(f.pl)));
+        return fft_line_lds_opt_in((const void *)sp_lines_kernel<true>, fft_line_lds_bytes(f.pl));
     }
-    return splitpsf_dense_take(ctx, f.d, true, who);
+    return dft_dense_take(ctx, f.d, true, who);
 }
 
 // one pass: the lines of `planes` planes of `in`, transformed, into `out` transposed
@@ -174,13 +104,13 @@ static int sp_lines_T(imcom_ctx *ctx, const SpFft &f, const cplx *in, cplx *out,
     const long nlines = planes * N;
     if (f.route == SPLITPSF_ROUTE_LINES) {
         const int W = f.pl.waves;
-        const size_t lds = ((size_t)W * f.pl.npad + f.pl.twn) * 16;
+        const size_t lds = fft_line_lds_bytes(f.pl);
         const unsigned grid = (unsigned)((nlines + W - 1) / W);
         if (inv) hipLaunchKernelGGL(sp_lines_kernel<true>, dim3(grid), dim3(64 * W), lds, ctx->stream, in, out, nlines, f.pl, (const cplx *)f.tw);
         else hipLaunchKernelGGL(sp_lines_kernel<false>, dim3(grid), dim3(64 * W), lds, ctx->stream, in, out, nlines, f.pl, (const cplx *)f.tw);
         return check_launch("sp_lines_kernel");
     }
-    IMCOM_TRY(splitpsf_dense_product(ctx, f.d, in, nlines, inv));
+    IMCOM_TRY(dft_dense_product(ctx, f.d, in, nlines, inv));
     hipLaunchKernelGGL(sp_dense_transpose_kernel, dim3((N + 15) / 16, (N + 15) / 16, (unsigned)planes), dim3(16, 16), 0, ctx->stream, (const double *)f.d.C, N, f.d.Np,
                        out);
     return check_launch("sp_dense_transpose_kernel");
@@ -535,10 +465,10 @@ int imcom_splitpsf_tophat(imcom_ctx *ctx, const double *cube, int nplane, int n,
 {
     IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(cube && out, "null pointer");
-    IMCOM_REQUIRE(nplane >= 1 && nplane <= 65535 && n >= 1 && n <= SPLITPSF_MAXN && width > 0.0 && width <= 4096.0, "splitpsf tophat: %d planes of side %d, width %g",
+    IMCOM_REQUIRE(nplane >= 1 && nplane <= 65535 && n >= 1 && n <= DFT_DENSE_MAXN && width > 0.0 && width <= 4096.0, "splitpsf tophat: %d planes of side %d, width %g",
                   nplane, n, width);
     if (!splitpsf_route(n + 2 * splitpsf_tophat_npad(width))) {
-        set_error("splitpsf tophat: a padded side of %d is beyond the %d this build transforms", n + 2 * splitpsf_tophat_npad(width), SPLITPSF_MAXN);
+        set_error("splitpsf tophat: a padded side of %d is beyond the %d this build transforms", n + 2 * splitpsf_tophat_npad(width), DFT_DENSE_MAXN);
         return IMCOM_ERR_UNSUPPORTED;
     }
     Stage st(ctx, memspace, __func__);
@@ -560,7 +490,7 @@ int imcom_splitpsf_split(imcom_ctx *ctx, const double *cube, int npoly, int n, i
 {
     IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(cube && smallpsf && resid, "null pointer");
-    IMCOM_REQUIRE(npoly >= 1 && n >= 2 && n <= SPLITPSF_MAXN && n % 2 == 0 && ns >= 2 && ns <= n && ns % 2 == 0, "SplitPSF requires even dimension (%d, %d)", n, ns);
+    IMCOM_REQUIRE(npoly >= 1 && n >= 2 && n <= DFT_DENSE_MAXN && n % 2 == 0 && ns >= 2 && ns <= n && ns % 2 == 0, "SplitPSF requires even dimension (%d, %d)", n, ns);
     IMCOM_REQUIRE(std::isfinite(r_in) && std::isfinite(r_out) && r_in != r_out && m_trunc >= 0 && 2 * m_trunc <= n, "splitpsf: radii %g, %g, m_trunc %d", r_in,
                   r_out, m_trunc);
     // the 1-D factor of Truncate_2D_integratedBlackman (splitpsf.py:122-128), Window_integratedBlackman (79-89) on the host
@@ -605,7 +535,7 @@ int imcom_splitpsf_points(imcom_ctx *ctx, const double *resid, int nsca, int npo
                       "splitpsf: covariance %ld is not positive definite", e);
     }
     if (!splitpsf_route(2 * n)) {
-        set_error("splitpsf: a cube side of %d needs transforms of %d, beyond the %d this build transforms", n, 2 * n, SPLITPSF_MAXN);
+        set_error("splitpsf: a cube side of %d needs transforms of %d, beyond the %d this build transforms", n, 2 * n, DFT_DENSE_MAXN);
         return IMCOM_ERR_UNSUPPORTED;
     }
     Stage st(ctx, memspace, __func__);

@@ -195,6 +195,23 @@ def test_dense_route_of_the_deconvolution_and_sides_beyond_1024(sp):
     assert e.value.status == -4
 
 
+@pytest.mark.parametrize("n,width,N,waves", [(2, 3.0, 10, 12), (794, 8.0, 810, 11), (992, 2.5, 1000, 9), (1008, 6.5, 1024, 9)])
+def test_tophat_on_the_line_route_at_the_edges_of_the_plan(sp, n, width, N, waves):
+    """The transform side N = n + 2 npad at the edges of fft_line_plan (csrc/fft_plan_core.h; tests/test_fft_plan.py pins the lines per
+    workgroup): 10 is the smallest side the filter can reach, 810 has six stages and 11 lines per workgroup, 1000 three radix-5 stages and
+    9 lines, 1024 9 lines.  Three planes ride as two complex ones: 2 N lines, no multiple of the lines per workgroup, so the last workgroup
+    is ragged.  Against the restatement, with its extended-precision yardstick."""
+    from pyimcom_amd._lib import MEM_HOST, check, default_context, lib, ptr
+
+    sz = sp._sizes(n, 3, width)
+    assert (int(sz[1]), int(sz[2])) == (N, sp.ROUTE_LINES) and (2 * N) % waves != 0
+    cube = np.random.default_rng(N).standard_normal((3, n, n))
+    out = np.empty_like(cube)
+    check(lib.imcom_splitpsf_tophat(default_context().handle, ptr(cube), 3, n, width, ptr(out), MEM_HOST))
+    want = ref.tophatfilter(cube, width)
+    _check(f"tophat N = {N}", out, want, np.abs(want - ref.tophatfilter(cube, width, extended=True)).max())
+
+
 def test_value_errors_as_the_reference(sp):
     with pytest.raises(ValueError, match="SplitPSF requires even dimension"):
         sp.SplitPSF(np.zeros((4, 31, 31)), None, {})
