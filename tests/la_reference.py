@@ -123,6 +123,23 @@ not cond eps as the plain solve."""
     return XL
 
 
+def solve_refined_lu(A, kappa, B, steps=2):
+    """solve_refined for A + kappa I that is indefinite but well conditioned: LU with partial pivoting (scipy lu_factor) in
+    place of the Cholesky factorisation, the same long-double residuals."""
+    from scipy.linalg import lu_factor, lu_solve
+
+    n = A.shape[0]
+    F = lu_factor(A + kappa * np.eye(n), check_finite=False)
+    AL = A.astype(LD)
+    AL[np.diag_indices(n)] += LD(kappa)
+    BL = B.astype(LD)
+    XL = lu_solve(F, B, check_finite=False).astype(LD)
+    for _ in range(steps):
+        R = BL - AL @ XL
+        XL = XL + lu_solve(F, R.astype(np.float64), check_finite=False).astype(LD)
+    return XL
+
+
 def chol_maps_refined(A, mBhalf, C, kappaC):
     """lakernel.CholKernel._call_single_kappa (one kappa node) from the refined solve: T [m][n] (long double), UC, Sigma, and the
     scale (kappa N + |D|) / C of the two terms whose difference UC is."""
