@@ -755,6 +755,39 @@ int imcom_pcg64_normal_ex(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, 
                           long count, double *out, long *tail_idx, uint64_t *tail_raw, uint64_t *info, int memspace, int tile, long chunk_tiles,
                           double guard_band);
 
+/* numpy's Poisson draws of a PCG64 stream (Generator.poisson(lam = array); reference src/pyimcom/layer.py:1385-1387, the noise of the nstar
+ * layer).  The stream is given as for imcom_pcg64_uniform.  A draw of rate 0 consumes nothing, one of 0 < lam < 10 as many outputs as its
+ * value plus one, one of lam >= 10 two outputs per attempt of a transformed rejection (csrc/poisson_core.h), so where draw i starts depends
+ * on every draw before it and on their rates; the path is found superchunk by superchunk through windows of candidate positions, and a
+ * superchunk whose path leaves its windows is redone one draw after another (csrc/poisson.hip).
+ *   imcom_pcg64_poisson_sizes  the device workspace a call of `count` draws takes with its arrays in device memory, and the part of it
+ *                              that is scratch of one superchunk.
+ *   imcom_pcg64_poisson        out[i], i < count (int64): what Generator.poisson(lam = lam[0 .. count)) returns after
+ *                              bit_generator.advance(offset), bit for bit.  info [4], host memory whatever the memspace: the stream outputs
+ *                              the draws consume (the state numpy is left in is that many steps on); 1 if the call is UNDECIDED: a
+ *                              comparison of a draw ON THE PATH that depends on log / exp fell inside the guard band (absolute, 2^-47
+ *                              times the summed magnitudes of the terms, for the rejection's logarithmic test; relative 2^-47 for prod >
+ *                              exp(-lam)) or a draw ran into its loop cap (32 attempts, 64 outputs) -- then `out` is not numpy's and the
+ *                              caller draws the request on the host, at most one 4088^2 frame in 1.2e4 at lam = 86; the superchunks redone
+ *                              by the sequential walk; 1 if a rate is negative, NaN or above numpy's POISSON_LAM_MAX: then nothing is
+ *                              written and the call returns IMCOM_ERR_ARG.  IMCOM_ERR_ARG also for count < 0.  The call waits for its work.
+ *   imcom_pcg64_poisson_ex     the same with, for tests and measurements, the draws of a superchunk (a multiple of `tile`, <= 65536), the
+ *                              window (2 .. 4096), the draws of a tile, the guard band (0: none; 1: every comparison undecided) and
+ *                              force_walk (every superchunk by the sequential walk).  0 -- for the guard band a negative value -- is the
+ *                              default.  No result depends on any of them except through info[1] and info[2].
+ *   imcom_nstar_layer          layer.py:1385-1387 for `count` pixels: lam = brightness tot_int + bg, _lam = max(lam, 0), out = ((P - _lam) +
+ *                              lam) - bg in float64 in that order, rounded to float32, P the draws of the rates _lam; no int64 frame is
+ *                              stored.  info as above.
+ *   lam, brightness and out follow `memspace`. */
+int imcom_pcg64_poisson_sizes(long count, long *workspace_bytes, long *scratch_bytes);
+int imcom_pcg64_poisson(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                        const double *lam, long count, long *out, uint64_t *info, int memspace);
+int imcom_pcg64_poisson_ex(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                           const double *lam, long count, long *out, uint64_t *info, int memspace, int superchunk, int window, int tile, double guard_band,
+                           int force_walk);
+int imcom_nstar_layer(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                      const double *brightness, double tot_int, double bg, long count, float *out, uint64_t *info, int memspace);
+
 /* The transform of the 1/f noise layer (reference src/pyimcom/layer.py:896-913, the channel loop of CplxNoise.noise_1f_frame; the draws of
  * 899-900 are imcom_pcg64_normal's, the amplitudes of 892-895 the caller's).  normals [2 nch][len]: rows 2c, 2c + 1 are the real and the
  * imaginary draws of channel c; amp [len].  Per channel: the forward DFT of (re + i im) amp in float64 (a four-step transform, len = N1 N2),

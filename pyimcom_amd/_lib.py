@@ -177,6 +177,9 @@ SIGNATURES = {
     "imcom_pcg64_uniform_at": [_vp, _u64, _u64, _u64, _u64, _vp, _l, _vp, _i],
     "imcom_pcg64_normal_ex": [_vp, _u64, _u64, _u64, _u64, _u64, _u64, _l, _vp, _vp, _vp, _vp, _i, _i, _l, _d],
     "imcom_pcg64_normal": [_vp, _u64, _u64, _u64, _u64, _u64, _u64, _l, _vp, _vp, _vp, _vp, _i],
+    "imcom_pcg64_poisson": [_vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _l, _vp, _vp, _i],
+    "imcom_pcg64_poisson_ex": [_vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _l, _vp, _vp, _i, _i, _i, _i, _d, _i],
+    "imcom_nstar_layer": [_vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _d, _d, _l, _vp, _vp, _i],
     "imcom_noise_1f": [_vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _i],
     "imcom_cr_mask": [_vp, _u64, _u64, _u64, _u64, _i, _i, _i, _i, _d, _vp, _d, _vp, _vp, _i],
     "imcom_select_kth": [_vp, _vp, _i, _l, _vp, _i, _d, _l, _vp, _vp, _i],
@@ -280,10 +283,13 @@ _cdll.imcom_smooth_pad_width.argtypes = [_d, _d]
 _cdll.imcom_smooth_pad_width.restype = C.c_int
 _cdll.imcom_pcg64_normal_sizes.argtypes = [_l, C.POINTER(C.c_long)]
 _cdll.imcom_pcg64_normal_sizes.restype = C.c_int
+_cdll.imcom_pcg64_poisson_sizes.argtypes = [_l, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+_cdll.imcom_pcg64_poisson_sizes.restype = C.c_int
 _cdll.imcom_last_error.argtypes = []
 _cdll.imcom_last_error.restype = C.c_char_p
 
-EXPORTED = sorted(list(SIGNATURES) + ["imcom_version", "imcom_last_error", "imcom_psf_spectra_size", "imcom_smooth_pad_width", "imcom_pcg64_normal_sizes"])
+EXPORTED = sorted(list(SIGNATURES) + ["imcom_version", "imcom_last_error", "imcom_psf_spectra_size", "imcom_smooth_pad_width", "imcom_pcg64_normal_sizes",
+                                            "imcom_pcg64_poisson_sizes"])
 
 
 def source_sha16():

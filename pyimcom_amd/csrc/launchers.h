@@ -145,6 +145,14 @@ constexpr int PCG64_JUMPS = 128;
 constexpr long PCG64_MAX_COUNT = 1L << 36;  // most draws of one call
 int pcg64_jumps(imcom_ctx *ctx, uint64_t inc_lo, uint64_t inc_hi, const unsigned long long **jumps_d, const char *who);
 
+// poisson.hip: numpy's Poisson draws of a PCG64 stream, for the entries at the end of ziggurat.hip.  pcg64_poisson_plan fills in the
+// defaults of S, W, T (0) and the guard band (negative), refuses what is out of range and counts the workspace; pcg64_poisson_device makes
+// the draws (every pointer device memory; values or layer; info_h [4]: outputs consumed, undecided, superchunks recovered, invalid rate)
+int pcg64_poisson_plan(long count, int *S, int *W, int *T, double *guard, size_t *ws_bytes, size_t *scratch_bytes);
+int pcg64_poisson_device(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long inc[2], const unsigned long long offset[2],
+                         const double *lam, const double *brightness, double tot_int, double bg, long count, long *values, float *layer, int S, int W, int T,
+                         double guard, int force_walk, unsigned long long *info_h, const char *who);
+
 // wcs.hip: what every entry that takes packed descriptors does with them -- the refusals of a descriptor and of an error table's geometry, and
 // the rotation product M = R_to R_from^T (row-major, nine doubles) that wcs_pix2pix (wcs_core.h) takes
 struct WcsDesc;

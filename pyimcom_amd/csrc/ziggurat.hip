@@ -379,3 +379,80 @@ int imcom_pcg64_normal_ex(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, 
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// C entries: numpy's Poisson draws of a PCG64 stream and the nstar layer made of them (the kernels and the launch sequence: poisson.hip)
+
+namespace {
+int poisson_entry(imcom_ctx *ctx, const unsigned long long state[2], const unsigned long long inc[2], const unsigned long long offset[2], const double *lam,
+                  const double *brightness, double tot_int, double bg, long count, long *out_i64, float *out_f32, uint64_t *info, int memspace, int S, int W, int T,
+                  double guard, int force_walk, const char *who)
+{
+    IMCOM_TRY(enter(ctx));
+    size_t ws = 0, scratch = 0;
+    IMCOM_TRY(pcg64_poisson_plan(count, &S, &W, &T, &guard, &ws, &scratch));
+    IMCOM_REQUIRE(info && (count == 0 || ((lam || brightness) && (out_i64 || out_f32))), "null pointer");
+    for (int i = 0; i < 4; i++) info[i] = 0;
+    if (count == 0) return IMCOM_OK;
+    Stage st(ctx, memspace, who);
+    WsPlan plan;
+    plan.add(ws);
+    st.plan(plan, {(size_t)count * 8, (size_t)count * (out_i64 ? 8 : 4)});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const double *l_d = nullptr, *b_d = nullptr;
+    long *o_d = nullptr;
+    float *f_d = nullptr;
+    IMCOM_TRY(st.in(brightness ? brightness : lam, (size_t)count, brightness ? &b_d : &l_d));
+    if (out_i64)
+        IMCOM_TRY(st.out(out_i64, (size_t)count, &o_d));
+    else
+        IMCOM_TRY(st.out(out_f32, (size_t)count, &f_d));
+    unsigned long long info_h[4];
+    IMCOM_TRY(pcg64_poisson_device(ctx, state, inc, offset, l_d, b_d, tot_int, bg, count, o_d, f_d, S, W, T, guard, force_walk, info_h, who));
+    for (int i = 0; i < 4; i++) info[i] = info_h[i];
+    IMCOM_REQUIRE(!info_h[3], "%s: a rate is negative, NaN or above 9.223372006484771e+18", who);
+    if (out_i64)
+        IMCOM_TRY(st.back(out_i64, (const long *)o_d, (size_t)count));
+    else
+        IMCOM_TRY(st.back(out_f32, (const float *)f_d, (size_t)count));
+    return st.done();
+}
+}  // namespace
+
+extern "C" {
+
+int imcom_pcg64_poisson_sizes(long count, long *workspace_bytes, long *scratch_bytes)
+{
+    IMCOM_REQUIRE(workspace_bytes && scratch_bytes, "null pointer");
+    int S = 0, W = 0, T = 0;
+    double guard = -1.0;
+    size_t ws = 0, scratch = 0;
+    IMCOM_TRY(pcg64_poisson_plan(count, &S, &W, &T, &guard, &ws, &scratch));
+    *workspace_bytes = (long)ws;
+    *scratch_bytes = (long)scratch;
+    return IMCOM_OK;
+}
+
+int imcom_pcg64_poisson(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                        const double *lam, long count, long *out, uint64_t *info, int memspace)
+{
+    return imcom_pcg64_poisson_ex(ctx, state_lo, state_hi, inc_lo, inc_hi, offset_lo, offset_hi, lam, count, out, info, memspace, 0, 0, 0, -1.0, 0);
+}
+
+int imcom_pcg64_poisson_ex(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                           const double *lam, long count, long *out, uint64_t *info, int memspace, int superchunk, int window, int tile, double guard_band,
+                           int force_walk)
+{
+    const unsigned long long state[2] = {state_lo, state_hi}, inc[2] = {inc_lo, inc_hi}, offset[2] = {offset_lo, offset_hi};
+    return poisson_entry(ctx, state, inc, offset, lam, nullptr, 0.0, 0.0, count, out, nullptr, info, memspace, superchunk, window, tile, guard_band, force_walk,
+                         __func__);
+}
+
+int imcom_nstar_layer(imcom_ctx *ctx, uint64_t state_lo, uint64_t state_hi, uint64_t inc_lo, uint64_t inc_hi, uint64_t offset_lo, uint64_t offset_hi,
+                      const double *brightness, double tot_int, double bg, long count, float *out, uint64_t *info, int memspace)
+{
+    const unsigned long long state[2] = {state_lo, state_hi}, inc[2] = {inc_lo, inc_hi}, offset[2] = {offset_lo, offset_hi};
+    return poisson_entry(ctx, state, inc, offset, nullptr, brightness, tot_int, bg, count, nullptr, out, info, memspace, 0, 0, 0, -1.0, 0, __func__);
+}
+
+}  // extern "C"

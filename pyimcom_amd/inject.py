@@ -1,5 +1,6 @@
 """Injected star-grid layers on the device: ``GridInject.make_image_from_grid`` (reference src/pyimcom/layer.py:792-854), the image of the
-``cstar`` layer and the brightness of ``nstar`` (layer.py:1346-1388; its Poisson draw stays numpy's on the host).
+``cstar`` layer and the brightness of ``nstar`` (layer.py:1346-1388), and the ``nstar`` layer made of that brightness with numpy's Poisson
+draws on the device (``nstar_layer``, layer.py:1364-1387; INTEGRATION.md, seam 22).
 
 The reference loops over the HEALPix grid points near an SCA in Python: per star one PSF out of ``InImage.get_psf_pos`` (for the cube
 formats a Legendre contraction and two FFTs, coadd.py:624-640) and one ``iD5512C`` call over a 128 x 128 box.  Here the PSFs of a chunk of
@@ -9,12 +10,14 @@ staticmethod(pyimcom_amd.inject.make_image_from_grid)`` is the whole binding (IN
 
 Arrays may be numpy (host in, host out) or torch CUDA tensors (device in, device out, on torch's current stream)."""
 
+import re
+
 import numpy as np
 
 from ._dev import bound_context, is_torch
 from ._lib import MEM_DEVICE, MEM_HOST, check, default_context, lib, ptr
 
-__all__ = ["lpoly_arr", "psf_from_cube", "draw_stars", "on_chip", "star_image", "make_image_from_grid"]
+__all__ = ["lpoly_arr", "psf_from_cube", "draw_stars", "on_chip", "star_image", "make_image_from_grid", "parse_nstar", "nstar_layer"]
 
 NB = 128  # tile of the library's GEMM (csrc/common.h): smooth_and_pad works on images padded to it
 FILL = 0.8  # share of the free device memory a chunk is planned into
@@ -240,3 +243,46 @@ def make_image_from_grid(res, inpsf, idsca, obsdata, mywcs, nside_sca, inpsf_ove
         elif fmt == "dc2_imsim":
             kw = {"psf": first}
     return star_image(xsca, ysca, nside, inpsf_oversamp, **kw).cpu().numpy()
+
+
+def parse_nstar(extrainput_string):
+    """``res, tot_int, bg, q`` of an ``nstar<res>,<tot_int>,<bg>,<q>`` layer name as layer.py:1357-1363 reads them; None when the string
+    is no nstar layer."""
+    m = re.search(r"^nstar(\d+),", extrainput_string, re.IGNORECASE)
+    if not m:
+        return None
+    extargs = extrainput_string.split(",")[1:]
+    return int(m.group(1)), float(extargs[0]), float(extargs[1]), int(extargs[2])
+
+
+def nstar_layer(brightness, tot_int, bg, q, idsca, device_out=False):
+    """layer.py:1364-1387 after the brightness image: the float32 ``nstar`` layer ``rng.poisson(lam=_lam) - _lam + lam - bg`` with ``lam =
+    brightness * tot_int + bg``, ``_lam = np.clip(lam, 0, None)`` and ``rng = default_rng(1000000 * (18 * q + idsca[1]) + idsca[0])``, bit
+    for bit.  ``brightness``: the float64 image of ``star_image`` / ``make_image_from_grid``, a tensor on the device (it stays there; no
+    int64 frame is stored) or numpy.  Returns a numpy array, or with ``device_out`` the tensor on the device.  A request the device
+    cannot decide (``noiselayers.last_poisson_info["undecided"]``) is drawn by numpy on the host."""
+    from . import noiselayers as nl
+
+    tot_int, bg = float(tot_int), float(bg)
+    seed = 1000000 * (18 * int(q) + int(idsca[1])) + int(idsca[0])
+    if not is_torch(brightness):
+        brightness = np.ascontiguousarray(brightness, dtype=np.float64)
+    shape = tuple(int(s) for s in brightness.shape)
+    device = brightness.device if is_torch(brightness) and brightness.is_cuda else ("cuda:0" if device_out else None)
+
+    def call(ctx, stream, values, count, out, info, mem):
+        return lib.imcom_nstar_layer(ctx.handle, *stream, values, tot_int, bg, count, out, info, mem)
+
+    def host(gen, b):
+        lam = b.reshape(shape) * tot_int + bg
+        _lam = np.clip(lam, 0, None)
+        return (gen.poisson(lam=_lam) - _lam + lam - bg).astype(np.float32)
+
+    out, _ = nl._poisson_call(np.random.PCG64(seed), 0, brightness, shape, np.float32, device, call, host, "nstar_layer")
+    if is_torch(out):
+        return out if device_out else out.cpu().numpy()
+    if device_out:
+        import torch
+
+        return torch.from_numpy(out).to("cuda:0")
+    return out

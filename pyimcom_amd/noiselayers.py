@@ -24,7 +24,10 @@ subtracts the channel means, casts to float32 and lays the channels into the fra
 another float64 evaluation of the same sums than pocketfft's, so a pixel can differ from the reference's by one float32 unit in the last
 place where the two float64 values lie on either side of a float32 rounding boundary (tests/test_gpu_noise1f.py bounds how often).
 
-Only float64 draws of PCG64 streams are served; ``Generator.poisson`` (``nstar``) stays on the host."""
+``Generator.poisson(lam=array)``, the noise of the ``nstar`` layer (layer.py:1385-1387), is served too (``poisson``; INTEGRATION.md, seam
+22): a Poisson draw consumes a number of outputs that depends on its rate and on the outputs, so the draws are a path through (draw,
+position) that csrc/poisson.hip finds superchunk by superchunk through windows of candidate positions.  Its comparisons that depend on
+``log`` / ``exp`` carry a guard band as well (csrc/poisson_core.h); an undecided request, at most one 4088^2 frame in 1.2e4, is drawn by numpy."""
 
 import ctypes as C
 import math
@@ -35,11 +38,12 @@ from ._dev import bound_context, out_array
 from ._lib import MEM_DEVICE, check, lib, ptr
 from .simmask import halves
 
-__all__ = ["standard_normal", "normal", "white_noise_frame", "noise_1f", "noise_1f_amp", "noise_1f_frame", "last_info"]
+__all__ = ["standard_normal", "normal", "white_noise_frame", "noise_1f", "noise_1f_amp", "noise_1f_frame", "poisson", "last_info", "last_poisson_info"]
 
 ZIG_R = 3.6541528853610088  # numpy/random/src/distributions/ziggurat_constants.h: ziggurat_nor_r, ziggurat_nor_inv_r
 ZIG_INV_R = 0.27366123732975828
 last_info = {}  # the info of the last call of standard_normal
+last_poisson_info = {}  # the info of the last call of poisson / of inject.nstar_layer
 
 
 def _bitgen(bitgen_or_seed):
@@ -187,3 +191,89 @@ def noise_1f_frame(seed, device_out=False, _length=8192 * 128, _nch=32, _w=128):
     normals = standard_normal(np.random.PCG64(int(seed)), (2 * _nch, _length), device=dev)
     frame = noise_1f(normals, noise_1f_amp(_length), _nch, _w)
     return frame if device_out else frame.cpu().numpy()
+
+
+def _leave_advanced(keep, steps):
+    """``keep`` (a PCG64) ``steps`` outputs on, with its cached 32-bit half as it was (advance() drops it; the draws leave it)."""
+    if keep is None or not steps:
+        return
+    st = keep.state
+    keep.advance(steps % (1 << 128))
+    after = keep.state
+    after["has_uint32"], after["uinteger"] = st["has_uint32"], st["uinteger"]
+    keep.state = after
+
+
+def _host_generator(bg, offset):
+    host = np.random.PCG64()
+    host.state = bg.state
+    if offset:
+        host.advance(offset)
+    return host
+
+
+def _poisson_call(bitgen_or_seed, offset, values, shape, out_dtype, device, call, host_draw, who):
+    """The frame of ``poisson`` and ``inject.nstar_layer``: the output array, the library call ``call(ctx, stream halves, pointers)``, the
+    request drawn by numpy (``host_draw(Generator)``) when the device is undecided or a rate is invalid (numpy raises its ValueError), and
+    the state a PCG64 passed in is left in.  ``values``: the rates or the brightness, numpy or a tensor on the device."""
+    from ._dev import is_torch, staged
+
+    keep, bg, state, inc = _bitgen(bitgen_or_seed)
+    offset = int(offset)
+    if offset < 0 or offset >= 1 << 128:
+        raise ValueError(f"{who}: offset in 0 .. 2^128 - 1")
+    if is_torch(values) and values.is_cuda and device is None:
+        device = values.device
+    out, mem, ctx = out_array(shape, out_dtype, device)
+    if device is not None:
+        values = staged(values, out.device, astype=np.float64)
+    count = int(np.prod(shape, dtype=object)) if shape else 1
+    info = np.zeros(4, dtype=np.uint64)
+    rc = call(ctx, halves(state) + halves(inc) + halves(offset), ptr(values) if count else None, count, ptr(out) if count else None, ptr(info), mem)
+    consumed, undecided, recovered, invalid = (int(v) for v in info)
+    if not invalid:
+        check(rc)
+    if undecided or invalid:  # the whole request from numpy (which raises for an invalid rate); the state it leaves is the one to keep
+        host = _host_generator(bg, offset)
+        draws = host_draw(np.random.Generator(host), values.cpu().numpy() if is_torch(values) else values)
+        if device is None:
+            out = draws
+        else:
+            import torch
+
+            out.copy_(torch.from_numpy(np.ascontiguousarray(draws)))
+        if keep is not None:
+            keep.state = host.state
+        consumed = None
+    else:
+        _leave_advanced(keep, offset + consumed)
+    last_poisson_info.clear()
+    last_poisson_info.update(consumed=consumed, undecided=undecided, recovered=recovered)
+    return out, dict(last_poisson_info)
+
+
+def poisson(bitgen_or_seed, lam, offset=0, device=None, return_info=False, _superchunk=0, _window=0, _tile=0, _guard=None, _force_walk=False):
+    """What ``Generator(bg).poisson(lam=lam)`` returns after ``bg.advance(offset)``: int64 of ``lam``'s shape, bit for bit; a numpy array, or a
+    torch tensor on the device when ``lam`` is one there or ``device`` is given.  A ``np.random.PCG64`` (or a Generator of one) passed in
+    is left advanced by ``offset`` and the outputs the draws consumed, as numpy leaves it; any other bit generator raises TypeError.  A
+    rate that is negative, NaN or too large raises numpy's ValueError.  ``return_info``: also a dict with the outputs ``consumed``,
+    ``undecided`` (1: the draws came from numpy on the host) and the superchunks ``recovered`` by the sequential walk.  The arguments with
+    an underscore are for tests: the draws of a superchunk, the window, the draws of a tile, the guard band (None: the production band,
+    0: none, 1: everything undecided) and the walk for every superchunk; no result depends on them."""
+    from ._dev import is_torch
+
+    if is_torch(lam) and not lam.is_cuda:
+        lam = lam.numpy()
+    if not is_torch(lam):
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+    shape = tuple(int(s) for s in lam.shape)
+    guard = -1.0 if _guard is None else float(_guard)
+    if not 0 <= int(_superchunk) <= 65536 or not 0 <= int(_window) <= 4096 or not 0 <= int(_tile) <= 4096 or guard > 1.0:
+        raise ValueError("poisson: _superchunk at most 65536, _window and _tile at most 4096, _guard at most 1")
+
+    def call(ctx, stream, values, count, out, info, mem):
+        return lib.imcom_pcg64_poisson_ex(ctx.handle, *stream, values, count, out, info, mem, int(_superchunk), int(_window), int(_tile), guard,
+                                          int(bool(_force_walk)))
+
+    out, info = _poisson_call(bitgen_or_seed, offset, lam, shape, np.int64, device, call, lambda g, v: g.poisson(lam=v.reshape(shape)), "poisson")
+    return (out, info) if return_info else out

@@ -10,8 +10,8 @@ numpy's bit for bit; the mask kernel keeps its hits in LDS and writes the uint8 
     pyimcom.layer.GalSimInject.subgen = staticmethod(pyimcom_amd.simmask.subgen)
 
 Seeding stays numpy's, on the host: the state and increment are read from ``np.random.PCG64(seed).state``.  Only draws that take one
-64-bit output each are served (``uniform`` / ``random``): numpy's normal and Poisson draws (the white-noise and 1/f layers,
-layer.py:1297-1313; the ``nstar`` layer) consume a data-dependent number of outputs through ziggurat tables and stay on the host.
+64-bit output each are served here (``uniform`` / ``random``): numpy's normal and Poisson draws (the white-noise and 1/f layers,
+layer.py:1297-1313; the ``nstar`` layer) consume a data-dependent number of outputs and are served by ``pyimcom_amd.noiselayers``.
 
 Outputs are numpy arrays (host memspace) or torch CUDA tensors (device memspace, on torch's current stream)."""
 
