@@ -19,6 +19,8 @@ namespace imcom {
 
 constexpr int PAIR_SWAP = 1 << 29, PAIR_FLIP = 1 << 30, PAIR_MASK = (1 << 28) - 1;
 typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef int __attribute__((may_alias)) lds_int;    // integers kept in the doubles of the row ring (build_A_kernel)
+typedef long __attribute__((may_alias)) lds_long;
 
 __device__ __forceinline__ void tile_index(long t, int ntile, int &ti, int &tj)
 {
@@ -45,11 +47,13 @@ constexpr int NCH = 5;     // 16-byte chunks per stencil row
 
 // Row buffers per wave; A_RING - 1 rows are in flight.  Three buffers (two workgroups per CU instead of three)
 // measured slower, 40.9 against 33.7 ms per 256 cfg-2 stamps: the gather needs the waves more than the depth.
+// And again from three workgroups to four, with the ring as the kernel's only LDS (40,960 B; every other shared array lives in
+// it, see the kernel): 24.6-24.7 against 28.1-28.3 ms, three alternating rounds on one box (profiles/r07_builder_occupancy_ab.txt).
 constexpr int A_RING = 2;
 constexpr int A_PMAX = 8;  // stamp-local PSFs up to which the pair table is staged in LDS (one PSF group: 6 x 6 entries); a stamp of four
                            // groups (24 x 24) has every thread fetch its own entry instead: staging 576 entries per tile cost 1.3 ms per block
 
-__global__ __launch_bounds__(256, 3) void build_A_kernel(const int *__restrict__ n, int ldn,
+__global__ __launch_bounds__(256, 4) void build_A_kernel(const int *__restrict__ n, int ldn,
                                                       const double *__restrict__ x,
                                                       const double *__restrict__ y,
                                                       const int *__restrict__ psf,
@@ -59,18 +63,27 @@ __global__ __launch_bounds__(256, 3) void build_A_kernel(const int *__restrict__
                                                       const double *__restrict__ pair_pen, int npsf_max,
                                                       double *__restrict__ A, int ntile, const int *__restrict__ desc)
 {
+    // The ring is the kernel's whole LDS, 40,960 B, a quarter of the CU's 160 KiB: everything else lives in it while no row does.
     __shared__ __attribute__((aligned(16))) double seg[A_RING][256 * SEG_W];
-    __shared__ long seg0[256];  // first element (ascending address order) of stencil row 0, as a 64-bit offset into the table stack
-                                // (a block of the reference's size keeps > 2^31 table elements resident); < 0: no loads
-    __shared__ int rstep[256];  // element step between stencil rows (+ng, or -ng for a flipped table)
-    __shared__ double tile[16][17];
+    static_assert(A_RING == 2 && 4 * sizeof(seg) <= 160 * 1024, "four workgroups per CU: the ring is all the LDS there is");
     // the tile's 16 + 16 pixels and the stamp's pair table, fetched once by a few lanes in ONE round trip (every thread doing its
-    // own psf -> pair_tab -> pair_pen chain of dependent global loads made the prologue 40 % of this kernel)
-    __shared__ int pix_psf[32];
-    __shared__ double pix_x[32], pix_y[32];
-    __shared__ int ptab[A_PMAX * A_PMAX];
-    __shared__ double ppen[A_PMAX * A_PMAX];
+    // own psf -> pair_tab -> pair_pen chain of dependent global loads made the prologue 40 % of this kernel).  Shared by all waves,
+    // at the head of buffer 0; last read before the barrier of the near_end vote below, which every wave passes before it stages
+    // its first row.
+    double *const pix_x = seg[0], *const pix_y = seg[0] + 32, *const ppen = seg[0] + 64;  // [32], [32], [A_PMAX * A_PMAX]
+    lds_int *const pix_psf = (lds_int *)(seg[0] + 64 + A_PMAX * A_PMAX), *const ptab = pix_psf + 32;  // [32], [A_PMAX * A_PMAX]
+    static_assert(64 + A_PMAX * A_PMAX + (32 + A_PMAX * A_PMAX) / 2 <= 256 * SEG_W, "prologue arrays inside buffer 0");
+    // seg0: first element (ascending address order) of stencil row 0, as a 64-bit offset into the table stack (a block of the
+    // reference's size keeps > 2^31 table elements resident); < 0: no loads.  rstep: element step between stencil rows (+ng, or
+    // -ng for a flipped table).  Written and read by the same wave, and kept in that wave's own 640 doubles of buffer 1 (64 + 32
+    // of them): the waves drift in the row loop, and no other wave's DMA ever lands there.  The wave's own first DMA into buffer 1
+    // is issued after stage(seg[0]), which needs every one of these reads for its addresses.
     const int s = blockIdx.y, tid = threadIdx.x;
+    lds_long *const seg0_w = (lds_long *)(seg[1] + (tid & ~63) * SEG_W);  // [64], this wave's samples
+    lds_int *const rstep_w = (lds_int *)(seg[1] + (tid & ~63) * SEG_W + 64);  // [64]
+    // the 16 x 16 results, transposed through LDS for the mirror tile: buffer 0 again, once every wave is through with its rows
+    double (*const tile)[17] = (double (*)[17])seg[0];
+    static_assert(16 * 17 <= 256 * SEG_W, "tile inside buffer 0");
     int ti, tj;
     // Workgroups are dealt round-robin over the 8 XCDs (dispatch order % 8), each with its own L2: give every XCD a
     // contiguous eighth of the tile list, so that the tiles it works on at one time use the same few tables.
@@ -142,8 +155,8 @@ __global__ __launch_bounds__(256, 3) void build_A_kernel(const int *__restrict__
             }
         }
     }
-    seg0[tid] = my_seg0;
-    rstep[tid] = my_step;
+    seg0_w[tid & 63] = my_seg0;
+    rstep_w[tid & 63] = my_step;
     double wt[10];  // the x weights as the row loop uses them (set below, once the first row is on its way)
     // A stencil row is staged as the FIVE 16-byte chunks that hold exactly its 10 taps: the LDS-DMA takes 8-byte aligned
     // global addresses, so a chunk may start on any double (round 1 fetched six aligned chunks per row and carried two
@@ -152,7 +165,13 @@ __global__ __launch_bounds__(256, 3) void build_A_kernel(const int *__restrict__
     // stride 80 B = 20 banks, which takes the 16 lanes of a ds_read_b128 group through all 64 banks.
     // does any stencil of this tile end within a chunk of the end of the table stack?  (block-uniform; almost never)
     const long my_last = my_seg0 < 0 ? 0 : (my_step > 0 ? my_seg0 + 9L * my_step : my_seg0) + 10;
-    const int near_end = __syncthreads_or(my_last >= tab_elems);
+    // (not __syncthreads_or: the runtime's carries 256 B of LDS of its own, which is the fourth workgroup.)  Every wave leaves its
+    // vote in all four waves' own part of buffer 1, behind seg0 / rstep, and reads back the four it was left.
+    const bool wave_end = __ballot(my_last >= tab_elems) != 0;
+    if ((tid & 63) < 4) ((lds_int *)(seg[1] + (tid & 63) * 64 * SEG_W + 96))[tid >> 6] = wave_end;
+    __syncthreads();
+    const lds_int *const votes = (const lds_int *)(seg[1] + (tid & ~63) * SEG_W + 96);
+    const int near_end = votes[0] | votes[1] | votes[2] | votes[3];
     // the five (sample, chunk) pairs this thread fetches for every stencil row.  A wave stages the chunks of its
     // own 64 samples (work item w = lane + 64 q of the wave's 320), so that producer and consumer of an LDS row are
     // the same wave: no workgroup barrier in the row loop, only counted vmcnt waits, and the four waves drift freely.
@@ -160,13 +179,14 @@ __global__ __launch_bounds__(256, 3) void build_A_kernel(const int *__restrict__
     int st1[NCH];           // and the element step between rows
 #pragma unroll
     for (int q = 0; q < NCH; q++) {
-        const int w = (tid & 63) + 64 * q, sm = (tid & ~63) + w / NCH, ch = w % NCH;
-        const long e0 = seg0[sm];
-        const int stp = rstep[sm];
+        const int w = (tid & 63) + 64 * q, sm = w / NCH, ch = w % NCH;  // sm: sample of this wave
+        const long e0 = seg0_w[sm];
+        const int stp = rstep_w[sm];
         const bool on = e0 >= 0;  // samples without a stencil fetch element 0: harmless, and the fast path stays branch-free
         at[q] = tables + (on ? e0 + 2 * ch : 0);
         st1[q] = on ? stp : 0;
     }
+    asm volatile("" ::: "memory");  // every read of seg0 / rstep stays ahead of the first row staged into the ring
     const int wave_base = (tid & ~63) * SEG_W;  // this wave's 64 x 10 doubles of a row buffer
     auto stage = [&](double *buf) {  // branch-free: every lane issues its five chunk loads
 #pragma unroll
@@ -244,6 +264,7 @@ __global__ __launch_bounds__(256, 3) void build_A_kernel(const int *__restrict__
     }
     val += pen;
     if (i >= ns || j >= ns) val = (i == j) ? 1.0 : 0.0;  // identity padding
+    __syncthreads();  // the tile lies in the ring: a wave that is through must not write it while another still consumes rows
     tile[li][lj] = val;
     __syncthreads();
     if (ti == tj) {
