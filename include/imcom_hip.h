@@ -1052,6 +1052,26 @@ int imcom_pool_assemble(imcom_ctx *ctx, int n_img, int nstamps, int n_inframe, c
                         const long *xy_pitch, const long *data_pitch, const long *frame_stride, const int *expo_of, const unsigned int *count, long npool, double *x,
                         double *y, float *data, int *expo, long *inst_off);
 
+/* ---- The input-layer cube (seam 23): reference src/pyimcom/layer.py:1199-1527, get_all_data, fills inimage.indata [n_inframe][nside][nside]
+ * float32 plane by plane.  imcom_layer_place writes every plane that no generator writes: the science frame minus its sky (1261, 1264),
+ * truth with its flip and rescale (1284-1295), labnoise with the literal crop [4:4092, 4:4092] and its flip (1322-1335), skyerr (1344), a
+ * saved noise slice (1484), and the float64 images of the white-noise (1304) and star-grid (1351) seams on their way into the cube.
+ *
+ *   dst[y][x] = post(op(src[y0 + sy][x0 + sx])),  (sy, sx) = (y, x), (y, nside - 1 - x) for flip 1 (`[:, ::-1]`), (nside - 1 - y, x) for
+ *               flip 2 (`[::-1, :]`); src [src_ny][src_nx] of src_type 0 float32, 1 float64, 2 int16, 3 uint16, 4 int32, 5 uint8; with
+ *               src_swapped = 1 its elements are in the other byte order than the machine's (a FITS image as the file holds it) and
+ *               are swapped as they are read.
+ *   op          0: the value as it is; 1: value - sub, as numpy >= 2 forms `data - float(sky)`: float32 - float32(sub) in float32 for a
+ *               float32 source, else the exact double of the value minus sub in double.
+ *   the result  rounded to float32 to nearest even (a float32 source is not rounded again), then with post_scale_flag = 1 multiplied by
+ *               float32(scale) in float32 (`plane *= rescale`, 1295).  NaN stays NaN, infinities pass, -0.0 keeps its sign.
+ *
+ * src and dst follow `memspace` (host: staged through the workspace, the call waits; device: one launch on the context's stream, pointers
+ * aligned to their elements).  IMCOM_ERR_ARG, before anything is queued, for a type, flip, op or flag outside its range, a side outside
+ * 0 .. 65536 and a window that leaves the source (y0, x0 < 0, y0 + nside > src_ny, x0 + nside > src_nx); nside = 0 is a no-op. */
+int imcom_layer_place(imcom_ctx *ctx, const void *src, int src_type, int src_swapped, int src_ny, int src_nx, int y0, int x0, int flip, int op, double sub,
+                      int post_scale_flag, double scale, float *dst, int nside, int memspace);
+
 /* ---- HEALPix star grids (seam 18): the pixels of the RING scheme (Gorski et al. 2005, ApJ 622, 759; nside = 2^res, res 0 .. 29, int64
  * indices) inside a circle on the sky, their centres, and those centres through a WCS.  healpy is not needed; the arithmetic is that of the
  * paper (section 4.1, eqs. 2-9, and the inverse) in float64 and has not been compared with healpy.  NEST order is not served.

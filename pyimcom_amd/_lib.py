@@ -218,6 +218,7 @@ SIGNATURES = {
     "imcom_partition_wcs": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp,
                             C.POINTER(_l)],
     "imcom_extract_layers": [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "imcom_layer_place": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, _i, _d, _vp, _i, _i],
     "imcom_pool_assemble": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp],
     "imcom_healpix_pix2ang": [_vp, _i, _vp, _l, _i, _vp, _vp, _i],
     "imcom_healpix_ang2pix": [_vp, _i, _vp, _vp, _l, _i, _vp, _i],

@@ -161,4 +161,9 @@ int wcs_table_check(const void *tab, int f64, int n2, double lo, double hi, cons
 void wcs_rotation_product(const WcsDesc &from, const WcsDesc &to, double *M);
 size_t wcs_gain_ws_bytes(int nside);  // the workspace of imcom_wcs_effective_gain (a destripe mosaic plans for it)
 
+// layers.hip: one plane of the input-layer cube for imcom_layer_place (partition.hip) -- src and dst device memory, the arguments checked
+// by layer_place_check (layers_core.h), nside >= 1
+int launch_layer_place(imcom_ctx *ctx, const void *src, int src_type, int src_swapped, int src_nx, int y0, int x0, int flip, int op, double sub, int post_scale_flag,
+                       double scale, float *dst, int nside);
+
 }  // namespace imcom

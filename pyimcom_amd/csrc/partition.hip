@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "launchers.h"
+#include "layers_core.h"
 #include "partition_core.h"
 #include "wcs_core.h"
 
@@ -451,6 +452,36 @@ extern "C" int imcom_extract_layers(imcom_ctx *ctx, const float *indata, int n_i
     hipLaunchKernelGGL(extract_layers_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, ctx->stream, indata, n_inframe, nside, y_idx, x_idx, pix_count, nstamps,
                        npixmax, max_count, data);
     return check_launch("extract_layers_kernel");
+}
+
+// The cube that imcom_extract_layers reads, plane by plane (kernel and launcher: layers.hip).
+extern "C" int imcom_layer_place(imcom_ctx *ctx, const void *src, int src_type, int src_swapped, int src_ny, int src_nx, int y0, int x0, int flip, int op,
+                                 double sub, int post_scale_flag, double scale, float *dst, int nside, int memspace)
+{
+    const char *who = "layer_place";
+    IMCOM_TRY(enter(ctx));
+    static const char *const rule[] = {"", "the source type is 0 .. 5 (float32, float64, int16, uint16, int32, uint8)", "src_swapped and post_scale_flag are 0 or 1",
+                                       "flip is 0 (none), 1 (x) or 2 (y)", "op is 0 (none) or 1 (subtract)", "sides are 0 .. 65536",
+                                       "the window leaves the source"};
+    const int broken = layer_place_check(src_type, src_swapped, src_ny, src_nx, y0, x0, flip, op, post_scale_flag, nside);
+    IMCOM_REQUIRE(broken == 0, "%s: %s (type %d, source %d x %d, origin (%d, %d), flip %d, op %d, nside %d)", who, rule[broken], src_type, src_ny, src_nx, y0, x0, flip,
+                  op, nside);
+    IMCOM_REQUIRE(memspace == IMCOM_MEM_HOST || memspace == IMCOM_MEM_DEVICE, "%s: memspace %d", who, memspace);
+    if (nside == 0) return IMCOM_OK;
+    IMCOM_REQUIRE(src && dst, "%s: null pointer", who);
+    const size_t esz = (size_t)layer_type_size(src_type), nsrc = (size_t)src_ny * src_nx, ndst = (size_t)nside * nside;
+    IMCOM_REQUIRE(memspace == IMCOM_MEM_HOST || ((uintptr_t)src % esz == 0 && (uintptr_t)dst % 4 == 0), "%s: a pointer is not aligned to its element", who);
+    Stage st(ctx, memspace, __func__);
+    WsPlan plan;
+    st.plan(plan, {nsrc * esz, ndst * 4});
+    IMCOM_TRY(ws_reserve(ctx, plan.total));
+    const char *s_d;
+    float *d_d;
+    IMCOM_TRY(st.in((const char *)src, nsrc * esz, &s_d));
+    IMCOM_TRY(st.out(dst, ndst, &d_d));
+    IMCOM_TRY(launch_layer_place(ctx, s_d, src_type, src_swapped, src_nx, y0, x0, flip, op, sub, post_scale_flag, scale, d_d, nside));
+    IMCOM_TRY(st.back(dst, (const float *)d_d, ndst));
+    return st.done();
 }
 
 extern "C" int imcom_pool_assemble(imcom_ctx *ctx, int n_img, int nstamps, int n_inframe, const void *const *x_src, const void *const *y_src,

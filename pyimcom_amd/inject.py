@@ -17,7 +17,7 @@ import numpy as np
 from ._dev import bound_context, is_torch
 from ._lib import MEM_DEVICE, MEM_HOST, check, default_context, lib, ptr
 
-__all__ = ["lpoly_arr", "psf_from_cube", "draw_stars", "on_chip", "star_image", "make_image_from_grid", "parse_nstar", "nstar_layer"]
+__all__ = ["lpoly_arr", "psf_from_cube", "draw_stars", "on_chip", "star_image", "make_image_from_grid", "make_image_from_grid_device", "parse_nstar", "nstar_layer"]
 
 NB = 128  # tile of the library's GEMM (csrc/common.h): smooth_and_pad works on images padded to it
 FILL = 0.8  # share of the free device memory a chunk is planned into
@@ -212,6 +212,12 @@ def make_image_from_grid(res, inpsf, idsca, obsdata, mywcs, nside_sca, inpsf_ove
     ``star_grid=pyimcom_amd.healpix.generate_star_grid`` forms the grid and its positions on the device.  ``inpsf`` is
     ``InImage.get_psf_pos``: when its ``InImage`` holds a Legendre cube (``anlsim`` / ``L2_2506``) the PSFs are formed on the device
     from the cube, a ``dc2_imsim`` PSF is used for all stars, and anything else is called once per star that reaches the chip."""
+    return make_image_from_grid_device(res, inpsf, idsca, obsdata, mywcs, nside_sca, inpsf_oversamp, star_grid=star_grid).cpu().numpy()
+
+
+def make_image_from_grid_device(res, inpsf, idsca, obsdata, mywcs, nside_sca, inpsf_oversamp, star_grid=None):
+    """``make_image_from_grid`` with its image left where it is made: the float64 tensor of ``star_image`` on the device
+    (``layers.build_cube`` rounds it into the ``cstar`` plane and draws the ``nstar`` plane from it there)."""
     if star_grid is None:
         from pyimcom.layer import GridInject  # the reference package (INTEGRATION.md, seam 5)
 
@@ -221,7 +227,9 @@ def make_image_from_grid(res, inpsf, idsca, obsdata, mywcs, nside_sca, inpsf_ove
     nside = int(nside_sca)
     idx = np.nonzero(on_chip(xsca, ysca, nside))[0]
     if idx.size == 0:
-        return np.zeros((nside, nside))
+        import torch
+
+        return torch.zeros((nside, nside), dtype=torch.float64, device="cuda:0")
 
     def psf_fn(i):
         return inpsf((rapix[i], decpix[i]), use_drawpsf=True)
@@ -242,7 +250,7 @@ def make_image_from_grid(res, inpsf, idsca, obsdata, mywcs, nside_sca, inpsf_ove
                   "tophatwidth": float(cfg.inpsf_oversamp), "scale": 1.0 / 64.0 if fmt == "anlsim" else 1.0}
         elif fmt == "dc2_imsim":
             kw = {"psf": first}
-    return star_image(xsca, ysca, nside, inpsf_oversamp, **kw).cpu().numpy()
+    return star_image(xsca, ysca, nside, inpsf_oversamp, **kw)
 
 
 def parse_nstar(extrainput_string):

@@ -16,8 +16,9 @@ the relevant cells (csrc/partition_core.h), forms the pixel's position with csrc
 ``imcom_wcs_pix2pix`` on the same integer pixel --, and partitions stably by stamp with the radix sort of that file.
 
 Agreement of the positions with astropy is inherited from seam 16 (pyimcom_amd/wcs.py) and is still unchecked: astropy is not installed where
-this is built and tested.  What stays on the host: FITS / ASDF, the permanent, cosmic-ray and file masks and ``get_all_data`` (their product is
-passed in), ``get_psf_pos``, the visualisation branches."""
+this is built and tested.  What stays on the host: FITS / ASDF, the permanent and file masks (their product is passed in), ``get_psf_pos``,
+the visualisation branches.  The layer cube ``indata`` comes from the device as well: ``layers.get_all_data(inimage, device_out=True)``
+(seam 23) builds it there and only the file bytes are uploaded; the cosmic-ray mask is seam 10's."""
 
 import ctypes as C
 
