@@ -347,6 +347,9 @@ int imcom_ctx_last_repair(imcom_ctx *ctx, int *count, double *w0_min, double *w0
  *   expo         [batch][ldn] int32 exposure (input image) index of each pixel, < n_expo
  *   outimage     [batch][n_inframe][m] float32
  *   Tsum_stamp   [batch][n_expo] float64; Tsum_inpix, Neff [batch][m] float64 (numpy's result dtype)
+ * ldm must be a multiple of 128 (the layout imcom_build_B and the resident solves leave) and ldn >= every n[s]; n_expo <= 64.  Rows
+ * i >= n[s] and columns a >= m of Tt, indata[..][i >= n[s]] and expo[i >= n[s]] enter no output (with fade > 0 the columns m .. m + 2 of Tt
+ * may be overwritten).
  */
 int imcom_coadd_epilogue(imcom_ctx *ctx, int batch, const int *n_host, int ldn, int m, int ldm,
                          int n2f, int fade, int n2, float *Tt, const float *indata, int n_inframe,

@@ -907,6 +907,10 @@ int imcom_coadd_epilogue(imcom_ctx *ctx, int batch, const int *n_host, int ldn, 
     IMCOM_TRY(enter(ctx));
     IMCOM_REQUIRE(batch >= 1 && n_host && Tt && indata && expo && outimage && Tsum_stamp && Tsum_inpix && Neff, "null pointer");
     IMCOM_REQUIRE(m == n2f * n2f && m <= ldm && n_inframe >= 1 && n_expo >= 1 && fade >= 0 && n2 >= 1, "bad sizes");
+    // the 4-column kernel moves 16 bytes at Tt + i ldm + a0, a0 a multiple of 4 below m: aligned and inside the row for these ldm only
+    IMCOM_REQUIRE(ldm % 128 == 0, "imcom_coadd_epilogue: ldm=%d must be a multiple of 128", ldm);
+    for (int s = 0; s < batch; s++)
+        IMCOM_REQUIRE(n_host[s] >= 0 && n_host[s] <= ldn, "imcom_coadd_epilogue: ldn=%d is below n[%d]=%d", ldn, s, n_host[s]);
     IMCOM_TRY(ws_reserve(ctx, (size_t)batch * 4 + (size_t)batch * m * n_expo * 8 + 2048));
     int *n_dev = (int *)ws_take(ctx, (size_t)batch * 4);
     double *Tsum_image = (double *)ws_take(ctx, (size_t)batch * m * n_expo * 8);
