@@ -449,7 +449,7 @@ extern "C" {
 int imcom_splitpsf_sizes(int n, int npoly, double width, int nsca, int npts, long *out)
 {
     IMCOM_REQUIRE(out, "null out");
-    IMCOM_REQUIRE(n >= 2 && n <= 65536 && npoly >= 1 && npoly <= 4096 && nsca >= 1 && npts >= 1 && npts <= npoly && width > 0.0 && width <= 4096.0,
+    IMCOM_REQUIRE(n >= 1 && n <= 65536 && npoly >= 1 && npoly <= 4096 && nsca >= 1 && npts >= 1 && npts <= npoly && width > 0.0 && width <= 4096.0,
                   "splitpsf: side %d, %d planes, tophat width %g, %d SCAs or %d grid points out of range", n, npoly, width, nsca, npts);
     const int npad = splitpsf_tophat_npad(width);
     out[0] = npad;

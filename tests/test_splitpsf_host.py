@@ -100,6 +100,9 @@ def test_sizes_and_routes(sp):
     assert lib.imcom_splitpsf_sizes(520, 16, 8.0, 1, 1, ptr(sz)) == 0 and sz[3] == sp.ROUTE_DENSE  # 2n = 1040 > 1024: the dense route
     assert lib.imcom_splitpsf_sizes(2050, 16, 8.0, 1, 1, ptr(sz)) == 0 and sz[3] == 0 and sz[5] == 0  # 2n > 4096: not served
     assert lib.imcom_splitpsf_sizes(512, 16, 8.0, 1, 17, ptr(sz)) == -1
+    # a single sample is a side imcom_splitpsf_tophat takes (9 = 3 x 3 with a tophat of width 1: the smallest odd butterfly side)
+    assert lib.imcom_splitpsf_sizes(1, 3, 1.0, 1, 1, ptr(sz)) == 0 and list(sz[:3]) == [4, 9, sp.ROUTE_LINES] and sz[4] > 0
+    assert lib.imcom_splitpsf_sizes(0, 3, 1.0, 1, 1, ptr(sz)) == -1
 
 
 def test_package_does_not_import_scipy_or_the_tests():
